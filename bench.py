@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: predicted-trajectories/sec (K=20 best-of-K) of the STTODE forward path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1: either launched by ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...`` (one rank
 per GPU, RCCL), or -- when WORLD_SIZE is not in the environment -- bench.py starts exactly that launcher itself as a child
@@ -26,6 +26,9 @@ The JSON line carries
                  -- a second figure, never `value`;
   per_scene    : the reference's evaluation call pattern, ONE scene per call (set_data + inference + .cpu(), test.py:171-188): ms per scene;
   train        : training steps/s of the train.py loop, with its own CPU baseline.
+
+--dump-outputs DIR writes what the headline region's last timed step computed (predictions, best-of-K ADE / FDE, latents) as .npy files
+(dump_outputs); the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -253,6 +256,7 @@ class Leg:
         # Nothing goes onto the caller's stream here; whoever needs the call's outputs or its slot waits for the event (settle()).
         import torch
         self.last_pred = h['pred']
+        self.last_z = h['z']
         self.unsettled = h
         out = self.model.best_of_k_async(h, gt=h['gt'])        # per-agent (ade, fde) of the slot; summed ONCE, after the last step
         if self.d2h_bufs is not None:                           # by a few persistent workgroups on ITS stream, behind its groups
@@ -299,6 +303,7 @@ class Leg:
             self._load()
             pred = self.model.inference(None)
             self.last_pred = self.model.diverse_pred            # contiguous [n, K, Tf, 2]
+            self.last_z = None                                  # (drawn inside inference(), not handed back)
             return self.model.best_of_k(pred.permute(1, 0, 2, 3))
         st = self.model.next_async_stream(self.n)
         if st is None:
@@ -378,6 +383,7 @@ class Leg:
         if self.gather_counts is not None:
             torch.cuda.current_stream().wait_stream(self.comm_stream)   # the last gathers complete inside the timed region
         self.d2h_bufs, self.gather_counts = None, None
+        self.last_metrics = acc                                   # (ade [n], fde [n]) of the last step, for --dump-outputs
         acc = self.sums(acc)                                      # the last step's per-agent best-of-K values -> (sum ADE, sum FDE, agents)
         if dist is not None:
             allreduce(dist, acc)                                  # metrics of the last step over all ranks
@@ -800,6 +806,35 @@ def per_scene_leg(dev, n_scenes=256):
             'form': 'one launch of cooperating workgroups per call (csrc/scene_lat.hip)'}
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(leg, path):
+    """--dump-outputs: what the LAST timed step of `leg` computed, as the caller of that path receives it, one float32 .npy per array:
+    pred [K, n, Tf, 2] (what wait() / inference() return), ade [n] and fde [n] (best-of-K per agent), and latents [n K, zdim] (the z the
+    call drew; pipelined form only).  Above DUMP_LIMIT_BYTES in all, the same arrays for a fixed seeded sample of the agents, whose
+    indices go to agent_index.npy.  Called right after the timed region, before any other call can reuse the slot's buffers."""
+    import torch
+    torch.cuda.synchronize()
+    n = leg.n
+    arrs = {'pred': leg.last_pred.permute(1, 0, 2, 3), 'ade': leg.last_metrics[0], 'fde': leg.last_metrics[1]}
+    if leg.last_z is not None:
+        arrs['latents'] = leg.last_z.view(n, K, -1)
+    arrs = {k: v.detach().to(torch.float32).cpu().numpy() for k, v in arrs.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep = max(1, (DUMP_LIMIT_BYTES - 4096) * n // (total + 8 * n))   # (8 bytes per agent for agent_index.npy, 4 KB for the headers)
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrs = {k: (a[:, idx] if k == 'pred' else a[idx]) for k, a in arrs.items()}
+        arrs['agent_index'] = idx.astype(np.float64)
+    if 'latents' in arrs:
+        arrs['latents'] = arrs['latents'].reshape(-1, arrs['latents'].shape[-1])
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + '.npy'), np.ascontiguousarray(a))
+    return sorted(arrs)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -828,6 +863,8 @@ def main():
     ap.add_argument('--no-exploratory', action='store_true', help='skip the exploratory bf16x3 region (key exploratory_bf16x3)')
     ap.add_argument('--no-serial-check', action='store_true', help='skip the few serial steps that give roofline.frac_serial_equivalent')
     ap.add_argument('--no-gather-futures', action='store_true', help='multi-rank runs: skip the all-gather of the futures (check + value_incl_gather)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default='',
+                    help='after the headline region, write what its last timed step computed (rank 0) as DIR/<name>.npy (float32, at most 64 MB)')
     ap.add_argument('--selftest-dist', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--dist-backend', choices=('nccl', 'gloo'), default='nccl', help=argparse.SUPPRESS)   # gloo: rehearsal, all ranks on cuda:0
     args = ap.parse_args()
@@ -835,12 +872,21 @@ def main():
     if args.gpus < 1:
         sys.stderr.write('bench.py: --gpus must be >= 1\n')
         return 2
+    if args.steps < 1 or args.warmup < 0:
+        sys.stderr.write('bench.py: --steps must be >= 1 and --warmup >= 0\n')
+        return 2
+    if args.dump_outputs and (args.train or args.only_leg):
+        sys.stderr.write('bench.py: --dump-outputs writes the headline region\'s outputs; it does not combine with --train or --only-leg\n')
+        return 2
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         return self_launch(args)            # before any GPU call in this process
     if args.selftest_dist:
         return selftest_dist(args)
 
     import torch
+    # every step's latents are keyed from torch's generators, whose default seed differs from process to process: seeded here, the inputs of
+    # a run are the same from run to run, and two builds run with the same arguments can be compared output for output (--dump-outputs)
+    torch.manual_seed(0)
     rank, world, local, dist = init_dist(args)
     if args.dist_backend == 'gloo':
         local = 0                                               # rehearsal: every rank computes on cuda:0
@@ -874,6 +920,7 @@ def main():
         return 0
     head = Leg('eth_512', rank, dev, size=args.scenes)
     r = head.timed(args.steps, args.warmup, dist, args.time_every, serial=args.serial, prewarm=args.prewarm)
+    dumped = dump_outputs(head, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     roof, kern = head.roofline(r['stage_ms'], r['value'] / world, args.time_every, calls=None if args.serial else args.steps)
     if roof:
         roof['path_frac_survey_flops_superseded'] = r['value'] / world * F_TRAJ_SURVEY / PEAK_F32_MFMA
@@ -904,6 +951,8 @@ def main():
                            '(same shapes: its FLOP are one call\'s)'}
     if rank == 0:
         out['ade_fde_synthetic'] = [float(acc[0] / acc[2]), float(acc[1] / acc[2])]
+    if dumped:
+        out['dump_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped, 'step': 'the last timed step of the headline region'}
     # D2H-inclusive figure (second key, not the headline): same steps with every step's futures copied to pinned host memory
     # (the region of the headline: as many steps, as much warm-up -- half of them made filling / draining the pipeline and the last copies
     # behind the drain weigh twice as much as they do in `value`)

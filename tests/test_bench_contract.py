@@ -1,7 +1,10 @@
 """CPU check of the bench.py output contract on the committed round-1 line (profiles/r01/final_bench.json): the keys the driver
-and the judge read must be there with sane values, and the roofline numbers must be self-consistent."""
+and the judge read must be there with sane values, and the roofline numbers must be self-consistent.  One GPU test runs bench.py itself
+(--dump-outputs)."""
 import json
 import os
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -95,3 +98,43 @@ def test_bench_self_launch_spawns_the_ranks():
     assert d['n_gpus'] == 2 and d['rccl_ranks'] == 2 and d['self_launched'] is True and d['steps'] == 3
     assert d['value'] > 0 and d['backend'].startswith('gloo')
     assert d['gather'] == {'check': 'ok', 'gathered_rows': 5, 'ranks': 2}      # the futures all-gather of the multi-rank line, rehearsed on host rows
+
+
+@pytest.mark.gpu
+def test_dump_outputs_is_what_the_last_timed_step_computed(tmp_path):
+    """--dump-outputs DIR: the arrays of the headline region's last timed step (pipelined form, 128 scenes) are what that call computed --
+    predictions == the CPU oracle fed the dumped latents (every agent of the first eight scenes), ADE / FDE == their NumPy restatement on
+    those predictions, the line's ade_fde_synthetic == their means -- and a second run with the same arguments draws the same latents."""
+    import numpy as np
+    from helpers import assert_close, oracle_model, oracle_scene_inference
+    from oracle.metrics_ref import best_of_k_ade_fde
+    from sttode_amd import scenes
+    args = ('--gpus', '1', '--steps', '5', '--warmup', '1', '--prewarm', '0', '--scenes', '128', '--legs', 'none', '--no-cpu', '--no-train',
+            '--no-sustained', '--no-per-scene', '--no-exploratory', '--no-serial-check')
+    runs = []
+    for i in range(2):
+        d = str(tmp_path / f'run{i}')
+        r = _run_bench(*args, '--dump-outputs', d)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
+        assert line['steps'] == 5 and line['ms_per_step'] > 0 and line['dump_outputs']['arrays'] == ['ade', 'fde', 'latents', 'pred']
+        runs.append((line, {k: np.load(os.path.join(d, k + '.npy')) for k in line['dump_outputs']['arrays']}))
+    line, out = runs[0]
+    sb = scenes.make_scene_batch(range(128), 'eth')
+    n = sb.n_agents
+    assert out['pred'].shape == (20, n, 12, 2) and out['latents'].shape == (n * 20, 32)
+    assert out['ade'].shape == out['fde'].shape == (n,) and all(a.dtype == np.float32 for a in out.values())
+    assert sum(os.path.getsize(os.path.join(tmp_path, 'run0', k + '.npy')) for k in out) <= 64 * 10 ** 6
+    ora = oracle_model('eth', 8, 12)
+    for s in range(8):
+        a, b = int(sb.scene_ptr[s]), int(sb.scene_ptr[s + 1])
+        obs, fut = sb.scene(s)
+        ref = oracle_scene_inference(ora, obs, fut, out['latents'][a * 20:b * 20])
+        assert_close(out['pred'][:, a:b], ref, what=f'dumped predictions of scene {s} vs oracle')
+    ade, fde = best_of_k_ade_fde(out['pred'].transpose(1, 0, 2, 3).astype(np.float64), sb.future.astype(np.float64))
+    assert_close(out['ade'], ade, what='dumped ADE')
+    assert_close(out['fde'], fde, what='dumped FDE')
+    assert np.allclose(line['ade_fde_synthetic'], [out['ade'].mean(), out['fde'].mean()], rtol=1e-5)
+    again = runs[1][1]
+    assert np.array_equal(again['latents'], out['latents'])
+    assert_close(again['pred'], out['pred'], rtol=1e-5, atol=1e-5, what='the same arguments, a second run')

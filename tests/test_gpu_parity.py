@@ -2262,13 +2262,16 @@ def _grad_yardstick(got, g64, g32, what, digests=None, factor=2.0, floor=1e-4, m
     return rows
 
 
-def _dump_grad_table(what, rows):
+def _dump_grad_table(what, rows, text=None):
     """The per-parameter table of one gradient test, as text under gpurun_out/ (copied into profiles/ by the collection script)."""
     import os
     out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'gpurun_out', 'grad_tables')
     try:
         os.makedirs(out, exist_ok=True)
         with open(os.path.join(out, what.replace(' ', '_').replace('/', '_') + '.txt'), 'w') as f:
+            if text is not None:                                   # (a table its caller formatted)
+                f.write(text)
+                return
             keys = [k for k in rows[0] if k != 'param']
             f.write('# ' + what + '\n# param ' + ' '.join(keys) + '\n')
             for r in rows:
@@ -3305,11 +3308,8 @@ def test_non_default_hyperparameters_training_step_vs_reference(golden, tag):
             if not err_hip <= max(6 * err_f32, 5e-4 * np.abs(g64n).max()) + 1e-12:
                 bad.append((name, err_hip, err_f32, float(np.abs(g64n).max())))
             checked += 1
-        import os
-        os.makedirs('gpurun_out/grad_tables', exist_ok=True)
-        with open(f'gpurun_out/grad_tables/dims_{k}.txt', 'w') as fh:
-            for row in rows:
-                fh.write('%-80s err_hip %.3e  err_fp32_autograd %.3e  max|g| %.3e  rel %.2e\n' % row)
+        _dump_grad_table(f'dims_{k}', None, text=''.join('%-80s err_hip %.3e  err_fp32_autograd %.3e  max|g| %.3e  rel %.2e\n' % row
+                                                            for row in rows))
         assert not bad, (k, [b_[0] for b_ in bad])
         assert checked > 80
         # no-grad forward(): the same values
