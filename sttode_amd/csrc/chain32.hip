@@ -572,21 +572,85 @@ __device__ __forceinline__ void gru32_steps_b3(ST& st, const float* gb, const fl
     }
 }
 
-// conv1d(k=3) + relu + GRU(32 -> 96) over Tp steps for this wave's 32 columns, every weight tile streamed per step
-// (model/STTODE.py:62-69; gate rows pre-scaled, chain.hpp): d = the flattened (t, c) input rows in accumulator layout, hs = h (in/out),
-// gb = gate biases [4][96] (r, z, b_in, b_hn), cb = conv bias [32], both in LDS.  Per step: 1 conv tile (a chunk of its own) and 36
-// gate tiles = 12 chunks.  Shared by the fused chain (block 1, per trajectory) and gru32_kernel (block 0, per agent).
-template <class ST>
-__device__ __forceinline__ void gru32_steps(ST& st, const float* gb, const float* cb, const f32x16& d, f32x16 (&hs)[3], int Tp, int h) {
-#pragma unroll 1
-    for (int t = 0; t < Tp; ++t) {
-        f32x16 e = ldrows(cb, h);
-        Frag fa, fb;
+// conv tile of step t (a chunk of its own) + relu.  ZS: only the fragment groups g (k = 8g .. 8g+7) that meet the tile's non-zero
+// columns 2t-2 .. 2t+3 (frames t-1 .. t+1, packing.toeplitz_conv) are read and multiplied: the others add exact zeros.
+template <bool ZS, class ST>
+__device__ __forceinline__ f32x16 gru32_conv(ST& st, const float* cb, const f32x16& d, int t, int Tp, int h) {
+    f32x16 e = ldrows(cb, h);
+    Frag fa, fb;
+    if (ZS) {
+        const int k0 = 2 * t - 2, k1 = 2 * t + 3;
+        const int g0 = (k0 > 0 ? k0 : 0) >> 3, g1 = (k1 < 2 * Tp - 1 ? k1 : 2 * Tp - 1) >> 3;   // (uniform)
+        const f32x4* tc = st.cur();
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+            if (g >= g0 && g <= g1) fa.a[g] = tc[g * 64];
+        st.begin();
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+            if (g >= g0 && g <= g1)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) e = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.a[g][r], d[4 * g + r], e, 0, 0, 0);
+    } else {
         ldfrag(fa, st.cur());
         st.begin();
         tile_mma2(e, fa, d, fb, nullptr);
-        e = relu16(e);
-        st.end();
+    }
+    e = relu16(e);
+    st.end();
+    return e;
+}
+
+// conv1d(k=3) + relu + GRU(32 -> 96) over Tp steps for this wave's 32 columns, every weight tile streamed per step
+// (model/STTODE.py:62-69; gate rows pre-scaled, chain.hpp): d = the flattened (t, c) input rows in accumulator layout, hs = h (in/out),
+// gb = gate biases [4][96] (r, z, b_in, b_hn), cb = conv bias [32], both in LDS.  Per step: 1 conv tile (a chunk of its own) and 36
+// gate tiles = 12 chunks.  Shared by the fused chain (block 1, per trajectory), gru32_kernel and the throughput-form roles (block 0, per agent).
+// ZS (skip products known to be zero): the initial state is h = 0 (hs is not read) and step 0 issues no MFMA on it -- its 27 recurrent
+// tiles are still consumed chunk by chunk, so the program is the same -- and the conv tiles issue only their non-zero fragment groups.
+// A skipped product adds an exact zero: results are unchanged up to the sign of an exactly-zero value.  ZS = false: every tile in full
+// (STTODE_GRU_ZERO_SKIP=0, A/B).
+template <bool ZS, class ST>
+__device__ __forceinline__ void gru32_steps(ST& st, const float* gb, const float* cb, const f32x16& d, f32x16 (&hs)[3], int Tp, int h) {
+    if (ZS) {   // step 0, h = 0: per j only the three e tiles; the third of the four chunks holds recurrent tiles alone
+        const f32x16 e = gru32_conv<ZS>(st, cb, d, 0, Tp, h);
+        Frag fa, fb;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            STT_FENCE();
+            f32x16 ar = ldrows(gb + 0 * 96 + 32 * j, h);
+            ldfrag(fa, st.cur()); st.begin();                          // [r:e h0 h1]
+            tile_mma2(ar, fa, e, fb, nullptr);
+            st.end(); ldfrag(fa, st.cur() + 1 * C32_TILE); st.begin();  // [r:h2 z:e h0]
+#pragma unroll
+            for (int r = 0; r < 16; ++r) ar[r] = C32_SIG(ar[r]);
+            STT_FENCE();
+            f32x16 az = ldrows(gb + 1 * 96 + 32 * j, h);
+            tile_mma2(az, fa, e, fb, nullptr);
+            st.end(); st.begin();                                       // [z:h1 h2 n_h:h0]
+#pragma unroll
+            for (int r = 0; r < 16; ++r) az[r] = C32_SIG(az[r]);
+            STT_FENCE();
+            f32x16 an = ldrows(gb + 3 * 96 + 32 * j, h);                  // W_hn h = 0
+            {
+                const f32x16 bi = ldrows(gb + 2 * 96 + 32 * j, h);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) an[r] = fmaf(ar[r], an[r], bi[r]);     // b_in + r * (W_hn h + b_hn)
+            }
+            st.end(); ldfrag(fa, st.cur() + 2 * C32_TILE); st.begin();  // [n_h:h1 h2 n_i:e]
+            STT_FENCE();
+            tile_mma2(an, fa, e, fb, nullptr);                           // + W_in e
+            st.end();
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float ng = C32_TANH(an[r]);
+                hs[j][r] = fmaf(az[r], 0.f - ng, ng);   // (1-z) n + z h; the other tiles of hs are not read in step 0
+            }
+        }
+    }
+#pragma unroll 1
+    for (int t = ZS ? 1 : 0; t < Tp; ++t) {
+        const f32x16 e = gru32_conv<ZS>(st, cb, d, t, Tp, h);
+        Frag fa, fb;
         f32x16 hn[3];
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
@@ -680,8 +744,9 @@ __host__ __device__ __forceinline__ int xcd_group(int b, int G) {
 }
 
 // FUSE: 0 = trajectory groups only; 1 = round-3 fused launch (latency-form roles of THIS call in front, tile flags); 2 = lagged launch
-// (round 4: throughput-form roles of a LATER call in front, no dependency inside the launch; either part may be empty)
-template <int NY, int FUSE, bool B3M>
+// (round 4: throughput-form roles of a LATER call in front, no dependency inside the launch; either part may be empty).
+// ZS: the GRUs run as gru32_steps<ZS> (a template argument: a run-time choice inside the kernel costs the group path spills)
+template <int NY, int FUSE, bool B3M, bool ZS>
 __global__ __launch_bounds__(256, 2) void traj_chain_kernel(ChainArgs A) {
     typedef ChainStreamT<B3M ? C32_BUF_B3 : C32_CMAX * C32_TILE, B3M> Stream;   // B3M: exploratory bf16-split mode (block-0 MLPs)
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -703,7 +768,7 @@ __global__ __launch_bounds__(256, 2) void traj_chain_kernel(ChainArgs A) {
 
     C32_TRACE_BEGIN();
     if (FUSE == 2 && (int)blockIdx.x < A.R32.nwg) {   // (uniform) a throughput-form role workgroup: 128 agents of the roles' call
-        role32_body(*(KRole32Args*)((const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(ChainArgs, R32)),
+        role32_body<ZS>(*(KRole32Args*)((const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(ChainArgs, R32)),
                     blockIdx.x, smem);
         C32_TRACE_END(1);
         return;
@@ -839,7 +904,7 @@ __global__ __launch_bounds__(256, 2) void traj_chain_kernel(ChainArgs A) {
 #pragma unroll
             for (int j = 0; j < 3; ++j) hs[j] = splat16(0.f);
             if (B3M) gru32_steps_b3(st, cst + CO::gb, cst + CO::cb, d, hs, A.Tp, h);
-            else gru32_steps(st, cst + CO::gb, cst + CO::cb, d, hs, A.Tp, h);
+            else gru32_steps<ZS>(st, cst + CO::gb, cst + CO::cb, d, hs, A.Tp, h);
         }
         STT_FENCE();
         C32_STAMP(3);
@@ -941,6 +1006,7 @@ struct Gru32Args {
     float* state;                                 // [ncols][96]
     int ncols, Tp;
 };
+template <bool ZS>
 __global__ __launch_bounds__(256, 2) void gru32_kernel(Gru32Args A) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     f32x4* ring = reinterpret_cast<f32x4*>(smem);
@@ -971,7 +1037,7 @@ __global__ __launch_bounds__(256, 2) void gru32_kernel(Gru32Args A) {
     f32x16 hs[3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) hs[j] = splat16(0.f);
-    gru32_steps(st, cst, cst + 384, d, hs, A.Tp, h);
+    gru32_steps<ZS>(st, cst, cst + 384, d, hs, A.Tp, h);
     if (col < A.ncols) {
 #pragma unroll
         for (int j = 0; j < 3; ++j)
@@ -996,6 +1062,11 @@ static int chain_cus() {
     }
     return n;
 }
+// STTODE_GRU_ZERO_SKIP=0: the GRUs of the chain, the throughput-form roles and gru32_kernel run gru32_steps<false> (A/B and tests only)
+static int gru_zero_skip() {
+    static const int v = getenv("STTODE_GRU_ZERO_SKIP") ? atoi(getenv("STTODE_GRU_ZERO_SKIP")) != 0 : 1;
+    return v;
+}
 static int chain_lds(int NY, int prog_len, bool b3 = false) { return ((b3 ? 2 * C32_BUF_B3 : C32_RING) + 8 * C32_SLOT) * 16 + (1216 + 64 * NY) * 4 + prog_len * 8 + 16; }
 
 static int role_lds(int Tp) {   // agent_role's phases: embed (Tp*256 + 512 f32x4), GRU (h tiles 12 KiB + image of hidden tiles 4, 5: 48 KiB)
@@ -1006,7 +1077,8 @@ static int role_lds(int Tp) {   // agent_role's phases: embed (Tp*256 + 512 f32x
 static int role32_lds(int prog_len) { return C32_RING * 16 + R32C::total * 4 + prog_len * 8 + 16; }
 
 template <int NY, int FUSE, bool B3M = false> static int chain_launch(ChainArgs a, int wgs_per_cu, hipStream_t s) {
-    STT_SET_LDS_ONCE((traj_chain_kernel<NY, FUSE, B3M>), 96 * 1024);   // once per (instantiation, device)
+    void (*kern)(ChainArgs) = gru_zero_skip() ? traj_chain_kernel<NY, FUSE, B3M, true> : traj_chain_kernel<NY, FUSE, B3M, false>;
+    STT_SET_LDS_ONCE(kern, 96 * 1024);   // once per (instantiation, device): the switch is read once per process
     const int ngroups = (a.ncols + 127) / 128;
     // STTODE_CHAIN_RESERVE=r leaves r of the chip's 2-per-CU workgroup slots to concurrently running kernels (the per-agent stage
     // of the next call in the pipelined form); the work queue makes the remaining workgroups absorb the groups
@@ -1037,7 +1109,7 @@ template <int NY, int FUSE, bool B3M = false> static int chain_launch(ChainArgs 
     if (wgs == 1 && lds < 84 * 1024) lds = 84 * 1024;
     STT_REQUIRE(lds <= 96 * 1024, "sttode_traj_chain: dynamic LDS beyond the 96 KiB the kernel is registered for");
     if (FUSE == 1) STT_HIP(hipMemsetAsync(a.R.flags, 0, (((size_t)(a.R.split ? 5 : 1) * a.R.ntiles + 1) * 4 + 15) / 16 * 16, s));   // tile flags + time-out word
-    hipLaunchKernelGGL((traj_chain_kernel<NY, FUSE, B3M>), dim3(grid), dim3(256), lds, s, a);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a);
     STT_HIP(hipGetLastError());
     return 0;
 }
@@ -1053,7 +1125,7 @@ extern "C" int sttode_gru_cols32(const float* xin, int ldx, const float* pool, c
     a.xin = xin; a.ldx = ldx; a.pool = (const f32x4*)pool; a.prog = (const int2*)prog; a.prog_len = prog_len; a.consts = consts;
     a.state = state; a.ncols = ncols; a.Tp = Tp;
     const int lds = C32_RING * 16 + 416 * 4 + prog_len * 8 + 16;
-    hipLaunchKernelGGL(gru32_kernel, dim3((ncols + 127) / 128), dim3(256), lds, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(gru_zero_skip() ? gru32_kernel<true> : gru32_kernel<false>, dim3((ncols + 127) / 128), dim3(256), lds, (hipStream_t)stream, a);
     STT_HIP(hipGetLastError());
     return 0;
 }

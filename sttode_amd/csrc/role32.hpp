@@ -168,6 +168,7 @@ __device__ __forceinline__ void frontend32(KRole32Args& R, int wg) {
 }
 
 // The whole per-agent stage of 128 agents: workgroup `wg` of R.nwg, 4 waves x 32 columns.  smem: ring (24 KiB) | consts | program.
+template <bool ZS>
 __device__ __forceinline__ void role32_body(KRole32Args& R, int wg, char* smem) {
     f32x4* ring = reinterpret_cast<f32x4*>(smem);
     float* cst = reinterpret_cast<float*>(ring + C32_RING);
@@ -211,7 +212,7 @@ __device__ __forceinline__ void role32_body(KRole32Args& R, int wg, char* smem) 
     f32x16 hs[3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) hs[j] = splat16(0.f);
-    gru32_steps(st, cst + R32C::gb, cst + R32C::cb, d, hs, R.Tp, h);   // block-0 conv + GRU (model/STTODE.py:62-69, x_hat = 0)
+    gru32_steps<ZS>(st, cst + R32C::gb, cst + R32C::cb, d, hs, R.Tp, h);   // block-0 conv + GRU (model/STTODE.py:62-69, x_hat = 0)
     if (live) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) strows(R.state0 + (size_t)col * 96 + 32 * j, hs[j], h);
