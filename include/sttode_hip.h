@@ -24,7 +24,7 @@ extern "C" {
 #endif
 
 /* Version of this header: the library returns it from sttode_abi_version(); a binding compares before its first call (round 1-2: 1). */
-#define STTODE_ABI_VERSION 7
+#define STTODE_ABI_VERSION 8
 int sttode_abi_version(void);
 const char* sttode_last_error(void);
 
@@ -535,7 +535,28 @@ int sttode_set_lagged(SttodeModel* m, int streams /* 0 = off, 2 or 3 (default, o
  *     bit) against metrics_gt [n][Tf][2], scaled by metrics_scale, into ade / fde [n]; valid once sttode_wait(slot) has passed.
  *   nba_groups > 1 (sttode_inference_nba_async only): the call carries that many forward-call batches [G][B][N][Tp][2]; the attention runs
  *     within each batch of B scenes (sttode_inference_nba_groups).
+ *   sampler != NULL (lagged form only; ABI 8): the call's latents come from the stage-2 sampler's Q-net (SttodeSamplerPlan; sampler.py:39-54,
+ *     test_sampler.py:136) instead of the caller: `z` is an OUTPUT buffer [n K][32], filled on the call's pipeline stream from the past
+ *     features its own per-agent roles wrote, before its trajectory groups read it.  Refused (before anything is enqueued) together with
+ *     device_latents, on a call that is not in the lagged form, and for a plan whose widths the Q-net kernel cannot stream.
  * sttode_async_is_lagged(m, n) tells beforehand whether a call of n agents will take the lagged form. */
+/* Stage-2 latent sampler (sampler.py:32-54) as a weight stream: the Q-net  h = linear(pf) 128 -> 64,  two tanh layers 64 -> h1 -> h2
+ * (utils/mlp.py:5-29, qnet_mlp; default 512, 256),  per sample k: b_k = q_b h (and A_k = q_A h when eps is given),  z_k = A_k eps + b_k
+ * (sampler.py:41-51; eps_mode 0: z = b (mean), 1: eps [nz] shared by every agent, 2: eps [n][nz] per agent).  pool / prog: PK32 tiles and
+ * the chunk program of the eps mode (sttode_amd/packing.py sampler_stream: mean mode skips the q_A tiles); biases:
+ * [linear 64 | layer 1 h1 | layer 2 h2 | q_b K nz | q_A K nz].  Streamable: nz == 32, h1 and h2 multiples of 32, h2 <= 256, prog_len <= 4096. */
+typedef struct SttodeSamplerPlan {
+    const float* pool;
+    const int* prog;
+    int prog_len;
+    const float* biases;
+    int K;
+    int nz;
+    int h1;
+    int h2;
+    int eps_mode;
+    const float* eps;
+} SttodeSamplerPlan;
 typedef struct SttodeAsyncOpts {
     int device_latents;
     unsigned long long zkey;
@@ -544,7 +565,11 @@ typedef struct SttodeAsyncOpts {
     float* fde;
     float metrics_scale;
     int nba_groups;
+    const SttodeSamplerPlan* sampler;
 } SttodeAsyncOpts;
+/* The sampler's Q-net as one launch (sampler.py:39-54; the latents test_sampler.py:136 decodes): past features pf [n][128] -> z [n K][nz],
+ * row agent K + k; 128 agents per workgroup, weights streamed through LDS.  Serves every call that has no lagged per-agent stage. */
+int sttode_sampler_qnet(const SttodeSamplerPlan* plan, const float* pf, int n, float* z, void* stream);
 /* Measurement aid: the shader clock at this moment.  out[0] = shader cycles, out[1] = ticks of the constant 100 MHz clock over ~20 us on
  * one lane (device memory, two int64): GHz = out[0] / (10 out[1]). */
 int sttode_clock_probe(long long* out, void* stream);

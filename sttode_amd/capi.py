@@ -11,7 +11,7 @@ _LIB = None
 LIB_PATH = os.environ.get('STTODE_HIP_LIB') or os.path.join(os.path.dirname(os.path.abspath(__file__)), 'lib', 'libsttode_hip.so')
 
 _P, _I, _L, _F, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double
-ABI_VERSION = 7   # == STTODE_ABI_VERSION of include/sttode_hip.h; lib() refuses a library built from another header
+ABI_VERSION = 8   # == STTODE_ABI_VERSION of include/sttode_hip.h; lib() refuses a library built from another header
 
 # name -> argtypes (mirrors include/sttode_hip.h; tests/test_capi_symbols.py checks header == table == .so)
 SIGNATURES = {
@@ -43,6 +43,7 @@ SIGNATURES = {
     'sttode_sampler_latent': [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P],
     'sttode_sampler_loss': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P],
     'sttode_sampler_loss_bwd': [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P],
+    'sttode_sampler_qnet': [_P, _P, _I, _P, _P],
     # training step (csrc/train.hip)
     'sttode_tlinear': [_P, _L, _I, _P, _L, _I, _P, _P, _L, _P, _L, _I, _I, _I, _I, _I, _P],
     'sttode_tlinear_tab': [_P, _L, _P, _L, _P, _P, _L, _I, _P, _L, _I, _I, _I, _I, _P],
@@ -142,7 +143,14 @@ STAGES = ('frontend', 'embed_qkv', 'mhgsa_attn', 'post_attn', 'gru_cols[block0,a
 class AsyncOpts(ctypes.Structure):
     """struct SttodeAsyncOpts of include/sttode_hip.h: everything an asynchronous call needs travels with the call."""
     _fields_ = [('device_latents', ctypes.c_int), ('zkey', ctypes.c_ulonglong), ('metrics_gt', ctypes.c_void_p), ('ade', ctypes.c_void_p),
-                ('fde', ctypes.c_void_p), ('metrics_scale', ctypes.c_float), ('nba_groups', ctypes.c_int)]
+                ('fde', ctypes.c_void_p), ('metrics_scale', ctypes.c_float), ('nba_groups', ctypes.c_int), ('sampler', ctypes.c_void_p)]
+
+
+class SamplerPlan(ctypes.Structure):
+    """struct SttodeSamplerPlan of include/sttode_hip.h: the stage-2 sampler's Q-net as a weight stream (packing.sampler_stream)."""
+    _fields_ = [('pool', ctypes.c_void_p), ('prog', ctypes.c_void_p), ('prog_len', ctypes.c_int), ('biases', ctypes.c_void_p),
+                ('K', ctypes.c_int), ('nz', ctypes.c_int), ('h1', ctypes.c_int), ('h2', ctypes.c_int), ('eps_mode', ctypes.c_int),
+                ('eps', ctypes.c_void_p)]
 
 
 class NativeModel:

@@ -1130,6 +1130,68 @@ extern "C" int sttode_gru_cols32(const float* xin, int ldx, const float* pool, c
     return 0;
 }
 
+// Stage-2 sampler's Q-net (role32.hpp qnet32) as a launch of its own: 128 agents per workgroup, 4 waves x 32 columns, the sampler's stream
+// through a 24-KiB ring like gru32_kernel (<= 256 VGPRs: two workgroups per CU, beside a chain workgroup of another stream).
+__global__ __launch_bounds__(256, 2) void sampler_qnet32_kernel(QNet32Args Q) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    f32x4* ring = reinterpret_cast<f32x4*>(smem);
+    int2* lprog = reinterpret_cast<int2*>(ring + C32_RING);
+    const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (int i = threadIdx.x; i < Q.prog_len; i += blockDim.x) lprog[i] = Q.prog[i];
+    __syncthreads();
+    ChainStream st;
+    st.init(Q.pool, lprog, Q.prog_len, ring);
+    const int col = blockIdx.x * 128 + wave * 32 + c;
+    const bool live = col < Q.n;
+    const int colc = live ? col : Q.n - 1;
+    f32x16 P[4];
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) P[kt] = ldrows(Q.pf + (size_t)colc * 128 + 32 * kt, h);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();                                            // chunk 0 has landed
+    TileFeed<ChainStream> fd(st);
+    fd.open();
+    qnet32(fd, Q, P, col, colc, live, h);
+    fd.close();
+}
+
+// Tiles one workgroup consumes (the program must hold exactly these): linear 8, per layer-1 tile 2 + h2/32, per sample h2/32 (x 2 with eps)
+static long sampler_tiles(const SttodeSamplerPlan* p) {
+    const long h1t = p->h1 / 32, h2t = p->h2 / 32;
+    return 8 + h1t * (2 + h2t) + (long)p->K * h2t * (p->eps_mode ? 2 : 1);
+}
+const char* stt_sampler_plan_check(const SttodeSamplerPlan* p, int K) {
+    if (!p || !p->pool || !p->prog || !p->biases) return "sampler plan: null pool / program / biases";
+    if (p->nz != 32) return "sampler plan: nz must be 32 (one MFMA tile of rows per sample)";
+    if (p->K <= 0 || (K > 0 && p->K != K)) return "sampler plan: K must be positive and equal the model's sample_k";
+    if (p->h1 <= 0 || p->h1 % 32 || p->h2 <= 0 || p->h2 % 32 || p->h2 > 256) return "sampler plan: hidden widths must be multiples of 32, h2 <= 256";
+    if (p->eps_mode < 0 || p->eps_mode > 2 || (p->eps_mode != 0 && !p->eps)) return "sampler plan: eps_mode 0 (mean) | 1 (shared [nz]) | 2 (per agent [n][nz]); eps required unless 0";
+    if (p->prog_len <= 0 || p->prog_len > 4096) return "sampler plan: prog_len must be in [1, 4096]";
+    if (3L * p->prog_len < sampler_tiles(p)) return "sampler plan: chunk program too short for the widths (<= 3 tiles per chunk)";
+    return nullptr;
+}
+int stt_sampler_qnet(const SttodeSamplerPlan* p, const float* pf, int n, float* z, void* stream) {
+    QNet32Args q;
+    q.pool = (const f32x4*)p->pool; q.prog = (const int2*)p->prog; q.prog_len = p->prog_len; q.bias = p->biases;
+    q.pf = pf; q.z = z; q.eps = p->eps; q.n = n; q.K = p->K; q.h1t = p->h1 / 32; q.h2t = p->h2 / 32; q.eps_mode = p->eps_mode;
+    const int lds = C32_RING * 16 + p->prog_len * 8 + 16;
+    hipLaunchKernelGGL(sampler_qnet32_kernel, dim3((n + 127) / 128), dim3(256), lds, (hipStream_t)stream, q);
+    STT_HIP(hipGetLastError());
+    return 0;
+}
+extern "C" int sttode_sampler_qnet(const SttodeSamplerPlan* plan, const float* pf, int n, float* z, void* stream) {
+    STT_REQUIRE(plan && pf && z, "sttode_sampler_qnet: null pointer");
+    STT_REQUIRE(n > 0 && (long)n * plan->K <= 0x7fffffffL / 32, "sttode_sampler_qnet: n must be positive (and n K 32 within int range)");
+    if (const char* why = stt_sampler_plan_check(plan, 0)) {
+        char b[256];
+        snprintf(b, sizeof(b), "sttode_sampler_qnet: %s", why);
+        stt_set_error(b);
+        return 1;
+    }
+    return stt_sampler_qnet(plan, pf, n, z, stream);
+}
+
 #if defined(C32_DIAG_STAMPS) || defined(C32_DIAG_TRACE)
 static long long* g_chain_dbg = nullptr;
 static int g_trace_tag = 0;

@@ -763,6 +763,10 @@ static int run_lagged(SttodeModel* m, const float* past, const int* scene_ptr, i
         g->valid = false;
         STT_HIP(hipEventRecord(m->evB_done[gs], sf));
     }
+    // stage-2 sampler: the Q-net turns the past features this launch's roles wrote into the call's latents, in stream order between this
+    // launch and the later one (or lag_flush) that carries the call's trajectory groups
+    if (o.sampler)
+        if (int rc = stt_sampler_qnet(o.sampler, ws + off[STT_B_PF], n, const_cast<float*>(z), sf)) return rc;
     LagPending& p = m->lag[slot];
     p.valid = true; p.ws = ws; p.n = n; p.z = z; p.pred = pred; p.s = sf; p.si = si;
     p.one_launch = fe_role;
@@ -785,6 +789,16 @@ static int run_async(SttodeModel* m, const float* past, const int* scene_ptr, in
     if (o.device_latents || o.metrics_gt) {
         STT_REQUIRE(use_lagged(m, n), "sttode_inference_*_async: device latents / fused metrics need the lagged form (sttode_async_is_lagged)");
         STT_REQUIRE(!o.metrics_gt || (o.ade && o.fde), "sttode_inference_*_async: fused metrics need the ade / fde outputs");
+    }
+    if (o.sampler) {
+        STT_REQUIRE(!o.device_latents, "sttode_inference_*_async: a sampler plan and device_latents both ask to fill z: pass one of them");
+        STT_REQUIRE(use_lagged(m, n), "sttode_inference_*_async: a sampler plan needs the lagged form (sttode_async_is_lagged)");
+        if (const char* why = stt_sampler_plan_check(o.sampler, m->K)) {
+            char b[256];
+            snprintf(b, sizeof(b), "sttode_inference_*_async: %s", why);
+            stt_set_error(b);
+            return 1;
+        }
     }
     arm_timing(m);
     long off[STT_B_COUNT], tot;

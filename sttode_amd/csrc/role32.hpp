@@ -299,3 +299,75 @@ __device__ __forceinline__ void role32_body(KRole32Args& R, int wg, char* smem) 
     table32<4>(fd, cst + R32C::b11, R.A1y, B7, col, live, h);
     fd.close();
 }
+
+// ---- Stage-2 sampler: the Q-net phase (sampler.py:39-54) ----------------------------------------------------------------------------------
+// From the past features pf of this wave's 32 agents (B operand, 4 k-tiles) to their latents z [agent K + k][32]:
+//     h0 = linear(pf) 128 -> 64  ->  tanh layer 64 -> h1  ->  tanh layer h1 -> h2  (utils/mlp.py:26-29)
+//     ->  per sample k:  b_k = q_b[k] h2 + bias,  A_k likewise (eps_mode != 0),  z_k = A_k eps + b_k  (sampler.py:41-51)
+// Weights arrive as PK32 tiles of the sampler's OWN stream (packing.sampler_stream) in exactly this order: linear (row tile j, k-tiles
+// 0..3); per 32-row tile ht of layer 1: its two k-tiles, then layer 2's tiles (row tile j2, k-tile ht) for j2 < h2/32 -- the wide layer
+// runs in 32-row tiles like the FFN 64 -> 1024 -> 64, its output accumulates in h2 (<= 8 tiles: h2 <= 256); per sample k: q_b (row tile k,
+// k-tiles 0..) then, in the eps program, q_A likewise.  nz == 32: one 32-row output tile IS one sample's latent row of the chain's z.
+// Biases from global memory: [linear 64 | layer 1 h1 | layer 2 h2 | q_b K 32 | q_A K 32].
+struct QNet32Args {
+    const f32x4* pool; const int2* prog; int prog_len; const float* bias;
+    const float* pf; float* z; const float* eps;
+    int n, K, h1t, h2t, eps_mode;   // h1t / h2t: 32-row tiles of the hidden layers (h2t <= 8)
+};
+
+__device__ __forceinline__ f32x16 tanh16(f32x16 v) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) v[e] = tanhf(v[e]);
+    return v;
+}
+
+template <class FD>
+__device__ __forceinline__ void qnet32(FD& fd, const QNet32Args& Q, const f32x16 (&P)[4], int col, int colc, bool live, int h) {
+    const float* bl = Q.bias;
+    const float* b1 = bl + 64;
+    const float* b2 = b1 + 32 * Q.h1t;
+    const float* bb = b2 + 32 * Q.h2t;
+    const float* bA = bb + 32 * Q.K;
+    f32x16 H0[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        H0[j] = ldrows(bl + 32 * j, h);
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt) fd.mma(H0[j], P[kt]);
+    }
+    f32x16 H2[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) H2[j] = splat16(0.f);
+#pragma unroll 1
+    for (int ht = 0; ht < Q.h1t; ++ht) {
+        f32x16 hid = ldrows(b1 + 32 * ht, h);
+        fd.mma(hid, H0[0]);
+        fd.mma(hid, H0[1]);
+        hid = tanh16(hid);
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (j < Q.h2t) fd.mma(H2[j], hid);   // (uniform)
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+        if (j < Q.h2t) H2[j] = tanh16(H2[j] + ldrows(b2 + 32 * j, h));
+    f32x16 E = splat16(0.f);
+    if (Q.eps_mode == 1) E = ldrows(Q.eps, h);
+    else if (Q.eps_mode == 2) E = ldrows(Q.eps + (size_t)colc * 32, h);
+#pragma unroll 1
+    for (int k = 0; k < Q.K; ++k) {
+        f32x16 zb = ldrows(bb + 32 * k, h);
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (j < Q.h2t) fd.mma(zb, H2[j]);
+        if (Q.eps_mode != 0) {   // (uniform)
+            f32x16 za = ldrows(bA + 32 * k, h);
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (j < Q.h2t) fd.mma(za, H2[j]);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) zb[r] = fmaf(za[r], E[r], zb[r]);
+        }
+        if (live) strows(Q.z + ((size_t)col * Q.K + k) * 32, zb, h);
+    }
+}

@@ -56,6 +56,50 @@ def eval_scenes(model, dataset, traj_scale=1.0, scenes_per_call=512, z_fn=None, 
 
 
 @torch.no_grad()
+def eval_sampler(model, sampler, dataset, traj_scale=1.0, scenes_per_call=512, mean=True, eps_fn=None, pipelined=True):
+    """Stage-2 evaluation, test_sampler.py:117-212: the latents come from the sampler's Q-net (mean mode by default, as test_sampler.py:136),
+    ADE / FDE best-of-K per agent weighted by agent count.  Returns (ADE, FDE, n_agents).  As eval_scenes: many scenes per call
+    (``dataset.scene_batch``), and ``pipelined`` (default) runs the calls through ``sampler.inference_async`` -- several in flight, the metrics
+    computed by the calls' own trajectory groups; ``pipelined=False``: one serial ``sampler.inference`` + ``best_of_k`` per batch.
+    ``mean=False``: sampled latents, eps drawn like sampler.py:41-46 or by ``eps_fn(rows)`` (rows = 1 with share_eps, else the call's agents)."""
+    tot_a = tot_f = 0.0
+    tot_n = 0
+    pend = []
+
+    def finish(h):
+        nonlocal tot_a, tot_f
+        ade, fde = model.best_of_k_async(h, scale=traj_scale)
+        model.wait(h)
+        tot_a += float(ade.double().sum())
+        tot_f += float(fde.double().sum())
+    for s0 in range(0, len(dataset), scenes_per_call):
+        sb = dataset.scene_batch(range(s0, min(s0 + scenes_per_call, len(dataset))))
+        model.set_scene_batch(sb.past, sb.future, sb.scene_ptr)
+        eps = None
+        if not mean and eps_fn is not None:
+            eps = eps_fn(1 if sampler.share_eps else sb.n_agents)
+        tot_n += sb.n_agents
+        if pipelined:
+            if len(model._async_bufs) > 12:                               # batches of ever new sizes: per-shape slot buffers are dropped in time
+                while pend:
+                    finish(pend.pop(0))
+                model.reset_async()
+            pend.append(sampler.inference_async(model, mean=mean, eps=eps, metrics_gt=model._future, metrics_scale=traj_scale))
+            if len(pend) > 4:
+                finish(pend.pop(0))
+            continue
+        pred = sampler.inference(model, mean=mean, eps=eps)                 # [K, n, Tf, 2]
+        ade, fde = model.best_of_k(pred.permute(1, 0, 2, 3), scale=traj_scale)
+        tot_a += float(ade.double().sum())
+        tot_f += float(fde.double().sum())
+    while pend:
+        finish(pend.pop(0))
+    if pipelined:
+        model.reset_async()
+    return tot_a / tot_n, tot_f / tot_n, tot_n
+
+
+@torch.no_grad()
 def eval_nba(model, loader, traj_scale=1.0, z_fn=None, pipelined=True, groups_per_call=16):
     """loader yields seq_collate dicts (data/dataloader_nba.py:7-18).  Returns {h: (avg_h, dest_h)} for h = 1..Tf, each the
     batch-size-weighted mean over batches of mean_n min_k (test.py:530-551).

@@ -816,7 +816,7 @@ class STTODENet(nn.Module):
         return pred.permute(1, 0, 2, 3)
 
     @torch.no_grad()
-    def inference_async(self, z=None, metrics_gt=None, metrics_scale=1.0, pred_host=False):
+    def inference_async(self, z=None, metrics_gt=None, metrics_scale=1.0, pred_host=False, sampler_plan=None):
         """Pipelined inference (build-defined): enqueue this batch and return a handle immediately.  ``async_depth`` (default 6, at most 8)
         workspace / prediction slots rotate, so at most that many calls may be in flight: call ``wait(handle)`` (which returns the
         [K, n, Tf, 2] view) before the ``async_depth``-th next call.  Inputs set by set_data / set_scene_batch / set_data_nba must stay
@@ -830,11 +830,15 @@ class STTODENet(nn.Module):
         without launching a kernel (the values of best_of_k on the same predictions, bit for bit).
         ``pred_host=True`` (lagged form only; raises otherwise): the call's futures are written by the launch STRAIGHT to pinned host
         memory (``handle['pred']`` is then a pinned CPU tensor [n, K, Tf, 2]; ``wait_host(handle)`` makes the host wait for it) -- what
-        test.py:186-188 does with a .cpu() per call, without a D2H copy."""
+        test.py:186-188 does with a .cpu() per call, without a D2H copy.
+        ``sampler_plan`` (a ``capi.SamplerPlan``; what ``Sampler.inference_async`` passes): the call's latents come from the stage-2 sampler's
+        Q-net, run on the call's pipeline stream from the past features of its own launch (lagged form only; ``z`` must be None)."""
         self._require_gpu()
         a = self.args
         if self._mode is None:
             raise capi.SttodeError('call set_data / set_data_nba / set_scene_batch before inference_async()')
+        if sampler_plan is not None and (self._generic or z is not None):
+            raise capi.SttodeError('inference_async: a sampler plan fills z itself and needs the lagged form of the reference widths')
         if self._generic:
             # widths outside the fused forms have no pipelined form: the call runs serially on the caller's stream; the handle keeps the
             # callers of the pipelined API (evaluate.eval_scenes / eval_nba) working unchanged
@@ -860,6 +864,8 @@ class STTODENet(nn.Module):
             raise ValueError(f'metrics_gt must be a contiguous float32 device tensor [{n}, {a.future_length}, 2]')
         if pred_host and not lagged:
             raise capi.SttodeError('pred_host=True needs the lagged pipelined form (a chain-sized batch, reference integrator)')
+        if sampler_plan is not None and not lagged:
+            raise capi.SttodeError('inference_async: a sampler plan needs the lagged pipelined form (a chain-sized batch, reference integrator)')
         slot = self._async_calls % max(2, min(8, int(self.async_depth)))
         key = (n, S, slot)
         if key not in self._async_bufs:
@@ -872,7 +878,11 @@ class STTODENet(nn.Module):
                                      torch.empty(n * K, a.zdim, dtype=torch.float32, device=self.device))
         self._async_calls += 1
         opts = capi.AsyncOpts()
-        if z is None:
+        if sampler_plan is not None:
+            import ctypes
+            opts.sampler = ctypes.addressof(sampler_plan)        # the Q-net writes the slot's latent buffer behind the call's launch
+            z = self._async_bufs[key][2]
+        elif z is None:
             # Latents like Normal.rsample (model/STTODE.py:89-93,609-616).  Lagged form: the call's own launch draws them (Philox4x32-10 on
             # device, csrc/role32.hpp) into the slot's latent buffer, keyed by 64 bits taken from torch's generator here -- reproducible
             # under torch.manual_seed, not the sequence torch.randn would give (device_latents = False: torch.randn on the caller's stream).

@@ -512,3 +512,51 @@ def pack_posterior(sd):
     g = lambda k: np.asarray(sd['future_encoder.' + k], np.float32)
     return {'outP': pk16(g('out_mlp.affine_layers.0.weight')), 'outb': g('out_mlp.affine_layers.0.bias'),
             'qzP': pk16(g('qz_layer.weight')), 'qzb': g('qz_layer.bias')}
+
+
+def _runs_to_chunks(tiles):
+    """Pool tile indices in consumption order -> chunk program [(first tile, tiles <= 3)]: runs of consecutive indices cut into chunks of <= 3."""
+    prog = []
+    for t in tiles:
+        if prog and prog[-1][1] < 3 and prog[-1][0] + prog[-1][1] == t:
+            prog[-1][1] += 1
+        else:
+            prog.append([t, 1])
+    return [tuple(e) for e in prog]
+
+
+def sampler_stream(sd):
+    """Weight stream of the stage-2 sampler's Q-net (sampler.py:39-54; csrc/role32.hpp qnet32, include/sttode_hip.h SttodeSamplerPlan) from
+    the Sampler's state_dict (``linear``, ``q_mlp.affine_layers.{0,1}``, ``q_A``, ``q_b``; ``q_c`` feeds only the K = 1 decode the fused
+    form does not produce).  PK32 tiles in the order one workgroup consumes them:
+      linear 128 -> 64: row tile j (2) x k-tile (4);  per 32-row tile ht of layer 1 (h1 / 32): its two k-tiles, then layer 2's tiles
+      (row tile j2 < h2 / 32, k-tile ht);  per sample k < K: q_b (row tile k, k-tiles 0 .. h2 / 32), then q_A likewise.
+    Returns pool [tiles, 1024]; prog_eps (every tile) and prog_mean (without the q_A tiles: z = b) int32 [chunks, 2]; biases float32
+    [linear 64 | layer 1 h1 | layer 2 h2 | q_b K nz | q_A K nz]; K, nz, h1, h2.  Widths the kernel streams: nz 32, h1 / h2 multiples of 32,
+    h2 <= 256 (sampler.unsupported_reason lists the rest)."""
+    f = lambda k: np.asarray(sd[k], np.float32)
+    Wl, W1, W2, Wb, WA = (f(k + '.weight') for k in ('linear', 'q_mlp.affine_layers.0', 'q_mlp.affine_layers.1', 'q_b', 'q_A'))
+    h1, h2 = W1.shape[0], W2.shape[0]
+    nz = 32
+    K = Wb.shape[0] // nz
+    assert Wl.shape == (64, 128) and W1.shape[1] == 64 and W2.shape[1] == h1 and Wb.shape == WA.shape == (K * nz, h2)
+    assert h1 % 32 == 0 and h2 % 32 == 0 and h2 <= 256
+    h1t, h2t = h1 // 32, h2 // 32
+    PL, P1, P2, PB, PA = pk32_tiles(Wl), pk32_tiles(W1), pk32_tiles(W2), pk32_tiles(Wb), pk32_tiles(WA)
+    tiles = [PL[j, kt] for j in range(2) for kt in range(4)]
+    for ht in range(h1t):
+        tiles += [P1[ht, 0], P1[ht, 1]] + [P2[j, ht] for j in range(h2t)]
+    head = len(tiles)
+    b_idx, a_idx = [], []
+    for k in range(K):
+        b_idx.append(list(range(len(tiles), len(tiles) + h2t)))
+        tiles += [PB[k, j] for j in range(h2t)]
+        a_idx.append(list(range(len(tiles), len(tiles) + h2t)))
+        tiles += [PA[k, j] for j in range(h2t)]
+    order_eps = list(range(len(tiles)))
+    order_mean = list(range(head)) + [t for k in range(K) for t in b_idx[k]]
+    biases = np.concatenate([f('linear.bias'), f('q_mlp.affine_layers.0.bias'), f('q_mlp.affine_layers.1.bias'), f('q_b.bias'), f('q_A.bias')])
+    return {'pool': np.ascontiguousarray(np.stack(tiles).astype(np.float32)),
+            'prog_eps': np.ascontiguousarray(np.asarray(_runs_to_chunks(order_eps), np.int32)),
+            'prog_mean': np.ascontiguousarray(np.asarray(_runs_to_chunks(order_mean), np.int32)),
+            'biases': np.ascontiguousarray(biases.astype(np.float32)), 'K': K, 'nz': nz, 'h1': h1, 'h2': h2}

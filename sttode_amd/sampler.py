@@ -5,10 +5,13 @@ Same constructor (``args``: sample_k, nz, share_eps, train_w_mean, qnet_mlp, dat
 ``sttode_amd.STTODENet`` that has data set.  The Q-net runs on ``sttode_linear_cols`` (MFMA column chain, tanh epilogue),
 the latent codes on ``sttode_sampler_latent``, both decodes on the model's HIP decoder.  No autograd graph (training the
 sampler is SURVEY.md §8f rank 1 territory: backward kernels)."""
+import ctypes
+
+import numpy as np
 import torch
 import torch.nn as nn
 
-from . import capi
+from . import capi, packing
 from .dist import Normal
 from .ops import linear_cols
 
@@ -98,6 +101,109 @@ class Sampler(nn.Module):
 
     def step_annealer(self):
         pass
+
+    # ------------------------------------------------------------------ evaluation form (test_sampler.py:117-212)
+    def unsupported_reason(self, net=None, n=None):
+        """Why the Q-net kernel (``sttode_sampler_qnet``) cannot serve this sampler -- or, given ``net`` and the agent count ``n`` of a call,
+        why that call cannot take the pipelined form with the Q-net on the call's own stream (SttodeAsyncOpts.sampler) -- or None.
+        The one list of refusals; ``inference`` / ``inference_async`` fall back to the next form down instead of raising."""
+        if self.nz != 32:
+            return f'nz = {self.nz}: the Q-net kernel writes one 32-row MFMA tile per sample (nz 32)'
+        if len(self.qnet_mlp) != 2:
+            return f'qnet_mlp {list(self.qnet_mlp)}: the Q-net kernel streams exactly two hidden layers'
+        if any(h % 32 for h in self.qnet_mlp) or self.qnet_mlp[1] > 256:
+            return f'qnet_mlp {list(self.qnet_mlp)}: hidden widths must be multiples of 32 and the second <= 256 (held in registers)'
+        if net is None:
+            return None
+        if getattr(net, '_generic', False):
+            return 'the model runs the generic form (non-reference widths): no lagged per-agent stage'
+        if self.nk != net.args.sample_k:
+            return f'sample_k {self.nk} of the sampler != {net.args.sample_k} of the model'
+        if (net.ode_method, net.ode_steps) != ('euler', 1):
+            return 'non-default integrator: the lagged form runs the reference Euler step only'
+        if n is not None and not capi.lib().sttode_async_is_lagged(net.native().h, int(n)):
+            return f'a call of {n} agents does not take the lagged form (below the chain threshold, or set_lagged(0))'
+        return None
+
+    def _weights_key(self):
+        ps = list(self.parameters())
+        return (self.device.index, tuple(p.data_ptr() for p in ps), tuple(p._version for p in ps))
+
+    def packed(self):
+        """Device copies of packing.sampler_stream, re-packed whenever a parameter changed (an optimizer step between two calls)."""
+        key = self._weights_key()
+        if getattr(self, '_packed_key', None) != key:
+            sd = {k: v.detach().cpu().numpy() for k, v in self.state_dict().items()}
+            host = packing.sampler_stream(sd)
+            self._packed = {k: (torch.from_numpy(v).to(self.device) if isinstance(v, np.ndarray) else v) for k, v in host.items()}
+            self._packed_key = key
+        return self._packed
+
+    def _plan(self, mode, eps):
+        """(SttodeSamplerPlan, the device tensors it points into) for eps mode 0 / 1 / 2."""
+        P = self.packed()
+        prog = P['prog_eps'] if mode else P['prog_mean']
+        plan = capi.SamplerPlan(pool=P['pool'].data_ptr(), prog=prog.data_ptr(), prog_len=prog.shape[0], biases=P['biases'].data_ptr(),
+                                K=P['K'], nz=P['nz'], h1=P['h1'], h2=P['h2'], eps_mode=mode, eps=eps.data_ptr() if mode else None)
+        return plan, (P['pool'], prog, P['biases']) + ((eps,) if mode else ())
+
+    def _latents(self, net, mode, eps):
+        """z [n K, nz] of sampler.py:39-51 from net's encoder: the Q-net kernel, or (widths it does not stream) the linear_cols composition."""
+        net.encode_history()
+        pf = net.past_feature.contiguous()
+        n = pf.shape[0]
+        st = capi.stream_ptr()
+        if self.unsupported_reason() is None and pf.shape[1] == 128:
+            z = torch.empty(n * self.nk, self.nz, device=self.device)
+            plan, _ = self._plan(mode, eps)
+            capi.call('sttode_sampler_qnet', ctypes.addressof(plan), pf, n, z, st)
+            return z
+        h = linear_cols(pf, self.linear.weight, self.linear.bias)
+        for lin in self.q_mlp.affine_layers:
+            h = linear_cols(h, lin.weight, lin.bias, act='tanh')
+        A = linear_cols(h, self.q_A.weight, self.q_A.bias)
+        b = linear_cols(h, self.q_b.weight, self.q_b.bias)
+        z = torch.empty(n * self.nk, self.nz, device=self.device)
+        logvar = torch.empty_like(z)
+        capi.call('sttode_sampler_latent', A, b, eps, mode, z, logvar, n, self.nk, self.nz, st)
+        return z
+
+    @torch.no_grad()
+    def inference(self, net, mean=True, eps=None):
+        """The sampler's latents decoded by the model (test_sampler.py:134-138): [K, n, Tf, 2] in world coordinates -- the values of
+        ``forward(net, mean, eps=eps)[0].permute(1, 0, 2, 3)`` (the K = 1 ``q_c`` decode, whose result test_sampler.py discards, is not
+        made).  ``eps`` ([1, nz] shared or [n, nz] per agent) may be injected; otherwise drawn like sampler.py:41-46.  One serial call:
+        encoder, Q-net kernel, then ``net.inference(z=z)``."""
+        if self.device.type != 'cuda':
+            raise capi.SttodeError('Sampler runs only on a HIP device (no CPU fallback): call set_device(cuda) first')
+        mode, eps = self._draw_eps(net._past.shape[0], mean, eps)
+        z = self._latents(net, mode, eps)
+        return net.inference(None, z=z)
+
+    @torch.no_grad()
+    def inference_async(self, net, mean=True, eps=None, metrics_gt=None, metrics_scale=1.0):
+        """``inference`` as a call of the model's pipeline: returns a handle for ``net.wait`` / ``net.best_of_k_async`` /
+        ``net.horizon_metrics_async`` (``metrics_gt``: fused best-of-K metrics, as ``net.inference_async``).  In the lagged form the Q-net
+        runs on the call's own pipeline stream from the past features its launch computes (include/sttode_hip.h SttodeAsyncOpts.sampler):
+        no encoder launches on the caller's stream.  Calls that form cannot serve (``unsupported_reason``): encoder + Q-net on the caller's
+        stream, then ``net.inference_async(z=z)``."""
+        if self.device.type != 'cuda':
+            raise capi.SttodeError('Sampler runs only on a HIP device (no CPU fallback): call set_device(cuda) first')
+        if net._mode is None:
+            raise capi.SttodeError('call set_data / set_data_nba / set_scene_batch before inference_async()')
+        n = net._past.shape[0]
+        mode, eps = self._draw_eps(n, mean, eps)
+        if self.unsupported_reason(net, n) is None:
+            plan, keep = self._plan(mode, eps)
+            h = net.inference_async(metrics_gt=metrics_gt, metrics_scale=metrics_scale, sampler_plan=plan)
+            st = h.get('stream')
+            if st is not None:
+                for t in keep:                   # read by the Q-net on the pipeline stream: not reused by the allocator before it has run
+                    t.record_stream(st)
+            h['sampler'] = (plan, keep)
+            return h
+        z = self._latents(net, mode, eps)
+        return net.inference_async(z=z, metrics_gt=metrics_gt, metrics_scale=metrics_scale)
 
 
 class _SamplerFn(torch.autograd.Function):
