@@ -24,7 +24,7 @@ extern "C" {
 #endif
 
 /* Version of this header: the library returns it from sttode_abi_version(); a binding compares before its first call (round 1-2: 1). */
-#define STTODE_ABI_VERSION 8
+#define STTODE_ABI_VERSION 9
 int sttode_abi_version(void);
 const char* sttode_last_error(void);
 
@@ -318,6 +318,69 @@ enum SttodeTrunkPtr {
 /* phase 0: the whole trunk (attention length 1).  Attention over the forward-call batch (the NBA branch): phase 1 = up to the in-projection
  * (writes qkv, xc, feat[:, :64]), then sttode_mhgsa_attn(_groups) as its own launch, then phase 2 = from ptrs[STT_TT_ATTN] on. */
 int sttode_ttrunk_fwd(const void* const* ptrs, int count, int n, int T, long ld_feat, float ode_time, int phase, void* stream);
+/* Training through a non-default encoder integrator (ABI 9; csrc/train_ode.hip): the linear stage combinations of the fixed-grid program
+ * (Euler, 3/8-rule 'rk4', classical RK4 on a uniform grid, oracle.sttode_ref.ode_integrate_ref) and of its discrete adjoint.  A job writes
+ * out[r, c] = sum_t c[t] v[t][r ld[t] + c] over rows x width (masked to 0 where mask[r ld_mask + c] <= 0 when mask != NULL) and, when
+ * relu_out != NULL, also relu_out[r ld_relu + c] = max(out, 0).  jobs = HOST array of `count` <= STT_ODE_MAX_JOBS records.  One launch. */
+#define STT_ODE_MAX_TERMS 6
+#define STT_ODE_MAX_JOBS 4
+typedef struct SttodeOdeCombine {
+    const float* v[STT_ODE_MAX_TERMS];
+    long ld[STT_ODE_MAX_TERMS];
+    float c[STT_ODE_MAX_TERMS];
+    float* out;
+    long ld_out;
+    float* relu_out;
+    long ld_relu;
+    const float* mask;
+    long ld_mask;
+    int nterms;
+    int rows;
+} SttodeOdeCombine;
+int sttode_ode_combine(const void* jobs, int count, int width, void* stream);
+/* The fixed-grid program's coefficients (sttode_amd/odestages.py TABLEAU): stage i reads y + h sum_j a[4 i + j] k_j, the step is
+ * y + h sum_i b[i] k_i; stages 1 (Euler) or 4. */
+typedef struct SttodeOdeProgram {
+    int stages;
+    int steps;
+    float h;
+    float a[16];
+    float b[4];
+} SttodeOdeProgram;
+/* Integration forward of `trunks` <= 2 encoder trunks in ONE launch, attention length 1, T <= 12 (as sttode_ttrunk_fwd): each trunk's
+ * layers up to ftraj_input exactly as sttode_ttrunk_fwd phase 1 (ptrs: trunks x STT_TT_COUNT pointers, as there), then the whole stage
+ * program of `prog` (HOST) inside the kernel.  Writes the stage inputs ys[t] [steps * stages * n[t], 64] (stage j's rows at j n[t]),
+ * y_T into yT[t] [n[t], 64] and relu(y_T) into feat[:, 64:128]. */
+int sttode_ttrunk_ode_fwd(const void* const* ptrs, int count, int trunks, const int* n, const int* T, const long* ld_feat, float* const* ys,
+                          float* const* yT, const void* prog, void* stream);
+/* Per-stage dX chain of the same program's backward (attention length 1), one launch for up to STT_ODE_MAX_JOBS / 2 trunks: per row, f is
+ * recomputed from the stage input y, dk = sum of the `kb` terms (the stage-combination adjoint; kb.out unused), back-propagated through
+ * LN2, linear2^T, the relu mask, linear1^T, LN1, the gate, temporal_info / temporal_gate^T, out_proj^T and in_proj(v)^T into dy; when
+ * next.out != NULL also next.out = dy + sum of the `next` terms (the gradient wrt the step's start state, on its first stage).  Writes
+ * every linear layer's X and dY columns (attn = v, ao, h, f1 [n,1024], dsum2, df1 [n,1024], du, dv, dao, dattn) and the LayerNorm
+ * parameter-gradient rows ln [n,256] = [dk xhat2 | dk | dh xhat1 | dh] for the deferred weight-gradient pass; no cross-row reductions.
+ * w: in_proj_weight, in_proj_bias, out_proj w / b, temporal_info w / b, temporal_gate w / b, norm1 w / b, linear1 w / b, linear2 w / b,
+ * norm2 w / b (row-major nn.Parameter storage).  jobs = HOST array of `count` records. */
+typedef struct SttodeOdeStageBwd {
+    const float* w[16];
+    const float* y;
+    SttodeOdeCombine kb;
+    float* dy;
+    SttodeOdeCombine next;
+    float* attn;
+    float* ao;
+    float* h;
+    float* f1;
+    float* dsum2;
+    float* df1;
+    float* du;
+    float* dv;
+    float* dao;
+    float* dattn;
+    float* ln;
+    int n;
+} SttodeOdeStageBwd;
+int sttode_ode_stage_bwd(const void* jobs, int count, void* stream);
 
 /* The four terms of forward()'s objective (:372-395,553-568) and all their gradients for ONE decoder pass over K1 = 1 + K samples per
  * agent (sample 0: decoded from the posterior draw, enters the prediction / recover terms; samples 1..K: the prior draws, best-of-K):

@@ -10,6 +10,7 @@
 // exchanged through LDS, and every tensor the backward pass needs is written on the way -- the same tape trunk_bwd reads.
 #include <mutex>
 #include "chain.hpp"
+#include "ode_body.hpp"
 #include "api_util.hpp"
 #include "../../include/sttode_hip.h"
 
@@ -350,6 +351,101 @@ extern "C" int sttode_ttrunk_fwd(const void* const* ptrs, int count, int n, int 
     tq_flush_locked();
     if (g_tq.on) { g_tq.a = a; g_tq.lds = lds; g_tq.stream = stream; g_tq.have = true; return 0; }
     hipLaunchKernelGGL(ttrunk_fwd_kernel, dim3((n + 15) / 16), dim3(256), lds, (hipStream_t)stream, a);
+    STT_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// Non-default encoder integrator (training, attention length 1): a trunk's layers up to ftraj_input (the phase-1 body above), then the
+// whole stage program in the SAME workgroup -- ONE launch for both trunks whatever the step count.  x leaves the body in LDS slot 1; wave w
+// keeps row tile w of the state y and of the stage slopes k_i (the combinations are lane-local), a stage input is exchanged through slot
+// 1 and f runs as ode_body.hpp ode_f.  Tape: the stage inputs alone (the backward pass recomputes f, train_ode.hip).
+struct OdeFwdArgs {
+    TrunkArgs t[2];
+    float* ys[2];
+    float* yT[2];
+    int tiles0;
+    SttodeOdeProgram p;
+};
+
+template <int S>
+__global__ __launch_bounds__(256) void ttrunk_ode_fwd_kernel(OdeFwdArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem_t[];
+    const int which = (int)blockIdx.x < a.tiles0 ? 0 : 1;
+    const int tile = which ? (int)blockIdx.x - a.tiles0 : (int)blockIdx.x;
+    const TrunkArgs& t = which ? a.t[1] : a.t[0];
+    ttrunk_fwd_body(t, tile, smem_t);                      // phase 1: feat[:, :64], xc, h3in, posin, tp (and qkv)
+    f32x4* sX = reinterpret_cast<f32x4*>(smem_t) + (size_t)t.T * 256;
+    const float* const* P = t.p;
+    const int lane = threadIdx.x & 63, q = lane >> 4;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int n = t.n, col = tile * 16 + (lane & 15);
+    const bool live = col < n;
+    const OdeW W = {P[STT_TT_INPROJ_W], P[STT_TT_INPROJ_B], P[STT_TT_OUT_W], P[STT_TT_OUT_B], P[STT_TT_INFO_W], P[STT_TT_INFO_B],
+                    P[STT_TT_GATE_W], P[STT_TT_GATE_B], P[STT_TT_LN1_W], P[STT_TT_LN1_B], P[STT_TT_L1_W], P[STT_TT_L1_B],
+                    P[STT_TT_L2_W], P[STT_TT_L2_B], P[STT_TT_LN2_W], P[STT_TT_LN2_B]};
+    __syncthreads();
+    f32x4 y = sX[(1 * 4 + w) * 64 + lane];                 // row tile w of x = y_0
+    float* ys = which ? a.ys[1] : a.ys[0];
+    const float h = a.p.h;
+#pragma unroll 1
+    for (int step = 0; step < a.p.steps; ++step) {
+        f32x4 kk[S];
+#pragma unroll
+        for (int i = 0; i < S; ++i) {
+            f32x4 Yw = y;
+#pragma unroll
+            for (int j = 0; j < i; ++j) Yw = Yw + (h * a.p.a[4 * i + j]) * kk[j];
+            if (live) st4(ys + ((long)(step * S + i) * n + col) * 64 + 16 * w + 4 * q, Yw);
+            __syncthreads();
+            sX[(1 * 4 + w) * 64 + lane] = Yw;
+            __syncthreads();
+            f32x4 Y[4], k[4];
+#pragma unroll
+            for (int Tk = 0; Tk < 4; ++Tk) Y[Tk] = sX[(1 * 4 + Tk) * 64 + lane];
+            OdeAct A;
+            ode_f(W, Y, sX, w, lane, q, live, nullptr, k, A);
+            kk[i] = ode_pick(k, w);
+        }
+#pragma unroll
+        for (int i = 0; i < S; ++i) y = y + (h * a.p.b[i]) * kk[i];
+    }
+    if (live) {
+        st4((which ? a.yT[1] : a.yT[0]) + (long)col * 64 + 16 * w + 4 * q, y);
+        st4(const_cast<float*>(P[STT_TT_FEAT]) + (long)col * t.ld_feat + 64 + 16 * w + 4 * q, relu4(y));
+    }
+}
+
+extern "C" int sttode_ttrunk_ode_fwd(const void* const* ptrs, int count, int trunks, const int* n, const int* T, const long* ld_feat, float* const* ys,
+                                     float* const* yT, const void* prog, void* stream) {
+    STT_REQUIRE(ptrs && n && T && ld_feat && ys && yT && prog && trunks >= 1 && trunks <= 2 && count == trunks * STT_TT_COUNT,
+                "sttode_ttrunk_ode_fwd: null argument, or trunks not 1..2, or count != trunks * STT_TT_COUNT");
+    OdeFwdArgs a = {};
+    a.p = *static_cast<const SttodeOdeProgram*>(prog);
+    STT_REQUIRE((a.p.stages == 1 || a.p.stages == 4) && a.p.steps >= 1, "sttode_ttrunk_ode_fwd: stages must be 1 or 4, steps positive");
+    size_t lds = 0;
+    int tiles = 0;
+    for (int k = 0; k < trunks; ++k) {
+        STT_REQUIRE(n[k] > 0 && T[k] >= 1 && ld_feat[k] >= 128 && (ld_feat[k] % 4) == 0 && ys[k] && yT[k], "sttode_ttrunk_ode_fwd: bad n / T / ld_feat / tape");
+        const size_t l = ((size_t)T[k] * 256 + 1024) * 16;
+        STT_REQUIRE(l <= 64 * 1024, "sttode_ttrunk_ode_fwd: T too large for the fused form (T <= 12): use the layer-by-layer path");
+        lds = l > lds ? l : lds;
+        TrunkArgs& t = a.t[k];
+        for (int i = 0; i < STT_TT_COUNT; ++i) {
+            t.p[i] = (const float*)ptrs[k * STT_TT_COUNT + i];
+            STT_REQUIRE(t.p[i] || i == STT_TT_DROP || i == STT_TT_LAST || i == STT_TT_ATTN, "sttode_ttrunk_ode_fwd: null pointer in the table");
+        }
+        t.n = n[k]; t.T = T[k]; t.ld_feat = ld_feat[k]; t.ode_time = 0.f; t.phase = 1;
+        a.ys[k] = ys[k]; a.yT[k] = yT[k];
+        if (k == 0) a.tiles0 = (n[k] + 15) / 16;
+        tiles += (n[k] + 15) / 16;
+    }
+    {
+        std::lock_guard<std::mutex> lk(g_tq_mu);
+        tq_flush_locked();                                   // (a fused trunk queued by an open group runs first)
+    }
+    if (a.p.stages == 1) hipLaunchKernelGGL(ttrunk_ode_fwd_kernel<1>, dim3(tiles), dim3(256), lds, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(ttrunk_ode_fwd_kernel<4>, dim3(tiles), dim3(256), lds, (hipStream_t)stream, a);
     STT_HIP(hipGetLastError());
     return 0;
 }

@@ -15,12 +15,27 @@ import os
 
 import torch
 
-from . import capi
+from . import capi, odestages
 from .capi import SttodeError
 
 # backward over the decoder columns that carry a gradient (Engine.decoder_live); STTODE_TRAIN_LIVE=0: over all 21 per agent, as rounds 1-4
 _LIVE_COLUMNS = os.environ.get('STTODE_TRAIN_LIVE', '1') != '0'
 _GATHER_MAX = 32
+
+
+class _OdeCombine(ctypes.Structure):                 # include/sttode_hip.h SttodeOdeCombine (sttode_ode_combine)
+    _fields_ = [('v', ctypes.c_void_p * 6), ('ld', ctypes.c_long * 6), ('c', ctypes.c_float * 6), ('out', ctypes.c_void_p),
+                ('ld_out', ctypes.c_long), ('relu_out', ctypes.c_void_p), ('ld_relu', ctypes.c_long), ('mask', ctypes.c_void_p),
+                ('ld_mask', ctypes.c_long), ('nterms', ctypes.c_int), ('rows', ctypes.c_int)]
+
+
+class _OdeProgram(ctypes.Structure):                 # include/sttode_hip.h SttodeOdeProgram (sttode_ttrunk_ode_fwd)
+    _fields_ = [('stages', ctypes.c_int), ('steps', ctypes.c_int), ('h', ctypes.c_float), ('a', ctypes.c_float * 16), ('b', ctypes.c_float * 4)]
+
+
+class _OdeStageBwd(ctypes.Structure):                # include/sttode_hip.h SttodeOdeStageBwd (sttode_ode_stage_bwd)
+    _fields_ = [('w', ctypes.c_void_p * 16), ('y', ctypes.c_void_p), ('kb', _OdeCombine), ('dy', ctypes.c_void_p), ('next', _OdeCombine)] + \
+               [(k, ctypes.c_void_p) for k in ('attn', 'ao', 'h', 'f1', 'dsum2', 'df1', 'du', 'dv', 'dao', 'dattn', 'ln')] + [('n', ctypes.c_int)]
 
 
 class _GatherItem(ctypes.Structure):                 # csrc/train.hip GatherItem (include/sttode_hip.h sttode_live_rows_gather)
@@ -45,6 +60,15 @@ _PAIRED = os.environ.get('STTODE_TRAIN_PAIRED', '1') != '0'   # decoder_x / deco
 # quantisation, tile start and the 15 MB tape store, not by the matrix pipe.
 _L1SPLIT_MIN_COLS = int(os.environ.get('STTODE_TRAIN_L1SPLIT_MIN', '2048')) if os.environ.get('STTODE_TRAIN_L1SPLIT', '0') != '0' else 1 << 60
 _SCRATCH_BATCH = 32 << 20     # floats (128 MB): split sums of one backward pass at batch sizes (more than 2048 GEMM columns)
+# non-default encoder integrators: cap of the per-stage activation and gradient columns the deferred weight-gradient pass holds at once
+# (the chunk buffers are allocated outside Engine.hold; with STTODE_TRAIN_STREAMS=1 the per-stage temporaries of the layer-by-layer
+# path are held until the step ends, so there the cap bounds the chunk columns but not the stage temporaries)
+_ODE_DW_CAP = int(os.environ.get('STTODE_ODE_DW_CAP_MB', '256')) << 20      # bytes
+
+
+def _ode_chunk_stages(nst, per_stage):
+    """Stages per chunk of the deferred weight-gradient pass: as many as fit under _ODE_DW_CAP (at least one)."""
+    return max(1, min(nst, _ODE_DW_CAP // per_stage))
 
 
 def _ld(t):
@@ -211,6 +235,9 @@ class Engine:
         """Forward of one or several trunks (past and future encoder: the same layers, separate weights, independent of each other).  Scene
         batches with T <= 12: each trunk is ONE launch (csrc/train_trunk.hip), two of them inside a group one launch together.  Otherwise
         (NBA: attention over the batch) layer by layer, layer i of every trunk inside one group -- one launch at scene sizes."""
+        prog = self.ode_program()
+        if prog is not None:                                     # a non-default integrator: the stage program (_ode_trunk_fwd)
+            return self._ode_trunk_fwd(items, *prog)
         P, net = self.P, self.net
         D, HD = self.D, self.HD
         S = []
@@ -238,30 +265,7 @@ class Engine:
             for t, src in tabs:
                 t.update(L=L, Nb=Nb, attn=src['attn'])
             return [t for t, _ in tabs]
-        with self.group():
-            for s in S:
-                s['posin'] = self.new(s['n'] * s['T'], 2 * D)
-                self.lin(s['X0'], P[s['pre'] + 'input_fc.weight'], P[s['pre'] + 'input_fc.bias'], out=s['posin'][:, :D])
-        for s in S:
-            pe = getattr(net, s['pre'][:-1]).pos_encoder.pe
-            capi.call('sttode_rows_copy', s['posin'][:, D:], 2 * D, pe, D, s['n'] * s['T'], D, 1, s['T'], self.st)
-        with self.group():
-            for s in S:
-                s['tp'] = self.lin(s['posin'], P[s['pre'] + 'pos_encoder.fc.weight'], P[s['pre'] + 'pos_encoder.fc.bias'])
-        with self.group():
-            for s in S:
-                if s['drop'] is not None:                        # nn.Dropout(0.1) of PositionalAgentEncoding (model/STTODE.py:140,176)
-                    self.ew(EW_MUL, s['tp'], s['tp'], s['drop'])
-        for s in S:
-            s['h3in'] = self.zeros(s['n'], D + 4)
-            s['h3in'][:, D + 2] = self.hold(s['last'].to(torch.float32))   # add_category: [0, 0, 1] for the last agent (model/STTODE.py:199-210)
-        with self.group():
-            for s in S:
-                self.lin(s['tp'].view(s['n'], s['T'] * D), P[s['pre'] + 'input_fc2.weight'], P[s['pre'] + 'input_fc2.bias'], out=s['h3in'][:, :D])
-        with self.group():
-            for s in S:
-                s['x'] = s['feat'][:, :D]
-                self.lin(s['h3in'][:, :D + 3], P[s['pre'] + 'input_fc3.weight'], P[s['pre'] + 'input_fc3.bias'], out=s['x'])
+        self._trunk_pre_layers(S)
         with self.group():
             for s in S:
                 sa = s['a'] + 'self_attn.temporal_attention_before.'
@@ -319,12 +323,40 @@ class Engine:
             out.append(t)
         return out
 
+    def _trunk_pre_layers(self, S):
+        """Layer by layer up to the ODE block's input (input_fc .. input_fc3, add_category): s['x'] = feat[:, :D] = ftraj_input."""
+        P, net, D = self.P, self.net, self.D
+        with self.group():
+            for s in S:
+                s['posin'] = self.new(s['n'] * s['T'], 2 * D)
+                self.lin(s['X0'], P[s['pre'] + 'input_fc.weight'], P[s['pre'] + 'input_fc.bias'], out=s['posin'][:, :D])
+        for s in S:
+            pe = getattr(net, s['pre'][:-1]).pos_encoder.pe
+            capi.call('sttode_rows_copy', s['posin'][:, D:], 2 * D, pe, D, s['n'] * s['T'], D, 1, s['T'], self.st)
+        with self.group():
+            for s in S:
+                s['tp'] = self.lin(s['posin'], P[s['pre'] + 'pos_encoder.fc.weight'], P[s['pre'] + 'pos_encoder.fc.bias'])
+        with self.group():
+            for s in S:
+                if s['drop'] is not None:                        # nn.Dropout(0.1) of PositionalAgentEncoding (model/STTODE.py:140,176)
+                    self.ew(EW_MUL, s['tp'], s['tp'], s['drop'])
+        for s in S:
+            s['h3in'] = self.zeros(s['n'], D + 4)
+            s['h3in'][:, D + 2] = self.hold(s['last'].to(torch.float32))   # add_category: [0, 0, 1] for the last agent (model/STTODE.py:199-210)
+        with self.group():
+            for s in S:
+                self.lin(s['tp'].view(s['n'], s['T'] * D), P[s['pre'] + 'input_fc2.weight'], P[s['pre'] + 'input_fc2.bias'], out=s['h3in'][:, :D])
+        with self.group():
+            for s in S:
+                s['x'] = s['feat'][:, :D]
+                self.lin(s['h3in'][:, :D + 3], P[s['pre'] + 'input_fc3.weight'], P[s['pre'] + 'input_fc3.bias'], out=s['x'])
+
     def _trunk_launch(self, src, n, T, feat, phase):
         import ctypes
         tbl = (ctypes.c_void_p * len(capi.TRUNK_PTRS))(*[(src[k].data_ptr() if src.get(k) is not None else None) for k in capi.TRUNK_PTRS])
         capi.call('sttode_ttrunk_fwd', tbl, len(capi.TRUNK_PTRS), n, T, feat.stride(0), float(self.net.ODE_TIME), phase, self.st)
 
-    def _trunk_fwd_fused(self, t, X0, last, feat, drop_mask, phase=0):
+    def _trunk_fwd_fused(self, t, X0, last, feat, drop_mask, phase=0, launch=True):
         """The same forward and the same tape in ONE launch (csrc/train_trunk.hip, attention length 1): the step is bound by the number of
         launches, and a trunk is 21 of them layer by layer.  ``phase=1``: only up to the in-projection (attention over the forward-call batch:
         the caller runs the attention and then phase 2 through _trunk_launch); returns (tape, pointer sources) then."""
@@ -349,7 +381,8 @@ class Engine:
             assert v is None or v.is_contiguous() or k == 'feat', k
         if phase == 1:
             src['attn'] = self.new(n, 64)
-        self._trunk_launch(src, n, T, feat, phase)
+        if launch:                                               # (launch=False: the caller launches the table itself, _ode_trunk_fwd)
+            self._trunk_launch(src, n, T, feat, phase)
         t.update(X0=X0, drop=drop_mask, attn=out['qkv'][:, 128:], L=1, Nb=n, **out)
         return (t, src) if phase == 1 else t
 
@@ -372,6 +405,8 @@ class Engine:
         """Backward of one or several trunks (the past and the future encoder: the same layers, separate weights, independent of each
         other) walked through TOGETHER: layer i of every trunk is issued inside one group, i.e. one launch -- a one-scene step is bound by
         the number of launches, and the two trunks are 2 x 10 linear-layer backward launches otherwise."""
+        if items[0][0].get('ode_prog') is not None:
+            return self._ode_trunk_bwd(items)
         P, g, net = self.P, self.grad, self.net
         D, HD = self.D, self.HD
         S = []
@@ -437,7 +472,11 @@ class Engine:
                     # attention length 1 (scene batches): the softmax over one key is 1, the output is v -- dv = dattn, and the gradients of
                     # q and k are exactly zero (their rows of the in-projection's gradient stay the zeros of the flat buffer)
                     self.lin_bwd(s['dattn'], W[2 * D:], t['xc'], gW[2 * D:], gb[2 * D:], out=s['dx'], accumulate=True)
-        # dx is now the gradient wrt ftraj_input
+        self._trunk_bwd_pre(S)                                   # s['dx'] is now the gradient wrt ftraj_input
+
+    def _trunk_bwd_pre(self, S):
+        """Backward of the layers in front of the ODE block (input_fc3 .. input_fc), s['dx'] = gradient wrt ftraj_input."""
+        P, g, D = self.P, self.grad, self.D
         with self.group():
             for s in S:
                 t, pre = s['t'], s['pre']
@@ -460,6 +499,290 @@ class Engine:
         with self.group():
             for s in S:
                 self.wgrad(s['dtf'], s['t']['X0'], g(s['pre'] + 'input_fc.weight'), g(s['pre'] + 'input_fc.bias'))
+
+    # ---------------------------------------------------------------- encoder trunk through a non-default integrator
+    def ode_program(self):
+        """(method, steps) of the model's encoder integrator when it is not the default one Euler step, else None (the default trunk path)."""
+        net = self.net
+        method, steps = getattr(net, 'ode_method', 'euler'), int(getattr(net, 'ode_steps', 1))
+        if (method, steps) == ('euler', 1):
+            return None
+        if getattr(net, '_generic', False) or self.D != 64:
+            raise NotImplementedError('non-default integrators are built for the reference widths (hidden_dim 64, zdim 32, two blocks)')
+        odestages.stages(method)
+        if steps < 1:
+            raise ValueError(f'ode_steps must be positive, got {steps}')
+        return method, steps
+
+    def _ode_comb(self, S, terms, dst, mask=None):
+        """One sttode_ode_combine launch over the trunks: per trunk sum of coef * value[trunk] for (coef, value) in terms.  dst: stage
+        index j (written into the trunk's tape of stage inputs), 'final' (y_T, and relu(y_T) into feat[:, D:2 D]) or None (new buffer)."""
+        D = self.D
+        jobs = (_OdeCombine * len(S))()
+        outs = []
+        for si, s in enumerate(S):
+            n, j = s['n'], jobs[si]
+            if dst is None:
+                out = self.new(n, D)
+            elif dst == 'final':
+                out, relu = s['yT'], s['feat'][:, D:2 * D]
+                j.relu_out, j.ld_relu = relu.data_ptr(), _ld(relu)
+            else:
+                out = s['Ys'][dst * n:(dst + 1) * n]
+            for ti, (c, v) in enumerate(terms):
+                j.v[ti], j.ld[ti], j.c[ti] = v[si].data_ptr(), _ld(v[si]), c
+            if mask is not None:
+                j.mask, j.ld_mask = mask[si].data_ptr(), _ld(mask[si])
+            j.out, j.ld_out, j.nterms, j.rows = out.data_ptr(), _ld(out), len(terms), n
+            outs.append(out)
+        capi.call('sttode_ode_combine', jobs, len(S), D, self.st)
+        return tuple(outs)
+
+    def _ode_f(self, S, Y, keep=None):
+        """k = f(Y) per trunk: the ODE block's TransformerEncoderLayer (in-projection, geodesic attention -- the value rows alone at attention
+        length 1 --, out_proj, tanh * sigmoid gate, add + LN1, FFN, add + LN2).  Layer i of every trunk in one group.  ``keep``: per trunk,
+        buffers for the activations the weight gradients read (qkv, attn, ao, h, f1); returns (k per trunk, activations per trunk)."""
+        P, D, HD, net = self.P, self.D, self.HD, self.net
+        A = [dict(keep[i]) if keep is not None else {} for i in range(len(S))]
+        with self.group():
+            for s, y, a in zip(S, Y, A):
+                W, b = P[s['op'] + 'in_proj_weight'], P[s['op'] + 'in_proj_bias']
+                if s['L'] > 1:
+                    a['qkv'] = self.lin(y, W, b, out=a.get('qkv'))
+                else:
+                    a['attn'] = self.lin(y, W[2 * D:], b[2 * D:], out=a.get('attn'))
+        for s, a in zip(S, A):
+            if s['L'] > 1:
+                qkv, L, Nb, e = a['qkv'], s['L'], s['Nb'], 4
+                a['attn'] = a['attn'] if 'attn' in a else self.new(s['n'], D)
+                gq, go = L * Nb * 3 * D, L * Nb * D
+                capi.call('sttode_mhgsa_attn_groups', qkv.data_ptr() + D * e, qkv.data_ptr(), qkv.data_ptr() + 2 * D * e, a['attn'], getattr(net, '_G', 1),
+                          gq, gq, gq, go, L, L, Nb, Nb * 3 * D, 3 * D, Nb * 3 * D, 3 * D, Nb * 3 * D, 3 * D, Nb * D, D, 1.0, float(HD) ** -0.5, HD, self.st)
+        with self.group():
+            for s, a in zip(S, A):
+                a['ao'] = self.lin(a['attn'], P[s['op'] + 'out_proj.weight'], P[s['op'] + 'out_proj.bias'], out=a.get('ao'))
+        with self.group():
+            for s, a in zip(S, A):
+                a['tt'] = self.lin(a['ao'], P[s['a'] + 'self_attn.temporal_info.weight'], P[s['a'] + 'self_attn.temporal_info.bias'], act='tanh')
+                a['ss'] = self.lin(a['ao'], P[s['a'] + 'self_attn.temporal_gate.weight'], P[s['a'] + 'self_attn.temporal_gate.bias'], act='sigmoid')
+        with self.group():
+            for s, a in zip(S, A):
+                a['gated'] = self.new(s['n'], D)
+                self.ew(EW_MUL, a['gated'], a['tt'], a['ss'])
+        for s, y, a in zip(S, Y, A):
+            n = s['n']
+            a['h'] = a['h'] if 'h' in a else self.new(n, D)
+            a['xh1'], a['rs1'] = self.new(n, D), self.new(n)
+            capi.call('sttode_add_ln_fwd', y, a['gated'], P[s['a'] + 'norm1.weight'], P[s['a'] + 'norm1.bias'], a['h'], a['xh1'], a['rs1'], n, D, self.st)
+        with self.group():
+            for s, a in zip(S, A):
+                a['f1'] = self.lin(a['h'], P[s['a'] + 'linear1.weight'], P[s['a'] + 'linear1.bias'], act='relu', out=a.get('f1'))
+        with self.group():
+            for s, a in zip(S, A):
+                a['f2'] = self.lin(a['f1'], P[s['a'] + 'linear2.weight'], P[s['a'] + 'linear2.bias'])
+        ks = []
+        for s, a in zip(S, A):
+            n = s['n']
+            k, a['xh2'], a['rs2'] = self.new(n, D), self.new(n, D), self.new(n)
+            capi.call('sttode_add_ln_fwd', a['h'], a['f2'], P[s['a'] + 'norm2.weight'], P[s['a'] + 'norm2.bias'], k, a['xh2'], a['rs2'], n, D, self.st)
+            ks.append(k)
+        return tuple(ks), A
+
+    def _ode_vjp(self, S, A, kb, keep):
+        """Gradient wrt the stage input Y of every trunk, given the gradient kb of k = f(Y) and f's activations A: LN2, linear2^T, the relu
+        mask, linear1^T, LN1, the gate, temporal_info / temporal_gate^T, out_proj^T, the attention and in_proj^T.  The LayerNorm parameter
+        gradients accumulate here; every linear layer's output gradient is written into ``keep`` for the deferred weight-gradient pass."""
+        P, g, D = self.P, self.grad, self.D
+        for s, a, d, k in zip(S, A, kb, keep):
+            capi.call('sttode_ln_bwd', d, a['xh2'], a['rs2'], P[s['a'] + 'norm2.weight'], k['dsum2'], g(s['a'] + 'norm2.weight'),
+                      g(s['a'] + 'norm2.bias'), s['n'], D, self.scratch, self.scratch.numel(), self.st)
+        with self.group():
+            for s, a, k in zip(S, A, keep):
+                self.lin_dx(k['dsum2'], P[s['a'] + 'linear2.weight'], mask=a['f1'], out=k['df1'])
+        with self.group():
+            for s, a, k in zip(S, A, keep):
+                a['dh'] = self.lin_dx(k['df1'], P[s['a'] + 'linear1.weight'])
+        with self.group():
+            for s, a, k in zip(S, A, keep):                    # dh = dsum2 (residual branch of LN2(h + f)) + W1^T df1
+                self.ew(EW_AXPY, a['dh'], k['dsum2'], f0=1.0)
+        dY = []
+        for s, a in zip(S, A):
+            d1 = self.new(s['n'], D)
+            capi.call('sttode_ln_bwd', a['dh'], a['xh1'], a['rs1'], P[s['a'] + 'norm1.weight'], d1, g(s['a'] + 'norm1.weight'), g(s['a'] + 'norm1.bias'),
+                      s['n'], D, self.scratch, self.scratch.numel(), self.st)
+            dY.append(d1)                                       # residual branch of LN1(Y + gated); the in-projection's part is added below
+        with self.group():
+            for a, k, d1 in zip(A, keep, dY):
+                self.ew(EW_GATE_BWD, d1, a['tt'], a['ss'], k['du'], k['dv'])
+        with self.group():
+            for s, k in zip(S, keep):
+                self.lin_dx(k['du'], P[s['a'] + 'self_attn.temporal_info.weight'], out=k['dao'])
+        with self.group():
+            for s, k in zip(S, keep):
+                self.lin_dx(k['dv'], P[s['a'] + 'self_attn.temporal_gate.weight'], out=k['dao'], accumulate=True)
+        with self.group():
+            for s, k in zip(S, keep):
+                self.lin_dx(k['dao'], P[s['op'] + 'out_proj.weight'], out=k['dattn'])
+        for s, a, k in zip(S, A, keep):
+            if s['L'] > 1:
+                capi.call('sttode_mhgsa_attn_bwd', a['qkv'], k['dattn'], k['dqkv'], s['L'], s['Nb'], self.HD, self.st)
+        with self.group():
+            for s, k, d1 in zip(S, keep, dY):
+                W = P[s['op'] + 'in_proj_weight']
+                if s['L'] > 1:
+                    self.lin_dx(k['dqkv'], W, out=d1, accumulate=True)
+                else:                                           # attention length 1: the output is v, q and k get no gradient
+                    self.lin_dx(k['dattn'], W[2 * D:], out=d1, accumulate=True)
+        return tuple(dY)
+
+    def _ode_wgrad(self, S, K, c0, c1):
+        """The deferred weight-gradient pass of stages c0 .. c1-1: ONE product per layer over all of their columns (stage j's rows of
+        every buffer at (j - c0) n .. (j - c0 + 1) n; the in-projection reads the stage inputs where the tape keeps them)."""
+        P, g, D = self.P, self.grad, self.D
+        rows = [(c1 - c0) * s['n'] for s in S]
+        for dy, x, lay in (('dsum2', 'f1', 'linear2.'), ('df1', 'h', 'linear1.'), ('du', 'ao', 'self_attn.temporal_info.'),
+                           ('dv', 'ao', 'self_attn.temporal_gate.'), ('dao', 'attn', 'self_attn.temporal_attention_before.out_proj.')):
+            with self.group():
+                for s, k, m in zip(S, K, rows):
+                    self.wgrad(k[dy][:m], k[x][:m], g(s['a'] + lay + 'weight'), g(s['a'] + lay + 'bias'))
+        for s, k, m in zip(S, K, rows):
+            if 'ln' in k:                                       # (the fused dX chain) LayerNorm parameter gradients: column sums of its rows
+                for off, name in ((0, 'norm2.weight'), (D, 'norm2.bias'), (2 * D, 'norm1.weight'), (3 * D, 'norm1.bias')):
+                    capi.call('sttode_rows_reduce', g(s['a'] + name), D, k['ln'][:, off:], 4 * D, 1, D, m, 1, self.st)
+        with self.group():
+            for s, k, m in zip(S, K, rows):
+                Y = s['Ys'][c0 * s['n']:c1 * s['n']]
+                gW, gb = g(s['op'] + 'in_proj_weight'), g(s['op'] + 'in_proj_bias')
+                if s['L'] > 1:
+                    self.wgrad(k['dqkv'][:m], Y, gW, gb)
+                else:
+                    self.wgrad(k['dattn'][:m], Y, gW[2 * D:], gb[2 * D:])
+
+    def _ode_trunk_fwd(self, items, method, steps):
+        """Forward of the trunks through ``steps`` steps of ``method`` (odestages.integrate).  Attention length 1 with T <= 12 (scene
+        batches): ONE launch for both trunks whatever the step count (sttode_ttrunk_ode_fwd: the layers in front of the ODE block, then
+        the stage loop inside the kernel).  Otherwise the layers in front as in the default path (the fused phase-1 launch when T <= 12),
+        then the stage program with f layer by layer, both trunks' layer i in one group.  Tape: the layers in front, and the stage inputs
+        Y_j alone ([stages * n, 64] per trunk); the backward pass recomputes f's activations from them."""
+        P, net, D = self.P, self.net, self.D
+        L, Nb = (net.batch_size, net._N) if net._mode == 'nba' else (1, None)
+        S = []
+        for pre, enc_in, last, feat, drop_mask in items:
+            n, T = enc_in.shape[0], enc_in.shape[1]
+            S.append(dict(t={'n': n, 'T': T, 'pre': pre, 'feat': feat}, pre=pre, a=pre + _ATT, op=pre + _ATT + 'self_attn.temporal_attention_before.',
+                          n=n, T=T, X0=enc_in.reshape(n * T, 4), last=last, feat=feat, drop=drop_mask, L=L, Nb=Nb if Nb is not None else n))
+        nst = steps * odestages.stages(method)
+        for s in S:
+            s['Ys'], s['yT'] = self.new(nst * s['n'], D), self.new(s['n'], D)
+        fused = all(s['T'] <= 12 for s in S) and self.fused_trunk
+        if fused and L == 1:
+            tabs = [self._trunk_fwd_fused(s['t'], s['X0'], s['last'], s['feat'], s['drop'], phase=1, launch=False) for s in S]
+            ptrs = [(src[k].data_ptr() if src.get(k) is not None else None) for _, src in tabs for k in capi.TRUNK_PTRS]
+            A, B = odestages.TABLEAU[method]
+            prog = _OdeProgram(stages=len(B), steps=steps, h=float(net.ODE_TIME) / steps)
+            for i, row in enumerate(A):
+                for j, c in enumerate(row):
+                    prog.a[4 * i + j] = c
+            for i, c in enumerate(B):
+                prog.b[i] = c
+            m = len(S)
+            capi.call('sttode_ttrunk_ode_fwd', (ctypes.c_void_p * len(ptrs))(*ptrs), len(ptrs), m, (ctypes.c_int * m)(*[s['n'] for s in S]),
+                      (ctypes.c_int * m)(*[s['T'] for s in S]), (ctypes.c_long * m)(*[s['feat'].stride(0) for s in S]),
+                      (ctypes.c_void_p * m)(*[s['Ys'].data_ptr() for s in S]), (ctypes.c_void_p * m)(*[s['yT'].data_ptr() for s in S]),
+                      ctypes.byref(prog), self.st)
+            for s, (t, _) in zip(S, tabs):
+                s['t'] = t
+        else:
+            if fused:                                            # phase 1 of the fused trunk launch, both trunks in one launch
+                with (self.group() if len(S) > 1 else contextlib.nullcontext()):
+                    tabs = [self._trunk_fwd_fused(s['t'], s['X0'], s['last'], s['feat'], s['drop'], phase=1) for s in S]
+                for s, (t, _) in zip(S, tabs):
+                    s['t'], s['y0'] = t, t['xc']
+            else:
+                self._trunk_pre_layers(S)
+                for s in S:
+                    s['y0'] = s['x']
+                    s['t'].update(X0=s['X0'], posin=s['posin'], tp=s['tp'], drop=s['drop'], h3in=s['h3in'])
+            odestages.integrate(lambda j, Y: self._ode_f(S, Y)[0], lambda terms, dst: self._ode_comb(S, terms, dst),
+                                tuple(s['y0'] for s in S), net.ODE_TIME, method, steps)
+        for s in S:
+            s['t'].update(ode_prog=(method, steps), ode_fused=fused and L == 1, Ys=s['Ys'], yT=s['yT'], L=L, Nb=s['Nb'])
+        return [s['t'] for s in S]
+
+    def _ode_stage_bwd(self, S, j, kb, close, keep, dY):
+        """One sttode_ode_stage_bwd launch for stage j of both trunks: f recomputed, dk from ``kb``, f's VJP into dY, the columns into
+        ``keep``; with ``close`` also the gradient wrt the step's start state (returned, per trunk)."""
+        P, D = self.P, self.D
+        jobs = (_OdeStageBwd * len(S))()
+        closed = []
+        for si, s in enumerate(S):
+            J, n, a, op = jobs[si], s['n'], s['a'], s['op']
+            for wi, name in enumerate((op + 'in_proj_weight', op + 'in_proj_bias', op + 'out_proj.weight', op + 'out_proj.bias',
+                                       a + 'self_attn.temporal_info.weight', a + 'self_attn.temporal_info.bias', a + 'self_attn.temporal_gate.weight',
+                                       a + 'self_attn.temporal_gate.bias', a + 'norm1.weight', a + 'norm1.bias', a + 'linear1.weight',
+                                       a + 'linear1.bias', a + 'linear2.weight', a + 'linear2.bias', a + 'norm2.weight', a + 'norm2.bias')):
+                J.w[wi] = P[name].data_ptr()
+            J.y, J.dy, J.n = s['Ys'][j * n:(j + 1) * n].data_ptr(), dY[si].data_ptr(), n
+            for ti, (c, v) in enumerate(kb):
+                J.kb.v[ti], J.kb.ld[ti], J.kb.c[ti] = v[si].data_ptr(), _ld(v[si]), c
+            J.kb.nterms, J.kb.rows = len(kb), n
+            if close is not None:
+                out = self.new(n, D)
+                for ti, (c, v) in enumerate(close):
+                    J.next.v[ti], J.next.ld[ti], J.next.c[ti] = v[si].data_ptr(), _ld(v[si]), c
+                J.next.nterms, J.next.rows, J.next.out, J.next.ld_out = len(close), n, out.data_ptr(), D
+                closed.append(out)
+            for k, v in keep[si].items():
+                setattr(J, k, v.data_ptr())
+        capi.call('sttode_ode_stage_bwd', jobs, len(S), self.st)
+        return tuple(closed) if close is not None else None
+
+    def _ode_trunk_bwd(self, items):
+        """Backward of _ode_trunk_fwd (odestages.integrate_adjoint): stages in reverse, each one f recomputed from its stage input, its
+        VJP, and the stage-combination adjoints -- ONE sttode_ode_stage_bwd launch per stage for both trunks at attention length 1, the
+        layer kernels and sttode_ode_combine otherwise; the linear layers' weight gradients in chunks of stages (_ode_wgrad) whose columns
+        stay under _ODE_DW_CAP bytes.  Then the layers in front of the ODE block as in the default path."""
+        D = self.D
+        method, steps = items[0][0]['ode_prog']
+        fused = items[0][0]['ode_fused']
+        S = []
+        for t, dfeat in items:
+            assert t['ode_prog'] == (method, steps) and t['ode_fused'] == fused and dfeat.stride(1) == 1 and dfeat.shape[1] >= 2 * D
+            pre = t['pre']
+            S.append(dict(t=t, pre=pre, a=pre + _ATT, op=pre + _ATT + 'self_attn.temporal_attention_before.', n=t['n'], T=t['T'], dfeat=dfeat,
+                          L=t['L'], Nb=t['Nb'], Ys=t['Ys']))
+        acts = ('attn', 'ao', 'h', 'f1')
+        width = dict(attn=D, ao=D, h=D, f1=1024, dsum2=D, df1=1024, du=D, dv=D, dao=D, dattn=D, qkv=3 * D, dqkv=3 * D, ln=4 * D)
+        names = [acts + ('dsum2', 'df1', 'du', 'dv', 'dao', 'dattn') + (('ln',) if fused else ()) + (('qkv', 'dqkv') if s['L'] > 1 else ())
+                 for s in S]
+        per_stage = sum(4 * s['n'] * sum(width[k] for k in nm) for s, nm in zip(S, names))
+        nst = steps * odestages.stages(method)
+        C = _ode_chunk_stages(nst, per_stage)
+        K = []
+
+        def vjp(j, kb, close):
+            c1 = nst - ((nst - 1 - j) // C) * C
+            c0 = max(0, c1 - C)
+            if j == c1 - 1:                                     # the chunk's first (highest) stage: its column buffers (one stream: not held)
+                K[:] = [{k: torch.empty((c1 - c0) * s['n'], width[k], dtype=torch.float32, device=self.dev) for k in nm} for s, nm in zip(S, names)]
+            keep = [{k: v[(j - c0) * s['n']:(j - c0 + 1) * s['n']] for k, v in kk.items()} for s, kk in zip(S, K)]
+            if fused:
+                dY = tuple(self.new(s['n'], D) for s in S)
+                closed = self._ode_stage_bwd(S, j, kb, close, keep, dY)
+            else:
+                Y = tuple(s['Ys'][j * s['n']:(j + 1) * s['n']] for s in S)
+                _, A = self._ode_f(S, Y, keep=[{k: kp[k] for k in kp if k in acts or k == 'qkv'} for kp in keep])
+                dY = self._ode_vjp(S, A, self._ode_comb(S, kb, None), keep)
+                closed = None if close is None else self._ode_comb(S, [(1.0, dY)] + close, None)
+            if j == c0:
+                self._ode_wgrad(S, K, c0, c1)
+            return dY, closed
+
+        ybar = self._ode_comb(S, [(1.0, tuple(s['dfeat'][:, D:2 * D] for s in S))], None, mask=tuple(s['t']['yT'] for s in S))
+        dx = odestages.integrate_adjoint(vjp, ybar, self.net.ODE_TIME, method, steps, extra=[(1.0, tuple(s['dfeat'][:, :D] for s in S))])
+        for s, d in zip(S, dx):
+            s['dx'] = d
+        self._trunk_bwd_pre(S)
 
     # ---------------------------------------------------------------- decoder (Decoder.forward, model/STTODE.py:320-347)
     def l1_fwd(self, pre, inp, tab, K):
@@ -1139,6 +1462,9 @@ def training_forward(net, eps_q=None, eps_p=None, eps20=None, drop_past=None, dr
            drop_future is not None or net.training, tuple(drawn), _LIVE_COLUMNS, _AGENT_GRU,
            ptr_token, params[0].data_ptr(), params[-1].data_ptr(),     # graphs hold raw parameter pointers ...
            float(a.min_clip), float(net.ODE_TIME))            # ... and bake scalar kernel arguments in
+    prog = eng.ode_program()                                        # (raises for a non-default integrator at generic widths)
+    if prog is not None:                                            # the stage program is part of what a graph holds (the default key is as before)
+        key = key + (prog,)
     # a step is ~170 launches of 5-30 us each and the host needs ~15 us to enqueue one: replay wins as long as the launches are short
     # (one scene: launch-bound; an NBA batch of 32 x 11 agents: 3.5 ms eager for 2.5 ms of kernels)
     graphs = getattr(net, 'train_graphs', os.environ.get('STTODE_TRAIN_GRAPHS', '1') != '0') and net._future is not None and n <= _GRAPH_MAX_AGENTS
