@@ -24,7 +24,7 @@ extern "C" {
 #endif
 
 /* Version of this header: the library returns it from sttode_abi_version(); a binding compares before its first call (round 1-2: 1). */
-#define STTODE_ABI_VERSION 9
+#define STTODE_ABI_VERSION 10
 int sttode_abi_version(void);
 const char* sttode_last_error(void);
 
@@ -282,6 +282,14 @@ int sttode_conv_bwd(const float* de, const float* x, const float* w, float* dx, 
  * row = l*Nb + slot; D = 8 head_dim), dO [L*Nb, D] (grad wrt the merged-head output before out_proj) -> dqkv [L*Nb, 3 D].
  * head_dim 4 / 8 / 16; L (4 head_dim + 4) floats of LDS (L <= 1137 at head_dim 8). */
 int sttode_mhgsa_attn_bwd(const float* qkv, const float* dO, float* dqkv, int L, int Nb, int head_dim, void* stream);
+/* Backward of sttode_mhgsa_attn (head_dim 8) for any rows x cols: R, C, V, dO in the operands' layout of the forward call (dO laid out like
+ * `out`, strides os_*) -> dR, dC, dV in the layouts of R, C, V (overwritten, not accumulated).  Both orientations of the drop-ins' mhgsa:
+ * L != S (R = q, C = k) and the untransposed L == S form (R = k, C = q).  Gradients through the clamp follow torch.clamp (bounds inclusive),
+ * through both normalisations and both scales.  One workgroup per (slot, head), deterministic; rows (2 head_dim + 3) + cols (2 head_dim + 1)
+ * floats of LDS must fit 64 KiB (rows = cols <= 455). */
+int sttode_mhgsa_attn_rc_bwd(const float* R, const float* C, const float* V, const float* dO, float* dR, float* dC, float* dV, int rows,
+                             int cols, int Nb, long rs_seq, long rs_b, long cs_seq, long cs_b, long vs_seq, long vs_b, long os_seq,
+                             long os_b, float rscale, float cscale, void* stream);
 /* torch.optim.Adam's step (train.py:122 constructs it, :66,87 call it) for ALL parameters in ONE launch: items = DEVICE array of n records
  * {float* p, float* m, float* v, long goff, long numel, long chunk0} (48 bytes each): parameter, first / second moment, the gradient's offset
  * in floats from gbase, element count, first 1024-element chunk (ascending from 0; `chunks` = their total).  step = t >= 1 (bias

@@ -11,7 +11,7 @@ _LIB = None
 LIB_PATH = os.environ.get('STTODE_HIP_LIB') or os.path.join(os.path.dirname(os.path.abspath(__file__)), 'lib', 'libsttode_hip.so')
 
 _P, _I, _L, _F, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double
-ABI_VERSION = 9   # == STTODE_ABI_VERSION of include/sttode_hip.h; lib() refuses a library built from another header
+ABI_VERSION = 10  # == STTODE_ABI_VERSION of include/sttode_hip.h; lib() refuses a library built from another header
 
 # name -> argtypes (mirrors include/sttode_hip.h; tests/test_capi_symbols.py checks header == table == .so)
 SIGNATURES = {
@@ -65,6 +65,7 @@ SIGNATURES = {
     'sttode_conv_fwd': [_P, _I, _P, _P, _P, _P, _P, _I, _I, _P],
     'sttode_conv_bwd': [_P, _P, _P, _P, _P, _P, _I, _I, _P, _L, _P],
     'sttode_mhgsa_attn_bwd': [_P, _P, _P, _I, _I, _I, _P],
+    'sttode_mhgsa_attn_rc_bwd': [_P] * 7 + [_I, _I, _I] + [_L] * 8 + [_F, _F, _P],
     'sttode_adam_step': [_P, _I, _L, _P, _D, _D, _D, _D, _D, _L, _P],
     'sttode_loss_sqerr': [_P, _P, _L, _F, _P, _P, _P],
     'sttode_loss_kl': [_P, _P, _I, _I, _I, _F, _F, _P, _P, _P, _P],

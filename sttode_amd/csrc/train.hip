@@ -2061,6 +2061,131 @@ extern "C" int sttode_mhgsa_attn_bwd(const float* qkv, const float* dO, float* d
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Backward of sttode_mhgsa_attn for any rows x cols and separate R / C / V operands (encoder.hip mhgsa_attn_kernel<8>: the op-level
+// drop-ins' cross-attention over a memory of another length, and equal-length attention whose rows and columns come from different
+// tensors).  Per (slot, head): rho = rscale R[r], gam = cscale C[c], x = clamp(rho^ . gam^), P = softmax_c(-acos x), out[r] = sum_c P V[c];
+//   dV[c] = sum_r P dO[r];  dS = P (dO[r] . V[c] - sum_c' P dP);  g = dS / sqrt(1 - x^2) where the clamp did not bind (torch.clamp's
+//   inclusive bounds), else 0;  dR[r] = rscale / |rho| (drho^ - rho^ (rho^ . drho^)) with drho^ = sum_c g gam^_c (dC likewise).
+// One WG per (slot, head) owns all rows and columns: no atomics, fixed summation order.  The outputs are overwritten.
+// LDS: rows (2 HD + 3) + cols (2 HD + 1) floats.
+// ---------------------------------------------------------------------------------------------------
+#define RC_ATT_LDS_BYTES (64 * 1024)
+__global__ __launch_bounds__(256) void attn_rc_bwd_kernel(const float* __restrict__ R, const float* __restrict__ C, const float* __restrict__ V,
+                                                          const float* __restrict__ dO, float* __restrict__ dR, float* __restrict__ dC,
+                                                          float* __restrict__ dV, int rows, int cols, long rs_seq, long rs_b, long cs_seq,
+                                                          long cs_b, long vs_seq, long vs_b, long os_seq, long os_b, float rscale, float cscale) {
+    constexpr int HD = 8;
+    extern __shared__ float sm[];
+    float* rh = sm;                 // [rows][HD] rho^
+    float* dd = rh + rows * HD;     // [rows][HD] dO
+    float* rinv = dd + rows * HD;   // [rows] 1 / sum_c exp
+    float* rdot = rinv + rows;      // [rows] sum_c P dP
+    float* rn = rdot + rows;        // [rows] rscale / |rho|
+    float* ch = rn + rows;          // [cols][HD] gam^
+    float* vv = ch + cols * HD;     // [cols][HD] V
+    float* cn = vv + cols * HD;     // [cols] cscale / |gam|
+    const int b = blockIdx.x / 8, h = blockIdx.x % 8;
+    for (int r = threadIdx.x; r < rows; r += blockDim.x) {
+        const float* p = R + r * rs_seq + b * rs_b + HD * h;
+        const float* po = dO + r * os_seq + b * os_b + HD * h;
+        float x[HD], ss = 0.f;
+#pragma unroll
+        for (int d = 0; d < HD; ++d) { x[d] = p[d] * rscale; ss += x[d] * x[d]; }
+        const float nrm = sqrtf(ss);
+#pragma unroll
+        for (int d = 0; d < HD; ++d) { rh[r * HD + d] = x[d] / nrm; dd[r * HD + d] = po[d]; }
+        rn[r] = rscale / nrm;
+    }
+    for (int c = threadIdx.x; c < cols; c += blockDim.x) {
+        const float* p = C + c * cs_seq + b * cs_b + HD * h;
+        const float* pv = V + c * vs_seq + b * vs_b + HD * h;
+        float x[HD], ss = 0.f;
+#pragma unroll
+        for (int d = 0; d < HD; ++d) { x[d] = p[d] * cscale; ss += x[d] * x[d]; }
+        const float nrm = sqrtf(ss);
+#pragma unroll
+        for (int d = 0; d < HD; ++d) { ch[c * HD + d] = x[d] / nrm; vv[c * HD + d] = pv[d]; }
+        cn[c] = cscale / nrm;
+    }
+    __syncthreads();
+    const float lo = -1.0f + 1e-4f, hi = 1.0f - 1e-4f;
+    // pass 1 (thread = row r): softmax denominator, sum_c P dP, dR[r]
+    for (int r = threadIdx.x; r < rows; r += blockDim.x) {
+        float se = 0.f, sp = 0.f;
+        for (int c = 0; c < cols; ++c) {
+            float dot = 0.f, dp = 0.f;
+#pragma unroll
+            for (int d = 0; d < HD; ++d) { dot += rh[r * HD + d] * ch[c * HD + d]; dp += dd[r * HD + d] * vv[c * HD + d]; }
+            const float ex = expf(-acosf(fminf(fmaxf(dot, lo), hi)));
+            se += ex;
+            sp += ex * dp;
+        }
+        const float ri = 1.0f / se, rd = sp / se;
+        rinv[r] = ri;
+        rdot[r] = rd;
+        float g[HD];
+#pragma unroll
+        for (int d = 0; d < HD; ++d) g[d] = 0.f;
+        for (int c = 0; c < cols; ++c) {
+            float dot = 0.f, dp = 0.f;
+#pragma unroll
+            for (int d = 0; d < HD; ++d) { dot += rh[r * HD + d] * ch[c * HD + d]; dp += dd[r * HD + d] * vv[c * HD + d]; }
+            const bool inside = dot >= lo && dot <= hi;
+            const float cl = fminf(fmaxf(dot, lo), hi);
+            const float P = expf(-acosf(cl)) * ri;
+            const float gs = inside ? P * (dp - rd) / sqrtf(1.0f - cl * cl) : 0.f;   // d(-acos x)/dx = 1/sqrt(1-x^2)
+#pragma unroll
+            for (int d = 0; d < HD; ++d) g[d] += gs * ch[c * HD + d];
+        }
+        float pr = 0.f;
+#pragma unroll
+        for (int d = 0; d < HD; ++d) pr += g[d] * rh[r * HD + d];
+        float* o = dR + r * rs_seq + b * rs_b + HD * h;
+#pragma unroll
+        for (int d = 0; d < HD; ++d) o[d] = (g[d] - rh[r * HD + d] * pr) * rn[r];
+    }
+    __syncthreads();
+    // pass 2 (thread = column c): dC[c], dV[c]
+    for (int c = threadIdx.x; c < cols; c += blockDim.x) {
+        float g[HD], dv[HD];
+#pragma unroll
+        for (int d = 0; d < HD; ++d) g[d] = dv[d] = 0.f;
+        for (int r = 0; r < rows; ++r) {
+            float dot = 0.f, dp = 0.f;
+#pragma unroll
+            for (int d = 0; d < HD; ++d) { dot += rh[r * HD + d] * ch[c * HD + d]; dp += dd[r * HD + d] * vv[c * HD + d]; }
+            const bool inside = dot >= lo && dot <= hi;
+            const float cl = fminf(fmaxf(dot, lo), hi);
+            const float P = expf(-acosf(cl)) * rinv[r];
+            const float gs = inside ? P * (dp - rdot[r]) / sqrtf(1.0f - cl * cl) : 0.f;
+#pragma unroll
+            for (int d = 0; d < HD; ++d) { g[d] += gs * rh[r * HD + d]; dv[d] += P * dd[r * HD + d]; }
+        }
+        float pr = 0.f;
+#pragma unroll
+        for (int d = 0; d < HD; ++d) pr += g[d] * ch[c * HD + d];
+        float* o = dC + c * cs_seq + b * cs_b + HD * h;
+        float* ov = dV + c * vs_seq + b * vs_b + HD * h;
+#pragma unroll
+        for (int d = 0; d < HD; ++d) { o[d] = (g[d] - ch[c * HD + d] * pr) * cn[c]; ov[d] = dv[d]; }
+    }
+}
+extern "C" int sttode_mhgsa_attn_rc_bwd(const float* R, const float* C, const float* V, const float* dO, float* dR, float* dC, float* dV,
+                                        int rows, int cols, int Nb, long rs_seq, long rs_b, long cs_seq, long cs_b, long vs_seq, long vs_b,
+                                        long os_seq, long os_b, float rscale, float cscale, void* stream) {
+    STT_REQUIRE(R && C && V && dO && dR && dC && dV, "sttode_mhgsa_attn_rc_bwd: null pointer");
+    STT_REQUIRE(rows > 0 && cols > 0 && Nb > 0 && (long)Nb * 8 <= 0x7fffffffL, "sttode_mhgsa_attn_rc_bwd: bad rows/cols/Nb");
+    const size_t shm = ((size_t)rows * (2 * 8 + 3) + (size_t)cols * (2 * 8 + 1)) * sizeof(float);
+    STT_REQUIRE(shm <= RC_ATT_LDS_BYTES, "sttode_mhgsa_attn_rc_bwd: rows x cols too large for the attention backward (rows (2 head_dim + 3) + "
+                                         "cols (2 head_dim + 1) floats of LDS must fit 64 KiB)");
+    const int mx = rows > cols ? rows : cols;
+    hipLaunchKernelGGL(attn_rc_bwd_kernel, dim3(Nb * 8), dim3(mx < 256 ? ((mx + 63) / 64) * 64 : 256), shm, (hipStream_t)stream, R, C, V, dO,
+                       dR, dC, dV, rows, cols, rs_seq, rs_b, cs_seq, cs_b, vs_seq, vs_b, os_seq, os_b, rscale, cscale);
+    STT_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Adam (train.py:122 torch.optim.Adam(model.parameters(), lr); its step at train.py:66,87) for ALL parameters of the model in ONE launch:
 //     m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  p -= (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps)      (g += wd p first)
 // torch's fused implementation walks the 88 small tensors with multi_tensor_apply: 3 launches of 41-44 us each per step (131 us of a 2.3-ms

@@ -6,6 +6,7 @@ hypertransformer.py:29, model/STTODE.py:190-194).
 """
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import capi, packing
 
@@ -38,22 +39,14 @@ def linear_cols(x, weight, bias=None, relu=False, act=None):
     return out
 
 
-@torch.no_grad()
-def mhgsa(query, key, value, in_proj_weight, in_proj_bias, out_proj_weight, out_proj_bias, num_heads=8, need_weights=False):
-    """Multi-head geodesic self/cross attention. query [L,Nb,64], key/value [S,Nb,64] -> (out [L,Nb,64], weights [Nb,L,S] | None)."""
-    if query.device.type != 'cuda':
-        raise capi.SttodeError('mhgsa runs only on a HIP device (no CPU fallback)')
+def _mhgsa_fwd(query, key, value, W, b, out_proj_weight, out_proj_bias, need_weights):
+    """The forward launches: in-projections, attention core, out_proj.  Returns (out, weights | None, tensors for the backward)."""
     L, Nb, E = query.shape
     S = key.shape[0]
-    if E != 64 or num_heads != 8:
-        raise NotImplementedError('mhgsa kernel is built for embed_dim=64, num_heads=8')
-    if key.shape != value.shape or key.shape[1] != Nb:
-        raise ValueError('key/value shape mismatch')
-    W, b = in_proj_weight, in_proj_bias
     q = linear_cols(query.reshape(L * Nb, E), W[:E].contiguous(), b[:E])
     k = linear_cols(key.reshape(S * Nb, E), W[E:2 * E].contiguous(), b[E:2 * E])
     v = linear_cols(value.reshape(S * Nb, E), W[2 * E:].contiguous(), b[2 * E:])
-    scale = float(E // num_heads) ** -0.5
+    scale = float(E // 8) ** -0.5
     if L == S:
         # scores [S, L] used untransposed (hyptransformerlib.py:261-265): rows = keys, columns = queries
         R, C, rows, cols, rs, cs = k, q, S, L, 1.0, scale
@@ -65,4 +58,89 @@ def mhgsa(query, key, value, in_proj_weight, in_proj_bias, out_proj_weight, out_
     st = Nb * E
     capi.call('sttode_mhgsa_attn', R, C, v, attn, rowsum, wout, rows, cols, Nb, st, E, st, E, st, E, st, E, rs, cs, capi.stream_ptr())
     out = linear_cols(attn, out_proj_weight, out_proj_bias).view(rows, Nb, E)
+    return out, wout, (q, k, v, attn, rows, cols, rs, cs)
+
+
+_SCRATCH = {}
+
+
+def scratch(device):
+    """Per-device workspace of the backward kernels (split weight-gradient partials, LayerNorm partials); stream-ordered reuse."""
+    key = str(device)
+    if key not in _SCRATCH:
+        _SCRATCH[key] = torch.empty(4 << 20, dtype=torch.float32, device=device)
+    return _SCRATCH[key]
+
+
+def linear_bwd(dY, W, X, dX, dW, db, mask=None, accumulate=False):
+    """Backward of one nn.Linear on sttode_tlinear_bwd: dX = mask(dY W) (+ dX), dW += dY^T X, db += sum dY.  2-d row-major operands."""
+    cols, N = dY.shape
+    K = W.shape[1]
+    sc = scratch(dY.device)
+    capi.call('sttode_tlinear_bwd', dY, dY.stride(0), W, W.stride(0), mask, mask.stride(0) if mask is not None else 0, dX, dX.stride(0), K,
+              int(accumulate), X, X.stride(0), 1, dW, dW.stride(0), db, cols, N, K, sc, sc.numel(), capi.stream_ptr())
+    return dX
+
+
+class _Mhgsa(torch.autograd.Function):
+    """mhgsa with a HIP backward: out_proj (sttode_tlinear_bwd), the attention core (sttode_mhgsa_attn_rc_bwd), the three in-projections
+    into one [3E, E] weight gradient.  Inputs that are the same tensor (self-attention, key = value) get one accumulated gradient."""
+
+    @staticmethod
+    def forward(ctx, need_weights, slots, query, key, value, W, b, Wo, bo):
+        out, wout, (q, k, v, attn, rows, cols, rs, cs) = _mhgsa_fwd(query, key, value, W, b, Wo, bo, need_weights)
+        ctx.meta = (slots, rows, cols, rs, cs)
+        ctx.save_for_backward(query, key, value, W, Wo, q, k, v, attn)
+        if wout is not None:
+            ctx.mark_non_differentiable(wout)
+        return out, wout
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout, _dw):
+        query, key, value, W, Wo, q, k, v, attn = ctx.saved_tensors
+        slots, rows, cols, rs, cs = ctx.meta
+        L, Nb, E = query.shape
+        S = key.shape[0]
+        dev = query.device
+        dO = dout.reshape(rows * Nb, E).contiguous()
+        dWo, dbo = torch.zeros_like(Wo), torch.zeros(E, device=dev)
+        dattn = linear_bwd(dO, Wo, attn, torch.empty(rows * Nb, E, device=dev), dWo, dbo)
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        dR, dC = (dk, dq) if L == S else (dq, dk)
+        R, C = (k, q) if L == S else (q, k)
+        st = Nb * E
+        capi.call('sttode_mhgsa_attn_rc_bwd', R, C, v, dattn, dR, dC, dv, rows, cols, Nb, st, E, st, E, st, E, st, E, rs, cs, capi.stream_ptr())
+        dW, db = torch.zeros_like(W), torch.zeros(3 * E, device=dev)
+        xs = (query, key, value)
+        dx = [None, None, None]
+        for i, (d, x) in enumerate(zip((dq, dk, dv), xs)):
+            s = slots[i]                                             # index of the first input that is the same tensor as input i
+            first = dx[s] is None
+            if first:
+                dx[s] = torch.empty(x.shape[0] * Nb, E, device=dev)
+            linear_bwd(d, W[i * E:(i + 1) * E], x.reshape(-1, E), dx[s], dW[i * E:(i + 1) * E], db[i * E:(i + 1) * E], accumulate=not first)
+        dx = [None if d is None else d.view(xs[i].shape) for i, d in enumerate(dx)]
+        return None, None, dx[0], dx[1], dx[2], dW, db, dWo, dbo
+
+
+def mhgsa(query, key, value, in_proj_weight, in_proj_bias, out_proj_weight, out_proj_bias, num_heads=8, need_weights=False,
+          differentiable=False):
+    """Multi-head geodesic self/cross attention. query [L,Nb,64], key/value [S,Nb,64] -> (out [L,Nb,64], weights [Nb,L,S] | None).
+    ``differentiable``: with grad mode on and an input or parameter that requires grad, the output carries a graph whose backward runs on
+    HIP kernels (the weights are not differentiable); otherwise forward values only, as by default."""
+    if query.device.type != 'cuda':
+        raise capi.SttodeError('mhgsa runs only on a HIP device (no CPU fallback)')
+    L, Nb, E = query.shape
+    if E != 64 or num_heads != 8:
+        raise NotImplementedError('mhgsa kernel is built for embed_dim=64, num_heads=8')
+    if key.shape != value.shape or key.shape[1] != Nb:
+        raise ValueError('key/value shape mismatch')
+    args = (query, key, value, in_proj_weight, in_proj_bias, out_proj_weight, out_proj_bias)
+    if differentiable and torch.is_grad_enabled() and any(t.requires_grad for t in args):
+        xs = (query, key, value)
+        slots = tuple(next(j for j in range(3) if xs[j] is xs[i]) for i in range(3))
+        return _Mhgsa.apply(need_weights, slots, *args)
+    with torch.no_grad():
+        out, wout, _ = _mhgsa_fwd(*args, need_weights)
     return out, wout
