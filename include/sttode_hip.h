@@ -24,7 +24,7 @@ extern "C" {
 #endif
 
 /* Version of this header: the library returns it from sttode_abi_version(); a binding compares before its first call (round 1-2: 1). */
-#define STTODE_ABI_VERSION 10
+#define STTODE_ABI_VERSION 11
 int sttode_abi_version(void);
 const char* sttode_last_error(void);
 
@@ -173,6 +173,16 @@ int sttode_best_of_k(const float* pred, const float* gt, int n, int K, int Tf, f
  * h - 1) out[a][h-1] = (min_k mean_{t < h} |scale (pred - gt)|, min_k |scale (pred_h - gt_h)|); the caller averages over agents and weighs by
  * the batch size like the reference.  K <= 64, K Tf <= 2048. */
 int sttode_horizon_metrics(const float* pred, const float* gt, int n, int K, int Tf, float scale, float* out, void* stream);
+/* Best-of-K selection per agent and per segment: compute_ADE / compute_FDE (utils/metrics.py:7-26), get_best_idx (:29-36) and
+ * count_miss_samples (:39-48), the per-agent loop of test.py:193-205 (its ade per scene: :201-205).  pred [n,K,Tf,2], gt [n,Tf,2], K <= 64
+ * (refused above that, nothing written).  Per agent: ade [n], fde [n] (the bits of sttode_best_of_k); best_ade_idx / best_fde_idx [n] = argmin
+ * over k of the mean / final displacement, the lowest k on exact ties (np.argmin); miss [n] = fde > miss_threshold (1 / 0, strictly);
+ * best [n,Tf,2] = pred[a, best_ade_idx[a]] (copied, unscaled).  Per segment s of the CSR seg_ptr [S+1] (scene_ptr; B segments of N for NBA):
+ * seg_ade / seg_fde [S] = mean over agents seg_ptr[s] .. seg_ptr[s+1]-1, seg_miss [S] = their miss count, summed in a fixed order (no
+ * atomics: the same bits on every run).  Every output but ade / fde may be NULL; seg_ptr may be NULL (S = 0) when no segment output is asked. */
+int sttode_best_of_k_select(const float* pred, const float* gt, int n, int K, int Tf, float scale, float miss_threshold, const int* seg_ptr,
+                            int S, float* ade, float* fde, int* best_ade_idx, int* best_fde_idx, unsigned char* miss, float* best,
+                            float* seg_ade, float* seg_fde, int* seg_miss, void* stream);
 
 /* Stage-2 latent sampler (sampler.py:47-54): z = b (eps_mode 0) or A*eps + b with eps shared [nz] (1, share_eps) or per agent
  * [n,nz] (2); logvar = log(A^2 + 1e-8).  A, b, z, logvar [n*K, nz] (row = agent*K + k). */
@@ -658,6 +668,12 @@ int sttode_inference_nba_async(SttodeModel* m, const float* past, int B, int N, 
 /* sttode_horizon_metrics of an asynchronous call's predictions on the pipeline stream the call of `slot` runs on (as sttode_async_best_of_k:
  * starts the moment the call's groups drain; the slot's completion event is re-recorded behind it). */
 int sttode_async_horizon_metrics(SttodeModel* m, int slot, const float* pred, const float* gt, int n, int K, int Tf, float scale, float* out);
+/* sttode_best_of_k_select of an asynchronous call's predictions (utils/metrics.py:7-48, test.py:193-205) on the pipeline stream the call of
+ * `slot` runs on, as sttode_async_best_of_k: the slot's outstanding trajectory groups are enqueued first, the selection follows them in stream
+ * order, and the slot's completion event is re-recorded behind it.  gt and seg_ptr must have been written before the call. */
+int sttode_async_best_of_k_select(SttodeModel* m, int slot, const float* pred, const float* gt, int n, int K, int Tf, float scale,
+                                  float miss_threshold, const int* seg_ptr, int S, float* ade, float* fde, int* best_ade_idx, int* best_fde_idx,
+                                  unsigned char* miss, float* best, float* seg_ade, float* seg_fde, int* seg_miss);
 int sttode_wait(SttodeModel* m, int slot, void* stream);
 /* Zero-copy futures (lagged form): the trajectory groups of a lagged call only WRITE `pred` (block 0's y_hat0 waits in the workspace), so
  * `pred` may be pinned host memory addressed by its host pointer: the futures reach the host with the launch itself, no D2H copy

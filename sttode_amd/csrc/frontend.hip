@@ -1,7 +1,7 @@
 // Batched scene front-end (set_data / set_data_nba equivalents) and best-of-K metrics.
 //   reference: model/STTODE.py:397-461 (scene normalisation, velocities, cur_location),
 //              model/STTODE.py:463-486,578-596 (NBA branch / inference() input assembly),
-//              utils/metrics.py:7-26 (min-over-K ADE / FDE).
+//              utils/metrics.py:7-26 (min-over-K ADE / FDE), :29-48 (best sample index, miss count).
 // HBM-bound byte shuffling: one thread per scene / agent, coalesced over agents.
 #include "api_util.hpp"
 #include "frontend_body.hpp"
@@ -250,6 +250,117 @@ extern "C" int sttode_horizon_metrics(const float* pred, const float* gt, int n,
     STT_REQUIRE(pred && gt && out, "sttode_horizon_metrics: null pointer");
     STT_REQUIRE(n > 0 && K > 0 && K <= 64 && Tf > 0 && K * Tf <= 2048, "sttode_horizon_metrics: need 0 < K <= 64 and K * Tf <= 2048");
     hipLaunchKernelGGL(horizon_metrics_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, pred, gt, n, K, Tf, scale, out);
+    STT_HIP(hipGetLastError());
+    return 0;
+}
+
+// Best-of-K selection (utils/metrics.py:7-48: compute_ADE / compute_FDE, get_best_idx, count_miss_samples) per agent, one wave per agent
+// and one lane per sample (K <= 64).  The K Tf displacement norms are staged in LDS by coalesced 8-byte reads when they fit (bok_dist, as
+// best_of_k_kernel), lane k sums sample k's frames in frame order, and the wave takes the minimum by xor shuffles: ade / fde are the bits
+// of sttode_best_of_k.  The index is the lowest k whose value equals that minimum (a ballot: np.argmin's first-index rule on exact ties).
+// miss = fde > thr (strictly).  best (optional) [n][Tf][2] = pred[a][best_ade_idx[a]], copied.  One read of pred, plus the gather.
+__global__ __launch_bounds__(256) void bok_select_kernel(const float* __restrict__ pred, const float* __restrict__ gt, int n, int K, int Tf,
+                                                         float scale, float thr, float* __restrict__ ade, float* __restrict__ fde,
+                                                         int* __restrict__ ia, int* __restrict__ ifd, unsigned char* __restrict__ miss,
+                                                         float* __restrict__ best) {
+    __shared__ float sd[4][1024];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int a = blockIdx.x * 4 + w;
+    if (a >= n) return;
+    const float2* g = reinterpret_cast<const float2*>(gt + (size_t)a * Tf * 2);
+    const float2* p = reinterpret_cast<const float2*>(pred + (size_t)a * K * Tf * 2);
+    const int tot = K * Tf;
+    float va = INFINITY, vf = INFINITY;
+    if (tot <= 1024) {
+        for (int i = lane; i < tot; i += 64) {
+            const float2 v = p[i], r = g[i % Tf];
+            sd[w][i] = bok_dist(v.x, v.y, r.x, r.y, scale);
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (lane < K) {
+            float sum = 0.f;
+            for (int t = 0; t < Tf; ++t) sum += sd[w][lane * Tf + t];
+            va = sum / (float)Tf;
+            vf = sd[w][lane * Tf + Tf - 1];
+        }
+    } else if (lane < K) {
+        float sum = 0.f, dl = 0.f;
+        for (int t = 0; t < Tf; ++t) {
+            const float2 v = p[lane * Tf + t], r = g[t];
+            dl = bok_dist(v.x, v.y, r.x, r.y, scale);
+            sum += dl;
+        }
+        va = sum / (float)Tf;
+        vf = dl;
+    }
+    float ma = va, mf = vf;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        ma = fminf(ma, __shfl_xor(ma, o, 64));
+        mf = fminf(mf, __shfl_xor(mf, o, 64));
+    }
+    // (no sample equals the minimum only if every value is NaN: index 0 then, so that the gather stays inside the agent's samples)
+    const unsigned long long ba = __ballot(lane < K && va == ma), bf = __ballot(lane < K && vf == mf);
+    const int ka = ba ? __builtin_ctzll(ba) : 0, kf = bf ? __builtin_ctzll(bf) : 0;
+    if (lane == 0) {
+        ade[a] = ma;
+        fde[a] = mf;
+        if (ia) ia[a] = ka;
+        if (ifd) ifd[a] = kf;
+        if (miss) miss[a] = mf > thr ? 1 : 0;
+    }
+    if (best) {
+        float2* b = reinterpret_cast<float2*>(best + (size_t)a * Tf * 2);
+        for (int t = lane; t < Tf; t += 64) b[t] = p[ka * Tf + t];
+    }
+}
+
+// Per segment s (agents seg_ptr[s] .. seg_ptr[s+1]-1 of the CSR): mean ade, mean fde and the miss count, one wave per segment.  Lane l sums
+// the agents a0 + l, a0 + l + 64, ... in order and the wave adds the 64 partial sums by a fixed xor tree: no atomics, the same bits on every
+// run.  Bounds are clamped to [0, n]; an empty segment gets 0 / 0 = NaN means and a zero count.
+__global__ __launch_bounds__(256) void bok_segments_kernel(const float* __restrict__ ade, const float* __restrict__ fde,
+                                                           const int* __restrict__ seg_ptr, int S, int n, float thr,
+                                                           float* __restrict__ seg_ade, float* __restrict__ seg_fde, int* __restrict__ seg_miss) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int s = blockIdx.x * 4 + w;
+    if (s >= S) return;
+    const int a0 = min(max(seg_ptr[s], 0), n), a1 = min(max(seg_ptr[s + 1], a0), n);
+    float sa = 0.f, sf = 0.f;
+    int m = 0;
+    for (int a = a0 + lane; a < a1; a += 64) {
+        const float f = fde[a];
+        sa += ade[a];
+        sf += f;
+        m += f > thr ? 1 : 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        sa += __shfl_xor(sa, o, 64);
+        sf += __shfl_xor(sf, o, 64);
+        m += __shfl_xor(m, o, 64);
+    }
+    if (lane == 0) {
+        const float c = (float)(a1 - a0);
+        if (seg_ade) seg_ade[s] = sa / c;
+        if (seg_fde) seg_fde[s] = sf / c;
+        if (seg_miss) seg_miss[s] = m;
+    }
+}
+
+extern "C" int sttode_best_of_k_select(const float* pred, const float* gt, int n, int K, int Tf, float scale, float miss_threshold,
+                                       const int* seg_ptr, int S, float* ade, float* fde, int* best_ade_idx, int* best_fde_idx,
+                                       unsigned char* miss, float* best, float* seg_ade, float* seg_fde, int* seg_miss, void* stream) {
+    STT_REQUIRE(pred && gt && ade && fde, "sttode_best_of_k_select: null pointer (pred, gt, ade and fde are required)");
+    STT_REQUIRE(n > 0 && K > 0 && Tf > 0, "sttode_best_of_k_select: n, K, Tf must be positive");
+    STT_REQUIRE(K <= 64, "sttode_best_of_k_select: K > 64 is not supported (one lane per sample); sttode_best_of_k takes any K for ADE / FDE");
+    const bool segs = seg_ade || seg_fde || seg_miss;
+    STT_REQUIRE(!segs || (seg_ptr && S > 0), "sttode_best_of_k_select: per-segment outputs need seg_ptr and S > 0");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(bok_select_kernel, dim3((n + 3) / 4), dim3(256), 0, st, pred, gt, n, K, Tf, scale, miss_threshold, ade, fde,
+                       best_ade_idx, best_fde_idx, miss, best);
+    if (segs)
+        hipLaunchKernelGGL(bok_segments_kernel, dim3((S + 3) / 4), dim3(256), 0, st, (const float*)ade, (const float*)fde, seg_ptr, S, n,
+                           miss_threshold, seg_ade, seg_fde, seg_miss);
     STT_HIP(hipGetLastError());
     return 0;
 }

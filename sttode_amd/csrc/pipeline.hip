@@ -893,6 +893,23 @@ extern "C" int sttode_async_best_of_k(SttodeModel* m, int slot, const float* pre
     return 0;
 }
 
+// Best-of-K selection (utils/metrics.py:7-48) of an asynchronous call's predictions, on the call's own pipeline stream like
+// sttode_async_best_of_k: the slot's outstanding groups first, then sttode_best_of_k_select, then the slot's completion event behind it.
+extern "C" int sttode_async_best_of_k_select(SttodeModel* m, int slot, const float* pred, const float* gt, int n, int K, int Tf, float scale,
+                                             float miss_threshold, const int* seg_ptr, int S, float* ade, float* fde, int* best_ade_idx,
+                                             int* best_fde_idx, unsigned char* miss, float* best, float* seg_ade, float* seg_fde,
+                                             int* seg_miss) {
+    STT_REQUIRE(m && slot >= 0 && slot < STT_MAX_SLOTS, "sttode_async_best_of_k_select: bad model / slot");
+    std::lock_guard<std::mutex> lk(m->mu);
+    STT_REQUIRE(m->slot_stream[slot] != nullptr, "sttode_async_best_of_k_select: no asynchronous call has used this slot");
+    if (int rc = lag_flush(m, slot)) return rc;
+    if (int rc = sttode_best_of_k_select(pred, gt, n, K, Tf, scale, miss_threshold, seg_ptr, S, ade, fde, best_ade_idx, best_fde_idx, miss,
+                                         best, seg_ade, seg_fde, seg_miss, m->slot_stream[slot]))
+        return rc;
+    STT_HIP(hipEventRecord(m->evB_done[slot], m->slot_stream[slot]));
+    return 0;
+}
+
 // The NBA evaluation's per-horizon metric (test.py:530-551) of an asynchronous call, on the call's own pipeline stream like
 // sttode_async_best_of_k: out [n][Tf][2] = per agent and horizon h the min over K of (mean displacement over the first h frames, displacement
 // of frame h) -- sttode_horizon_metrics on the slot's predictions.

@@ -5,8 +5,11 @@
                   Here many scenes go through ONE batched call (set_scene_batch) instead of a Python loop per scene.
   eval_nba     == test.py:495-552  (NBA): per DataLoader batch, min-over-K of the mean / final displacement at the horizons
                   1..future_length (the reference prints every 0.4 s step), weighted by batch size.
+  eval_scenes_report / eval_sampler_report / eval_nba_report: the same loops returning an EvalReport -- global ADE / FDE and miss rate,
+                  per-scene (per NBA batch) ADE / FDE / miss count, the best sample of every agent (utils/metrics.py:29-48).
 """
 import contextlib
+import dataclasses
 
 import numpy as np
 import torch
@@ -169,3 +172,176 @@ def eval_nba(model, loader, traj_scale=1.0, z_fn=None, pipelined=True, groups_pe
     model.reset_async()
     acc = torch.stack(totals).sum(dim=0).cpu().numpy() / count
     return {h + 1: (float(acc[h, 0]), float(acc[h, 1])) for h in range(Tf)}
+
+
+# ----- report forms: per-scene results, best samples and miss rate (utils/metrics.py:29-48, test.py:193-205, test_sampler.py:214-217) ------
+
+@dataclasses.dataclass
+class EvalReport:
+    """What the report loops return.  Global: ``ade`` / ``fde`` (mean over agents, the values eval_scenes / eval_sampler return),
+    ``n_agents``, ``miss_count`` / ``miss_rate`` (agents whose best FDE exceeds ``miss_threshold``, count_miss_samples).  Per scene -- per
+    loader batch for NBA -- in dataset order: ``scene_ade`` / ``scene_fde`` (compute_ADE / compute_FDE of that scene alone), ``scene_miss``
+    (its miss count), ``scene_agents``.  Per agent in dataset order: ``best_idx`` (get_best_idx: the sample with the smallest ADE, the first
+    on ties), ``best_fde_idx``, and with ``gather=True`` ``best`` [n, Tf, 2], the predictions of that sample (unscaled)."""
+    ade: float
+    fde: float
+    n_agents: int
+    miss_count: int
+    miss_rate: float
+    miss_threshold: float
+    scene_ade: np.ndarray
+    scene_fde: np.ndarray
+    scene_miss: np.ndarray
+    scene_agents: np.ndarray
+    best_idx: np.ndarray
+    best_fde_idx: np.ndarray
+    best: np.ndarray = None
+
+
+class _ReportAcc:
+    """Host side of a report loop: per call, the same double sums eval_scenes forms (so the global ADE / FDE agree bit for bit), and the
+    small per-scene / per-agent arrays."""
+
+    def __init__(self, miss_threshold):
+        self.thr = float(miss_threshold)
+        self.tot_a = self.tot_f = 0.0
+        self.n = 0
+        self.parts = []
+
+    def add(self, sel, seg_ptr):
+        self.tot_a += float(sel.ade.double().sum())
+        self.tot_f += float(sel.fde.double().sum())
+        self.n += int(sel.ade.numel())
+        sp = seg_ptr.cpu().numpy() if isinstance(seg_ptr, torch.Tensor) else np.asarray(seg_ptr)
+        self.parts.append((sel.seg_ade.cpu().numpy(), sel.seg_fde.cpu().numpy(), sel.seg_miss.cpu().numpy(), np.diff(sp),
+                           sel.best_ade_idx.cpu().numpy(), sel.best_fde_idx.cpu().numpy(), None if sel.best is None else sel.best.cpu().numpy()))
+
+    def report(self, gather):
+        cat = [np.concatenate([p[i] for p in self.parts]) for i in range(6)]
+        miss = int(cat[2].sum())
+        return EvalReport(ade=self.tot_a / self.n, fde=self.tot_f / self.n, n_agents=self.n, miss_count=miss, miss_rate=miss / self.n,
+                          miss_threshold=self.thr, scene_ade=cat[0], scene_fde=cat[1], scene_miss=cat[2], scene_agents=cat[3].astype(np.int64),
+                          best_idx=cat[4], best_fde_idx=cat[5], best=np.concatenate([p[6] for p in self.parts]) if gather else None)
+
+
+def _scenes_report(model, dataset, scenes_per_call, pipelined, traj_scale, miss_threshold, gather, launch, serial):
+    acc = _ReportAcc(miss_threshold)
+    pend = []
+
+    def finish(item):
+        h, sel, sp = item
+        model.wait(h)
+        acc.add(sel, sp)
+    for s0 in range(0, len(dataset), scenes_per_call):
+        sb = dataset.scene_batch(range(s0, min(s0 + scenes_per_call, len(dataset))))
+        model.set_scene_batch(sb.past, sb.future, sb.scene_ptr)
+        if pipelined:
+            if len(model._async_bufs) > 12:                               # batches of ever new sizes: per-shape slot buffers are dropped in time
+                while pend:
+                    finish(pend.pop(0))
+                model.reset_async()
+            h = launch(sb)
+            sel = model.select_best_of_k_async(h, scale=traj_scale, miss_threshold=miss_threshold, seg_ptr='scenes', gather=gather)
+            pend.append((h, sel, sb.scene_ptr))
+            if len(pend) > 4:
+                finish(pend.pop(0))
+            continue
+        pred = serial(sb)                                                  # [K, n, Tf, 2]
+        sel = model.select_best_of_k(pred.permute(1, 0, 2, 3), scale=traj_scale, miss_threshold=miss_threshold, seg_ptr=model._scene_ptr,
+                                     gather=gather)
+        acc.add(sel, sb.scene_ptr)
+    while pend:
+        finish(pend.pop(0))
+    if pipelined:
+        model.reset_async()
+    return acc.report(gather)
+
+
+@torch.no_grad()
+def eval_scenes_report(model, dataset, traj_scale=1.0, scenes_per_call=512, z_fn=None, pipelined=True, miss_threshold=1.0, gather=False):
+    """eval_scenes with the per-scene breakdown, the best sample of every agent and the miss rate (an ``EvalReport``).  The same calls, latents
+    and global ADE / FDE as eval_scenes; each call adds one selection pass on its own pipeline stream (``select_best_of_k_async``)."""
+    K, zd = model.args.sample_k, model.args.zdim
+
+    def latents(sb):
+        rows = sb.n_agents * K
+        return z_fn(rows) if z_fn is not None else torch.randn(rows, zd, device=model.device)
+    return _scenes_report(model, dataset, scenes_per_call, pipelined, traj_scale, miss_threshold, gather,
+                          lambda sb: model.inference_async(z=latents(sb), metrics_gt=model._future, metrics_scale=traj_scale),
+                          lambda sb: model.inference(None, z=latents(sb)))
+
+
+@torch.no_grad()
+def eval_sampler_report(model, sampler, dataset, traj_scale=1.0, scenes_per_call=512, mean=True, eps_fn=None, pipelined=True,
+                        miss_threshold=1.0, gather=False):
+    """eval_sampler with the per-scene breakdown, the best sample of every agent and the miss rate (an ``EvalReport``; test_sampler.py:214-217
+    asks count_miss_samples of the same loop)."""
+    def eps_of(sb):
+        return eps_fn(1 if sampler.share_eps else sb.n_agents) if (not mean and eps_fn is not None) else None
+    return _scenes_report(model, dataset, scenes_per_call, pipelined, traj_scale, miss_threshold, gather,
+                          lambda sb: sampler.inference_async(model, mean=mean, eps=eps_of(sb), metrics_gt=model._future,
+                                                             metrics_scale=traj_scale),
+                          lambda sb: sampler.inference(model, mean=mean, eps=eps_of(sb)))
+
+
+@torch.no_grad()
+def eval_nba_report(model, loader, traj_scale=1.0, z_fn=None, pipelined=True, groups_per_call=16, miss_threshold=1.0, gather=False):
+    """NBA evaluation (test.py:495-552) as an ``EvalReport``: ADE / FDE over the whole horizon (the last horizon of eval_nba), the miss rate,
+    per loader batch its ADE / FDE / miss count, the best sample of every agent.  Calls as eval_nba: up to ``groups_per_call`` loader batches
+    of one shape per call, several in flight, the selection on each call's pipeline stream with one segment per loader batch."""
+    Tf, K = model.args.future_length, model.args.sample_k
+    dev = model.device
+    acc = _ReportAcc(miss_threshold)
+    if not pipelined:
+        for data in loader:
+            model.set_data_nba(data)
+            n = data['past_traj'].shape[0] * data['past_traj'].shape[1]
+            z = z_fn(n * K) if z_fn is not None else None
+            pred = model.inference(data, z=z)                                   # [K, n, Tf, 2]
+            sp = np.array([0, n], dtype=np.int32)
+            acc.add(model.select_best_of_k(pred.permute(1, 0, 2, 3), scale=traj_scale, miss_threshold=miss_threshold, seg_ptr=sp,
+                                           gather=gather), sp)
+        return acc.report(gather)
+
+    pend = []
+    seg_ptrs = {}
+
+    def finish(item):
+        h, sel, sp = item
+        model.wait(h)
+        acc.add(sel, sp)
+
+    def submit(group):
+        B, N = group[0]['past_traj'].shape[:2]
+        G = len(group)
+        past = torch.stack([torch.as_tensor(d['past_traj'], dtype=torch.float32) for d in group])
+        fut = torch.stack([torch.as_tensor(d['future_traj'], dtype=torch.float32) for d in group])
+        n = G * B * N
+        if (G, B * N) not in seg_ptrs:                                     # one segment per loader batch, complete before any stream reads it
+            seg_ptrs[(G, B * N)] = torch.arange(0, n + 1, B * N, dtype=torch.int32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+        sp = seg_ptrs[(G, B * N)]
+        model.packed()
+        st = model.next_async_stream(n)
+        with torch.cuda.stream(st) if st is not None else contextlib.nullcontext():
+            model.set_data_nba({'past_traj': past.to(dev, non_blocking=True), 'future_traj': fut.to(dev, non_blocking=True)})
+            z = torch.cat([torch.as_tensor(z_fn(B * N * K)).to(dev) for _ in group]) if z_fn is not None else None
+            h = model.inference_async(z=z)
+        sel = model.select_best_of_k_async(h, gt=model._future, scale=traj_scale, miss_threshold=miss_threshold, seg_ptr=sp, gather=gather)
+        pend.append((h, sel, np.arange(0, n + 1, B * N)))
+        if len(pend) > 3:
+            finish(pend.pop(0))
+
+    group = []
+    for data in loader:
+        shape = tuple(data['past_traj'].shape)
+        if group and (tuple(group[0]['past_traj'].shape) != shape or len(group) >= groups_per_call):
+            submit(group)
+            group = []
+        group.append(data)
+    if group:
+        submit(group)
+    while pend:
+        finish(pend.pop(0))
+    model.reset_async()
+    return acc.report(gather)

@@ -1016,6 +1016,51 @@ class STTODENet(nn.Module):
         return mb[0], mb[1]
 
     @torch.no_grad()
+    def select_best_of_k(self, pred_nk, gt=None, scale=1.0, miss_threshold=1.0, seg_ptr=None, gather=False):
+        """Best-of-K selection on device (utils/metrics.py:7-48): pred_nk [n,K,Tf,2], gt [n,Tf,2] (default: the futures set with the batch).
+        Returns a ``metrics.Selection``: per agent ade / fde (the values of best_of_k, bit for bit), best_ade_idx / best_fde_idx (get_best_idx:
+        the first sample on exact ties), miss (fde > miss_threshold, count_miss_samples) and, with ``gather=True``, best [n,Tf,2] =
+        pred_nk[a, best_ade_idx[a]]; per segment of the CSR ``seg_ptr`` [S+1] (e.g. the scene_ptr of set_scene_batch) the mean ADE / FDE and
+        the miss count.  K <= 64."""
+        from . import metrics
+        gt = self._future if gt is None else _f32(gt, self.device)
+        return metrics.select(pred_nk, gt, scale=scale, miss_threshold=miss_threshold, seg_ptr=seg_ptr, gather=gather)
+
+    def select_best_of_k_async(self, handle, gt=None, scale=1.0, miss_threshold=1.0, seg_ptr=None, gather=False):
+        """select_best_of_k of an inference_async() call, enqueued on the pipeline stream the call runs on, behind its trajectory groups
+        (fused metrics of the call or not); nothing goes onto the caller's stream.  ``gt`` (default: the futures set with the batch) and
+        ``seg_ptr`` (a device int32 tensor, or 'scenes': the call's own scene_ptr) must have been written before the inference_async()
+        call.  Returns a ``metrics.Selection`` whose tensors are valid after ``wait(handle)``; the handle keeps it alive."""
+        from . import metrics
+        if isinstance(seg_ptr, str):
+            if seg_ptr != 'scenes' or handle['inputs'][1] is None:
+                raise ValueError("seg_ptr='scenes' needs a call made on a scene batch (set_scene_batch / set_data)")
+            seg_ptr = handle['inputs'][1]
+        gt = handle.get('gt_default') if gt is None else gt
+        if handle.get('generic'):
+            sel = self.select_best_of_k(handle['pred'], gt=gt, scale=scale, miss_threshold=miss_threshold, seg_ptr=seg_ptr, gather=gather)
+            handle['selection'] = sel
+            return sel
+        if not (isinstance(gt, torch.Tensor) and gt.is_cuda and gt.dtype == torch.float32 and gt.is_contiguous()):
+            raise ValueError('select_best_of_k_async needs a contiguous float32 device tensor gt [n, Tf, 2] that was written before the call')
+        if seg_ptr is not None and not (isinstance(seg_ptr, torch.Tensor) and seg_ptr.is_cuda and seg_ptr.dtype == torch.int32
+                                        and seg_ptr.is_contiguous()):
+            raise ValueError('select_best_of_k_async needs seg_ptr as a contiguous int32 device tensor written before the call')
+        pred = handle['pred']                                    # contiguous [n, K, Tf, 2]
+        n, K, Tf = pred.shape[:3]
+        metrics.check_k(K)
+        if tuple(gt.shape) != (n, Tf, 2):
+            raise ValueError(f'gt must be [{n}, {Tf}, 2], got {tuple(gt.shape)}')
+        S = int(seg_ptr.numel()) - 1 if seg_ptr is not None else 0
+        sel = metrics.Selection(n, S, Tf, self.device, gather)
+        capi.call('sttode_async_best_of_k_select', self.native().h, handle['slot'], pred, gt, n, K, Tf, float(scale), float(miss_threshold),
+                  seg_ptr, S, *sel.args())
+        if handle.get('stream') is not None:
+            sel.record_stream(handle['stream'])
+        handle['selection'] = sel
+        return sel
+
+    @torch.no_grad()
     def horizon_metrics(self, pred_nk, gt=None, scale=1.0):
         """The NBA evaluation's per-horizon metric (test.py:530-551) on device: pred_nk [n,K,Tf,2], gt [n,Tf,2] -> [n,Tf,2] with
         [a, h-1] = (min_k mean_{t<h} |scale (pred - gt)|, min_k |scale (pred_h - gt_h)|)."""
