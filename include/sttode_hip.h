@@ -24,7 +24,7 @@ extern "C" {
 #endif
 
 /* Version of this header: the library returns it from sttode_abi_version(); a binding compares before its first call (round 1-2: 1). */
-#define STTODE_ABI_VERSION 11
+#define STTODE_ABI_VERSION 12
 int sttode_abi_version(void);
 const char* sttode_last_error(void);
 
@@ -113,9 +113,8 @@ int sttode_gru_cols(const float* xin, const float* convP, const float* convB, co
 
 /* Process-wide crossover between the latency forms of sttode_gru_cols / sttode_mlp_block0 / sttode_mlp_block1 / sttode_embed_qkv (one
  * 16-column tile per WORKGROUP, its waves splitting the rows: a single scene of test.py:171-188) and their throughput forms (a tile per
- * wave): the latency form serves calls of at most this many 16-column tiles.  Negative = leave unchanged; defaults 512 / 1024 / 1024
- * (env STTODE_GRU_LAT_TILES / STTODE_MLP_LAT_TILES / STTODE_ENC_LAT_TILES).  Both forms sum in the same order: results are bitwise
- * independent of the setting. */
+ * wave): the latency form serves calls of at most this many 16-column tiles.  Negative = leave unchanged; defaults 512 / 1024 / 1024.
+ * Both forms sum in the same order: results are bitwise independent of the setting. */
 int sttode_set_latency_tiles(int gru_tiles, int mlp_tiles, int enc_tiles);
 
 /* Generic per-column linear out[col, 0:N] = act(W [X1 | X2] + b) (nn.Linear; used for the per-agent part of
@@ -507,13 +506,10 @@ int sttode_workspace_layout(const SttodeModel* m, int n, int S, long* offsets /*
  * workgroup of every launch zeroes them again -- so it needs no memset in front of a launch and a captured sttode_inference_scenes replays
  * correctly; launched on a workspace that was never initialised it refuses the flag words it finds: NaN predictions, time-out word 2. */
 int sttode_workspace_init(SttodeModel* m, float* workspace, int n, int S, void* stream);
-/* number of column parts (1..8) the per-trajectory kernels are pipelined over on separate streams (default 1,
- * or env STTODE_COL_PARTS); results are bitwise independent of it. */
-int sttode_set_col_parts(SttodeModel* m, int parts);
 /* per-trajectory stage: 1 = fused chain kernel (sttode_traj_chain), 0 = the three-kernel form (mlp_block0 -> gru_cols -> mlp_block1),
- * -1 = automatic (fused when the batch has >= 128 trajectories per workgroup slot to fill; default, or env STTODE_CHAIN). */
+ * -1 = automatic (fused when the batch has >= 128 trajectories per workgroup slot to fill; default). */
 int sttode_set_chain(SttodeModel* m, int mode);
-/* Calls whose per-trajectory stage takes the fused chain: 1 (default, or env STTODE_FUSED) = the per-agent stage (encoder, block-0 GRU,
+/* Calls whose per-trajectory stage takes the fused chain: 1 (default) = the per-agent stage (encoder, block-0 GRU,
  * layer-1 pre-activation tables: PastEncoder.forward model/STTODE.py:214-236, DecomposeBlock.forward :62-75 of block 0) runs as the
  * leading workgroups of the chain launch, trajectory groups wait on one flag per 16-agent tile (attention groups > 1, the NBA branch:
  * the embedding and the attention stay launches in front, the roles start at the post-attention layer); 2 = as 1, and for scene batches
@@ -556,7 +552,7 @@ int sttode_async_best_of_k(SttodeModel* m, int slot, const float* pred, const fl
 /* Serial scene calls (sttode_inference_scenes) below the chain threshold -- the reference's evaluation loop hands over ONE scene per call
  * (test.py:171-188) -- run as ONE launch whose workgroups take the roles front-end + per-agent stage / block-0 decoder_y / block-0
  * decoder_x -> block-1 GRU -> block-1 decoder_y and hand tables over through flags (csrc/scene_lat.hip), when the call has at most
- * `max_tiles` 16-trajectory tiles: -1 = default (128, or env STTODE_SCENE_LAUNCH), 0 = never (six launches, as round 2).  Bitwise the
+ * `max_tiles` 16-trajectory tiles: -1 = default (128), 0 = never (six launches, as round 2).  Bitwise the
  * same predictions either way.  Replaces: model/STTODE.py:397-461 + :553-627 for one scene. */
 int sttode_set_scene_launch(SttodeModel* m, int max_tiles);
 /* Grid order of the fused launch (host-callable, no GPU): block -> group index (>= 0) or -1 - tile for the per-agent role of a 16-agent

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Same-box A/B of one environment switch on the headline bench, alternating runs (the first process on a fresh box runs slow: discarded):
-#   gpurun -- 'bash profiles/exp_ab_env.sh STTODE_GRU0_LAT_TILES 1 4096 "512 256"'
+#   bash profiles/exp_ab_env.sh STTODE_LAGGED 2 3 "512 256"      (from the repository root, on the GPU box)
 VAR=$1; A=$2; B=$3; SCENES=${4:-512}
 timeout -k 10 200 python bench.py --legs none --no-cpu --steps 10 > /dev/null 2>&1
 for S in $SCENES; do

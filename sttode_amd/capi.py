@@ -11,7 +11,7 @@ _LIB = None
 LIB_PATH = os.environ.get('STTODE_HIP_LIB') or os.path.join(os.path.dirname(os.path.abspath(__file__)), 'lib', 'libsttode_hip.so')
 
 _P, _I, _L, _F, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double
-ABI_VERSION = 11  # == STTODE_ABI_VERSION of include/sttode_hip.h; lib() refuses a library built from another header
+ABI_VERSION = 12  # == STTODE_ABI_VERSION of include/sttode_hip.h; lib() refuses a library built from another header
 
 # name -> argtypes (mirrors include/sttode_hip.h; tests/test_capi_symbols.py checks header == table == .so)
 SIGNATURES = {
@@ -92,7 +92,6 @@ SIGNATURES = {
     'sttode_workspace_init': [_P, _P, _I, _I, _P],
     'sttode_timeout_word': [_P, ctypes.POINTER(ctypes.c_void_p)],
     'sttode_timeout_clear': [_P],
-    'sttode_set_col_parts': [_P, _I],
     'sttode_set_chain': [_P, _I],
     'sttode_set_fused': [_P, _I],
     'sttode_set_mfma_mode': [_P, _I],
@@ -200,10 +199,6 @@ class NativeModel:
                 raise SttodeError('sttode_workspace_layout failed: ' + lib().sttode_last_error().decode())
             self._layouts[key] = (dict(zip(BUFFERS, list(off))), int(tot.value))
         return self._layouts[key]
-
-    def set_col_parts(self, parts):
-        if lib().sttode_set_col_parts(self.h, int(parts)) != 0:
-            raise SttodeError('sttode_set_col_parts failed: ' + lib().sttode_last_error().decode())
 
     def set_chain(self, mode):
         """1: fused per-trajectory chain kernel, 0: three-kernel form, -1: automatic."""

@@ -74,7 +74,7 @@ struct Role32Args {   // throughput-form per-agent roles (role32.hpp)
     float* pf; float* state0; float* A0x; float* A0y; float* A1y;             // [n][128], [n][96], [n][512] x 3
     int n, Tp, kte, nwg;                                                      // agents, observed frames, k-tiles of x, role workgroups in the grid
     float ode_time;
-    int prio;       // > 0: the role waves run at s_setprio 3 (default; STTODE_ROLE_PRIO=0: A/B)
+    int prio;       // > 0: the role waves run at s_setprio 3 (stt_chain_lagged sets 3)
     int* counter;   // work queue of THIS call's trajectory groups (a later launch of the same stream): zeroed by role workgroup 0
     float* zgen; unsigned zkey0, zkey1; int K;   // zgen != nullptr: the roles draw this call's latents z [n K][32] ~ N(0, I) themselves (role32.hpp latents32)
     // past != nullptr (scene batches): the roles run STTODENet.set_data for their own 128 agents first (role32.hpp frontend32) -- no front-end
@@ -1080,33 +1080,23 @@ template <int NY, int FUSE, bool B3M = false> static int chain_launch(ChainArgs 
     void (*kern)(ChainArgs) = gru_zero_skip() ? traj_chain_kernel<NY, FUSE, B3M, true> : traj_chain_kernel<NY, FUSE, B3M, false>;
     STT_SET_LDS_ONCE(kern, 96 * 1024);   // once per (instantiation, device): the switch is read once per process
     const int ngroups = (a.ncols + 127) / 128;
-    // STTODE_CHAIN_RESERVE=r leaves r of the chip's 2-per-CU workgroup slots to concurrently running kernels (the per-agent stage
-    // of the next call in the pipelined form); the work queue makes the remaining workgroups absorb the groups
-    static int reserve = -1;
-    if (reserve < 0) { const char* e = getenv("STTODE_CHAIN_RESERVE"); reserve = e ? atoi(e) : 0; if (reserve < 0 || reserve > chain_cus()) reserve = 0; }
-    int grid = 2 * chain_cus() - reserve;
-    if (grid > ngroups || !a.persistent) grid = ngroups;
+    int grid = ngroups;   // FUSE 0: one group per workgroup
     if (FUSE == 1) grid = (a.R.split ? 5 : 1) * a.R.ntiles + ngroups;   // roles ahead of their consumers, one group per workgroup
     else if (FUSE == 2) {   // another call's throughput-form roles, then this call's groups: one workgroup each, or (persistent) workers
         int workers = ngroups;
-        const int cap = a.persistent > 1 ? a.persistent : 2 * chain_cus();   // workers: the chip's workgroup slots (or STTODE_LAG_WORKERS=count)
-        if (a.persistent && workers > cap) workers = cap;
+        if (a.persistent && workers > 2 * chain_cus()) workers = 2 * chain_cus();   // workers: the chip's workgroup slots
         grid = a.R32.nwg + (a.ncols > 0 ? workers : 0);
         a.nworkers = workers;
         if (workers < ngroups) a.xcd_map = 0;   // (the XCD-aware order is a permutation of one-workgroup-per-group grids)
     }
-    else if (a.persistent) STT_HIP(hipMemsetAsync(a.counter, 0, sizeof(int), s));   // the work queue of the persistent form
     // wgs_per_cu == 1: ask for more than half of the CU's LDS so that only ONE chain workgroup is resident per CU.  A lone workgroup
     // keeps the matrix pipe about as busy as two do (469 vs 2 x 397 us per group), and the other half of the register file plus ~76 KiB
     // of LDS stay free for kernels of OTHER streams (the separate per-agent launches of the unfused pipeline).  The fused launch needs
     // no co-residency and runs two per CU everywhere.
-    static int wgs_env = -1;   // STTODE_CHAIN_WGS=1|2 overrides the caller's choice (experiments)
-    if (wgs_env < 0) { const char* e = getenv("STTODE_CHAIN_WGS"); wgs_env = e ? atoi(e) : 0; }
-    const int wgs = wgs_env > 0 ? wgs_env : wgs_per_cu;
     int lds = chain_lds(NY, a.prog_len, B3M);
     if (FUSE == 1 && lds < role_lds(a.Tp)) lds = role_lds(a.Tp);
     if (FUSE == 2 && a.R32.nwg > 0 && lds < role32_lds(a.R32.prog_len)) lds = role32_lds(a.R32.prog_len);
-    if (wgs == 1 && lds < 84 * 1024) lds = 84 * 1024;
+    if (wgs_per_cu == 1 && lds < 84 * 1024) lds = 84 * 1024;
     STT_REQUIRE(lds <= 96 * 1024, "sttode_traj_chain: dynamic LDS beyond the 96 KiB the kernel is registered for");
     if (FUSE == 1) STT_HIP(hipMemsetAsync(a.R.flags, 0, (((size_t)(a.R.split ? 5 : 1) * a.R.ntiles + 1) * 4 + 15) / 16 * 16, s));   // tile flags + time-out word
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a);
@@ -1225,13 +1215,9 @@ static int traj_chain_impl(const float* A0x, const float* A0y, const float* A1y,
     a.ncols = ncols; a.K = K; a.Tp = Tp; a.Tf2 = 2 * Tf;
     a.dbg = nullptr; a.trace_tag = 0; a.xcd_map = 0; a.nworkers = 0; a.m_gt = nullptr; a.m_ade = a.m_fde = nullptr; a.m_scale = 1.0f;
     a.R = RoleArgs();   // unused by the unfused instantiation
-    {
-        static int pers = -1;   // default 0: one group per workgroup (slots free up continuously, so kernels of other streams -- the next
-                                // call's per-agent stage, the next chain -- interleave at group granularity; measured 1.38 vs 1.87 ms per
-                                // 256-scene step); STTODE_CHAIN_PERSISTENT=1: workgroups pull groups from the atomic work queue
-        if (pers < 0) { const char* e = getenv("STTODE_CHAIN_PERSISTENT"); pers = e ? (atoi(e) != 0) : 0; }
-        a.persistent = pers;
-    }
+    // one group per workgroup (slots free up continuously, so kernels of other streams -- the next call's per-agent stage, the next chain --
+    // interleave at group granularity; measured 1.38 vs 1.87 ms per 256-scene step against workgroups pulling groups from a work queue)
+    a.persistent = 0;
 #if defined(C32_DIAG_STAMPS) || defined(C32_DIAG_TRACE)
     a.dbg = g_chain_dbg;
     a.trace_tag = g_trace_tag++;
@@ -1239,7 +1225,6 @@ static int traj_chain_impl(const float* A0x, const float* A0y, const float* A1y,
     const int NY = (2 * Tf + 31) / 32;
     hipStream_t s = (hipStream_t)stream;
     if (b3) {
-        a.persistent = 0;
         switch (NY) {
             case 1: return chain_launch<1, 0, true>(a, wgs_per_cu, s);
             case 2: return chain_launch<2, 0, true>(a, wgs_per_cu, s);
@@ -1307,11 +1292,7 @@ int stt_chain_fused(const float* const* W, float* ws, const long* off, int n, in
     // SERIAL launch is 5 % slower interleaved (0.65 vs 0.69 of peak): a role beside a trajectory group runs 2x longer than beside
     // other roles, and holds its slot all the while
     r.lead = lead < 0 ? (1 << 28) : lead;
-    {   // XCD-aware group order whenever all roles sit in front of the groups (STTODE_XCD_MAP=0: plain block order, for A/B)
-        static int xm = -1;
-        if (xm < 0) { const char* e = getenv("STTODE_XCD_MAP"); xm = e ? atoi(e) != 0 : 1; }
-        a.xcd_map = xm && lead < 0;
-    }
+    a.xcd_map = lead < 0;   // XCD-aware group order whenever all roles sit in front of the groups (profiles/r03/ab_xcd_map.txt)
     r.split = lead == -2;   // -2: roles first, each tile's role split into E | G | three table workgroups (opt-in, sttode_set_fused mode 4); -1 (default): one workgroup per tile
     r.gflags = r.flags + r.ntiles + 1; r.pflags = r.gflags + r.ntiles;
     r.drop_tile = drop_tile;
@@ -1360,19 +1341,15 @@ int stt_chain_lagged(const float* const* W, const LagRoles& lr, const LagGroups&
         a.z = z; a.xpad = ws_g + off_g[STT_B_XPAD]; a.cur = ws_g + off_g[STT_B_CUR]; a.orig = ws_g + off_g[STT_B_ORIG]; a.pred = pred;
         a.park = ws_g + off_g[STT_B_YBUF];   // (m x 16 NOY floats >= m x 2 Tf): the kernel never reads `pred`, which may be pinned host memory
         a.ncols = n_g * K;
-        // Workers (default): the launch holds at most the chip's 2-per-CU workgroup slots, and its workgroups pull groups from the call's
-        // work queue.  One workgroup per group (STTODE_LAG_WORKERS=0) deals the groups to the 8 XCDs statically (block % 8), the next launch
-        // on another queue starts only when this grid is fully dispatched, and the XCDs do not run at one speed: the block trace shows six
-        // XCDs idle for 250-700 us at the end of every launch while the slowest still has blocks to place (profiles/r04/trace_lagged_static.txt)
-        static int workers = -1;
-        if (workers < 0) { const char* e = getenv("STTODE_LAG_WORKERS"); workers = e ? atoi(e) : 1; if (workers < 0) workers = 1; }
+        // Workers: the launch holds at most the chip's 2-per-CU workgroup slots, and its workgroups pull groups from the call's work queue.
+        // One workgroup per group deals the groups to the 8 XCDs statically (block % 8), the next launch on another queue starts only when
+        // this grid is fully dispatched, and the XCDs do not run at one speed: the block trace shows six XCDs idle for 250-700 us at the end
+        // of every launch while the slowest still has blocks to place (profiles/r04/trace_lagged_static.txt)
         // (calls with launches in front of the roles -- the NBA branch's front-end, embedding and attention -- keep one workgroup per group:
         // workers hold every slot until their queue is empty and those kernels would wait for the launch's end; measured -8 % there)
-        a.persistent = lag_workers_ok ? workers : 0;
+        a.persistent = lag_workers_ok ? 1 : 0;
         a.counter = (int*)(ws_g + off_g[STT_B_QUEUE]);       // zeroed by the roles of this call (an earlier launch of this stream)
-        static int xm = -1;
-        if (xm < 0) { const char* e = getenv("STTODE_XCD_MAP"); xm = e ? atoi(e) != 0 : 1; }
-        a.xcd_map = xm;
+        a.xcd_map = 1;
     }
     if (ws_r) {
         STT_REQUIRE(off_r && n_r > 0, "stt_chain_lagged: bad role arguments");
@@ -1390,8 +1367,7 @@ int stt_chain_lagged(const float* const* W, const LagRoles& lr, const LagGroups&
         r.pf = ws_r + off_r[STT_B_PF]; r.state0 = ws_r + off_r[STT_B_STATE0];
         r.A0x = ws_r + off_r[STT_B_A0X]; r.A0y = ws_r + off_r[STT_B_A0Y]; r.A1y = ws_r + off_r[STT_B_A1Y];
         r.n = n_r; r.Tp = Tp; r.nwg = (n_r + 127) / 128; r.ode_time = ode_time;
-        static const int role_prio = getenv("STTODE_ROLE_PRIO") ? atoi(getenv("STTODE_ROLE_PRIO")) : 3;   // role waves outlast the groups of a small launch: SDD-256 / NBA-128 +1..2 %, 512 scenes the same (profiles/r04/role_prio_ab.txt)
-        r.prio = role_prio;
+        r.prio = 3;   // role waves outlast the groups of a small launch: SDD-256 / NBA-128 +1..2 %, 512 scenes the same (profiles/r04/role_prio_ab.txt)
         r.counter = (int*)(ws_r + off_r[STT_B_QUEUE]);
         r.zgen = zgen; r.zkey0 = (unsigned)zkey; r.zkey1 = (unsigned)(zkey >> 32); r.K = K;
         STT_REQUIRE(!past || (scene_ptr && S > 0 && !attn), "stt_chain_lagged: the in-role front-end needs scene_ptr, S > 0 and attention length 1");

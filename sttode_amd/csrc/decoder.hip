@@ -540,12 +540,9 @@ __global__ __launch_bounds__(256) void mlp1_lat_kernel(MlpLatArgs a) {
     __shared__ f32x4 sH1[2 * 4 * 64], sH2[16 * 64];
     mlp_lat_run<8, NOY, 2>(a, sH1, sH2, blockIdx.x);
 }
-// STTODE_MLP_LAT_TILES: largest 16-column tile count served by the latency form of the MLP kernels
-static int g_mlp_lat_tiles = -1, g_gru_lat_tiles = -1;
-static int mlp_lat_tiles() {
-    if (g_mlp_lat_tiles < 0) { const char* e = getenv("STTODE_MLP_LAT_TILES"); g_mlp_lat_tiles = e ? atoi(e) : 1024; }
-    return g_mlp_lat_tiles;
-}
+// largest 16-column tile count served by the latency form of the MLP kernels / of sttode_gru_cols (measured crossover) /
+// of the encoder (encoder.hip); all three set by sttode_set_latency_tiles
+static int g_mlp_lat_tiles = 1024, g_gru_lat_tiles = 512, g_enc_lat_tiles = 1024;
 
 // generic single MLP over columns (training-forward needs decoder_x of the LAST block too: recover_traj sums the x_hat of
 // every block, model/STTODE.py:339-341).  KTV = 8: B = [z | state];  output raw tiles [ncols][16*NO].
@@ -590,12 +587,6 @@ __global__ __launch_bounds__(256, 2) void mlp_cols_kernel(const float* __restric
 // ---------------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------------
-// STTODE_NONPERSISTENT=1 (experiment): one work item per workgroup instead of persistent grids
-static int nonpersistent() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("STTODE_NONPERSISTENT"); v = (e && e[0] == '1') ? 1 : 0; }
-    return v;
-}
 static int g_num_cu = 0;
 static int num_cus() {
     if (!g_num_cu) {
@@ -607,17 +598,8 @@ static int num_cus() {
     return g_num_cu;
 }
 
-// STTODE_GRU_LAT_TILES: largest tile count served by the latency form (default: measured crossover)
-static int gru_lat_tiles() {
-    if (g_gru_lat_tiles < 0) { const char* e = getenv("STTODE_GRU_LAT_TILES"); g_gru_lat_tiles = e ? atoi(e) : 512; }
-    return g_gru_lat_tiles;
-}
-int stt_gru_lat_tiles() { return gru_lat_tiles(); }
-static int g_enc_lat_tiles = -1;
-int stt_enc_lat_tiles() {
-    if (g_enc_lat_tiles < 0) { const char* e = getenv("STTODE_ENC_LAT_TILES"); g_enc_lat_tiles = e ? atoi(e) : 1024; }
-    return g_enc_lat_tiles;
-}
+int stt_gru_lat_tiles() { return g_gru_lat_tiles; }
+int stt_enc_lat_tiles() { return g_enc_lat_tiles; }
 extern "C" int sttode_set_latency_tiles(int gru_tiles, int mlp_tiles, int enc_tiles) {
     if (gru_tiles >= 0) g_gru_lat_tiles = gru_tiles;
     if (mlp_tiles >= 0) g_mlp_lat_tiles = mlp_tiles;
@@ -637,7 +619,7 @@ int stt_gru_cols_form(const float* xin, const float* convP, const float* convB, 
     STT_REQUIRE(ncols > 0 && Tp > 0 && (TPX == 1 || TPX == 2) && 2 * Tp <= 16 * TPX, "sttode_gru_cols: bad ncols/Tp/TPX");
     hipStream_t s = (hipStream_t)stream;
     const int ntiles = (ncols + 15) / 16;
-    if (ntiles <= (lat_max_tiles > 0 ? lat_max_tiles : gru_lat_tiles())) {   // few columns: one tile per workgroup, gate sums split evenly over four waves (latency form)
+    if (ntiles <= (lat_max_tiles > 0 ? lat_max_tiles : g_gru_lat_tiles)) {   // few columns: one tile per workgroup, gate sums split evenly over four waves (latency form)
         if (lat_max_tiles > 0) {   // beside a chain workgroup of another stream: the six-wave form (<= 128 VGPRs per wave); the balanced one needs 270-290
             if (TPX == 1)
                 hipLaunchKernelGGL(gru_cols_lat_kernel<1>, dim3(ntiles), dim3(384), 0, s, xin, (const f32x4*)convP, convB, (const f32x4*)wihP,
@@ -736,7 +718,7 @@ extern "C" int sttode_mlp_block0(const float* A0x, const float* A0y, const float
     STT_REQUIRE(A0x && A0y && stream && z && xpad && dbuf && ybuf, "sttode_mlp_block0: null pointer");
     STT_REQUIRE(ncols > 0 && K > 0, "sttode_mlp_block0: ncols and K must be positive");
     STT_REQUIRE(total_chunks == 64 + TPX + NOY, "sttode_mlp_block0: weight stream must hold (32+TPX) + (32+NOY) chunks");
-    if ((ncols + 15) / 16 <= mlp_lat_tiles()) {   // few columns: latency form (four waves share one 16-column tile)
+    if ((ncols + 15) / 16 <= g_mlp_lat_tiles) {   // few columns: latency form (four waves share one 16-column tile)
         MlpLatArgs ax, ay;
         ax.A0 = A0x; ax.blob = (const f32x4*)stream; ax.z = z; ax.state = nullptr; ax.xpad = xpad; ax.ybuf = nullptr; ax.cur = nullptr;
         ax.orig = nullptr; ax.out = dbuf; ax.ncols = ncols; ax.K = K; ax.Tf2 = 0; ax.out_lds = nullptr; ax.state_lds = nullptr; ax.a0_lds = nullptr;
@@ -765,7 +747,7 @@ extern "C" int sttode_mlp_block0(const float* A0x, const float* A0y, const float
     }
     const int ngroups = (ncols + 63) / 64;
     int grid = MLP0_WGS * num_cus();   // workgroups per CU; even blockIdx = x role, odd = y role
-    if (grid > 2 * ngroups || nonpersistent()) grid = 2 * ngroups;
+    if (grid > 2 * ngroups) grid = 2 * ngroups;
     grid &= ~1;
     if (grid < 2) grid = 2;
     hipStream_t s = (hipStream_t)stream_;
@@ -795,7 +777,7 @@ extern "C" int sttode_mlp_block1(const float* A1y, const float* stream, int tota
     STT_REQUIRE(A1y && stream && z && state1 && ybuf && cur && orig && pred, "sttode_mlp_block1: null pointer");
     STT_REQUIRE(ncols > 0 && K > 0 && Tf > 0 && 2 * Tf <= 16 * NOY, "sttode_mlp_block1: bad ncols/K/Tf/NOY");
     STT_REQUIRE(total_chunks == 32 + NOY, "sttode_mlp_block1: weight stream must hold 32+NOY chunks");
-    if ((ncols + 15) / 16 <= mlp_lat_tiles()) {   // few columns: latency form
+    if ((ncols + 15) / 16 <= g_mlp_lat_tiles) {   // few columns: latency form
         MlpLatArgs a;
         a.A0 = A1y; a.blob = (const f32x4*)stream; a.z = z; a.state = state1; a.xpad = nullptr; a.ybuf = ybuf; a.cur = cur; a.orig = orig;
         a.out = pred; a.ncols = ncols; a.K = K; a.Tf2 = 2 * Tf; a.out_lds = nullptr; a.state_lds = nullptr; a.a0_lds = nullptr;
@@ -820,7 +802,7 @@ extern "C" int sttode_mlp_block1(const float* A1y, const float* stream, int tota
     }
     const int ngroups = (ncols + 63) / 64;
     int grid = 3 * num_cus();
-    if (grid > ngroups || nonpersistent()) grid = ngroups;
+    if (grid > ngroups) grid = ngroups;
     hipStream_t s = (hipStream_t)stream_;
 #define L1(NY)                                                                                                              \
     do {                                                                                                                    \

@@ -15,11 +15,14 @@
 #include <utility>
 #include <cstring>
 #include <mutex>
-
 #include <cstdlib>
-#define STT_MAX_PARTS 8
+
 #define STT_MAX_DEVICES 64
 #define STT_MAX_SLOTS 8   // workspace / prediction slots of the cross-call pipeline (sttode_inference_*_async)
+// Pipelined form's block-0 GRU: the latency form up to this many 16-agent tiles -- its workgroups (no LDS-resident weights) co-reside with the
+// previous calls' chain workgroups, the resident-weights form (144 KiB of LDS) only gets chain-free CUs: 65 -> 68 M trajectories/s at 512
+// scenes (same box), neutral at 128 / 256 / 1024 / 2048 scenes
+#define STT_GRU0_LAT_TILES 4096
 struct TimRec { int stage; hipEvent_t e0, e1; };
 
 // LAGGED form: a call whose per-agent roles have been enqueued (in the launch it made) but whose trajectory groups have not yet
@@ -33,9 +36,6 @@ struct SttodeModel {
     int n_chunks0, n_chunks1;
     hipStream_t side;
     hipEvent_t ev_fork, ev_join;
-    // column-part pipelining of the per-trajectory kernels: part p runs mlp_block0 -> gru_cols -> mlp_block1 on its own
-    // stream, so the grid tail of one part's kernel is filled by the next part's kernel (columns are independent).
-    int col_parts;
     int chain_mode;  // 1 fused chain kernel, 0 three-kernel form, -1 automatic
     int fused_mode;  // 1 per-agent roles inside the chain launch wherever the shape is covered, 0 separate per-agent launches
     int role_lead;   // fused launch's grid order: groups of head start of a role over its first consumer, < 0 = all roles first (default)
@@ -43,11 +43,9 @@ struct SttodeModel {
     int scene_launch; // largest number of 16-trajectory tiles a serial scene call runs as ONE launch (scene_lat.hip); 0: never
     int drop_tile;   // fault injection (tests): the role of this 16-agent tile does not publish its flag in fused launches (-1: none)
     int b3;          // exploratory: block-0 MLPs of the fused launch as a three-way bf16 split (sttode_set_mfma_mode)
-    bool fe_in_role; // fused scene batches: the roles also run the scene front-end (STTODE_FE_IN_ROLE=1; default: a launch in front)
+    bool fe_in_role; // fused scene batches: the roles also run the scene front-end (sttode_set_fused mode 2; default: a launch in front)
     int ode_method, ode_steps;  // integrator of the encoder ODE (0, 1 = one Euler step = the reference)
     int prog_len;
-    hipStream_t part_stream[STT_MAX_PARTS];
-    hipEvent_t ev_agents, ev_part[STT_MAX_PARTS];
     // cross-call software pipeline (sttode_inference_*_async): stage A (per agent) of call i+1 runs on sA beside stage B
     // (per trajectory) of call i on sB; two workspace slots alternate.
     hipStream_t sA, sB, sB2;
@@ -57,10 +55,8 @@ struct SttodeModel {
     long lag_calls;
     LagPending lag[STT_MAX_SLOTS];   // per slot
     int lag_q[4][STT_MAX_SLOTS]; int lag_qn[4];   // per stream: slots with outstanding groups, oldest first
-    hipStream_t sX[3];   // extra streams of the fused rotation (STTODE_FUSED_STREAMS = 4..6; experiments: they share the runtime's hardware queues)
-    int fused_streams;
-    int b_streams;  // 1: all per-trajectory stages on sB; 2: alternate calls between sB and sB2
-    long acalls;
+    hipStream_t sLag4;   // fourth stream of the lagged rotation (lag_streams == 4; it shares a hardware queue with one of the other three)
+    long acalls;         // asynchronous calls not of the lagged form: the unfused ones alternate their per-trajectory stage between sB and sB2
     hipEvent_t ev_call, evA_done[STT_MAX_SLOTS], evB_done[STT_MAX_SLOTS];
     bool timing;        // brackets active for the CURRENT call
     int timing_every;   // 0 = off, n = bracket every n-th forward call
@@ -122,15 +118,12 @@ extern "C" int sttode_model_create(SttodeModel** out, const void* const* weights
     m->timing = false;
     m->timing_every = 0;
     m->calls = 0;
-    m->b_streams = 2;
     m->acalls = 0;
-    if (const char* e = getenv("STTODE_B_STREAMS")) m->b_streams = atoi(e) == 2 ? 2 : 1;
     m->chain_mode = -1;
     m->ode_method = 0; m->ode_steps = 1;
-    if (const char* e = getenv("STTODE_CHAIN")) m->chain_mode = atoi(e) > 0 ? 1 : atoi(e) == 0 ? 0 : -1;
     m->fused_mode = 1;
     m->b3 = 0;   // (STTODE_BF16X3=1 is honoured by the Python layer, which packs the bf16-split stream before switching the mode on)
-    m->role_lead = getenv("STTODE_ROLE_LEAD") ? atoi(getenv("STTODE_ROLE_LEAD")) : -1;   // -1: one role workgroup per tile, all in front (default); -2: split roles
+    m->role_lead = -1;   // -1: one role workgroup per tile, all in front (default); -2: split roles
     m->drop_tile = -1;
     for (int p = 0; p < STT_MAX_SLOTS; ++p) { m->slot_stream[p] = nullptr; m->lag[p].valid = false; }
     // 3 streams: the small legs gain 3-9 % over 2, 512 scenes tie (profiles/r04/streams_2_vs_3.txt); 4: -5..-12 % everywhere -- the fourth
@@ -141,58 +134,35 @@ extern "C" int sttode_model_create(SttodeModel** out, const void* const* weights
     for (int i = 0; i < 4; ++i) m->lag_qn[i] = 0;
     if (const char* e = getenv("STTODE_LAGGED")) m->lag_streams = atoi(e) >= 2 && atoi(e) <= 4 ? atoi(e) : 0;
     m->scene_launch = 128;
-    if (const char* e = getenv("STTODE_SCENE_LAUNCH")) m->scene_launch = atoi(e) > 0 ? atoi(e) : 0;
-    if (const char* e = getenv("STTODE_FUSED")) m->fused_mode = atoi(e) != 0;
     // default off: measured neutral to -0.6 % pipelined and -1.5 % serial at 512 scenes (the two front-end launches cost less than the
     // ~10 us they add to every role), +1 % on the 256-scene SDD leg (profiles/r03/ab_lead_frontend_depth.txt)
-    m->fe_in_role = getenv("STTODE_FE_IN_ROLE") && atoi(getenv("STTODE_FE_IN_ROLE")) != 0;
+    m->fe_in_role = false;
     m->prog_len = sttode_chain_prog_len(Tp, Tf);
-    m->col_parts = 1;  // measured on MI355X: 1 -> 62.1, 2 -> 60.6, 4 -> 55.4 M traj/s (kernels of different streams do not fill each other's tails)
-    if (const char* e = getenv("STTODE_COL_PARTS")) m->col_parts = atoi(e);
-    if (m->col_parts < 1) m->col_parts = 1;
-    if (m->col_parts > STT_MAX_PARTS) m->col_parts = STT_MAX_PARTS;
     // All internal streams run at normal priority.  Measured on MI355X: high priority for the per-agent streams makes the
     // cross-call pipeline slower (61.6 M traj/s with sA+side raised, 65.6 M with only side raised, 66.9 M with neither).
-    // STTODE_A_PRIORITY=1: the per-agent streams (sA, side) get the highest stream priority, so their small kernels are dispatched
-    // first whenever a running per-trajectory kernel frees workgroup slots
-    int prio_lo = 0, prio_hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    const bool a_prio = getenv("STTODE_A_PRIORITY") && atoi(getenv("STTODE_A_PRIORITY")) > 0;
-    auto mk_stream = [&](hipStream_t* st, bool high) {
-        return (high ? hipStreamCreateWithPriority(st, hipStreamNonBlocking, prio_hi) : hipStreamCreateWithFlags(st, hipStreamNonBlocking)) == hipSuccess;
-    };
     m->side = nullptr;   // created on the first serial call
-    bool ok =              hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&m->ev_join, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&m->ev_agents, hipEventDisableTiming) == hipSuccess;
-    for (int p = 0; p < STT_MAX_PARTS && ok; ++p) {
-        m->part_stream[p] = nullptr;
-        ok = hipEventCreateWithFlags(&m->ev_part[p], hipEventDisableTiming) == hipSuccess &&
-             true;   // part streams are created on first use (every stream takes a share of the 4 hardware queues)
-    }
+    bool ok = hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming) == hipSuccess &&
+              hipEventCreateWithFlags(&m->ev_join, hipEventDisableTiming) == hipSuccess;
     // The pipeline's streams are PROCESS-WIDE (created with the first model, shared by every later one, never destroyed).  The runtime
     // deals its few hardware queues (4) to streams round-robin at creation: the first model's three streams get the three queues the
     // default stream does not use, but the streams of a second model -- or of one created after an earlier model was destroyed -- start
     // wherever the counter stands, and a per-agent or chain stream that shares the caller's queue serialises the pipeline (measured: the
     // same leg of the bench at 51 or 63 M trajectories/s depending on how many models had been created before it).
     static hipStream_t g_sA[STT_MAX_DEVICES] = {}, g_sB[STT_MAX_DEVICES] = {}, g_sB2[STT_MAX_DEVICES] = {};   // per device of this process
+    static hipStream_t g_sLag4[STT_MAX_DEVICES] = {};
     int dev = 0;
     ok = ok && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < STT_MAX_DEVICES;
     if (ok) {
         std::lock_guard<std::mutex> lk(g_stream_mu);   // models may be created from several host threads
         if (!g_sA[dev]) {
-            ok = mk_stream(&g_sA[dev], a_prio) && hipStreamCreateWithFlags(&g_sB[dev], hipStreamNonBlocking) == hipSuccess &&
+            ok = hipStreamCreateWithFlags(&g_sA[dev], hipStreamNonBlocking) == hipSuccess &&
+                 hipStreamCreateWithFlags(&g_sB[dev], hipStreamNonBlocking) == hipSuccess &&
                  hipStreamCreateWithFlags(&g_sB2[dev], hipStreamNonBlocking) == hipSuccess;
             if (!ok) g_sA[dev] = nullptr;
         }
         if (ok) { m->sA = g_sA[dev]; m->sB = g_sB[dev]; m->sB2 = g_sB2[dev]; }
-        m->fused_streams = 1;
-        if (const char* e = getenv("STTODE_FUSED_STREAMS")) m->fused_streams = atoi(e) < 1 ? 1 : atoi(e) > 6 ? 6 : atoi(e);
-        static hipStream_t g_sX[STT_MAX_DEVICES][3] = {};
-        for (int i = 0; ok && i < (m->fused_streams > 4 ? m->fused_streams - 3 : 1); ++i) {   // (sX[0]: also the fourth stream of the lagged rotation)
-            if (!g_sX[dev][i]) ok = hipStreamCreateWithFlags(&g_sX[dev][i], hipStreamNonBlocking) == hipSuccess;
-            m->sX[i] = g_sX[dev][i];
-        }
+        if (ok && !g_sLag4[dev]) ok = hipStreamCreateWithFlags(&g_sLag4[dev], hipStreamNonBlocking) == hipSuccess;
+        m->sLag4 = g_sLag4[dev];
     }
     ok = ok && hipEventCreateWithFlags(&m->ev_call, hipEventDisableTiming) == hipSuccess;
     // the model's time-out word lives in pinned host memory (device-visible): a group that gives up stores to it with system scope, the
@@ -228,9 +198,8 @@ extern "C" int sttode_model_destroy(SttodeModel* m) {
     if (!exchanged) (void)hipGetLastError();
     for (auto& r : m->recs) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
     for (auto e : m->pool) (void)hipEventDestroy(e);
-    (void)hipEventDestroy(m->ev_fork); (void)hipEventDestroy(m->ev_join); (void)hipEventDestroy(m->ev_agents);
-    for (int p = 0; p < STT_MAX_PARTS; ++p) { (void)hipEventDestroy(m->ev_part[p]); if (p && m->part_stream[p]) (void)hipStreamDestroy(m->part_stream[p]); }
-    // sA / sB / sB2 are process-wide (sttode_model_create)
+    (void)hipEventDestroy(m->ev_fork); (void)hipEventDestroy(m->ev_join);
+    // sA / sB / sB2 / sLag4 are process-wide (sttode_model_create)
     (void)hipEventDestroy(m->ev_call);
     for (int p = 0; p < STT_MAX_SLOTS; ++p) { (void)hipEventDestroy(m->evA_done[p]); (void)hipEventDestroy(m->evB_done[p]); }
     tmo_word_give(m->tmo_host);   // (back to the process-wide block: no hipHostFree here -- a destructor may run during a stream capture)
@@ -326,13 +295,6 @@ extern "C" int sttode_set_ode(SttodeModel* m, int method, int steps) {
     STT_REQUIRE(m, "sttode_set_ode: null model");
     STT_REQUIRE(method >= 0 && method <= 2 && steps >= 1 && steps <= 1024, "sttode_set_ode: method in {0,1,2}, 1 <= steps <= 1024");
     m->ode_method = method; m->ode_steps = steps;
-    return 0;
-}
-
-extern "C" int sttode_set_col_parts(SttodeModel* m, int parts) {
-    STT_REQUIRE(m, "sttode_set_col_parts: null model");
-    STT_REQUIRE(parts >= 1 && parts <= STT_MAX_PARTS, "sttode_set_col_parts: parts must be in [1, 8]");
-    m->col_parts = parts;
     return 0;
 }
 
@@ -432,12 +394,10 @@ static int stage_agents(SttodeModel* m, float* ws, const long* off, int n, int g
 
     // Scene batches (attention length 1) with the reference's integrator: encoder and block-0 GRU of every 16-agent tile as two workgroup
     // roles of ONE launch (csrc/encoder.hip agents_fused_kernel) -- no side stream, no event fork / join, three launches fewer.  Used
-    // wherever the latency forms of both halves would be chosen anyway (same code, same bits); STTODE_AGENTS_FUSED=0 disables it.
-    static const bool fuse_on = !(getenv("STTODE_AGENTS_FUSED") && atoi(getenv("STTODE_AGENTS_FUSED")) == 0);
-    static const int gru0_lat_p = getenv("STTODE_GRU0_LAT_TILES") ? atoi(getenv("STTODE_GRU0_LAT_TILES")) : 4096;
+    // wherever the latency forms of both halves would be chosen anyway (same code, same bits).
     const int ntiles = (n + 15) / 16;
-    if (fuse_on && attn_len == 1 && m->ode_method == 0 && m->ode_steps == 1 && stt_agents_fused_covers(Tp, TPX) &&
-        ntiles <= (use_side ? stt_gru_lat_tiles() : gru0_lat_p) && ntiles <= stt_enc_lat_tiles()) {
+    if (attn_len == 1 && m->ode_method == 0 && m->ode_steps == 1 && stt_agents_fused_covers(Tp, TPX) &&
+        ntiles <= (use_side ? stt_gru_lat_tiles() : STT_GRU0_LAT_TILES) && ntiles <= stt_enc_lat_tiles()) {
         RUN(STT_STAGE_AGENTS, s,
             stt_agents_fused(W, ws + off[STT_B_ENC_IN], (const int*)(ws + off[STT_B_LAST]), g, qkv, pf, xpad, state0, n, Tp, TPX, 12.0f, s));
         RUN(STT_STAGE_LINEAR, s,
@@ -464,24 +424,16 @@ static int stage_agents(SttodeModel* m, float* ws, const long* off, int n, int g
         STT_HIP(hipEventRecord(m->ev_fork, s));
         STT_HIP(hipStreamWaitEvent(m->side, m->ev_fork, 0));
     }
-    // STTODE_GRU0_STREAM=1 (default off): same-box A/Bs showed no gain over the resident-weights kernel once the chain keeps one
-    // workgroup per CU (63.7 vs 65.7 / 64.3 M trajectories/s), so the streaming form stays an option, not the default
-    static const bool gru0_stream = getenv("STTODE_GRU0_STREAM") && atoi(getenv("STTODE_GRU0_STREAM")) != 0;
-    // Tp > 8 (two 16-wide input tiles): always the streaming form -- the resident-weights instantiation for that shape spills 44 B per lane
-    if ((!use_side && gru0_stream && (long)n * m->K >= 16384) || TPX == 2) {
-        // streaming GRU (24 KiB of LDS): co-resides with the previous calls' chain workgroups
+    // Tp > 8 (two 16-wide input tiles): the streaming form (24 KiB of LDS) -- the resident-weights instantiation for that shape spills 44 B
+    // per lane.  (As the pipelined form's GRU-0 at every Tp, same-box A/Bs showed no gain over the resident-weights kernel once the chain
+    // keeps one workgroup per CU: 63.7 vs 65.7 / 64.3 M trajectories/s.)
+    if (TPX == 2) {
         RUN(STT_STAGE_GRU0, gs,
             sttode_gru_cols32(xpad, 16 * TPX, W[STT_W_G0_POOL], (const int*)W[STT_W_G0_PROG], 13 * Tp, W[STT_W_G0_CONSTS], state0, n, Tp, gs));
     } else
-    {
-    // pipelined form: the latency form up to 4096 tiles -- its workgroups (no LDS-resident weights) co-reside with the previous calls' chain
-    // workgroups, the resident-weights form (144 KiB of LDS) only gets chain-free CUs: 65 -> 68 M trajectories/s at 512 scenes (same box),
-    // neutral at 128 / 256 / 1024 / 2048 scenes (STTODE_GRU0_LAT_TILES overrides)
-    const int gru0_lat = gru0_lat_p;
-    RUN(STT_STAGE_GRU0, gs,
-        stt_gru_cols_form(xpad, W[STT_W_B0_CONVP], W[STT_W_B0_CONVB], W[STT_W_B0_WIHP], W[STT_W_B0_WHHP], W[STT_W_B0_GBIAS], state0, n,
-                          Tp, TPX, use_side ? 0 : gru0_lat, gs));
-    }
+        RUN(STT_STAGE_GRU0, gs,
+            stt_gru_cols_form(xpad, W[STT_W_B0_CONVP], W[STT_W_B0_CONVB], W[STT_W_B0_WIHP], W[STT_W_B0_WHHP], W[STT_W_B0_GBIAS], state0, n,
+                              Tp, TPX, use_side ? 0 : STT_GRU0_LAT_TILES, gs));
     if (use_side) STT_HIP(hipEventRecord(m->ev_join, m->side));
 
     RUN(STT_STAGE_EMBED, s,
@@ -579,31 +531,14 @@ static int stage_trajectories(SttodeModel* m, float* ws, const long* off, int n,
                               Tp, Tf, pipelined ? 1 : 2, s));
         return 0;
     }
-    // optional split into column parts at agent boundaries (pointers are simply offset)
-    int P = m->col_parts;
-    if (P > n) P = n;
-    if (P > 1) STT_HIP(hipEventRecord(m->ev_agents, s));
-    const float* cur = ws + off[STT_B_CUR];
-    const float* orig = ws + off[STT_B_ORIG];
-    for (int p = 0; p < P; ++p) {
-        const long a0 = (long)n * p / P, a1 = (long)n * (p + 1) / P;
-        const int na = (int)(a1 - a0), nc = na * K;
-        const long c0 = a0 * K;
-        if (p > 0 && !m->part_stream[p]) STT_HIP(hipStreamCreateWithFlags(&m->part_stream[p], hipStreamNonBlocking));
-        hipStream_t ps = p == 0 ? s : m->part_stream[p];
-        if (p > 0) STT_HIP(hipStreamWaitEvent(ps, m->ev_agents, 0));
-        RUN(STT_STAGE_MLP0, ps,
-            sttode_mlp_block0(A0x + a0 * 512, A0y + a0 * 512, W[STT_W_B0_STREAM], m->n_chunks0, z + c0 * 32,
-                              xpad + a0 * 16 * TPX, dbuf + c0 * 16 * TPX, ybuf + c0 * 16 * NOY, nc, K, TPX, NOY, ps));
-        RUN(STT_STAGE_GRU1, ps,
-            sttode_gru_cols(dbuf + c0 * 16 * TPX, W[STT_W_B1_CONVP], W[STT_W_B1_CONVB], W[STT_W_B1_WIHP], W[STT_W_B1_WHHP],
-                            W[STT_W_B1_GBIAS], state1 + c0 * 96, nc, Tp, TPX, ps));
-        RUN(STT_STAGE_MLP1, ps,
-            sttode_mlp_block1(A1y + a0 * 512, W[STT_W_B1_STREAM], m->n_chunks1, z + c0 * 32, state1 + c0 * 96,
-                              ybuf + c0 * 16 * NOY, cur + a0 * 2, orig + a0 * 2, pred + c0 * 2 * Tf, nc, K, Tf, NOY, ps));
-        if (p > 0) STT_HIP(hipEventRecord(m->ev_part[p], ps));
-    }
-    for (int p = 1; p < P; ++p) STT_HIP(hipStreamWaitEvent(s, m->ev_part[p], 0));
+    const int nc = (int)ncols_all;
+    RUN(STT_STAGE_MLP0, s,
+        sttode_mlp_block0(A0x, A0y, W[STT_W_B0_STREAM], m->n_chunks0, z, xpad, dbuf, ybuf, nc, K, TPX, NOY, s));
+    RUN(STT_STAGE_GRU1, s,
+        sttode_gru_cols(dbuf, W[STT_W_B1_CONVP], W[STT_W_B1_CONVB], W[STT_W_B1_WIHP], W[STT_W_B1_WHHP], W[STT_W_B1_GBIAS], state1, nc, Tp, TPX, s));
+    RUN(STT_STAGE_MLP1, s,
+        sttode_mlp_block1(A1y, W[STT_W_B1_STREAM], m->n_chunks1, z, state1, ybuf, ws + off[STT_B_CUR], ws + off[STT_B_ORIG], pred, nc, K, Tf,
+                          NOY, s));
     return 0;
 }
 
@@ -636,7 +571,7 @@ static bool use_scene_launch(const SttodeModel* m, int n, const int* scene_ptr) 
     const long ncols_all = (long)n * m->K;
     const bool chain = m->chain_mode == 1 || (m->chain_mode < 0 && ncols_all >= 16384);
     return scene_ptr != nullptr && !chain && m->scene_launch > 0 && (ncols_all + 15) / 16 <= m->scene_launch && m->ode_method == 0 &&
-           m->ode_steps == 1 && m->col_parts <= 1 && stt_scene_lat_covers(m->Tp, m->TPX, m->NOY);
+           m->ode_steps == 1 && stt_scene_lat_covers(m->Tp, m->TPX, m->NOY);
 }
 static int stage_fused(SttodeModel* m, float* ws, const long* off, int n, int groups, int attn_len, int attn_slots, const float* z, float* pred,
                        const float* past, const int* scene_ptr, int S, hipStream_t s) {
@@ -694,7 +629,7 @@ static bool use_lagged(const SttodeModel* m, int n) {
     const bool chain = m->chain_mode == 1 || (m->chain_mode < 0 && ncols_all >= 16384);
     return m->lag_streams > 0 && m->fused_mode == 1 && chain && m->ode_method == 0 && m->ode_steps == 1 && stt_chain_lagged_covers(m->Tp);
 }
-static hipStream_t lag_stream(const SttodeModel* m, int si) { return si == 0 ? m->sB : si == 1 ? m->sB2 : si == 2 ? m->sA : m->sX[0]; }
+static hipStream_t lag_stream(const SttodeModel* m, int si) { return si == 0 ? m->sB : si == 1 ? m->sB2 : si == 2 ? m->sA : m->sLag4; }
 static void lag_unqueue(SttodeModel* m, int slot) {
     const int si = m->lag[slot].si;
     int w = 0;
@@ -727,11 +662,10 @@ static int run_lagged(SttodeModel* m, const float* past, const int* scene_ptr, i
     ++m->lag_calls;
     STT_HIP(hipStreamWaitEvent(sf, m->ev_call, 0));              // inputs and z of this call (a wait for itself when the caller works on sf)
     STT_HIP(hipStreamWaitEvent(sf, m->evB_done[slot], 0));       // the slot's previous user has drained (same stream in a 2 x streams rotation)
-    // scene batches: set_data runs inside the roles (role32.hpp frontend32): the call is ONE launch (STTODE_LAG_FE=0: front-end launches)
-    static const bool fe_in = !(getenv("STTODE_LAG_FE") && atoi(getenv("STTODE_LAG_FE")) == 0);
-    const bool fe_role = fe_in && scene_ptr != nullptr;
+    // scene batches: set_data runs inside the roles (role32.hpp frontend32): the call is ONE launch
+    const bool fe_role = scene_ptr != nullptr;
     // NBA, attention groups > 1: set_data_nba rides in the embedding's launch (one launch fewer in front of the roles)
-    const bool fe_embed = fe_in && !scene_ptr && B > 1 && stt_embed_qkv_fe_covers(n, m->Tp);
+    const bool fe_embed = !scene_ptr && B > 1 && stt_embed_qkv_fe_covers(n, m->Tp);
     if (!fe_role && !fe_embed)
         if (int rc = frontend(m, ws, off, past, scene_ptr, n, S, N, sf)) return rc;
     const float* attn = nullptr;
@@ -809,10 +743,9 @@ static int run_async(SttodeModel* m, const float* past, const int* scene_ptr, in
     if (use_fused(m, n)) {
         // ONE stream per call.  Round 5: these launches hand tables over INSIDE the launch (tile flags, bounded spin), and workgroups are
         // dispatched in index order per XCD only -- several of them in flight on different queues could wait on each other across XCDs
-        // (round-3/4 advice) -- so by default they run one at a time on ONE stream (STTODE_FUSED_STREAMS > 1 restores the rotation for A/B).
-        // The product's pipelined path is the lagged form above, which has no hand-off.
-        const int si = (int)(m->acalls % m->fused_streams);
-        hipStream_t sf = si == 0 ? m->sB : si == 1 ? m->sB2 : si == 2 ? m->sA : m->sX[si - 3];
+        // (round-3/4 advice) -- so they run one at a time on ONE stream, sB.  The product's pipelined path is the lagged form above, which
+        // has no hand-off.
+        hipStream_t sf = m->sB;
         ++m->acalls;
         STT_HIP(hipStreamWaitEvent(sf, m->ev_call, 0));
         STT_HIP(hipStreamWaitEvent(sf, m->evB_done[slot], 0));   // the slot's previous user has drained
@@ -829,9 +762,9 @@ static int run_async(SttodeModel* m, const float* past, const int* scene_ptr, in
     if (int rc = frontend(m, ws, off, past, scene_ptr, n, S, N, m->sA)) return rc;
     if (int rc = stage_agents(m, ws, off, n, G, scene_ptr ? 1 : B, scene_ptr ? 1 : N, m->sA, false)) return rc;
     STT_HIP(hipEventRecord(m->evA_done[slot], m->sA));
-    // per-trajectory stages of consecutive calls alternate between two streams (b_streams == 2): the persistent chain kernel of
-    // call i+1 then starts on the compute units its predecessor's last workgroups leave (no chip-wide resource is held)
-    hipStream_t sb = (m->b_streams == 2 && (m->acalls++ & 1)) ? m->sB2 : m->sB;
+    // per-trajectory stages of consecutive calls alternate between two streams: the persistent chain kernel of call i+1 then starts on the
+    // compute units its predecessor's last workgroups leave (no chip-wide resource is held)
+    hipStream_t sb = (m->acalls++ & 1) ? m->sB2 : m->sB;
     STT_HIP(hipStreamWaitEvent(sb, m->ev_call, 0));
     STT_HIP(hipStreamWaitEvent(sb, m->evA_done[slot], 0));
     if (int rc = stage_trajectories(m, ws, off, n, z, pred, sb, true)) return rc;
@@ -932,9 +865,7 @@ extern "C" int sttode_async_next_stream(SttodeModel* m, int n, void** stream) {
     std::lock_guard<std::mutex> lk(m->mu);
     *stream = nullptr;
     if (use_lagged(m, n)) { *stream = lag_stream(m, (int)(m->lag_calls % m->lag_streams)); return 0; }
-    if (!use_fused(m, n)) return 0;
-    const int si = (int)(m->acalls % m->fused_streams);
-    *stream = si == 0 ? m->sB : si == 1 ? m->sB2 : si == 2 ? m->sA : m->sX[si - 3];
+    if (use_fused(m, n)) *stream = m->sB;
     return 0;
 }
 

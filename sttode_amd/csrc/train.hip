@@ -572,21 +572,15 @@ __global__ __launch_bounds__(256) void tgemm_reduce_kernel(TGRed r) {
 #define TLIN_MEDIUM_BELOW 4096   // throughput-mode wave count below which the 32 x 32 tiling is used instead
 #endif
 
-// columns above which the LDS-tiled kernel takes over from the generic ones (STTODE_TGEMM_MIN_COLS: experiments; measured at 1024: the
-// one-scene step the same 1.04-1.08 ms, and the NBA 16 x 11 gradient yardstick fails -- profiles/r04/tgemm_min_cols_ab.txt)
-// Round 5: the BACKWARD products (input gradient, weight gradient) switch at 600 columns (STTODE_TGEMM_MIN_COLS_BWD).  With the decoder's
+// columns above which the LDS-tiled kernel takes over from the generic ones (measured at 1024: the one-scene step the same 1.04-1.08 ms,
+// and the NBA 16 x 11 gradient yardstick fails -- profiles/r04/tgemm_min_cols_ab.txt)
+// Round 5: the BACKWARD products (input gradient, weight gradient) switch at 600 columns (TGEMM_MIN_COLS_BWD; training.py allocates its
+// reduction scratch by the same number).  With the decoder's
 // backward over the live columns only, an NBA-size step's backward products have 2 n = 704 columns -- below 2048, on the generic kernels:
 // 1.155 -> 1.086 ms per step with the LDS-tiled kernel (profiles/r05/train_tgemm_min_cols_ab.txt, measured with both thresholds at 600;
 // the forward products keep 2048: at 600 the forward of a 32-agent scene (672 columns) changes its summation order and three gradient
 // yardsticks on the known ill-conditioned rows move from 0.8 to 1.05-1.8 of their bounds, for no gain at one scene per step).
-static inline int tg_min_cols() {
-    static const int v = getenv("STTODE_TGEMM_MIN_COLS") ? atoi(getenv("STTODE_TGEMM_MIN_COLS")) : 2048;
-    return v;
-}
-static inline int tg_min_cols_bwd() {
-    static const int v = getenv("STTODE_TGEMM_MIN_COLS_BWD") ? atoi(getenv("STTODE_TGEMM_MIN_COLS_BWD")) : 600;
-    return v;
-}
+static constexpr int TGEMM_MIN_COLS = 2048, TGEMM_MIN_COLS_BWD = 600;
 static inline int aligned16(const void* p, long ld) { return (((size_t)p) % 16 == 0) && (ld % 4 == 0); }
 // tg_fetch_fast: aligned operands without broadcast rows; the contiguous index of each operand (k, or the row index of a transposed one)
 // a multiple of 4 and at least 4; every split of the reduction a multiple of 4 long
@@ -777,8 +771,7 @@ static int tlinear_impl(const float* X, long ldx, int xdiv, const float* W, long
     a.asrc = asrc; a.ldas = ldas; a.adiv = adiv;
     a.xvec = aligned16(X, ldx); a.wvec = aligned16(W, ldw); a.yvec = aligned16(Y, ldy);
     a.evec = I % 4 == 0 && a.yvec && (!bias || aligned16(bias, 4)) && (!mask || aligned16(mask, ldm)) && (!accumulate || aligned16(asrc, ldas));
-    static const bool tg_on = !(getenv("STTODE_TGEMM") && atoi(getenv("STTODE_TGEMM")) == 0);   // STTODE_TGEMM=0: the generic kernels (A/B)
-    if (tg_on && cols > (trans ? tg_min_cols_bwd() : tg_min_cols())) {   // batch sizes: the LDS-tiled kernel (trans: an input gradient)
+    if (cols > (trans ? TGEMM_MIN_COLS_BWD : TGEMM_MIN_COLS)) {   // batch sizes: the LDS-tiled kernel (trans: an input gradient)
         TG g;
         g.A = X; g.lda = ldx; g.B = W; g.ldb = ldw; g.C = Y; g.ldc = ldy;
         g.M = cols; g.N = I; g.Kt = J; g.adiv = xdiv; g.bkdiv = 1; g.ones_row = -1;
@@ -946,8 +939,7 @@ extern "C" int sttode_twgrad(const float* dY, long ldy, const float* X, long ldx
     a.ldy = ldy; a.ldx = ldx; a.ldw = ldw; a.cols = cols; a.N = N; a.K = K; a.xdiv = xdiv;
     const int chunks = (cols + 15) / 16;
     const long per = (long)N * (K + 1);
-    static const bool tg_on = !(getenv("STTODE_TGEMM") && atoi(getenv("STTODE_TGEMM")) == 0);
-    if (tg_on && cols > tg_min_cols_bwd()) {   // batch sizes: the LDS-tiled kernel, reduction over the columns split so that the chip is full
+    if (cols > TGEMM_MIN_COLS_BWD) {   // batch sizes: the LDS-tiled kernel, reduction over the columns split so that the chip is full
         std::lock_guard<std::mutex> lk(g_red_mu);
         TG g;
         if (tg_wgrad_fill(g, dY, ldy, X, ldx, xdiv, dW, ldw, db, cols, N, K, scratch, scratch_floats, 480, stream)) {
@@ -982,9 +974,7 @@ extern "C" int sttode_tlinear_bwd(const float* dY, long ldy, const float* W, lon
                                   float* db, int cols, int N, int K, float* scratch, long scratch_floats, void* stream) {
     STT_REQUIRE(dY && W && dX && X && dW, "sttode_tlinear_bwd: null pointer");
     STT_REQUIRE(cols > 0 && N > 0 && K > 0 && Kdx > 0 && Kdx <= K && xdiv > 0, "sttode_tlinear_bwd: bad sizes");
-    static const bool tg_on = !(getenv("STTODE_TGEMM") && atoi(getenv("STTODE_TGEMM")) == 0);
-    static const bool fuse_on = !(getenv("STTODE_TGEMM_BWD") && atoi(getenv("STTODE_TGEMM_BWD")) == 0);   // =0: the two products as two launches (A/B)
-    if (tg_on && fuse_on && cols > tg_min_cols_bwd() && xdiv == 1) {   // batch sizes: both products of the layer's backward in ONE launch
+    if (cols > TGEMM_MIN_COLS_BWD && xdiv == 1) {   // batch sizes: both products of the layer's backward in ONE launch
         STT_REQUIRE(ldy >= N && ldx >= K && ldgw >= K && ldw >= K && lddx >= Kdx, "sttode_tlinear_bwd: leading dimension smaller than the row length");
         std::lock_guard<std::mutex> lk(g_red_mu);
         TG gx;
@@ -1572,7 +1562,7 @@ __global__ __launch_bounds__(384) void gru_seq_bwd_kernel(const float* __restric
 }
 
 // ---------------------------------------------------------------------------------------------------
-// The same two launches for FEW columns (round 5; m <= gseq_small_max(), default 1024: one scene per step, the live columns of a backward
+// The same two launches for FEW columns (round 5; m <= GSEQ_SMALL_MAX = 1024: one scene per step, the live columns of a backward
 // pass, the per-agent first block).  The kernels above put 16 columns on a 16-wide MFMA tile and all of a tile's W_hh products on ONE CU:
 // 885 kFLOP per step = 1.4-1.9 us of that CU's matrix pipe per step of the recurrence, whatever m is -- with m = 32 columns two CUs work
 // and 254 idle, 28-33 us per launch, four launches per training step (20 % of a one-scene step).  Here a workgroup owns FOUR columns and
@@ -1694,17 +1684,14 @@ __global__ __launch_bounds__(384) void gru_seq_bwd_small_kernel(const float* __r
         // (sG and sP are rewritten only after the next step's first barrier / this step's readers are past the second one)
     }
 }
-static inline int gseq_small_max() {
-    static const int v = getenv("STTODE_GRU_SMALL_MAX") ? atoi(getenv("STTODE_GRU_SMALL_MAX")) : 1024;
-    return v;
-}
+static constexpr int GSEQ_SMALL_MAX = 1024;   // columns up to which the few-column kernels above run (profiles/r05/train_gru_small_ab.txt)
 
 extern "C" int sttode_gru_seq_fwd(const float* gi, const float* Whh, const float* bhh, float* H, float* tapes, float* hfinal,
                                   long ldhf, int m, int Tp, void* stream) {
     STT_REQUIRE(gi && Whh && bhh && H && tapes && m > 0 && Tp > 0, "sttode_gru_seq_fwd: bad argument");
     STT_REQUIRE(((size_t)Whh) % 16 == 0 && ((size_t)gi) % 16 == 0, "sttode_gru_seq_fwd: pointers must be 16-byte aligned");
     STT_REQUIRE(!hfinal || (((size_t)hfinal) % 16 == 0 && ldhf % 4 == 0 && ldhf >= 96), "sttode_gru_seq_fwd: hfinal must be 16-byte aligned rows of >= 96 floats");
-    if (m <= gseq_small_max())
+    if (m <= GSEQ_SMALL_MAX)
         hipLaunchKernelGGL(gru_seq_fwd_small_kernel, dim3((m + GSEQ_SC - 1) / GSEQ_SC), dim3(384), 0, (hipStream_t)stream, gi, Whh, bhh, H, tapes, hfinal, ldhf, m, Tp);
     else
         hipLaunchKernelGGL(gru_seq_fwd_kernel, dim3((m + 15) / 16), dim3(384), 0, (hipStream_t)stream, gi, Whh, bhh, H, tapes, hfinal, ldhf, m, Tp);
@@ -1715,7 +1702,7 @@ extern "C" int sttode_gru_seq_bwd(const float* dh_last, long lddh, const float* 
                                   float* dgh, int m, int Tp, void* stream) {
     STT_REQUIRE(dh_last && tapes && H && Whh && dgi && dgh && m > 0 && Tp > 0, "sttode_gru_seq_bwd: bad argument");
     STT_REQUIRE(((size_t)dh_last) % 16 == 0 && lddh % 4 == 0 && lddh >= 96, "sttode_gru_seq_bwd: dh_last must be 16-byte aligned rows of >= 96 floats");
-    if (m <= gseq_small_max())
+    if (m <= GSEQ_SMALL_MAX)
         hipLaunchKernelGGL(gru_seq_bwd_small_kernel, dim3((m + GSEQ_SC - 1) / GSEQ_SC), dim3(384), 0, (hipStream_t)stream, dh_last, lddh, tapes, H, Whh, dgi, dgh, m, Tp);
     else
         hipLaunchKernelGGL(gru_seq_bwd_kernel, dim3((m + 15) / 16), dim3(384), 0, (hipStream_t)stream, dh_last, lddh, tapes, H, Whh, dgi, dgh, m, Tp);
@@ -2048,8 +2035,7 @@ extern "C" int sttode_mhgsa_attn_bwd(const float* qkv, const float* dO, float* d
         STT_SET_LDS_ONCE(attn_bwd_pairs_kernel<HD>, 160 * 1024);                                                                      \
         hipLaunchKernelGGL(attn_bwd_pairs_kernel<HD>, dim3(Nb * 8), dim3(256), shm2, (hipStream_t)stream, qkv, dO, dqkv, L, Nb);        \
     } while (0)
-    static const bool pairs = !(getenv("STTODE_ATTN_BWD_PAIRS") && atoi(getenv("STTODE_ATTN_BWD_PAIRS")) == 0);
-    if (pairs && L >= 4 && shm2 <= 150 * 1024) {
+    if (L >= 4 && shm2 <= 150 * 1024) {
         if (head_dim == 8) ATTB_PAIRS(8); else if (head_dim == 4) ATTB_PAIRS(4); else ATTB_PAIRS(16);
     } else {
         if (head_dim == 8) ATTB_GO(8); else if (head_dim == 4) ATTB_GO(4); else ATTB_GO(16);

@@ -60,6 +60,7 @@ _PAIRED = os.environ.get('STTODE_TRAIN_PAIRED', '1') != '0'   # decoder_x / deco
 # quantisation, tile start and the 15 MB tape store, not by the matrix pipe.
 _L1SPLIT_MIN_COLS = int(os.environ.get('STTODE_TRAIN_L1SPLIT_MIN', '2048')) if os.environ.get('STTODE_TRAIN_L1SPLIT', '0') != '0' else 1 << 60
 _SCRATCH_BATCH = 32 << 20     # floats (128 MB): split sums of one backward pass at batch sizes (more than 2048 GEMM columns)
+_TGEMM_MIN_COLS_BWD = 600     # == TGEMM_MIN_COLS_BWD of csrc/train.hip: backward products above it take the LDS-tiled GEMM (split sums)
 # non-default encoder integrators: cap of the per-stage activation and gradient columns the deferred weight-gradient pass holds at once
 # (the chunk buffers are allocated outside Engine.hold; with STTODE_TRAIN_STREAMS=1 the per-stage temporaries of the layer-by-layer
 # path are held until the step ends, so there the cap bounds the chunk columns but not the stage temporaries)
@@ -1064,7 +1065,7 @@ class Engine:
         n, Tp, Tf, zd = net._past.shape[0], a.past_length, a.future_length, a.zdim
         mode = 0 if net._mode == 'scenes' else 1
         K1 = 21
-        if n * K1 * Tp > int(os.environ.get('STTODE_TGEMM_MIN_COLS_BWD', '600')) and self.red_scratch is None:         # batch sizes: room for a backward pass's deferred split sums
+        if n * K1 * Tp > _TGEMM_MIN_COLS_BWD and self.red_scratch is None:         # batch sizes: room for a backward pass's deferred split sums
             self.red_scratch = torch.empty(_SCRATCH_BATCH, dtype=torch.float32, device=self.dev)
         V = self.V = {}
 
