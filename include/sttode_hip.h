@@ -24,7 +24,7 @@ extern "C" {
 #endif
 
 /* Version of this header: the library returns it from sttode_abi_version(); a binding compares before its first call (round 1-2: 1). */
-#define STTODE_ABI_VERSION 12
+#define STTODE_ABI_VERSION 13
 int sttode_abi_version(void);
 const char* sttode_last_error(void);
 
@@ -182,6 +182,25 @@ int sttode_horizon_metrics(const float* pred, const float* gt, int n, int K, int
 int sttode_best_of_k_select(const float* pred, const float* gt, int n, int K, int Tf, float scale, float miss_threshold, const int* seg_ptr,
                             int S, float* ade, float* fde, int* best_ade_idx, int* best_fde_idx, unsigned char* miss, float* best,
                             float* seg_ade, float* seg_fde, int* seg_miss, void* stream);
+/* Scene-level metrics of K sampled futures.  The reference computes none of them, so there is no line of it to cite.
+ * pred [n,K,Tf,2], gt [n,Tf,2] (float32, device), coordinates multiplied by `scale`; a segment s of the CSR seg_ptr [S+1] (a scene, or one
+ * NBA game of N players) is the agents seg_ptr[s] .. seg_ptr[s+1]-1.  Both entry points refuse a K they do not take before anything is
+ * written; there are no atomics and every sum has a fixed order: the same bits on every run.
+ * sttode_joint_select (1 <= K <= 64):
+ *   ADE(a, k) / FDE(a, k): per-(agent, sample) mean / final displacement, the bits bok_select_kernel computes for lane k (a one-agent
+ *   segment reproduces sttode_best_of_k_select's ade / fde / best_ade_idx / best_fde_idx bitwise).
+ *   seg_jade[s] = min_k (sum over the segment's agents of ADE(a, k), in double, / agent count) as float32; seg_jade_idx[s] = its k, the
+ *   lowest on exact ties of the double values (np.argmin); seg_jfde / seg_jfde_idx the same of FDE.  An empty segment gets NaN, index 0.
+ *   radius > 0: agent a collides in sample k if some other agent b of its segment has dx^2 + dy^2 < radius^2 (strictly; dx, dy float32
+ *   differences of the scaled coordinates) at some frame; seg_col[s] = sum over k of the colliding agents of sample k, seg_gt_col[s] =
+ *   the colliding agents of gt.  A one-agent segment has none.  radius <= 0: no collision pass; seg_col / seg_gt_col may be NULL.
+ * sttode_kde_nll (2 <= K <= 64), Trajectron++'s compute_kde_nll (scipy.stats.gaussian_kde per agent and frame), all in float64 with
+ *   x = (double)(x * scale): per frame C = the unbiased (/ (K-1)) 2 x 2 covariance of the K samples, Sigma = f^2 C with Scott's factor
+ *   f = K^(-1/6), logpdf = logsumexp_k(-(g - x_k)^T Sigma^-1 (g - x_k) / 2) - log K - log det(2 pi Sigma) / 2 clipped below at -20;
+ *   nll [n] = -mean over frames.  NaN if C is not positive definite at some frame (C00 <= 0 or det C <= 0: where gaussian_kde raises). */
+int sttode_joint_select(const float* pred, const float* gt, int n, int K, int Tf, float scale, const int* seg_ptr, int S, float radius,
+                        float* seg_jade, float* seg_jfde, int* seg_jade_idx, int* seg_jfde_idx, int* seg_col, int* seg_gt_col, void* stream);
+int sttode_kde_nll(const float* pred, const float* gt, int n, int K, int Tf, float scale, double* nll, void* stream);
 
 /* Stage-2 latent sampler (sampler.py:47-54): z = b (eps_mode 0) or A*eps + b with eps shared [nz] (1, share_eps) or per agent
  * [n,nz] (2); logvar = log(A^2 + 1e-8).  A, b, z, logvar [n*K, nz] (row = agent*K + k). */
@@ -670,6 +689,13 @@ int sttode_async_horizon_metrics(SttodeModel* m, int slot, const float* pred, co
 int sttode_async_best_of_k_select(SttodeModel* m, int slot, const float* pred, const float* gt, int n, int K, int Tf, float scale,
                                   float miss_threshold, const int* seg_ptr, int S, float* ade, float* fde, int* best_ade_idx, int* best_fde_idx,
                                   unsigned char* miss, float* best, float* seg_ade, float* seg_fde, int* seg_miss);
+/* sttode_joint_select / sttode_kde_nll of an asynchronous call's predictions on the pipeline stream the call of `slot` runs on, as
+ * sttode_async_best_of_k_select: the slot's outstanding trajectory groups first, the pass behind them in stream order, the slot's completion
+ * event re-recorded behind it.  gt and seg_ptr must have been written before the call; arguments are checked before anything is enqueued. */
+int sttode_async_joint_select(SttodeModel* m, int slot, const float* pred, const float* gt, int n, int K, int Tf, float scale,
+                              const int* seg_ptr, int S, float radius, float* seg_jade, float* seg_jfde, int* seg_jade_idx, int* seg_jfde_idx,
+                              int* seg_col, int* seg_gt_col);
+int sttode_async_kde_nll(SttodeModel* m, int slot, const float* pred, const float* gt, int n, int K, int Tf, float scale, double* nll);
 int sttode_wait(SttodeModel* m, int slot, void* stream);
 /* Zero-copy futures (lagged form): the trajectory groups of a lagged call only WRITE `pred` (block 0's y_hat0 waits in the workspace), so
  * `pred` may be pinned host memory addressed by its host pointer: the futures reach the host with the launch itself, no D2H copy

@@ -11,7 +11,7 @@ _LIB = None
 LIB_PATH = os.environ.get('STTODE_HIP_LIB') or os.path.join(os.path.dirname(os.path.abspath(__file__)), 'lib', 'libsttode_hip.so')
 
 _P, _I, _L, _F, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double
-ABI_VERSION = 12  # == STTODE_ABI_VERSION of include/sttode_hip.h; lib() refuses a library built from another header
+ABI_VERSION = 13  # == STTODE_ABI_VERSION of include/sttode_hip.h; lib() refuses a library built from another header
 
 # name -> argtypes (mirrors include/sttode_hip.h; tests/test_capi_symbols.py checks header == table == .so)
 SIGNATURES = {
@@ -40,6 +40,8 @@ SIGNATURES = {
     'sttode_best_of_k': [_P, _P, _I, _I, _I, _F, _P, _P, _P],
     'sttode_horizon_metrics': [_P, _P, _I, _I, _I, _F, _P, _P],
     'sttode_best_of_k_select': [_P, _P, _I, _I, _I, _F, _F, _P, _I] + [_P] * 10,
+    'sttode_joint_select': [_P, _P, _I, _I, _I, _F, _P, _I, _F] + [_P] * 7,
+    'sttode_kde_nll': [_P, _P, _I, _I, _I, _F, _P, _P],
     # stage-2 sampler (csrc/sampler.hip)
     'sttode_sampler_latent': [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P],
     'sttode_sampler_loss': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P],
@@ -116,6 +118,8 @@ SIGNATURES = {
     'sttode_inference_nba_async': [_P, _P, _I, _I, _P, _P, _P, _I, _P, _P],
     'sttode_async_horizon_metrics': [_P, _I, _P, _P, _I, _I, _I, _F, _P],
     'sttode_async_best_of_k_select': [_P, _I, _P, _P, _I, _I, _I, _F, _F, _P, _I] + [_P] * 9,
+    'sttode_async_joint_select': [_P, _I, _P, _P, _I, _I, _I, _F, _P, _I, _F] + [_P] * 6,
+    'sttode_async_kde_nll': [_P, _I, _P, _P, _I, _I, _I, _F, _P],
     'sttode_wait': [_P, _I, _P],
     'sttode_async_is_lagged': [_P, _I],
     'sttode_wait_host': [_P, _I],

@@ -85,3 +85,9 @@ int stt_trunk_group(int on);   // train_trunk.hip: the trunk-forward half of stt
 struct SttodeSamplerPlan;
 const char* stt_sampler_plan_check(const SttodeSamplerPlan* plan, int K);
 int stt_sampler_qnet(const SttodeSamplerPlan* plan, const float* pf, int n, float* z, void* stream);
+// metrics.hip: argument checks of sttode_joint_select / sttode_kde_nll, shared with their asynchronous forms (0, or 1 with the error set,
+// naming `who`)
+int stt_joint_check(const char* who, const float* pred, const float* gt, int n, int K, int Tf, const int* seg_ptr, int S, float radius,
+                    const float* seg_jade, const float* seg_jfde, const int* seg_jade_idx, const int* seg_jfde_idx, const int* seg_col,
+                    const int* seg_gt_col);
+int stt_kde_check(const char* who, const float* pred, const float* gt, int n, int K, int Tf, const double* nll);

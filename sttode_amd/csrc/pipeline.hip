@@ -843,6 +843,36 @@ extern "C" int sttode_async_best_of_k_select(SttodeModel* m, int slot, const flo
     return 0;
 }
 
+// Scene-level metrics (joint min ADE / FDE and collisions; KDE NLL: metrics.hip) of an asynchronous call's predictions, on the call's own
+// pipeline stream like sttode_async_best_of_k_select.  The arguments are checked before the slot's groups are enqueued.
+extern "C" int sttode_async_joint_select(SttodeModel* m, int slot, const float* pred, const float* gt, int n, int K, int Tf, float scale,
+                                         const int* seg_ptr, int S, float radius, float* seg_jade, float* seg_jfde, int* seg_jade_idx,
+                                         int* seg_jfde_idx, int* seg_col, int* seg_gt_col) {
+    STT_REQUIRE(m && slot >= 0 && slot < STT_MAX_SLOTS, "sttode_async_joint_select: bad model / slot");
+    if (stt_joint_check("sttode_async_joint_select", pred, gt, n, K, Tf, seg_ptr, S, radius, seg_jade, seg_jfde, seg_jade_idx, seg_jfde_idx,
+                        seg_col, seg_gt_col))
+        return 1;
+    std::lock_guard<std::mutex> lk(m->mu);
+    STT_REQUIRE(m->slot_stream[slot] != nullptr, "sttode_async_joint_select: no asynchronous call has used this slot");
+    if (int rc = lag_flush(m, slot)) return rc;
+    if (int rc = sttode_joint_select(pred, gt, n, K, Tf, scale, seg_ptr, S, radius, seg_jade, seg_jfde, seg_jade_idx, seg_jfde_idx, seg_col,
+                                     seg_gt_col, m->slot_stream[slot]))
+        return rc;
+    STT_HIP(hipEventRecord(m->evB_done[slot], m->slot_stream[slot]));
+    return 0;
+}
+
+extern "C" int sttode_async_kde_nll(SttodeModel* m, int slot, const float* pred, const float* gt, int n, int K, int Tf, float scale, double* nll) {
+    STT_REQUIRE(m && slot >= 0 && slot < STT_MAX_SLOTS, "sttode_async_kde_nll: bad model / slot");
+    if (stt_kde_check("sttode_async_kde_nll", pred, gt, n, K, Tf, nll)) return 1;
+    std::lock_guard<std::mutex> lk(m->mu);
+    STT_REQUIRE(m->slot_stream[slot] != nullptr, "sttode_async_kde_nll: no asynchronous call has used this slot");
+    if (int rc = lag_flush(m, slot)) return rc;
+    if (int rc = sttode_kde_nll(pred, gt, n, K, Tf, scale, nll, m->slot_stream[slot])) return rc;
+    STT_HIP(hipEventRecord(m->evB_done[slot], m->slot_stream[slot]));
+    return 0;
+}
+
 // The NBA evaluation's per-horizon metric (test.py:530-551) of an asynchronous call, on the call's own pipeline stream like
 // sttode_async_best_of_k: out [n][Tf][2] = per agent and horizon h the min over K of (mean displacement over the first h frames, displacement
 // of frame h) -- sttode_horizon_metrics on the slot's predictions.

@@ -6,7 +6,8 @@
   eval_nba     == test.py:495-552  (NBA): per DataLoader batch, min-over-K of the mean / final displacement at the horizons
                   1..future_length (the reference prints every 0.4 s step), weighted by batch size.
   eval_scenes_report / eval_sampler_report / eval_nba_report: the same loops returning an EvalReport -- global ADE / FDE and miss rate,
-                  per-scene (per NBA batch) ADE / FDE / miss count, the best sample of every agent (utils/metrics.py:29-48).
+                  per-scene (per NBA batch) ADE / FDE / miss count, the best sample of every agent (utils/metrics.py:29-48); on request
+                  the scene-level metrics of DESIGN.md 4l: joint min ADE / FDE, collision rates, KDE NLL.
 """
 import contextlib
 import dataclasses
@@ -182,7 +183,15 @@ class EvalReport:
     ``n_agents``, ``miss_count`` / ``miss_rate`` (agents whose best FDE exceeds ``miss_threshold``, count_miss_samples).  Per scene -- per
     loader batch for NBA -- in dataset order: ``scene_ade`` / ``scene_fde`` (compute_ADE / compute_FDE of that scene alone), ``scene_miss``
     (its miss count), ``scene_agents``.  Per agent in dataset order: ``best_idx`` (get_best_idx: the sample with the smallest ADE, the first
-    on ties), ``best_fde_idx``, and with ``gather=True`` ``best`` [n, Tf, 2], the predictions of that sample (unscaled)."""
+    on ties), ``best_fde_idx``, and with ``gather=True`` ``best`` [n, Tf, 2], the predictions of that sample (unscaled).
+
+    Scene-level metrics, None unless asked; segments are scenes (NBA: games of N players), in dataset order.  ``joint=True``:
+    ``joint_ade`` / ``joint_fde`` (mean over segments of the min over k of the segment's mean ADE / FDE of sample k), ``scene_joint_ade`` /
+    ``scene_joint_fde`` [S] and ``scene_joint_idx`` [S] (the k of the joint ADE, the lowest on ties).  ``collision_radius=r``:
+    ``collision_rate`` (colliding agent-samples / (K n)), ``gt_collision_rate`` (colliding agents of the ground truth / n) and
+    ``scene_collision`` [S, 2] (per segment: colliding agent-samples, colliding ground-truth agents).  ``kde=True``: ``kde_nll`` (mean over
+    the agents whose NLL is finite), ``kde_nll_agents`` [n] float64 (NaN where the samples' covariance is singular) and ``kde_invalid`` (the
+    number of NaN agents)."""
     ade: float
     fde: float
     n_agents: int
@@ -196,17 +205,44 @@ class EvalReport:
     best_idx: np.ndarray
     best_fde_idx: np.ndarray
     best: np.ndarray = None
+    joint_ade: float = None
+    joint_fde: float = None
+    scene_joint_ade: np.ndarray = None
+    scene_joint_fde: np.ndarray = None
+    scene_joint_idx: np.ndarray = None
+    collision_radius: float = None
+    collision_rate: float = None
+    gt_collision_rate: float = None
+    scene_collision: np.ndarray = None
+    kde_nll: float = None
+    kde_nll_agents: np.ndarray = None
+    kde_invalid: int = None
 
 
 class _ReportAcc:
     """Host side of a report loop: per call, the same double sums eval_scenes forms (so the global ADE / FDE agree bit for bit), and the
     small per-scene / per-agent arrays."""
 
-    def __init__(self, miss_threshold):
+    def __init__(self, miss_threshold, joint=False, kde=False, collision_radius=None, K=None):
+        from .metrics import check_radius
         self.thr = float(miss_threshold)
         self.tot_a = self.tot_f = 0.0
         self.n = 0
         self.parts = []
+        self.joint, self.kde, self.radius, self.K = bool(joint), bool(kde), check_radius(collision_radius), K
+        self.jparts, self.kparts = [], []
+
+    @property
+    def scene_metrics(self):
+        """Whether a joint pass runs (for the joint values, the collision counts or both)."""
+        return self.joint or self.radius is not None
+
+    def add_scene_metrics(self, js, kd):
+        if js is not None:
+            self.jparts.append((js.seg_jade.cpu().numpy(), js.seg_jfde.cpu().numpy(), js.seg_jade_idx.cpu().numpy(),
+                                None if js.seg_col is None else torch.stack([js.seg_col, js.seg_gt_col], dim=1).cpu().numpy()))
+        if kd is not None:
+            self.kparts.append(kd.cpu().numpy())
 
     def add(self, sel, seg_ptr):
         self.tot_a += float(sel.ade.double().sum())
@@ -219,19 +255,36 @@ class _ReportAcc:
     def report(self, gather):
         cat = [np.concatenate([p[i] for p in self.parts]) for i in range(6)]
         miss = int(cat[2].sum())
-        return EvalReport(ade=self.tot_a / self.n, fde=self.tot_f / self.n, n_agents=self.n, miss_count=miss, miss_rate=miss / self.n,
-                          miss_threshold=self.thr, scene_ade=cat[0], scene_fde=cat[1], scene_miss=cat[2], scene_agents=cat[3].astype(np.int64),
-                          best_idx=cat[4], best_fde_idx=cat[5], best=np.concatenate([p[6] for p in self.parts]) if gather else None)
+        rep = EvalReport(ade=self.tot_a / self.n, fde=self.tot_f / self.n, n_agents=self.n, miss_count=miss, miss_rate=miss / self.n,
+                         miss_threshold=self.thr, scene_ade=cat[0], scene_fde=cat[1], scene_miss=cat[2], scene_agents=cat[3].astype(np.int64),
+                         best_idx=cat[4], best_fde_idx=cat[5], best=np.concatenate([p[6] for p in self.parts]) if gather else None)
+        if self.joint:
+            rep.scene_joint_ade, rep.scene_joint_fde, rep.scene_joint_idx = (np.concatenate([p[i] for p in self.jparts]) for i in range(3))
+            rep.joint_ade = float(rep.scene_joint_ade.astype(np.float64).mean())
+            rep.joint_fde = float(rep.scene_joint_fde.astype(np.float64).mean())
+        if self.radius is not None:
+            col = np.concatenate([p[3] for p in self.jparts]).astype(np.int64)
+            rep.collision_radius, rep.scene_collision = self.radius, col
+            rep.collision_rate = int(col[:, 0].sum()) / (self.K * self.n)
+            rep.gt_collision_rate = int(col[:, 1].sum()) / self.n
+        if self.kde:
+            v = np.concatenate(self.kparts)
+            ok = np.isfinite(v)
+            rep.kde_nll_agents, rep.kde_invalid = v, int((~ok).sum())
+            rep.kde_nll = float(v[ok].mean()) if ok.any() else float('nan')
+        return rep
 
 
-def _scenes_report(model, dataset, scenes_per_call, pipelined, traj_scale, miss_threshold, gather, launch, serial):
-    acc = _ReportAcc(miss_threshold)
+def _scenes_report(model, dataset, scenes_per_call, pipelined, traj_scale, miss_threshold, gather, launch, serial, joint, kde,
+                   collision_radius):
+    acc = _ReportAcc(miss_threshold, joint, kde, collision_radius, model.args.sample_k)
     pend = []
 
     def finish(item):
-        h, sel, sp = item
+        h, sel, sp, js, kd = item
         model.wait(h)
         acc.add(sel, sp)
+        acc.add_scene_metrics(js, kd)
     for s0 in range(0, len(dataset), scenes_per_call):
         sb = dataset.scene_batch(range(s0, min(s0 + scenes_per_call, len(dataset))))
         model.set_scene_batch(sb.past, sb.future, sb.scene_ptr)
@@ -242,7 +295,9 @@ def _scenes_report(model, dataset, scenes_per_call, pipelined, traj_scale, miss_
                 model.reset_async()
             h = launch(sb)
             sel = model.select_best_of_k_async(h, scale=traj_scale, miss_threshold=miss_threshold, seg_ptr='scenes', gather=gather)
-            pend.append((h, sel, sb.scene_ptr))
+            js = model.select_joint_async(h, seg_ptr='scenes', scale=traj_scale, collision_radius=acc.radius) if acc.scene_metrics else None
+            kd = model.kde_nll_async(h, scale=traj_scale) if kde else None
+            pend.append((h, sel, sb.scene_ptr, js, kd))
             if len(pend) > 4:
                 finish(pend.pop(0))
             continue
@@ -250,6 +305,10 @@ def _scenes_report(model, dataset, scenes_per_call, pipelined, traj_scale, miss_
         sel = model.select_best_of_k(pred.permute(1, 0, 2, 3), scale=traj_scale, miss_threshold=miss_threshold, seg_ptr=model._scene_ptr,
                                      gather=gather)
         acc.add(sel, sb.scene_ptr)
+        if acc.scene_metrics or kde:
+            pnk = pred.permute(1, 0, 2, 3).contiguous()
+            acc.add_scene_metrics(model.select_joint(pnk, seg_ptr=model._scene_ptr, scale=traj_scale, collision_radius=acc.radius)
+                                  if acc.scene_metrics else None, model.kde_nll(pnk, scale=traj_scale) if kde else None)
     while pend:
         finish(pend.pop(0))
     if pipelined:
@@ -258,9 +317,12 @@ def _scenes_report(model, dataset, scenes_per_call, pipelined, traj_scale, miss_
 
 
 @torch.no_grad()
-def eval_scenes_report(model, dataset, traj_scale=1.0, scenes_per_call=512, z_fn=None, pipelined=True, miss_threshold=1.0, gather=False):
+def eval_scenes_report(model, dataset, traj_scale=1.0, scenes_per_call=512, z_fn=None, pipelined=True, miss_threshold=1.0, gather=False,
+                       joint=False, kde=False, collision_radius=None):
     """eval_scenes with the per-scene breakdown, the best sample of every agent and the miss rate (an ``EvalReport``).  The same calls, latents
-    and global ADE / FDE as eval_scenes; each call adds one selection pass on its own pipeline stream (``select_best_of_k_async``)."""
+    and global ADE / FDE as eval_scenes; each call adds one selection pass on its own pipeline stream (``select_best_of_k_async``).
+    ``joint`` / ``collision_radius`` / ``kde`` add the scene-level passes (``select_joint_async``, ``kde_nll_async``; after the serial call
+    with ``pipelined=False``); every other field is the same with them on or off."""
     K, zd = model.args.sample_k, model.args.zdim
 
     def latents(sb):
@@ -268,30 +330,32 @@ def eval_scenes_report(model, dataset, traj_scale=1.0, scenes_per_call=512, z_fn
         return z_fn(rows) if z_fn is not None else torch.randn(rows, zd, device=model.device)
     return _scenes_report(model, dataset, scenes_per_call, pipelined, traj_scale, miss_threshold, gather,
                           lambda sb: model.inference_async(z=latents(sb), metrics_gt=model._future, metrics_scale=traj_scale),
-                          lambda sb: model.inference(None, z=latents(sb)))
+                          lambda sb: model.inference(None, z=latents(sb)), joint, kde, collision_radius)
 
 
 @torch.no_grad()
 def eval_sampler_report(model, sampler, dataset, traj_scale=1.0, scenes_per_call=512, mean=True, eps_fn=None, pipelined=True,
-                        miss_threshold=1.0, gather=False):
+                        miss_threshold=1.0, gather=False, joint=False, kde=False, collision_radius=None):
     """eval_sampler with the per-scene breakdown, the best sample of every agent and the miss rate (an ``EvalReport``; test_sampler.py:214-217
-    asks count_miss_samples of the same loop)."""
+    asks count_miss_samples of the same loop).  ``joint`` / ``collision_radius`` / ``kde`` as eval_scenes_report."""
     def eps_of(sb):
         return eps_fn(1 if sampler.share_eps else sb.n_agents) if (not mean and eps_fn is not None) else None
     return _scenes_report(model, dataset, scenes_per_call, pipelined, traj_scale, miss_threshold, gather,
                           lambda sb: sampler.inference_async(model, mean=mean, eps=eps_of(sb), metrics_gt=model._future,
                                                              metrics_scale=traj_scale),
-                          lambda sb: sampler.inference(model, mean=mean, eps=eps_of(sb)))
+                          lambda sb: sampler.inference(model, mean=mean, eps=eps_of(sb)), joint, kde, collision_radius)
 
 
 @torch.no_grad()
-def eval_nba_report(model, loader, traj_scale=1.0, z_fn=None, pipelined=True, groups_per_call=16, miss_threshold=1.0, gather=False):
+def eval_nba_report(model, loader, traj_scale=1.0, z_fn=None, pipelined=True, groups_per_call=16, miss_threshold=1.0, gather=False,
+                    joint=False, kde=False, collision_radius=None):
     """NBA evaluation (test.py:495-552) as an ``EvalReport``: ADE / FDE over the whole horizon (the last horizon of eval_nba), the miss rate,
     per loader batch its ADE / FDE / miss count, the best sample of every agent.  Calls as eval_nba: up to ``groups_per_call`` loader batches
-    of one shape per call, several in flight, the selection on each call's pipeline stream with one segment per loader batch."""
+    of one shape per call, several in flight, the selection on each call's pipeline stream with one segment per loader batch.
+    ``joint`` / ``collision_radius`` / ``kde`` as eval_scenes_report; the joint and collision segments are games (N players each)."""
     Tf, K = model.args.future_length, model.args.sample_k
     dev = model.device
-    acc = _ReportAcc(miss_threshold)
+    acc = _ReportAcc(miss_threshold, joint, kde, collision_radius, K)
     if not pipelined:
         for data in loader:
             model.set_data_nba(data)
@@ -301,15 +365,21 @@ def eval_nba_report(model, loader, traj_scale=1.0, z_fn=None, pipelined=True, gr
             sp = np.array([0, n], dtype=np.int32)
             acc.add(model.select_best_of_k(pred.permute(1, 0, 2, 3), scale=traj_scale, miss_threshold=miss_threshold, seg_ptr=sp,
                                            gather=gather), sp)
+            if acc.scene_metrics or kde:
+                pnk = pred.permute(1, 0, 2, 3).contiguous()
+                games = np.arange(0, n + 1, data['past_traj'].shape[1], dtype=np.int32)
+                acc.add_scene_metrics(model.select_joint(pnk, seg_ptr=games, scale=traj_scale, collision_radius=acc.radius)
+                                      if acc.scene_metrics else None, model.kde_nll(pnk, scale=traj_scale) if kde else None)
         return acc.report(gather)
 
     pend = []
     seg_ptrs = {}
 
     def finish(item):
-        h, sel, sp = item
+        h, sel, sp, js, kd = item
         model.wait(h)
         acc.add(sel, sp)
+        acc.add_scene_metrics(js, kd)
 
     def submit(group):
         B, N = group[0]['past_traj'].shape[:2]
@@ -321,6 +391,9 @@ def eval_nba_report(model, loader, traj_scale=1.0, z_fn=None, pipelined=True, gr
             seg_ptrs[(G, B * N)] = torch.arange(0, n + 1, B * N, dtype=torch.int32, device=dev)
             torch.cuda.current_stream(dev).synchronize()
         sp = seg_ptrs[(G, B * N)]
+        if acc.scene_metrics and ('games', G * B, N) not in seg_ptrs:                # one segment per game
+            seg_ptrs[('games', G * B, N)] = torch.arange(0, n + 1, N, dtype=torch.int32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
         model.packed()
         st = model.next_async_stream(n)
         with torch.cuda.stream(st) if st is not None else contextlib.nullcontext():
@@ -328,7 +401,10 @@ def eval_nba_report(model, loader, traj_scale=1.0, z_fn=None, pipelined=True, gr
             z = torch.cat([torch.as_tensor(z_fn(B * N * K)).to(dev) for _ in group]) if z_fn is not None else None
             h = model.inference_async(z=z)
         sel = model.select_best_of_k_async(h, gt=model._future, scale=traj_scale, miss_threshold=miss_threshold, seg_ptr=sp, gather=gather)
-        pend.append((h, sel, np.arange(0, n + 1, B * N)))
+        js = (model.select_joint_async(h, gt=model._future, seg_ptr=seg_ptrs[('games', G * B, N)], scale=traj_scale, collision_radius=acc.radius)
+              if acc.scene_metrics else None)
+        kd = model.kde_nll_async(h, gt=model._future, scale=traj_scale) if kde else None
+        pend.append((h, sel, np.arange(0, n + 1, B * N), js, kd))
         if len(pend) > 3:
             finish(pend.pop(0))
 

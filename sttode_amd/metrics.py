@@ -1,6 +1,9 @@
 """Best-of-K metrics on the device: utils/metrics.py of the reference, on the HIP selection kernel (csrc/frontend.hip
 sttode_best_of_k_select).
 
+``joint_select`` and ``kde_nll`` (csrc/metrics.hip) are the scene-level metrics the reference does not compute: joint min ADE / FDE
+and collision counts per segment, and the KDE NLL per agent.
+
 ``select`` is the kernel call: per agent the min-over-K ADE / FDE, the index of the best sample by ADE and by final displacement
 (``get_best_idx``), the miss flag (``count_miss_samples``) and optionally the best trajectory; per CSR segment (a scene, an NBA batch) the
 mean ADE / FDE and the miss count.  ``STTODENet.select_best_of_k`` / ``select_best_of_k_async`` call it on a model's data and pipeline.
@@ -75,6 +78,106 @@ def select(pred_nk, gt, scale=1.0, miss_threshold=1.0, seg_ptr=None, gather=Fals
     with torch.cuda.device(dev):
         capi.call('sttode_best_of_k_select', pred_nk, gt, n, K, Tf, float(scale), float(miss_threshold), sp, S, *out.args(),
                   capi.stream_ptr())
+    return out
+
+
+# ----- scene-level metrics (csrc/metrics.hip: sttode_joint_select, sttode_kde_nll) -------------------------------------------
+
+class JointSelection:
+    """Outputs of one joint pass (device tensors), per segment s of ``seg_ptr``: ``seg_jade`` / ``seg_jfde`` [S] float32 (min over k of the
+    segment's mean ADE / FDE of sample k), ``seg_jade_idx`` / ``seg_jfde_idx`` [S] int32 (that k, the lowest on exact ties); with a collision
+    radius ``seg_col`` [S] int32 (colliding agents summed over the K samples) and ``seg_gt_col`` [S] int32 (colliding agents of the ground
+    truth), else None."""
+    __slots__ = ('seg_jade', 'seg_jfde', 'seg_jade_idx', 'seg_jfde_idx', 'seg_col', 'seg_gt_col', 'radius')
+
+    def __init__(self, S, device, radius):
+        f = torch.empty(2 * S, dtype=torch.float32, device=device)
+        i = torch.empty((4 if radius else 2) * S, dtype=torch.int32, device=device)
+        self.seg_jade, self.seg_jfde = f[:S], f[S:]
+        self.seg_jade_idx, self.seg_jfde_idx = i[:S], i[S:2 * S]
+        self.seg_col = i[2 * S:3 * S] if radius else None
+        self.seg_gt_col = i[3 * S:] if radius else None
+        self.radius = radius
+
+    def args(self):
+        """radius and output pointers in the order of sttode_joint_select."""
+        return (float(self.radius or 0.0), self.seg_jade, self.seg_jfde, self.seg_jade_idx, self.seg_jfde_idx, self.seg_col, self.seg_gt_col)
+
+    def record_stream(self, stream):
+        for t in (self.seg_jade, self.seg_jade_idx):   # (views: the record covers the whole allocation)
+            t.record_stream(stream)
+
+
+def check_radius(collision_radius):
+    """None (no collision pass) or a positive float."""
+    if collision_radius is None:
+        return None
+    r = float(collision_radius)
+    if not r > 0.0:
+        raise ValueError(f'collision_radius must be positive (or None: no collision pass), got {collision_radius}')
+    return r
+
+
+def check_kde_k(K):
+    if K < 2 or K > 64:
+        raise ValueError(f'KDE NLL needs 2 <= K <= 64 samples (a covariance; one LDS tile per frame block), got K = {K}')
+
+
+def _inputs(pred_nk, gt, what):
+    if not (isinstance(pred_nk, torch.Tensor) and pred_nk.is_cuda):
+        raise capi.SttodeError(f'{what} runs on a HIP device only (no CPU fallback): pass device tensors')
+    if pred_nk.dim() != 4 or pred_nk.shape[3] != 2 or 0 in pred_nk.shape:
+        raise ValueError(f'pred_nk must be [n, K, Tf, 2] with n, K, Tf > 0, got {tuple(pred_nk.shape)}')
+    dev = pred_nk.device
+    pred_nk = pred_nk.to(torch.float32).contiguous()
+    n, K, Tf = pred_nk.shape[:3]
+    gt = torch.as_tensor(gt, dtype=torch.float32).to(dev).contiguous()
+    if tuple(gt.shape) != (n, Tf, 2):
+        raise ValueError(f'gt must be [{n}, {Tf}, 2], got {tuple(gt.shape)}')
+    return pred_nk, gt, n, K, Tf
+
+
+def check_seg_ptr(sp, n):
+    """A CSR [S+1] with S >= 1; a host one must also run non-decreasing from 0 to n (a device one is not read back: the kernels clamp every
+    segment to [0, n])."""
+    if isinstance(sp, torch.Tensor) and sp.is_cuda:
+        if sp.dim() != 1 or sp.numel() < 2:
+            raise ValueError(f'seg_ptr must be a CSR [S+1] with S >= 1, got shape {tuple(sp.shape)}')
+        return
+    v = sp.numpy() if isinstance(sp, torch.Tensor) else np.asarray(sp)
+    if v.ndim != 1 or v.size < 2 or v[0] != 0 or v[-1] != n or (np.diff(v) < 0).any():
+        raise ValueError(f'seg_ptr must be a non-decreasing CSR [S+1] from 0 to n = {n}')
+
+
+@torch.no_grad()
+def joint_select(pred_nk, gt, seg_ptr, scale=1.0, collision_radius=None):
+    """Joint (scene-level) best-of-K of pred_nk [n, K, Tf, 2] against gt [n, Tf, 2] per segment of the CSR ``seg_ptr`` [S+1] (device or
+    host), on the current stream: one sample index k for the whole segment, min over k of the mean over its agents of ADE(a, k) / FDE(a, k)
+    (summed in double); with ``collision_radius`` r > 0 also the collision counts of the samples and of the ground truth (an agent collides
+    if another agent of its segment comes closer than r, strictly, at some frame of the same sample).  K <= 64.  Returns a
+    ``JointSelection``."""
+    pred_nk, gt, n, K, Tf = _inputs(pred_nk, gt, 'joint selection')
+    check_k(K)
+    r = check_radius(collision_radius)
+    check_seg_ptr(seg_ptr, n)
+    sp = seg_ptr_tensor(seg_ptr, pred_nk.device)
+    out = JointSelection(int(sp.numel()) - 1, pred_nk.device, r)
+    with torch.cuda.device(pred_nk.device):
+        capi.call('sttode_joint_select', pred_nk, gt, n, K, Tf, float(scale), sp, int(sp.numel()) - 1, *out.args(), capi.stream_ptr())
+    return out
+
+
+@torch.no_grad()
+def kde_nll(pred_nk, gt, scale=1.0):
+    """KDE negative log-likelihood of gt [n, Tf, 2] under the K samples of pred_nk [n, K, Tf, 2] per agent (Trajectron++'s
+    compute_kde_nll: a Gaussian KDE with Scott's bandwidth per frame, log-density clipped below at -20, averaged over the frames), in
+    float64 on the current stream.  Returns a float64 tensor [n]: NaN for an agent whose samples have a singular covariance at some frame
+    (where scipy.stats.gaussian_kde raises).  2 <= K <= 64."""
+    pred_nk, gt, n, K, Tf = _inputs(pred_nk, gt, 'KDE NLL')
+    check_kde_k(K)
+    out = torch.empty(n, dtype=torch.float64, device=pred_nk.device)
+    with torch.cuda.device(pred_nk.device):
+        capi.call('sttode_kde_nll', pred_nk, gt, n, K, Tf, float(scale), out, capi.stream_ptr())
     return out
 
 

@@ -1061,6 +1061,83 @@ class STTODENet(nn.Module):
         return sel
 
     @torch.no_grad()
+    def select_joint(self, pred_nk, gt=None, seg_ptr=None, scale=1.0, collision_radius=None):
+        """Joint (scene-level) best-of-K and, with ``collision_radius``, collision counts on device: pred_nk [n,K,Tf,2],
+        gt [n,Tf,2] (default: the futures set with the batch), ``seg_ptr`` [S+1] (default: the scene_ptr of set_scene_batch).  Returns a
+        ``metrics.JointSelection``.  K <= 64."""
+        from . import metrics
+        gt = self._future if gt is None else _f32(gt, self.device)
+        if seg_ptr is None:
+            seg_ptr = getattr(self, '_scene_ptr', None)
+            if seg_ptr is None:
+                raise ValueError('select_joint needs seg_ptr (no scene batch is set)')
+        return metrics.joint_select(pred_nk, gt, seg_ptr, scale=scale, collision_radius=collision_radius)
+
+    @torch.no_grad()
+    def kde_nll(self, pred_nk, gt=None, scale=1.0):
+        """KDE NLL per agent on device (Trajectron++'s compute_kde_nll): pred_nk [n,K,Tf,2], gt [n,Tf,2] (default: the
+        futures set with the batch) -> float64 [n], NaN where the samples' covariance is singular at some frame.  2 <= K <= 64."""
+        from . import metrics
+        gt = self._future if gt is None else _f32(gt, self.device)
+        return metrics.kde_nll(pred_nk, gt, scale=scale)
+
+    def _async_metric_inputs(self, handle, gt, what):
+        gt = handle.get('gt_default') if gt is None else gt
+        if not (isinstance(gt, torch.Tensor) and gt.is_cuda and gt.dtype == torch.float32 and gt.is_contiguous()):
+            raise ValueError(f'{what} needs a contiguous float32 device tensor gt [n, Tf, 2] that was written before the call')
+        pred = handle['pred']                                    # contiguous [n, K, Tf, 2]
+        n, K, Tf = pred.shape[:3]
+        if tuple(gt.shape) != (n, Tf, 2):
+            raise ValueError(f'gt must be [{n}, {Tf}, 2], got {tuple(gt.shape)}')
+        return pred, gt, n, K, Tf
+
+    def select_joint_async(self, handle, gt=None, seg_ptr='scenes', scale=1.0, collision_radius=None):
+        """select_joint of an inference_async() call, enqueued on the pipeline stream the call runs on, behind its trajectory groups; nothing
+        goes onto the caller's stream.  ``gt`` (default: the futures set with the batch) and ``seg_ptr`` (a device int32 tensor, or 'scenes':
+        the call's own scene_ptr) must have been written before the inference_async() call.  Returns a ``metrics.JointSelection`` whose
+        tensors are valid after ``wait(handle)``; the handle keeps it alive."""
+        from . import metrics
+        if isinstance(seg_ptr, str):
+            if seg_ptr != 'scenes' or handle['inputs'][1] is None:
+                raise ValueError("seg_ptr='scenes' needs a call made on a scene batch (set_scene_batch / set_data)")
+            seg_ptr = handle['inputs'][1]
+        if handle.get('generic'):
+            js = self.select_joint(handle['pred'], gt=handle.get('gt_default') if gt is None else gt, seg_ptr=seg_ptr, scale=scale,
+                                   collision_radius=collision_radius)
+            handle['joint'] = js
+            return js
+        if not (isinstance(seg_ptr, torch.Tensor) and seg_ptr.is_cuda and seg_ptr.dtype == torch.int32 and seg_ptr.is_contiguous()):
+            raise ValueError('select_joint_async needs seg_ptr as a contiguous int32 device tensor written before the call')
+        pred, gt, n, K, Tf = self._async_metric_inputs(handle, gt, 'select_joint_async')
+        metrics.check_k(K)
+        r = metrics.check_radius(collision_radius)
+        metrics.check_seg_ptr(seg_ptr, n)
+        S = int(seg_ptr.numel()) - 1
+        js = metrics.JointSelection(S, self.device, r)
+        capi.call('sttode_async_joint_select', self.native().h, handle['slot'], pred, gt, n, K, Tf, float(scale), seg_ptr, S, *js.args())
+        if handle.get('stream') is not None:
+            js.record_stream(handle['stream'])
+        handle['joint'] = js
+        return js
+
+    def kde_nll_async(self, handle, gt=None, scale=1.0):
+        """kde_nll of an inference_async() call on the pipeline stream the call runs on, behind its trajectory groups (as
+        select_joint_async).  Returns a float64 device tensor [n], valid after ``wait(handle)``; the handle keeps it alive."""
+        from . import metrics
+        if handle.get('generic'):
+            out = self.kde_nll(handle['pred'], gt=handle.get('gt_default') if gt is None else gt, scale=scale)
+            handle['kde_nll'] = out
+            return out
+        pred, gt, n, K, Tf = self._async_metric_inputs(handle, gt, 'kde_nll_async')
+        metrics.check_kde_k(K)
+        out = torch.empty(n, dtype=torch.float64, device=self.device)
+        capi.call('sttode_async_kde_nll', self.native().h, handle['slot'], pred, gt, n, K, Tf, float(scale), out)
+        if handle.get('stream') is not None:
+            out.record_stream(handle['stream'])
+        handle['kde_nll'] = out
+        return out
+
+    @torch.no_grad()
     def horizon_metrics(self, pred_nk, gt=None, scale=1.0):
         """The NBA evaluation's per-horizon metric (test.py:530-551) on device: pred_nk [n,K,Tf,2], gt [n,Tf,2] -> [n,Tf,2] with
         [a, h-1] = (min_k mean_{t<h} |scale (pred - gt)|, min_k |scale (pred_h - gt_h)|)."""
