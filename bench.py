@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: predicted-trajectories/sec (K=20 best-of-K) of the STTODE forward path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: either launched by ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...`` (one rank
 per GPU, RCCL), or -- when WORLD_SIZE is not in the environment -- bench.py starts exactly that launcher itself as a child
@@ -13,9 +13,15 @@ K=20 decomposition decoder -> device-side best-of-K ADE/FDE) over one batch of s
 Headline workload = BASELINE.json configs[1]: 512 ETH-shaped scenes per GPU (<= 32 pedestrians, obs 8 / pred 12, K = 20);
 weak scaling (each rank owns its own scenes, no data-path collective; one 3-scalar all-reduce of ADE/FDE sums at the end).
 
-The JSON line carries
+A plain run sets up, warms up, times the headline region, writes --dump-outputs and prints the line: `value`, `ms_per_step`, the
+headline region's `clock_ghz`, `ade_fde_synthetic` and
   roofline     : dominant kernel's algorithmic FLOP / its mean duration (HIP events on the launch stream, inside the
-                 timed region) vs the dense fp32 MFMA peak (157.3 TFLOP/s, MI355X_MICROARCH.md);
+                 timed region) vs the dense fp32 MFMA peak (157.3 TFLOP/s, MI355X_MICROARCH.md).
+--full goes on after the headline region and adds what takes runs of its own (the --no-* options and --legs select among them):
+  roofline.*_serial : the same kernel with one launch in flight (a few serial steps);
+  value_incl_d2h : the headline region again with every step's futures copied to pinned host memory;
+  exploratory_bf16x3 : the headline region with the opt-in bf16x3 decoder mode, never `value`;
+  gather       : N > 1: the futures all-gathered over the ranks (check + value_incl_gather);
   cpu_baseline : the CPU oracle (PyTorch-eager port of the reference path, per-scene loop as test.py:171-184) timed on
                  this box's host cores over a bounded sample of the same scenes (rank 0, N = 1 only), 16 threads and 1 thread;
   parity       : HIP vs oracle on the sampled scenes with injected latents (max relative coordinate error, ADE/FDE);
@@ -845,6 +851,10 @@ def main():
     ap.add_argument('--scenes', type=int, default=512, help='scenes per GPU per step of the headline workload')
     ap.add_argument('--cpu-seconds', type=float, default=8.0, help='budget of the headline CPU-baseline sample at 16 threads (half of it again at 1 thread)')
     ap.add_argument('--leg-cpu-seconds', type=float, default=1.5, help='CPU-baseline budget of each secondary leg')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline region, everything else the line can carry: the serial roofline check, value_incl_d2h, sustained, '
+                         'exploratory_bf16x3, the multi-rank gather leg, the configs legs, train, cpu_baseline + parity and per_scene '
+                         '(the --no-* and --legs options below select among them)')
     ap.add_argument('--no-cpu', action='store_true')
     ap.add_argument('--time-every', type=int, default=4, help='bracket the kernels of every n-th step with HIP events (0 = never)')
     ap.add_argument('--serial', action='store_true', help='no cross-step pipelining (one inference() per step)')
@@ -924,7 +934,7 @@ def main():
     roof, kern = head.roofline(r['stage_ms'], r['value'] / world, args.time_every, calls=None if args.serial else args.steps)
     if roof:
         roof['path_frac_survey_flops_superseded'] = r['value'] / world * F_TRAJ_SURVEY / PEAK_F32_MFMA
-    if roof and not args.serial and not args.no_serial_check:
+    if args.full and roof and not args.serial and not args.no_serial_check:
         # the same kernel with ONE launch in flight (a few serial steps, every launch bracketed): the plain per-launch formula
         # flop_per_launch / mean launch duration, the figure `rocprofv3 --kernel-trace --stats` of `bench.py --serial` reproduces
         rs = head.timed(8, 2, dist, 1, serial=True)
@@ -943,7 +953,7 @@ def main():
            'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic', 'clock_ghz': r['clock_ghz'], 'clock_prewarm_steps': args.prewarm,
            'config': head.config(world), 'roofline': roof, 'kernels': kern,
            'timed_region': 'per step: H2D of the scene batch (pinned host -> HBM), set_scene_batch, z ~ N(0,I) on device, the whole forward, '
-                           'device-side best-of-K ADE/FDE; D2H of the futures excluded (value_incl_d2h includes it)',
+                           'device-side best-of-K ADE/FDE; D2H of the futures excluded (value_incl_d2h of --full includes it)',
            'step_form': f'pipelined, lagged launches over {Leg.STREAMS} streams: launch k = per-agent roles of call k (throughput form) + trajectory '
                         f'groups of call k-{Leg.STREAMS}; every step completes inside the timed region (the drain enqueues the outstanding groups)',
            'kernels_note': 'HIP-event durations on the launch streams; launches of consecutive pipelined steps share the chip, so a launch takes '
@@ -953,6 +963,13 @@ def main():
         out['ade_fde_synthetic'] = [float(acc[0] / acc[2]), float(acc[1] / acc[2])]
     if dumped:
         out['dump_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped, 'step': 'the last timed step of the headline region'}
+    if not args.full:
+        # a plain run ends with the headline region: everything below takes timed runs of its own
+        if rank == 0:
+            print(json.dumps(out))
+        if dist is not None:
+            dist.destroy_process_group()
+        return 0
     # D2H-inclusive figure (second key, not the headline): same steps with every step's futures copied to pinned host memory
     # (the region of the headline: as many steps, as much warm-up -- half of them made filling / draining the pipeline and the last copies
     # behind the drain weigh twice as much as they do in `value`)

@@ -8,7 +8,7 @@ R=$PWD
 O=$R/gpurun_out/r04col
 mkdir -p $O
 rm -rf $O/prof_* $O/pmc_* $O/tl_*
-timeout -k 10 600 python bench.py --steps 20 --warmup 5 > $O/final_bench.json 2> $O/final_bench.err || { echo "bench failed"; tail -5 $O/final_bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 > $O/final_bench.json 2> $O/final_bench.err || { echo "bench failed"; tail -5 $O/final_bench.err; exit 1; }
 BQ="--legs none --no-cpu --no-train --no-exploratory --no-per-scene --no-sustained"
 cd /tmp
 # (1) SERIAL kernel stats, no counters: flop_per_launch / AverageNs / 157.3e12 is the plain per-launch roofline fraction of a serial call

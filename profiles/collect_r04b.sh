@@ -10,7 +10,7 @@ timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/gputests.log 2>&1 || 
 tail -2 $O/gputests.log
 timeout -k 10 300 python __graft_entry__.py smoke > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
-timeout -k 10 600 python bench.py --steps 20 --warmup 5 > $O/final_bench.json 2> $O/final_bench.err || { echo "bench failed"; tail -5 $O/final_bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 > $O/final_bench.json 2> $O/final_bench.err || { echo "bench failed"; tail -5 $O/final_bench.err; exit 1; }
 BQ="--legs none --no-cpu --no-train --no-exploratory --no-per-scene --no-sustained"
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_serial_headline -- python3 $R/bench.py --serial $BQ --steps 20 --warmup 3 > $O/prof_serial_headline.log 2>&1 || echo "serial prof failed"

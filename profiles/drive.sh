@@ -28,7 +28,7 @@ train)
             echo "$1 $(env $2 timeout -k 10 300 python bench.py --train --no-cpu 2>/dev/null | trainline)" | tee -a "$OUT/train_step.txt"; }
     if [ -n "$1" ]; then for i in 1 2; do run "$1=$2" "$1=$2"; run "$1=$3" "$1=$3"; done; else run "" "X_=1"; run "" "X_=1"; fi ;;
 bench)
-    timeout -k 10 1100 python bench.py $1 > "$OUT/bench.json" 2> "$OUT/bench.err"; short < "$OUT/bench.json" ;;
+    timeout -k 10 1100 python bench.py --full $1 > "$OUT/bench.json" 2> "$OUT/bench.err"; short < "$OUT/bench.json" ;;
 prof)
     NAME=$1; shift 2
     R=$PWD; ARGS=(); for a in "$@"; do if [ -e "$R/$a" ]; then ARGS+=("$R/$a"); else ARGS+=("$a"); fi; done; set -- "${ARGS[@]}"   # (rocprofv3 runs from /tmp: repo files by absolute path)

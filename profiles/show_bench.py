@@ -1,4 +1,4 @@
-"""Short summary of a bench.py line (the figures DESIGN.md §7 quotes):  python profiles/show_bench.py path/to/final_bench.json"""
+"""Short summary of a `bench.py --full` line (the figures DESIGN.md §7 quotes):  python profiles/show_bench.py path/to/final_bench.json"""
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 r = d['roofline']

@@ -104,13 +104,13 @@ def test_bench_self_launch_spawns_the_ranks():
 def test_dump_outputs_is_what_the_last_timed_step_computed(tmp_path):
     """--dump-outputs DIR: the arrays of the headline region's last timed step (pipelined form, 128 scenes) are what that call computed --
     predictions == the CPU oracle fed the dumped latents (every agent of the first eight scenes), ADE / FDE == their NumPy restatement on
-    those predictions, the line's ade_fde_synthetic == their means -- and a second run with the same arguments draws the same latents."""
+    those predictions, the line's ade_fde_synthetic == their means -- and a second run with the same arguments draws the same latents.
+    Without --full the line carries the headline region alone: none of the keys that take timed runs of their own."""
     import numpy as np
     from helpers import assert_close, oracle_model, oracle_scene_inference
     from oracle.metrics_ref import best_of_k_ade_fde
     from sttode_amd import scenes
-    args = ('--gpus', '1', '--steps', '5', '--warmup', '1', '--prewarm', '0', '--scenes', '128', '--legs', 'none', '--no-cpu', '--no-train',
-            '--no-sustained', '--no-per-scene', '--no-exploratory', '--no-serial-check')
+    args = ('--gpus', '1', '--steps', '5', '--warmup', '1', '--prewarm', '0', '--scenes', '128')
     runs = []
     for i in range(2):
         d = str(tmp_path / f'run{i}')
@@ -118,6 +118,8 @@ def test_dump_outputs_is_what_the_last_timed_step_computed(tmp_path):
         assert r.returncode == 0, r.stderr[-3000:]
         line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
         assert line['steps'] == 5 and line['ms_per_step'] > 0 and line['dump_outputs']['arrays'] == ['ade', 'fde', 'latents', 'pred']
+        assert not set(line) & {'value_incl_d2h', 'sustained', 'exploratory_bf16x3', 'gather', 'configs', 'train', 'cpu_baseline', 'parity', 'per_scene'}
+        assert 'mean_launch_s_serial' not in (line['roofline'] or {})
         runs.append((line, {k: np.load(os.path.join(d, k + '.npy')) for k in line['dump_outputs']['arrays']}))
     line, out = runs[0]
     sb = scenes.make_scene_batch(range(128), 'eth')

@@ -3187,7 +3187,7 @@ def test_pipelined_nba_evaluation_equals_the_serial_loop_and_the_oracle():
 
 
 def test_bench_default_line_rehearsed_at_world_two_on_one_gpu():
-    """Every multi-rank branch of bench.py with HIP kernels, once: the WHOLE default line at world size 2 -- headline, the four legs, `train`
+    """Every multi-rank branch of bench.py with HIP kernels, once: the WHOLE --full line at world size 2 -- headline, the four legs, `train`
     with parallel.average_gradients, the gather leg (futures all-gathered on a communication stream, counts exchanged once, `check: ok`) --
     as two ranks that share cuda:0 with the collectives under gloo (hidden flag --dist-backend gloo; the round-4 review: no N > 1 path of
     bench.py had ever executed with kernels).  A rehearsal of the code path, not a scaling measurement."""
@@ -3198,7 +3198,7 @@ def test_bench_default_line_rehearsed_at_world_two_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
     env.pop('WORLD_SIZE', None)
-    p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--dist-backend', 'gloo', '--steps', '6', '--warmup', '2',
+    p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--dist-backend', 'gloo', '--full', '--steps', '6', '--warmup', '2',
                         '--scenes', '128', '--leg-steps', '6', '--train-steps', '12', '--train-scenes', '6', '--no-exploratory'],
                        capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
