@@ -19,6 +19,7 @@ class Adam(torch.optim.Adam):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, **kw)
         self._plans = None        # per group: (group, params, device table, chunks, rows, gradient offsets from the first one) -- None: (re)build
         self._t = {}              # group index -> steps taken (the per-parameter ``step`` tensors of torch's state are written on demand)
+        self._ngrad = None        # per group: how many parameters had a gradient when the plans were built
 
     @staticmethod
     def _hip_ok(group, ps):
@@ -33,6 +34,7 @@ class Adam(torch.optim.Adam):
     def _build(self):
         """Validate every group once and upload its tensor table; None if any group needs an option the kernel does not implement."""
         plans = []
+        self._ngrad = self._grad_counts()
         for gi, group in enumerate(self.param_groups):
             ps = [p for p in group['params'] if p.grad is not None]
             if not ps:
@@ -63,6 +65,9 @@ class Adam(torch.optim.Adam):
                           [p.data_ptr() for p in ps]))
         return plans
 
+    def _grad_counts(self):
+        return [sum(p.grad is not None for p in group['params']) for group in self.param_groups]
+
     def _sync_steps(self):
         for gi, group, ps, *_ in (self._plans or ()):
             t = float(self._t.get(gi, 0))
@@ -91,10 +96,15 @@ class Adam(torch.optim.Adam):
         if plans is not None:
             # the hot path: the gradients must sit where the uploaded table expects them relative to the first one (the training engine
             # hands every step's gradients out as views of ONE flat buffer with a fixed layout) and the parameters where they were
+            # (a parameter outside the plans that has a gradient now -- an unfrozen layer -- changes its group's count, a non-contiguous
+            # gradient its offset: rebuild)
             try:
-                for gi, group, ps, table, chunks, nrows, offs, pptrs in plans:
+                if self._grad_counts() != self._ngrad:
+                    plans = None
+                for gi, group, ps, table, chunks, nrows, offs, pptrs in plans or ():
                     g0 = ps[0].grad.data_ptr()
-                    if [p.grad.data_ptr() - g0 for p in ps] != offs or ps[-1].data_ptr() != pptrs[-1] or ps[0].data_ptr() != pptrs[0]:
+                    if ([p.grad.data_ptr() - g0 if p.grad.is_contiguous() else -1 for p in ps] != offs or ps[-1].data_ptr() != pptrs[-1]
+                            or ps[0].data_ptr() != pptrs[0]):
                         plans = None
                         break
             except AttributeError:                                # a gradient is None this step
@@ -103,7 +113,9 @@ class Adam(torch.optim.Adam):
             self._sync_steps()
             plans = self._plans = self._build()
             if plans is None:                                     # an option the kernel does not implement: torch's own step throughout
-                return super().step()
+                super().step()
+                self._t = {}                                      # torch advanced the state's step tensors: the next plans read them again
+                return loss
         L, st = capi.lib(), capi.stream_ptr()
         for gi, group, ps, table, chunks, nrows, offs, pptrs in plans:
             t = self._t[gi] = self._t.get(gi, 0) + 1
