@@ -24,7 +24,7 @@ extern "C" {
 #endif
 
 /* Version of this header: the library returns it from sttode_abi_version(); a binding compares before its first call (round 1-2: 1). */
-#define STTODE_ABI_VERSION 13
+#define STTODE_ABI_VERSION 14
 int sttode_abi_version(void);
 const char* sttode_last_error(void);
 
@@ -474,6 +474,22 @@ int sttode_pmath_pair(int which, const float* x, const float* y, const float* A,
 int sttode_pmath_mean(const float* x, float* yl_ws, float* lam_ws, float* out, int rows, int d, float c, void* stream);
 /* Oblique.dist (core/manifolds/oblique.py:36-43): p1 [nb,n1,d], p2 [nb,n2,d] -> acos(clamp(p2 p1^T)) [nb,n2,n1]. */
 int sttode_oblique_dist(const float* p1, const float* p2, float* out, int nb, int n1, int n2, int d, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Gromov delta-hyperbolicity (hyptorch/delta.py:12-35).  Stand-alone analysis, not on the model's data flow.
+ * ------------------------------------------------------------------------------------------------ */
+/* scipy.spatial.distance_matrix of T row samples (delta.py:29-31): X [rows,d] row-major; idx [T,n] int32 row indices into X (NULL: the rows
+ * as given, then T == 1 and n == rows); dist [T,n,n] (dist_floats >= T n^2) gets sqrt(sum_k (x_i - x_j)^2) in fp32, k in order for every
+ * pair -- bitwise symmetric, exact zero diagonal; diam [T] gets each try's maximum (delta.py:32; zeroed on `stream` first).  An idx entry
+ * outside [0, rows) reads nothing and gives NaN distances and a NaN diameter.  1 <= n <= 32768, 1 <= T <= 65535, d >= 1. */
+int sttode_delta_dist(const float* X, int rows, int d, const int* idx, int T, int n, float* dist, long dist_floats, float* diam, void* stream);
+/* *floats = the workspace sttode_delta_hyp needs for T tries of n points, in floats (either path).  Host only. */
+int sttode_delta_workspace(int T, int n, long* floats);
+/* delta_hyp (delta.py:12-23) of T matrices at once: dist [T,n,n] (dist_floats >= T n^2; any finite values, symmetry not required) ->
+ * delta [T] = max_ij (max_k min(A[i,k], A[k,j]) - A[i,j]) with A[i,j] = 0.5f * ((D[0,j] + D[i,0]) - D[i,j]), all in fp32 (min / max exact):
+ * delta, not delta / diam.  symmetric = 1 only when every D is bitwise symmetric (sttode_delta_dist's output is): then only the tiles
+ * j-block >= i-block run, with the same result.  ws [ws_floats >= sttode_delta_workspace(T, n)] holds per-tile maxima; two launches. */
+int sttode_delta_hyp(const float* dist, int T, int n, long dist_floats, int symmetric, float* ws, long ws_floats, float* delta, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Native forward pipeline: one call enqueues STTODENet.inference (model/STTODE.py:574-623) end to end.

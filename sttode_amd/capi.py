@@ -11,7 +11,7 @@ _LIB = None
 LIB_PATH = os.environ.get('STTODE_HIP_LIB') or os.path.join(os.path.dirname(os.path.abspath(__file__)), 'lib', 'libsttode_hip.so')
 
 _P, _I, _L, _F, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double
-ABI_VERSION = 13  # == STTODE_ABI_VERSION of include/sttode_hip.h; lib() refuses a library built from another header
+ABI_VERSION = 14  # == STTODE_ABI_VERSION of include/sttode_hip.h; lib() refuses a library built from another header
 
 # name -> argtypes (mirrors include/sttode_hip.h; tests/test_capi_symbols.py checks header == table == .so)
 SIGNATURES = {
@@ -86,6 +86,10 @@ SIGNATURES = {
     'sttode_pmath_pair': [_I, _P, _P, _P, _P, _I, _I, _I, _F, _P],
     'sttode_pmath_mean': [_P, _P, _P, _P, _I, _I, _F, _P],
     'sttode_oblique_dist': [_P, _P, _P, _I, _I, _I, _I, _P],
+    # Gromov delta-hyperbolicity (csrc/delta.hip)
+    'sttode_delta_dist': [_P, _I, _I, _P, _I, _I, _P, _L, _P, _P],
+    'sttode_delta_workspace': [_I, _I, ctypes.POINTER(ctypes.c_long)],
+    'sttode_delta_hyp': [_P, _I, _I, _L, _I, _P, _L, _P, _P],
     # native pipeline (csrc/pipeline.hip)
     'sttode_model_create': [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), _I, _I, _I, _I, _I, _I],
     'sttode_model_destroy': [_P],

@@ -8,6 +8,8 @@
   eval_scenes_report / eval_sampler_report / eval_nba_report: the same loops returning an EvalReport -- global ADE / FDE and miss rate,
                   per-scene (per NBA batch) ADE / FDE / miss count, the best sample of every agent (utils/metrics.py:29-48); on request
                   the scene-level metrics of DESIGN.md 4l: joint min ADE / FDE, collision rates, KDE NLL.
+  embedding_delta  how tree-like the encoder's past features (or the observed tracks) of a dataset are: delta / diam of hyptorch/delta.py's
+                   batched_delta_hyp over all agents.
 """
 import contextlib
 import dataclasses
@@ -421,3 +423,35 @@ def eval_nba_report(model, loader, traj_scale=1.0, z_fn=None, pipelined=True, gr
         finish(pend.pop(0))
     model.reset_async()
     return acc.report(gather)
+
+
+@torch.no_grad()
+def embedding_delta(model, source, n_tries=10, batch_size=1500, scenes_per_call=512, what='past_feature', metric='euclidean'):
+    """Gromov delta / diam (sttode_amd.delta.batched_delta_hyp) of one row per agent of a dataset; returns (mean, std) as np.float64.
+    ``source``: a scene dataset (``scene_batch(indices)``, as eval_scenes takes), ``scenes_per_call`` scenes per set_scene_batch, or an NBA
+    loader of seq_collate dicts (as eval_nba takes), one set_data_nba per batch.  Rows, gathered on the device in dataset order:
+    ``what='past_feature'`` -- encode_history()'s [n, 128] encoder output (model/STTODE.py:488-496); ``'past_traj'`` -- the observed track
+    relative to the current location, [n, 2 Tp].  The samples are drawn from numpy's global RNG as batched_delta_hyp draws them."""
+    from .delta import batched_delta_hyp
+    if what not in ('past_feature', 'past_traj'):
+        raise ValueError(f"embedding_delta: what must be 'past_feature' or 'past_traj', got {what!r}")
+    rows = []
+
+    def take():
+        pf = model.encode_history()
+        if what == 'past_feature':
+            rows.append(pf.clone())                                       # a view into the model's workspace: the next batch overwrites it
+        else:
+            rows.append((model.past_traj - model.cur_location).reshape(model.past_traj.shape[0], -1).contiguous())
+    if hasattr(source, 'scene_batch'):
+        for s0 in range(0, len(source), scenes_per_call):
+            sb = source.scene_batch(range(s0, min(s0 + scenes_per_call, len(source))))
+            model.set_scene_batch(sb.past, sb.future, sb.scene_ptr)
+            take()
+    else:
+        for data in source:
+            model.set_data_nba(data)
+            take()
+    if not rows:
+        raise ValueError('embedding_delta: the source yielded no agents')
+    return batched_delta_hyp(torch.cat(rows), n_tries=n_tries, batch_size=batch_size, metric=metric)
