@@ -104,3 +104,14 @@ __device__ __forceinline__ void glds16_asm(const void* gsrc, unsigned lds_dst) {
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
 }
+// The same in the instruction's scalar-base form: address = sbase (wave-uniform, SGPRs) + voff (32-bit per-lane byte offset) + OFS.
+// No 64-bit per-lane address arithmetic (v_lshl_add_u64) per piece: the per-lane offset is computed once, the uniform part of the
+// address advances in SGPRs, and a constant step folds into OFS, the 13-bit signed immediate.  The hardware adds OFS to the LDS
+// address as well, so M0 is set to lds_dst - OFS.
+template <int OFS>
+__device__ __forceinline__ void glds16_sv(const void* sbase, unsigned voff, unsigned lds_dst) {
+    static_assert(OFS >= -4096 && OFS <= 4095, "global_load_lds_dwordx4: the immediate offset is 13-bit signed");
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:%4\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst - (unsigned)OFS), "i"(OFS) : "memory");
+}

@@ -18,7 +18,7 @@
 //     32 rows x 32 k), double buffered, one workgroup barrier per chunk; the chunk order is a host-built PROGRAM
 //     (packing.chain_stream), so the kernel only consumes tiles in order.  The GRU's recurrent weights are streamed per
 //     step like everything else (66 FLOP per streamed byte, the same intensity as the MLP layers), which frees the
-//     144 KiB of LDS round 1 pinned for them: LDS per workgroup is 24 KiB ring + 32 KiB gather / z slots + 8 KiB biases + program.
+//     144 KiB of LDS round 1 pinned for them: LDS per workgroup is 24 KiB ring + 32 KiB gather / z slots + 8 KiB biases.
 //   * workgroup = 4 waves x 32 columns = 128 trajectories, 2 workgroups per CU (<= 256 VGPRs per wave); groups are
 //     handed out by an atomic work counter (one tail for the whole chain instead of three, and a later launch on
 //     another stream fills it: the kernel holds no chip-wide resource).
@@ -137,43 +137,52 @@ __device__ __forceinline__ f32x16 ldrows(const float* p, int h) {
     return r;
 }
 
+// The chunk program in global memory, read with scalar loads (s_load_dwordx2: the entries arrive in SGPRs, no LDS copy, no readfirstlane).
+typedef const __attribute__((address_space(4))) int KProg;   // (first, count) pairs as flat ints
+
 // BUF: f32x4 per ring buffer (= the largest chunk).  GEN = false: program entries are (first PK32 tile, tiles <= 3) of 4-KiB tiles;
 // GEN = true (exploratory bf16-split mode: tiles of 6 and 4 KiB in one pool): (offset in f32x4 units, number of 1-KiB pieces).
+// Every address of the DMA is uniform but the lane's 16 B: the source advances in SGPRs (glds16_sv), the lane offset is one VGPR.
 template <int BUF, bool GEN>
 struct ChainStreamT {
     static constexpr int kBuf = BUF;
-    const f32x4* pool; const int2* lprog; f32x4* ring;  // lprog: the chunk program, copied to LDS at kernel start
-    unsigned ring_addr;
+    const char* pool; KProg* prog; f32x4* ring;
+    unsigned ring_addr, loff;  // loff: this lane's byte offset in a 1-KiB piece
     int len, p, par, lane, wave;
-    int2 nxt_v;  // program entry of the chunk after the one in flight: read from LDS one step early, consumed at the next begin()
+    int2 nxt_v;  // program entry of the chunk after the one in flight: loaded one step early, consumed at the next begin()
+    int cnt;     // tiles of the chunk whose begin() comes next (TileFeed)
+    __device__ __forceinline__ int2 entry(int q) const { return make_int2(prog[2 * q], prog[2 * q + 1]); }
     __device__ __forceinline__ void dma(int2 ev, int buf) {
         // a chunk = `pieces` pieces of 1 KiB; wave w moves pieces w, w+4, w+8, ...
-        const int off = __builtin_amdgcn_readfirstlane(ev.x), cnt = __builtin_amdgcn_readfirstlane(ev.y);
-        const f32x4* src = pool + (GEN ? (size_t)off : (size_t)off * C32_TILE) + lane;
-        const int pieces = GEN ? cnt : 4 * cnt;
+        const char* src = pool + (size_t)ev.x * (GEN ? 16 : C32_TILE * 16) + wave * 1024;
+        const int pieces = GEN ? ev.y : 4 * ev.y;
         const unsigned dst = __builtin_amdgcn_readfirstlane(ring_addr + (unsigned)buf * (BUF * 16) + (unsigned)wave * 1024);
 #ifndef C32_DIAG_NODMA
 #pragma unroll
         for (int i = 0; i < (BUF / 64 + 3) / 4; ++i)
-            if (4 * i + wave < pieces) glds16_asm(src + (4 * i + wave) * 64, dst + i * 4096);
+            if (4 * i + wave < pieces) glds16_sv<0>(src + i * 4096, loff, dst + i * 4096);
 #endif
     }
-    __device__ __forceinline__ void init(const f32x4* pool_, const int2* lprog_, int len_, f32x4* ring_) {
-        pool = pool_; lprog = lprog_; len = len_; ring = ring_;
+    __device__ __forceinline__ void init(const f32x4* pool_, const int2* prog_, int len_, f32x4* ring_) {
+        pool = reinterpret_cast<const char*>(pool_); prog = (KProg*)prog_; len = len_; ring = ring_;
         ring_addr = lds_addr(ring_);
         lane = threadIdx.x & 63;
+        loff = (unsigned)lane * 16;
         wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
         p = 0; par = 0;
-        dma(lprog[0], 0);
-        nxt_v = lprog[1 % len];
+        const int2 e0 = entry(0);
+        cnt = e0.y;
+        dma(e0, 0);
+        nxt_v = entry(1 % len);
     }
     // start of a chunk step: prefetch the next chunk into the other buffer (its readers passed the previous barrier)
     __device__ __forceinline__ void begin() {
         __builtin_amdgcn_sched_barrier(0);
+        cnt = nxt_v.y;
         dma(nxt_v, par ^ 1);
         int q = p + 2;
         q = q >= len ? q - len : q;
-        nxt_v = lprog[q];
+        nxt_v = entry(q);
         __builtin_amdgcn_sched_barrier(0);
     }
     __device__ __forceinline__ const f32x4* cur() const { return ring + par * BUF + lane; }
@@ -200,6 +209,17 @@ __device__ __forceinline__ void tile_mma(f32x16& acc, const f32x4* __restrict__ 
         for (int r = 0; r < 4; ++r) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[r], B[4 * g + r], acc, 0, 0, 0);
     }
 }
+
+// The four 1-KiB LDS-DMA pieces of a 32-feature block of per-lane rows into a gather slot: lane (c, h) fetches features 8a + 4h .. + 3,
+// a = 0..3, of the row at byte offset `voff` from the uniform `base` (voff includes the 16 h); the step of a folds into the immediate.
+__device__ __forceinline__ void gather_rows(const void* base, unsigned voff, unsigned slot_addr) {
+    glds16_sv<0>(base, voff, slot_addr);
+    glds16_sv<32>(base, voff, slot_addr + 1024);
+    glds16_sv<64>(base, voff, slot_addr + 2048);
+    glds16_sv<96>(base, voff, slot_addr + 3072);
+}
+// lane's byte offset of row `row` (of `width` floats) in a gather table, the lane half's 16 B included
+__device__ __forceinline__ unsigned row_off(int row, int width, int h) { return (unsigned)row * (unsigned)(width * 4) + (unsigned)h * 16; }
 
 // Software-pipelined form.  A lone wave per SIMD issues in order: with the fragment reads placed right in front of their MFMAs
 // (what hipcc does with tile_mma) every pair of reads costs ~40 idle matrix-pipe cycles (LDS latency ~100 vs the 64-cycle shadow of
@@ -228,10 +248,10 @@ __device__ __forceinline__ void tile_mma2(f32x16& acc, const Frag& cur, const f3
 // z (the first layer-1 k-tile's B operand) is read from the wave's LDS z slot every hidden tile (it would cost 16 VGPRs for the
 // whole group otherwise; the kernel has 256 and must not spill: a kernel with ANY scratch pays a scratch set-up per dispatch).
 // The per-agent pre-activation rows arrive through the wave's gather slot (4 x 16 B per lane per hidden tile, LDS-DMA):
-// a0 points at this lane's A0 row; a0_next at the row the NEXT phase starts with.
+// this lane's A0 row is at byte offset aoff of table tab; the row the NEXT phase starts with at aoff_next of tab_next.
 template <int KH, class ST>
-__device__ __forceinline__ void mlp_l12(ST& st, const f32x4* slot, const f32x4* zslot, const f32x16* Bh,
-                                        const float* __restrict__ a0, const float* __restrict__ a0_next, f32x16 (&acc2)[8], int lane, int h) {
+__device__ __forceinline__ void mlp_l12(ST& st, const f32x4* slot, const f32x4* zslot, const f32x16* Bh, const float* tab, unsigned aoff,
+                                        const float* tab_next, unsigned aoff_next, f32x16 (&acc2)[8], int lane) {
     const unsigned slot_addr = __builtin_amdgcn_readfirstlane(lds_addr(slot));
     constexpr int KT1 = 1 + KH;
     static_assert((KT1 + 8) % 3 == 0, "hidden tile must be a whole number of chunks");
@@ -252,7 +272,9 @@ __device__ __forceinline__ void mlp_l12(ST& st, const f32x4* slot, const f32x4* 
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slot is re-filled by the gather issued next
         __builtin_amdgcn_sched_barrier(0);
-        const float* nx = (ht + 1 < 16) ? a0 + 32 * (ht + 1) : a0_next;
+        const bool nl = ht + 1 < 16;   // (uniform) the next hidden tile's rows: the hidden-tile step advances the scalar base
+        const void* nb = nl ? (const void*)(reinterpret_cast<const char*>(tab) + 128 * (ht + 1)) : (const void*)tab_next;
+        const unsigned no = nl ? aoff : aoff_next;
         Frag fr[2];
 #pragma unroll
         for (int i = 0; i < KT1 + 8; ++i) {
@@ -262,8 +284,7 @@ __device__ __forceinline__ void mlp_l12(ST& st, const f32x4* slot, const f32x4* 
                 st.begin();
                 if (i == 0) {
 #ifndef C32_DIAG_NOGATHER
-#pragma unroll
-                    for (int a = 0; a < 4; ++a) glds16_asm(nx + 8 * a + 4 * h, slot_addr + a * 1024);
+                    gather_rows(nb, no, slot_addr);
 #endif
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -384,8 +405,8 @@ __device__ __forceinline__ void tile_mma_b3n(f32x16& acc, const f32x4* __restric
 // registers -- keeping three more tiles as planes would cost 72 VGPRs the kernel does not have) + 8 layer-2 row tiles.
 // PRE: fragment look-ahead across tiles (KH = 0); without it 24 fewer VGPRs (KH = 3).
 template <int KH, bool PRE, class ST>
-__device__ __forceinline__ void mlp_l12_b3(ST& st, const f32x4* slot, const f32x4* zslot, const f32x16* Bh, const float* __restrict__ a0,
-                                           const float* __restrict__ a0_next, f32x16 (&acc2)[8], int lane, int h) {
+__device__ __forceinline__ void mlp_l12_b3(ST& st, const f32x4* slot, const f32x4* zslot, const f32x16* Bh, const float* tab, unsigned aoff,
+                                           const float* tab_next, unsigned aoff_next, f32x16 (&acc2)[8], int lane) {
     const unsigned slot_addr = __builtin_amdgcn_readfirstlane(lds_addr(slot));
     constexpr int KT1 = 1 + KH;
     static_assert((KT1 + 8) % 3 == 0, "hidden tile must be a whole number of chunks");
@@ -425,7 +446,9 @@ __device__ __forceinline__ void mlp_l12_b3(ST& st, const f32x4* slot, const f32x
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slot is re-filled by the gather issued next
         __builtin_amdgcn_sched_barrier(0);
-        const float* nx = (ht + 1 < 16) ? a0 + 32 * (ht + 1) : a0_next;
+        const bool nl = ht + 1 < 16;
+        const void* nb = nl ? (const void*)(reinterpret_cast<const char*>(tab) + 128 * (ht + 1)) : (const void*)tab_next;
+        const unsigned no = nl ? aoff : aoff_next;
         Frag6 fr[2];
 #pragma unroll
         for (int i = 0; i < KT1 + 8; ++i) {
@@ -435,8 +458,7 @@ __device__ __forceinline__ void mlp_l12_b3(ST& st, const f32x4* slot, const f32x
                 st.begin();
                 if (i == 0) {
 #ifndef C32_DIAG_NOGATHER
-#pragma unroll
-                    for (int a = 0; a < 4; ++a) glds16_asm(nx + 8 * a + 4 * h, slot_addr + a * 1024);
+                    gather_rows(nb, no, slot_addr);
 #endif
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -754,8 +776,7 @@ __global__ __launch_bounds__(256, 2) void traj_chain_kernel(ChainArgs A) {
     f32x4* slots = ring + 2 * Stream::kBuf;
     f32x4* zslots = slots + 4 * C32_SLOT;
     float* cst = reinterpret_cast<float*>(zslots + 4 * C32_SLOT);
-    int2* lprog = reinterpret_cast<int2*>(cst + C32Const<NY>::total);
-    int* sq = reinterpret_cast<int*>(lprog + A.prog_len);  // [2]: this workgroup's first group / the group after the current one
+    int* sq = reinterpret_cast<int*>(cst + C32Const<NY>::total);  // [2]: this workgroup's first group / the group after the current one
     typedef C32Const<NY> CO;
 
     const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
@@ -787,7 +808,6 @@ __global__ __launch_bounds__(256, 2) void traj_chain_kernel(ChainArgs A) {
         return;
     }
     for (int i = threadIdx.x; i < CO::total; i += blockDim.x) cst[i] = A.consts[i];
-    for (int i = threadIdx.x; i < A.prog_len; i += blockDim.x) lprog[i] = A.prog[i];
     // A.persistent (FUSE 0 / 2): the workgroup is a WORKER that pulls groups from the call's work queue until it is empty.  Lagged launch:
     // worker w starts with group w and draws tickets only for its further groups, and not at all when every group has a worker --
     // same-address atomics of a whole grid starting together serialise at ~1 us each (measured: 213 workers, +0.2 ms per launch)
@@ -814,17 +834,13 @@ __global__ __launch_bounds__(256, 2) void traj_chain_kernel(ChainArgs A) {
     }
     if (g >= ngroups) return;  // (uniform) cannot happen with grid <= ngroups; nothing is in flight yet
     Stream st;
-    st.init(A.pool, lprog, A.prog_len, ring);
+    st.init(A.pool, A.prog, A.prog_len, ring);
 
     auto col_of = [&](int gg) { int col = gg * 128 + wave * 32 + c; return col < A.ncols ? col : A.ncols - 1; };
     {   // first gathers: A0x rows of hidden tile 0, and z of this group
         const int c0 = col_of(g);
-        const float* a0 = A.A0x + (size_t)(c0 / A.K) * 512;
-        const float* zp = A.z + (size_t)c0 * 32;
-#pragma unroll
-        for (int a = 0; a < 4; ++a) glds16_asm(a0 + 8 * a + 4 * h, slot_addr + a * 1024);
-#pragma unroll
-        for (int a = 0; a < 4; ++a) glds16_asm(zp + 8 * a + 4 * h, zslot_addr + a * 1024);
+        gather_rows(A.A0x, row_off(c0 / A.K, 512, h), slot_addr);
+        gather_rows(A.z, row_off(c0, 32, h), zslot_addr);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -849,11 +865,12 @@ __global__ __launch_bounds__(256, 2) void traj_chain_kernel(ChainArgs A) {
         {   // ---- block 0, decoder_x: x_hat0, d = x_true - x_hat0
             agent = opaque(agent);
             f32x16 xo[1];
+            const unsigned ao = row_off(agent, 512, h);
             if (B3M) {
-                mlp_l12_b3<0, true>(st, slot, zslot, nullptr, A.A0x + (size_t)agent * 512, A.A0y + (size_t)agent * 512, acc2, lane, h);
+                mlp_l12_b3<0, true>(st, slot, zslot, nullptr, A.A0x, ao, A.A0y, ao, acc2, lane);
                 mlp_l3_b3<1>(st, acc2, cst + CO::b2x, cst + CO::b3x, xo, h);
             } else {
-                mlp_l12<0>(st, slot, zslot, nullptr, A.A0x + (size_t)agent * 512, A.A0y + (size_t)agent * 512, acc2, lane, h);
+                mlp_l12<0>(st, slot, zslot, nullptr, A.A0x, ao, A.A0y, ao, acc2, lane);
                 mlp_l3<1>(st, acc2, cst + CO::b2x, cst + CO::b3x, xo, h);
             }
             agent = opaque(agent);
@@ -871,11 +888,12 @@ __global__ __launch_bounds__(256, 2) void traj_chain_kernel(ChainArgs A) {
         {   // ---- block 0, decoder_y: y_hat0 parked in pred (re-read by the epilogue)
             agent = opaque(agent);
             f32x16 yo[NY];
+            const unsigned ao = row_off(agent, 512, h);
             if (B3M) {
-                mlp_l12_b3<0, true>(st, slot, zslot, nullptr, A.A0y + (size_t)agent * 512, A.A1y + (size_t)agent * 512, acc2, lane, h);
+                mlp_l12_b3<0, true>(st, slot, zslot, nullptr, A.A0y, ao, A.A1y, ao, acc2, lane);
                 mlp_l3_b3<NY>(st, acc2, cst + CO::b2y, cst + CO::b3y, yo, h);
             } else {
-                mlp_l12<0>(st, slot, zslot, nullptr, A.A0y + (size_t)agent * 512, A.A1y + (size_t)agent * 512, acc2, lane, h);
+                mlp_l12<0>(st, slot, zslot, nullptr, A.A0y, ao, A.A1y, ao, acc2, lane);
                 mlp_l3<NY>(st, acc2, cst + CO::b2y, cst + CO::b3y, yo, h);
             }
             if (live) {
@@ -912,13 +930,11 @@ __global__ __launch_bounds__(256, 2) void traj_chain_kernel(ChainArgs A) {
         {   // ---- block 1, decoder_y + epilogue
             agent = opaque(agent);
             const int cnx = col_of(gnext < ngroups ? gnext : g);
-            if (B3M) mlp_l12_b3<3, false>(st, slot, zslot, hs, A.A1y + (size_t)agent * 512, A.A0x + (size_t)(cnx / A.K) * 512, acc2, lane, h);
-            else mlp_l12<3>(st, slot, zslot, hs, A.A1y + (size_t)agent * 512, A.A0x + (size_t)(cnx / A.K) * 512, acc2, lane, h);
-            {   // z of the NEXT group into the z slot (this group's last read of it is behind us); lands during layer 3
-                const float* zp = A.z + (size_t)opaque(cnx) * 32;
-#pragma unroll
-                for (int a = 0; a < 4; ++a) glds16_asm(zp + 8 * a + 4 * h, zslot_addr + a * 1024);
-            }
+            const unsigned ao = row_off(agent, 512, h), an = row_off(cnx / A.K, 512, h);
+            if (B3M) mlp_l12_b3<3, false>(st, slot, zslot, hs, A.A1y, ao, A.A0x, an, acc2, lane);
+            else mlp_l12<3>(st, slot, zslot, hs, A.A1y, ao, A.A0x, an, acc2, lane);
+            // z of the NEXT group into the z slot (this group's last read of it is behind us); lands during layer 3
+            gather_rows(A.z, row_off(opaque(cnx), 32, h), zslot_addr);
             f32x16 yo[NY];
             if (B3M) mlp_l3_b3<NY>(st, acc2, cst + CO::b2m, cst + CO::b3m, yo, h);
             else mlp_l3<NY>(st, acc2, cst + CO::b2m, cst + CO::b3m, yo, h);
@@ -1011,14 +1027,12 @@ __global__ __launch_bounds__(256, 2) void gru32_kernel(Gru32Args A) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     f32x4* ring = reinterpret_cast<f32x4*>(smem);
     float* cst = reinterpret_cast<float*>(ring + C32_RING);
-    int2* lprog = reinterpret_cast<int2*>(cst + 416);
     const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     for (int i = threadIdx.x; i < 416; i += blockDim.x) cst[i] = A.consts[i];
-    for (int i = threadIdx.x; i < A.prog_len; i += blockDim.x) lprog[i] = A.prog[i];
     __syncthreads();
     ChainStream st;
-    st.init(A.pool, lprog, A.prog_len, ring);
+    st.init(A.pool, A.prog, A.prog_len, ring);
     const int col = blockIdx.x * 128 + wave * 32 + c;
     const int colc = col < A.ncols ? col : A.ncols - 1;
     f32x16 d;
@@ -1067,14 +1081,14 @@ static int gru_zero_skip() {
     static const int v = getenv("STTODE_GRU_ZERO_SKIP") ? atoi(getenv("STTODE_GRU_ZERO_SKIP")) != 0 : 1;
     return v;
 }
-static int chain_lds(int NY, int prog_len, bool b3 = false) { return ((b3 ? 2 * C32_BUF_B3 : C32_RING) + 8 * C32_SLOT) * 16 + (1216 + 64 * NY) * 4 + prog_len * 8 + 16; }
+static int chain_lds(int NY, bool b3 = false) { return ((b3 ? 2 * C32_BUF_B3 : C32_RING) + 8 * C32_SLOT) * 16 + (1216 + 64 * NY) * 4 + 16; }
 
 static int role_lds(int Tp) {   // agent_role's phases: embed (Tp*256 + 512 f32x4), GRU (h tiles 12 KiB + image of hidden tiles 4, 5: 48 KiB)
     const int e = (Tp * 256 + 512) * 16, g = (2 * 6 * 64 + 2 * 24 * 64 + 2 * 4 * 64) * 16;   // h tiles 12 KiB + image 48 KiB + gate hand-off 8 KiB
     return e > g ? e : g;
 }
 
-static int role32_lds(int prog_len) { return C32_RING * 16 + R32C::total * 4 + prog_len * 8 + 16; }
+static int role32_lds() { return C32_RING * 16 + R32C::total * 4; }
 
 template <int NY, int FUSE, bool B3M = false> static int chain_launch(ChainArgs a, int wgs_per_cu, hipStream_t s) {
     void (*kern)(ChainArgs) = gru_zero_skip() ? traj_chain_kernel<NY, FUSE, B3M, true> : traj_chain_kernel<NY, FUSE, B3M, false>;
@@ -1093,11 +1107,13 @@ template <int NY, int FUSE, bool B3M = false> static int chain_launch(ChainArgs 
     // keeps the matrix pipe about as busy as two do (469 vs 2 x 397 us per group), and the other half of the register file plus ~76 KiB
     // of LDS stay free for kernels of OTHER streams (the separate per-agent launches of the unfused pipeline).  The fused launch needs
     // no co-residency and runs two per CU everywhere.
-    int lds = chain_lds(NY, a.prog_len, B3M);
+    int lds = chain_lds(NY, B3M);
     if (FUSE == 1 && lds < role_lds(a.Tp)) lds = role_lds(a.Tp);
-    if (FUSE == 2 && a.R32.nwg > 0 && lds < role32_lds(a.R32.prog_len)) lds = role32_lds(a.R32.prog_len);
+    if (FUSE == 2 && a.R32.nwg > 0 && lds < role32_lds()) lds = role32_lds();
     if (wgs_per_cu == 1 && lds < 84 * 1024) lds = 84 * 1024;
     STT_REQUIRE(lds <= 96 * 1024, "sttode_traj_chain: dynamic LDS beyond the 96 KiB the kernel is registered for");
+    STT_REQUIRE((long)a.ncols * 128 <= 0xffffffffL && (long)((a.ncols + a.K - 1) / a.K) * 2048 <= 0xffffffffL,
+                "sttode_traj_chain: z / per-agent table rows beyond the 32-bit byte offsets of the gathers");
     if (FUSE == 1) STT_HIP(hipMemsetAsync(a.R.flags, 0, (((size_t)(a.R.split ? 5 : 1) * a.R.ntiles + 1) * 4 + 15) / 16 * 16, s));   // tile flags + time-out word
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a);
     STT_HIP(hipGetLastError());
@@ -1114,7 +1130,7 @@ extern "C" int sttode_gru_cols32(const float* xin, int ldx, const float* pool, c
     Gru32Args a;
     a.xin = xin; a.ldx = ldx; a.pool = (const f32x4*)pool; a.prog = (const int2*)prog; a.prog_len = prog_len; a.consts = consts;
     a.state = state; a.ncols = ncols; a.Tp = Tp;
-    const int lds = C32_RING * 16 + 416 * 4 + prog_len * 8 + 16;
+    const int lds = C32_RING * 16 + 416 * 4;
     hipLaunchKernelGGL(gru_zero_skip() ? gru32_kernel<true> : gru32_kernel<false>, dim3((ncols + 127) / 128), dim3(256), lds, (hipStream_t)stream, a);
     STT_HIP(hipGetLastError());
     return 0;
@@ -1125,13 +1141,10 @@ extern "C" int sttode_gru_cols32(const float* xin, int ldx, const float* pool, c
 __global__ __launch_bounds__(256, 2) void sampler_qnet32_kernel(QNet32Args Q) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     f32x4* ring = reinterpret_cast<f32x4*>(smem);
-    int2* lprog = reinterpret_cast<int2*>(ring + C32_RING);
     const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    for (int i = threadIdx.x; i < Q.prog_len; i += blockDim.x) lprog[i] = Q.prog[i];
-    __syncthreads();
     ChainStream st;
-    st.init(Q.pool, lprog, Q.prog_len, ring);
+    st.init(Q.pool, Q.prog, Q.prog_len, ring);
     const int col = blockIdx.x * 128 + wave * 32 + c;
     const bool live = col < Q.n;
     const int colc = live ? col : Q.n - 1;
@@ -1165,7 +1178,7 @@ int stt_sampler_qnet(const SttodeSamplerPlan* p, const float* pf, int n, float* 
     QNet32Args q;
     q.pool = (const f32x4*)p->pool; q.prog = (const int2*)p->prog; q.prog_len = p->prog_len; q.bias = p->biases;
     q.pf = pf; q.z = z; q.eps = p->eps; q.n = n; q.K = p->K; q.h1t = p->h1 / 32; q.h2t = p->h2 / 32; q.eps_mode = p->eps_mode;
-    const int lds = C32_RING * 16 + p->prog_len * 8 + 16;
+    const int lds = C32_RING * 16;
     hipLaunchKernelGGL(sampler_qnet32_kernel, dim3((n + 127) / 128), dim3(256), lds, (hipStream_t)stream, q);
     STT_HIP(hipGetLastError());
     return 0;

@@ -40,7 +40,7 @@ template <class ST> struct TileFeed {
     Frag cur, nxt;
     __device__ __forceinline__ explicit TileFeed(ST& s) : st(s), t(0), cnt(0), pre(false) {}
     __device__ __forceinline__ void open() {        // the current chunk has landed and passed its barrier; begin() was not yet called for it
-        cnt = __builtin_amdgcn_readfirstlane(st.lprog[st.p].y);
+        cnt = st.cnt;
         t = 0;
         ldfrag(cur, st.cur());                      // first tile of the chunk: its read latency overlaps the DMA issue below
         st.begin();
@@ -167,12 +167,11 @@ __device__ __forceinline__ void frontend32(KRole32Args& R, int wg) {
     }
 }
 
-// The whole per-agent stage of 128 agents: workgroup `wg` of R.nwg, 4 waves x 32 columns.  smem: ring (24 KiB) | consts | program.
+// The whole per-agent stage of 128 agents: workgroup `wg` of R.nwg, 4 waves x 32 columns.  smem: ring (24 KiB) | consts.
 template <bool ZS>
 __device__ __forceinline__ void role32_body(KRole32Args& R, int wg, char* smem) {
     f32x4* ring = reinterpret_cast<f32x4*>(smem);
     float* cst = reinterpret_cast<float*>(ring + C32_RING);
-    int2* lprog = reinterpret_cast<int2*>(cst + R32C::total);
     const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (R.prio > 0) __builtin_amdgcn_s_setprio(3);     // (uniform) the role waves win their SIMD's issue arbitration: they are the long pole of a small launch
@@ -189,10 +188,9 @@ __device__ __forceinline__ void role32_body(KRole32Args& R, int wg, char* smem) 
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     }
     for (int i = threadIdx.x; i < R32C::total; i += blockDim.x) cst[i] = R.consts[i];
-    for (int i = threadIdx.x; i < R.prog_len; i += blockDim.x) lprog[i] = R.prog[i];
     __syncthreads();
     ChainStream st;
-    st.init(R.pool, lprog, R.prog_len, ring);
+    st.init(R.pool, R.prog, R.prog_len, ring);
     const int col = wg * 128 + wave * 32 + c;
     const bool live = col < R.n;
     const int colc = live ? col : R.n - 1;
