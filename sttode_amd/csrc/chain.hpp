@@ -108,10 +108,19 @@ __device__ __forceinline__ void glds16_asm(const void* gsrc, unsigned lds_dst) {
 // No 64-bit per-lane address arithmetic (v_lshl_add_u64) per piece: the per-lane offset is computed once, the uniform part of the
 // address advances in SGPRs, and a constant step folds into OFS, the 13-bit signed immediate.  The hardware adds OFS to the LDS
 // address as well, so M0 is set to lds_dst - OFS.
+// M0 is written and never saved or restored: these asm statements are its only users in the kernels that issue them (hipcc needs M0 on
+// gfx950 for s_movrel, LDS-direct and GWS only, none of which these kernels contain; tests/test_chunk_step_isa.py holds "no other M0 user"
+// for the headline kernel).  M0 is not named as a clobber: clang rejects the reserved register there with a warning and tracks nothing.
 template <int OFS>
 __device__ __forceinline__ void glds16_sv(const void* sbase, unsigned voff, unsigned lds_dst) {
     static_assert(OFS >= -4096 && OFS <= 4095, "global_load_lds_dwordx4: the immediate offset is 13-bit signed");
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:%4\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst - (unsigned)OFS), "i"(OFS) : "memory");
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 offset:%3"
+                 : : "v"(voff), "s"(sbase), "s"(lds_dst - (unsigned)OFS), "i"(OFS) : "memory");
+}
+// The same with M0 as the previous glds16_sv / glds16_m0 of this wave left it: the LDS destination is M0 + OFS (+ lane * 16), so two pieces
+// whose sources and destinations are both 4 096 B apart share one M0 write (offsets -4096 and 0 from the middle).
+template <int OFS>
+__device__ __forceinline__ void glds16_m0(const void* sbase, unsigned voff) {
+    static_assert(OFS >= -4096 && OFS <= 4095, "global_load_lds_dwordx4: the immediate offset is 13-bit signed");
+    asm volatile("global_load_lds_dwordx4 %0, %1 offset:%2" : : "v"(voff), "s"(sbase), "i"(OFS) : "memory");
 }

@@ -19,6 +19,9 @@
 //     (packing.chain_stream), so the kernel only consumes tiles in order.  The GRU's recurrent weights are streamed per
 //     step like everything else (66 FLOP per streamed byte, the same intensity as the MLP layers), which frees the
 //     144 KiB of LDS round 1 pinned for them: LDS per workgroup is 24 KiB ring + 32 KiB gather / z slots + 8 KiB biases.
+//     Between a chunk's barrier and its first MFMA a wave issues the ring's first fragment reads and the DMA instructions, nothing else:
+//     program entries are fetched in the middle of a step, addresses are made in front of the barrier, the tile count of the next chunk
+//     is a constant of the call site wherever it is known, M0 is written once per pair of pieces and never restored (ChainStreamT).
 //   * workgroup = 4 waves x 32 columns = 128 trajectories, 2 workgroups per CU (<= 256 VGPRs per wave); groups are
 //     handed out by an atomic work counter (one tail for the whole chain instead of three, and a later launch on
 //     another stream fills it: the kernel holds no chip-wide resource).
@@ -53,6 +56,7 @@ __shared__ long long g_tr_ph[4];   // role phase stamps (thread 0)
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // diagnostic builds (profiles/exp_chain_variants.sh; never shipped): -DC32_DIAG_NODMA / _NOGATHER / _NOBARRIER / _NOGATES
+// (timing ablations), -DC32_DIAG_STAMPS (stamps, also of the chunk steps), -DC32_DIAG_CHECK (a static tile count that is not the program's traps)
 #ifdef C32_DIAG_NOGATES
 #define C32_SIG(x) ((x) * 1e-3f)
 #define C32_TANH(x) ((x) * 1e-3f)
@@ -143,58 +147,139 @@ typedef const __attribute__((address_space(4))) int KProg;   // (first, count) p
 // BUF: f32x4 per ring buffer (= the largest chunk).  GEN = false: program entries are (first PK32 tile, tiles <= 3) of 4-KiB tiles;
 // GEN = true (exploratory bf16-split mode: tiles of 6 and 4 KiB in one pool): (offset in f32x4 units, number of 1-KiB pieces).
 // Every address of the DMA is uniform but the lane's 16 B: the source advances in SGPRs (glds16_sv), the lane offset is one VGPR.
-template <int BUF, bool GEN>
+//
+// A chunk step is  begin() .. MFMAs .. end().  What a wave issues between the barrier in end() and the first MFMA behind it is serial, un-hidden
+// issue time once per 48 MFMAs, so the step keeps that stretch to the ring's first fragment reads and the DMA instructions themselves:
+//   * fetch(): the program entry of the chunk after next is loaded in the MIDDLE of a step (tile_mma2f: halfway through the step's first
+//     tile), never behind the barrier: scalar loads and LDS reads share lgkmcnt and scalar loads return out of order, so a scalar load in
+//     flight turns every fragment wait into lgkmcnt(0) and exposes its full latency.  A step without MFMAs in front of its end() has its
+//     entry fetched one step early (fetch_more / take_prefetched); a step that fetched nothing loads in end(), in front of the barrier.
+//   * end(): everything the next begin() needs -- pool addresses (64-bit), the
+//     M0 values of the ring destination, the piece count -- is computed IN FRONT of the barrier, where it is free for every wave but the
+//     last to arrive, and carried in SGPRs.
+//   * begin(N): the next chunk's tile count as a constant argument wherever the call site knows it: N DMA instructions in a straight
+//     line, no compare / branch per piece.  begin() is the run-time form (TileFeed, phase ends, GEN).  A wave's pieces i = 0, 1, 2 are
+//     4 096 B apart in the pool and in the ring: pieces 2k and 2k + 1 share one scalar base and one M0 write (glds16_m0).
+//
+// DYN: begin(N) ignores N and takes the program's count (traj_chain_kernel sets it for the two instantiations that the straight-line
+// issue pushes into scratch).
+template <int BUF, bool GEN, bool DYN = false>
 struct ChainStreamT {
     static constexpr int kBuf = BUF;
+    static constexpr int kPieces = (BUF / 64 + 3) / 4, kPairs = (kPieces + 1) / 2;   // 1-KiB pieces per wave of the largest chunk, and pairs of them
     const char* pool; KProg* prog; f32x4* ring;
     unsigned ring_addr, loff;  // loff: this lane's byte offset in a 1-KiB piece
-    int len, p, par, lane, wave;
-    int2 nxt_v;  // program entry of the chunk after the one in flight: loaded one step early, consumed at the next begin()
-    int cnt;     // tiles of the chunk whose begin() comes next (TileFeed)
-    __device__ __forceinline__ int2 entry(int q) const { return make_int2(prog[2 * q], prog[2 * q + 1]); }
-    __device__ __forceinline__ void dma(int2 ev, int buf) {
-        // a chunk = `pieces` pieces of 1 KiB; wave w moves pieces w, w+4, w+8, ...
-        const char* src = pool + (size_t)ev.x * (GEN ? 16 : C32_TILE * 16) + wave * 1024;
-        const int pieces = GEN ? ev.y : 4 * ev.y;
-        const unsigned dst = __builtin_amdgcn_readfirstlane(ring_addr + (unsigned)buf * (BUF * 16) + (unsigned)wave * 1024);
+    unsigned qoff, qend;       // byte offset in the program of the entry the next fetch loads; the program's size in bytes
+    int par, lane, wave;
+    int2 ld_v, ld_w;           // loaded entries: of the chunk after next (consumed by end()), and one more (fetch_more)
+    bool fetched;              // this step has its entry (compile-time knowledge wherever the step is straight-line code)
+    int cnt;                   // tiles of the chunk whose begin() comes next (TileFeed)
+    // the DMA of the next begin(), made by end(): scalar base and M0 of piece pair k (both at the pair's second piece), pieces of this wave
+    const char* nsrc[kPairs]; unsigned nm0[kPairs]; int ncnt, npc;
+#ifdef C32_DIAG_STAMPS
+    long long t_bar, gap_cyc, gap_n, gap_cal;   // barrier -> fragments landed and DMA issued, summed over the chunk steps (s_memtime)
+#endif
+    __device__ __forceinline__ int2 entry_at(unsigned off) const {
+        const KProg* e = reinterpret_cast<const KProg*>(reinterpret_cast<const __attribute__((address_space(4))) char*>(prog) + off);
+        return make_int2(e[0], e[1]);
+    }
+    __device__ __forceinline__ unsigned next_off(unsigned off) const { return off + 8 >= qend ? 0u : off + 8; }
+    // addresses of chunk `ev` into ring buffer `buf`; the values are pinned where they are computed (hipcc would sink the arithmetic to its use)
+    __device__ __forceinline__ void stage(int2 ev, int buf) {
+        // (readfirstlane: a no-op where hipcc sees that the entry is uniform -- everywhere in the trajectory chain)
+        ncnt = __builtin_amdgcn_readfirstlane(ev.y);
+        npc = GEN ? (ncnt - wave + 3) >> 2 : ncnt;   // wave w moves pieces w, w + 4, w + 8, ... of 1 KiB; a PK32 tile is one piece per wave
+        const size_t src = (size_t)(unsigned)__builtin_amdgcn_readfirstlane(ev.x) * (GEN ? 16u : C32_TILE * 16u) + (unsigned)wave * 1024u;   // 64-bit, as it always was
+        const unsigned dst = __builtin_amdgcn_readfirstlane(ring_addr + (unsigned)buf * (BUF * 16) + (unsigned)wave * 1024u);
+#pragma unroll
+        for (int k = 0; k < kPairs; ++k) {
+            nsrc[k] = pool + (src + 4096u * (2 * k + 1));
+            nm0[k] = dst + 4096u * (2 * k + 1);
+            asm volatile("" : "+s"(nsrc[k]), "+s"(nm0[k]));
+        }
+        asm volatile("" : "+s"(npc));
+    }
+    __device__ __forceinline__ void issue(int N) {   // N > 0 (a constant once inlined): that many pieces, unconditionally; N == 0: npc of them
 #ifndef C32_DIAG_NODMA
 #pragma unroll
-        for (int i = 0; i < (BUF / 64 + 3) / 4; ++i)
-            if (4 * i + wave < pieces) glds16_sv<0>(src + i * 4096, loff, dst + i * 4096);
+        for (int k = 0; k < kPairs; ++k) {
+            if (N > 0 ? 2 * k < N : 2 * k < npc) {
+                glds16_sv<-4096>(nsrc[k], loff, nm0[k] - 4096u);   // (M0 = nm0[k])
+                if (2 * k + 1 < kPieces && (N > 0 ? 2 * k + 1 < N : 2 * k + 1 < npc)) glds16_m0<0>(nsrc[k], loff);
+            }
+        }
 #endif
     }
     __device__ __forceinline__ void init(const f32x4* pool_, const int2* prog_, int len_, f32x4* ring_) {
-        pool = reinterpret_cast<const char*>(pool_); prog = (KProg*)prog_; len = len_; ring = ring_;
-        ring_addr = lds_addr(ring_);
+        pool = reinterpret_cast<const char*>(pool_); prog = (KProg*)prog_; ring = ring_;
+        ring_addr = __builtin_amdgcn_readfirstlane(lds_addr(ring_));
         lane = threadIdx.x & 63;
         loff = (unsigned)lane * 16;
         wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        p = 0; par = 0;
-        const int2 e0 = entry(0);
+        par = 0;
+        qend = (unsigned)len_ * 8u;
+        const int2 e0 = entry_at(0);
+        stage(e0, 0);
+        issue(0);
         cnt = e0.y;
-        dma(e0, 0);
-        nxt_v = entry(1 % len);
+        qoff = next_off(0);
+        stage(entry_at(qoff), 1);
+        qoff = next_off(qoff);
+        fetched = false;
+#ifdef C32_DIAG_STAMPS
+        gap_cyc = 0; gap_n = 0;
+        const long long c0 = __builtin_amdgcn_s_memtime();
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        gap_cal = __builtin_amdgcn_s_memtime() - c0;   // an empty stamp pair
+        t_bar = 0;
+#endif
     }
-    // start of a chunk step: prefetch the next chunk into the other buffer (its readers passed the previous barrier)
-    __device__ __forceinline__ void begin() {
+    // the entry of the chunk after next: call once per chunk step between begin() and end(), with MFMAs on both sides
+    __device__ __forceinline__ void fetch() { ld_v = entry_at(qoff); qoff = next_off(qoff); fetched = true; }
+    // ... and the entry behind it, for a following step that has no MFMAs to fetch between; that step calls take_prefetched() instead
+    __device__ __forceinline__ void fetch_more() { ld_w = entry_at(qoff); qoff = next_off(qoff); }
+    __device__ __forceinline__ void take_prefetched() { ld_v = ld_w; fetched = true; }
+    __device__ __forceinline__ void stamp_gap() {
+#ifdef C32_DIAG_STAMPS
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        const long long c1 = __builtin_amdgcn_s_memtime();
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        if (t_bar) { gap_cyc += c1 - t_bar; ++gap_n; }
+#endif
+    }
+    // start of a chunk step: prefetch the next chunk into the other buffer (its readers passed the previous barrier).  N: its tiles, if the
+    // call site knows them (a constant after inlining; GEN = false); 0: the program's count
+    __device__ __forceinline__ void begin(int N = 0) {
         __builtin_amdgcn_sched_barrier(0);
-        cnt = nxt_v.y;
-        dma(nxt_v, par ^ 1);
-        int q = p + 2;
-        q = q >= len ? q - len : q;
-        nxt_v = entry(q);
+#ifdef C32_DIAG_CHECK
+        if (!GEN && N > 0 && ncnt != N) __builtin_trap();   // the call site's static tile count is not the program's
+#endif
+        cnt = ncnt;
+        issue(GEN || DYN ? 0 : N);
+        stamp_gap();
         __builtin_amdgcn_sched_barrier(0);
     }
     __device__ __forceinline__ const f32x4* cur() const { return ring + par * BUF + lane; }
-    // end of a chunk step: this wave's DMA pieces have landed (vmcnt), then everybody's (barrier)
-    __device__ __forceinline__ void end() {
+    // end of a chunk step: this wave's DMA pieces have landed (vmcnt), then everybody's (barrier).  has_entry: the caller knows that this
+    // step fetched (TileFeed, whose control flow hipcc cannot follow)
+    __device__ __forceinline__ void end(bool has_entry = false) {
+        __builtin_amdgcn_sched_barrier(0);
+#ifdef C32_DIAG_CHECK
+        if (has_entry && !fetched) __builtin_trap();   // the caller's claim does not hold: this step fetched nothing
+#endif
+        if (!has_entry && !fetched) fetch();
+        stage(ld_v, par);   // the chunk after next goes where this step's chunk is: its readers are done at the barrier below
         __builtin_amdgcn_sched_barrier(0);
 #ifndef C32_DIAG_NOBARRIER
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
 #endif
-        p = p + 1 >= len ? 0 : p + 1;
+#ifdef C32_DIAG_STAMPS
+        t_bar = __builtin_amdgcn_s_memtime();
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (no scalar load in flight across the fragment reads; its latency is gap_cal)
+#endif
         par ^= 1;
+        fetched = false;
         __builtin_amdgcn_sched_barrier(0);
     }
 };
@@ -243,6 +328,23 @@ __device__ __forceinline__ void tile_mma2(f32x16& acc, const Frag& cur, const f3
     }
 }
 
+// tile_mma2 for the FIRST tile of a chunk step: halfway through it the stream fetches its program entries (nf: 1, or 2 with fetch_more).
+template <class ST>
+__device__ __forceinline__ void tile_mma2f(ST& st, f32x16& acc, const Frag& cur, const f32x16& B, Frag& nxt, const f32x4* __restrict__ tn, int nf = 1) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        if (g == 2) {
+            __builtin_amdgcn_sched_barrier(0);   // the scalar load stays here: hoisted to the top of the step it would sit behind the barrier
+            if (nf >= 1) st.fetch();
+            if (nf >= 2) st.fetch_more();
+            if (tn) ldfrag(nxt, tn);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(cur.a[g][r], B[4 * g + r], acc, 0, 0, 0);
+    }
+}
+
 // Layers 1+2 of one MLP for this wave's 32 columns: acc2 (256 rows = 8 tiles) += W2 relu(A0[agent] + W1v [z | Bh]).
 // Per 32-row hidden tile: 1 + KH layer-1 tiles then 8 layer-2 tiles, a chunk boundary every 3 tiles ((1 + KH + 8) % 3 == 0).
 // z (the first layer-1 k-tile's B operand) is read from the wave's LDS z slot every hidden tile (it would cost 16 VGPRs for the
@@ -281,7 +383,7 @@ __device__ __forceinline__ void mlp_l12(ST& st, const f32x4* slot, const f32x4* 
             if (i % 3 == 0) {
                 if (i > 0) st.end();
                 ldfrag(fr[i & 1], st.cur());       // first tile of the chunk: its read latency overlaps the DMA issue below
-                st.begin();
+                st.begin(3);                       // the next chunk is one of this phase's or the first of layer 3: three tiles
                 if (i == 0) {
 #ifndef C32_DIAG_NOGATHER
                     gather_rows(nb, no, slot_addr);
@@ -291,12 +393,14 @@ __device__ __forceinline__ void mlp_l12(ST& st, const f32x4* slot, const f32x4* 
             }
             const f32x4* tn = (i % 3 < 2) ? st.cur() + (i % 3 + 1) * C32_TILE : nullptr;
             if (i == 0) {
-                tile_mma2(h1, fr[i & 1], zb, fr[(i + 1) & 1], tn);
+                tile_mma2f(st, h1, fr[i & 1], zb, fr[(i + 1) & 1], tn);
             } else if (i < KT1) {
-                tile_mma2(h1, fr[i & 1], Bh[i - 1], fr[(i + 1) & 1], tn);
+                if (i % 3 == 0) tile_mma2f(st, h1, fr[i & 1], Bh[i - 1], fr[(i + 1) & 1], tn);
+                else tile_mma2(h1, fr[i & 1], Bh[i - 1], fr[(i + 1) & 1], tn);
             } else {
                 if (i == KT1) h1 = relu16(h1);
-                tile_mma2(acc2[i - KT1], fr[i & 1], h1, fr[(i + 1) & 1], tn);
+                if (i % 3 == 0) tile_mma2f(st, acc2[i - KT1], fr[i & 1], h1, fr[(i + 1) & 1], tn);
+                else tile_mma2(acc2[i - KT1], fr[i & 1], h1, fr[(i + 1) & 1], tn);
             }
         }
         st.end();
@@ -304,7 +408,8 @@ __device__ __forceinline__ void mlp_l12(ST& st, const f32x4* slot, const f32x4* 
 }
 
 // Layer 3: out[o] = b3 + W3[o] relu(acc2 + b2), NO output tiles of 32 rows; 8 k-tiles per output tile, chunks of 3 tiles.
-template <int NO, class ST>
+// NEXT: tiles of the chunk that follows the layer's last one (the next phase's first), if the caller knows them; 0: the program's count.
+template <int NO, int NEXT = 0, class ST>
 __device__ __forceinline__ void mlp_l3(ST& st, f32x16 (&acc2)[8], const float* __restrict__ b2, const float* __restrict__ b3,
                                        f32x16 (&out)[NO], int h) {
 #pragma unroll
@@ -323,10 +428,12 @@ __device__ __forceinline__ void mlp_l3(ST& st, f32x16 (&acc2)[8], const float* _
         if (i % 3 == 0) {
             if (i > 0) st.end();
             ldfrag(fr[i & 1], st.cur());
-            st.begin();
+            const int left = 8 * NO - (i + 3);   // tiles of this layer behind the chunk that starts here
+            st.begin(left >= 3 ? 3 : left > 0 ? left : NEXT);
         }
         const f32x4* tn = (i % 3 < 2 && i + 1 < 8 * NO) ? st.cur() + (i % 3 + 1) * C32_TILE : nullptr;
-        tile_mma2(out[i / 8], fr[i & 1], acc2[i % 8], fr[(i + 1) & 1], tn);
+        if (i % 3 == 0) tile_mma2f(st, out[i / 8], fr[i & 1], acc2[i % 8], fr[(i + 1) & 1], tn);
+        else tile_mma2(out[i / 8], fr[i & 1], acc2[i % 8], fr[(i + 1) & 1], tn);
     }
     st.end();
 }
@@ -596,8 +703,10 @@ __device__ __forceinline__ void gru32_steps_b3(ST& st, const float* gb, const fl
 
 // conv tile of step t (a chunk of its own) + relu.  ZS: only the fragment groups g (k = 8g .. 8g+7) that meet the tile's non-zero
 // columns 2t-2 .. 2t+3 (frames t-1 .. t+1, packing.toeplitz_conv) are read and multiplied: the others add exact zeros.
+// The next chunk is a gate chunk of three tiles.  pre: the step in front fetched this step's program entry too (the conv chunk has at
+// most 16 MFMAs to hide a scalar load behind); otherwise it is fetched behind the MFMAs.
 template <bool ZS, class ST>
-__device__ __forceinline__ f32x16 gru32_conv(ST& st, const float* cb, const f32x16& d, int t, int Tp, int h) {
+__device__ __forceinline__ f32x16 gru32_conv(ST& st, const float* cb, const f32x16& d, int t, int Tp, int h, bool pre) {
     f32x16 e = ldrows(cb, h);
     Frag fa, fb;
     if (ZS) {
@@ -607,16 +716,20 @@ __device__ __forceinline__ f32x16 gru32_conv(ST& st, const float* cb, const f32x
 #pragma unroll
         for (int g = 0; g < 4; ++g)
             if (g >= g0 && g <= g1) fa.a[g] = tc[g * 64];
-        st.begin();
+        st.begin(3);
 #pragma unroll
         for (int g = 0; g < 4; ++g)
             if (g >= g0 && g <= g1)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) e = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.a[g][r], d[4 * g + r], e, 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (pre) st.take_prefetched();
+        else st.fetch();
     } else {
         ldfrag(fa, st.cur());
-        st.begin();
-        tile_mma2(e, fa, d, fb, nullptr);
+        st.begin(3);
+        tile_mma2f(st, e, fa, d, fb, nullptr, pre ? 0 : 1);
+        if (pre) st.take_prefetched();
     }
     e = relu16(e);
     st.end();
@@ -631,24 +744,29 @@ __device__ __forceinline__ f32x16 gru32_conv(ST& st, const float* cb, const f32x
 // tiles are still consumed chunk by chunk, so the program is the same -- and the conv tiles issue only their non-zero fragment groups.
 // A skipped product adds an exact zero: results are unchanged up to the sign of an exactly-zero value.  ZS = false: every tile in full
 // (STTODE_GRU_ZERO_SKIP=0, A/B).
+// Chunk steps (ChainStreamT): every chunk is followed by one of three tiles (begin(3)) but a step's last, which is followed by the next
+// step's conv tile or by whatever comes after the GRU (begin(): the program's count).  Each step's first tile fetches the program entry
+// (tile_mma2f); with ZS a step's last chunk fetches the following conv chunk's as well, and in step 0 the chunk in front of the one
+// without MFMAs fetches for both.
 template <bool ZS, class ST>
 __device__ __forceinline__ void gru32_steps(ST& st, const float* gb, const float* cb, const f32x16& d, f32x16 (&hs)[3], int Tp, int h) {
     if (ZS) {   // step 0, h = 0: per j only the three e tiles; the third of the four chunks holds recurrent tiles alone
-        const f32x16 e = gru32_conv<ZS>(st, cb, d, 0, Tp, h);
+        const f32x16 e = gru32_conv<ZS>(st, cb, d, 0, Tp, h, false);
         Frag fa, fb;
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             STT_FENCE();
             f32x16 ar = ldrows(gb + 0 * 96 + 32 * j, h);
-            ldfrag(fa, st.cur()); st.begin();                          // [r:e h0 h1]
-            tile_mma2(ar, fa, e, fb, nullptr);
-            st.end(); ldfrag(fa, st.cur() + 1 * C32_TILE); st.begin();  // [r:h2 z:e h0]
+            ldfrag(fa, st.cur()); st.begin(3);                          // [r:e h0 h1]
+            tile_mma2f(st, ar, fa, e, fb, nullptr);
+            st.end(); ldfrag(fa, st.cur() + 1 * C32_TILE); st.begin(3);  // [r:h2 z:e h0]
 #pragma unroll
             for (int r = 0; r < 16; ++r) ar[r] = C32_SIG(ar[r]);
             STT_FENCE();
             f32x16 az = ldrows(gb + 1 * 96 + 32 * j, h);
-            tile_mma2(az, fa, e, fb, nullptr);
-            st.end(); st.begin();                                       // [z:h1 h2 n_h:h0]
+            tile_mma2f(st, az, fa, e, fb, nullptr, 2);                   // (the entry of the next step too: it has no MFMAs)
+            st.end(); st.begin(3);                                       // [z:h1 h2 n_h:h0]
+            st.take_prefetched();
 #pragma unroll
             for (int r = 0; r < 16; ++r) az[r] = C32_SIG(az[r]);
             STT_FENCE();
@@ -658,9 +776,10 @@ __device__ __forceinline__ void gru32_steps(ST& st, const float* gb, const float
 #pragma unroll
                 for (int r = 0; r < 16; ++r) an[r] = fmaf(ar[r], an[r], bi[r]);     // b_in + r * (W_hn h + b_hn)
             }
-            st.end(); ldfrag(fa, st.cur() + 2 * C32_TILE); st.begin();  // [n_h:h1 h2 n_i:e]
+            st.end(); ldfrag(fa, st.cur() + 2 * C32_TILE);               // [n_h:h1 h2 n_i:e]
+            if (j < 2) st.begin(3); else st.begin();
             STT_FENCE();
-            tile_mma2(an, fa, e, fb, nullptr);                           // + W_in e
+            tile_mma2f(st, an, fa, e, fb, nullptr, (j == 2 && 1 < Tp) ? 2 : 1);   // + W_in e
             st.end();
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -671,7 +790,7 @@ __device__ __forceinline__ void gru32_steps(ST& st, const float* gb, const float
     }
 #pragma unroll 1
     for (int t = ZS ? 1 : 0; t < Tp; ++t) {
-        const f32x16 e = gru32_conv<ZS>(st, cb, d, t, Tp, h);
+        const f32x16 e = gru32_conv<ZS>(st, cb, d, t, Tp, h, ZS);
         Frag fa, fb;
         f32x16 hn[3];
 #pragma unroll
@@ -680,28 +799,29 @@ __device__ __forceinline__ void gru32_steps(ST& st, const float* gb, const float
             // One gate accumulator is live at a time (finished gates shrink to their 16 outputs).
             STT_FENCE();
             f32x16 ar = ldrows(gb + 0 * 96 + 32 * j, h);
-            ldfrag(fa, st.cur()); st.begin();
-            tile_mma2(ar, fa, e, fb, st.cur() + 1 * C32_TILE);
+            ldfrag(fa, st.cur()); st.begin(3);
+            tile_mma2f(st, ar, fa, e, fb, st.cur() + 1 * C32_TILE);
             tile_mma2(ar, fb, hs[0], fa, st.cur() + 2 * C32_TILE);
             tile_mma2(ar, fa, hs[1], fb, nullptr);
-            st.end(); ldfrag(fa, st.cur()); st.begin();
-            tile_mma2(ar, fa, hs[2], fb, st.cur() + 1 * C32_TILE);
+            st.end(); ldfrag(fa, st.cur()); st.begin(3);
+            tile_mma2f(st, ar, fa, hs[2], fb, st.cur() + 1 * C32_TILE);
 #pragma unroll
             for (int r = 0; r < 16; ++r) ar[r] = C32_SIG(ar[r]);          // r gate
             STT_FENCE();
             f32x16 az = ldrows(gb + 1 * 96 + 32 * j, h);
             tile_mma2(az, fb, e, fa, st.cur() + 2 * C32_TILE);
             tile_mma2(az, fa, hs[0], fb, nullptr);
-            st.end(); ldfrag(fa, st.cur()); st.begin();
-            tile_mma2(az, fa, hs[1], fb, st.cur() + 1 * C32_TILE);
+            st.end(); ldfrag(fa, st.cur()); st.begin(3);
+            tile_mma2f(st, az, fa, hs[1], fb, st.cur() + 1 * C32_TILE);
             tile_mma2(az, fb, hs[2], fa, st.cur() + 2 * C32_TILE);
 #pragma unroll
             for (int r = 0; r < 16; ++r) az[r] = C32_SIG(az[r]);          // z gate
             STT_FENCE();
             f32x16 an = ldrows(gb + 3 * 96 + 32 * j, h);
             tile_mma2(an, fa, hs[0], fb, nullptr);
-            st.end(); ldfrag(fa, st.cur()); st.begin();
-            tile_mma2(an, fa, hs[1], fb, st.cur() + 1 * C32_TILE);
+            st.end(); ldfrag(fa, st.cur());
+            if (j < 2) st.begin(3); else st.begin();
+            tile_mma2f(st, an, fa, hs[1], fb, st.cur() + 1 * C32_TILE, (ZS && j == 2 && t + 1 < Tp) ? 2 : 1);
             tile_mma2(an, fb, hs[2], fa, st.cur() + 2 * C32_TILE);
             {
                 const f32x16 bi = ldrows(gb + 2 * 96 + 32 * j, h);
@@ -770,7 +890,10 @@ __host__ __device__ __forceinline__ int xcd_group(int b, int G) {
 // ZS: the GRUs run as gru32_steps<ZS> (a template argument: a run-time choice inside the kernel costs the group path spills)
 template <int NY, int FUSE, bool B3M, bool ZS>
 __global__ __launch_bounds__(256, 2) void traj_chain_kernel(ChainArgs A) {
-    typedef ChainStreamT<B3M ? C32_BUF_B3 : C32_CMAX * C32_TILE, B3M> Stream;   // B3M: exploratory bf16-split mode (block-0 MLPs)
+    // <1, 2, false, false> and <2, 1, false, true> keep the run-time piece count: with the straight-line issue hipcc spills two VGPRs in them
+    // (12 B/lane of scratch that the parent form did not have); every other instantiation has the same or less scratch than before
+    constexpr bool kDynCount = !B3M && ((NY == 1 && FUSE == 2 && !ZS) || (NY == 2 && FUSE == 1 && ZS));
+    typedef ChainStreamT<B3M ? C32_BUF_B3 : C32_CMAX * C32_TILE, B3M, kDynCount> Stream;   // B3M: exploratory bf16-split mode (block-0 MLPs)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     f32x4* ring = reinterpret_cast<f32x4*>(smem);
     f32x4* slots = ring + 2 * Stream::kBuf;
@@ -871,7 +994,7 @@ __global__ __launch_bounds__(256, 2) void traj_chain_kernel(ChainArgs A) {
                 mlp_l3_b3<1>(st, acc2, cst + CO::b2x, cst + CO::b3x, xo, h);
             } else {
                 mlp_l12<0>(st, slot, zslot, nullptr, A.A0x, ao, A.A0y, ao, acc2, lane);
-                mlp_l3<1>(st, acc2, cst + CO::b2x, cst + CO::b3x, xo, h);
+                mlp_l3<1, 3>(st, acc2, cst + CO::b2x, cst + CO::b3x, xo, h);   // then decoder_y's layers 1 + 2: chunks of three
             }
             agent = opaque(agent);
             const float* xp = A.xpad + (size_t)agent * A.ldx;
@@ -894,7 +1017,7 @@ __global__ __launch_bounds__(256, 2) void traj_chain_kernel(ChainArgs A) {
                 mlp_l3_b3<NY>(st, acc2, cst + CO::b2y, cst + CO::b3y, yo, h);
             } else {
                 mlp_l12<0>(st, slot, zslot, nullptr, A.A0y, ao, A.A1y, ao, acc2, lane);
-                mlp_l3<NY>(st, acc2, cst + CO::b2y, cst + CO::b3y, yo, h);
+                mlp_l3<NY, 1>(st, acc2, cst + CO::b2y, cst + CO::b3y, yo, h);   // then the GRU's first conv tile
             }
             if (live) {
                 float* prow = A.park + (size_t)opaque(col) * A.Tf2;
@@ -937,7 +1060,7 @@ __global__ __launch_bounds__(256, 2) void traj_chain_kernel(ChainArgs A) {
             gather_rows(A.z, row_off(opaque(cnx), 32, h), zslot_addr);
             f32x16 yo[NY];
             if (B3M) mlp_l3_b3<NY>(st, acc2, cst + CO::b2m, cst + CO::b3m, yo, h);
-            else mlp_l3<NY>(st, acc2, cst + CO::b2m, cst + CO::b3m, yo, h);
+            else mlp_l3<NY, 3>(st, acc2, cst + CO::b2m, cst + CO::b3m, yo, h);   // then the program again from its start: the next group's decoder_x
             {
                 agent = opaque(agent);
                 const float cx = A.cur[2 * agent], cy = A.cur[2 * agent + 1];
@@ -1005,6 +1128,13 @@ __global__ __launch_bounds__(256, 2) void traj_chain_kernel(ChainArgs A) {
             }
         }
         C32_STAMP(4);
+#ifdef C32_DIAG_STAMPS
+        if (threadIdx.x == 0 && A.dbg && gi < 4) {   // wave 0's chunk steps of this group: cycles barrier -> first MFMA ready, steps, an empty stamp pair
+            long long* o = A.dbg + ((size_t)blockIdx.x * 4 + gi) * 16 + 10;
+            o[0] = st.gap_cyc; o[1] = st.gap_n; o[2] = st.gap_cal;
+        }
+        st.gap_cyc = 0; st.gap_n = 0;
+#endif
         ++gi;
         g = gnext;
         if (g >= ngroups) break;  // uniform: every wave read the same sq word

@@ -47,14 +47,14 @@ template <class ST> struct TileFeed {
         pre = false;
     }
     __device__ __forceinline__ void mma(f32x16& acc, const f32x16& B) {
-        if (t == cnt) { st.end(); open(); }
+        if (t == cnt) { st.end(true); open(); }
         else if (pre) cur = nxt;                    // (16 register moves per 16 MFMAs; the arrays must not be indexed by a run-time value)
         const f32x4* tn = t + 1 < cnt ? st.cur() + (t + 1) * C32_TILE : nullptr;
-        tile_mma2(acc, cur, B, nxt, tn);
+        tile_mma2f(st, acc, cur, B, nxt, tn, t == 0 ? 1 : 0);   // the first tile of a chunk step fetches the step's program entry
         pre = tn != nullptr;
         ++t;
     }
-    __device__ __forceinline__ void close() { st.end(); }   // drains the last prefetch (nobody reads it) before the workgroup leaves
+    __device__ __forceinline__ void close() { st.end(true); }   // drains the last prefetch (nobody reads it) before the workgroup leaves
 };
 
 __device__ __forceinline__ float halfsum32(float v) { return v + __shfl_xor(v, 32, 64); }   // lanes c and c + 32 hold the two halves of a column
@@ -205,12 +205,14 @@ __device__ __forceinline__ void role32_body(KRole32Args& R, int wg, char* smem) 
             for (int b = 0; b < 4; ++b) d[4 * a + b] = v[b];
         }
     }
+    int Tp = R.Tp;
+    asm volatile("" : "+s"(Tp));                                // read here: hipcc otherwise re-reads the argument behind the barrier, in front of the first conv tile
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();                                            // chunk 0 (the first conv tile) has landed
     f32x16 hs[3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) hs[j] = splat16(0.f);
-    gru32_steps<ZS>(st, cst + R32C::gb, cst + R32C::cb, d, hs, R.Tp, h);   // block-0 conv + GRU (model/STTODE.py:62-69, x_hat = 0)
+    gru32_steps<ZS>(st, cst + R32C::gb, cst + R32C::cb, d, hs, Tp, h);   // block-0 conv + GRU (model/STTODE.py:62-69, x_hat = 0)
     if (live) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) strows(R.state0 + (size_t)col * 96 + 32 * j, hs[j], h);
