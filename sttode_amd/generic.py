@@ -47,10 +47,7 @@ def _engine(net):
     if eng is None or eng.dev != net.device:
         eng = net._engine = Engine(net)
         net._graphs, net._graph_seen = {}, set()
-    eng.P = {k: v for k, v in net.named_parameters()}
-    eng._hold = []
-    eng.multi = False
-    eng._enter(-1)
+    eng.begin()
     return eng
 
 

@@ -18,9 +18,11 @@ import torch
 from . import capi, odestages
 from .capi import SttodeError
 
-# backward over the decoder columns that carry a gradient (Engine.decoder_live); STTODE_TRAIN_LIVE=0: over all 21 per agent, as rounds 1-4
-_LIVE_COLUMNS = os.environ.get('STTODE_TRAIN_LIVE', '1') != '0'
+# backward over the decoder columns that carry a gradient (Engine.decoder_live).  False -- over all 21 per agent, as rounds 1-4 -- is a test
+# reference only (tests/test_gpu_parity.py::test_live_column_backward_equals_the_dense_backward sets it); part of the graph key
+_LIVE_COLUMNS = True
 _GATHER_MAX = 32
+_K1 = 21                      # decoder columns per agent in forward(): the posterior draw + the 20 prior draws
 
 
 class _OdeCombine(ctypes.Structure):                 # include/sttode_hip.h SttodeOdeCombine (sttode_ode_combine)
@@ -49,21 +51,11 @@ ACT = {None: 0, 'relu': 1, 'tanh': 2, 'sigmoid': 3}
 _ATT = 'ODE_Encoder.odeblock.odefunc.layers.0.'
 
 
-_AGENT_GRU = os.environ.get('STTODE_TRAIN_AGENT_GRU', '1') != '0'   # the first block's conv + GRU once per agent (0: per trajectory column, A/B)
-_PAIRED = os.environ.get('STTODE_TRAIN_PAIRED', '1') != '0'   # decoder_x / decoder_y of a block layer by layer, grouped launches (0: A/B)
-# Layer 1 of the decoder MLPs split like the inference chain's (round 5): W1 cat(pf_rep, z, state) = (W1[:, pf] pf + b1) per AGENT -- a table of
-# n rows shared by the agent's K samples -- + W1[:, z | state] [z | state] per trajectory: half the layer's products forward and in both
-# gradient products (the pf part of dW1 and of dX is formed from the K-summed gradient rows, n of them).  At batch sizes only: below this
-# many trajectory columns the step is bound by its number of launches and the split adds four per block (STTODE_TRAIN_L1SPLIT=0: A/B).
-# MEASURED NEUTRAL and therefore OFF by default (STTODE_TRAIN_L1SPLIT=1 enables it): 2.301 / 2.308 ms per NBA-size step with, 2.304 / 2.291 ms without
-# (profiles/r05/train_l1split_ab.txt) -- halving the layer's products does not shorten its launches: at 7 392 columns they are bound by one-round
-# quantisation, tile start and the 15 MB tape store, not by the matrix pipe.
-_L1SPLIT_MIN_COLS = int(os.environ.get('STTODE_TRAIN_L1SPLIT_MIN', '2048')) if os.environ.get('STTODE_TRAIN_L1SPLIT', '0') != '0' else 1 << 60
+# the first block's conv + GRU once per agent.  False -- per trajectory column -- is a test reference only (the same test); part of the graph key
+_AGENT_GRU = True
 _SCRATCH_BATCH = 32 << 20     # floats (128 MB): split sums of one backward pass at batch sizes (more than 2048 GEMM columns)
 _TGEMM_MIN_COLS_BWD = 600     # == TGEMM_MIN_COLS_BWD of csrc/train.hip: backward products above it take the LDS-tiled GEMM (split sums)
 # non-default encoder integrators: cap of the per-stage activation and gradient columns the deferred weight-gradient pass holds at once
-# (the chunk buffers are allocated outside Engine.hold; with STTODE_TRAIN_STREAMS=1 the per-stage temporaries of the layer-by-layer
-# path are held until the step ends, so there the cap bounds the chunk columns but not the stage temporaries)
 _ODE_DW_CAP = int(os.environ.get('STTODE_ODE_DW_CAP_MB', '256')) << 20      # bytes
 
 
@@ -83,16 +75,12 @@ class Engine:
     def __init__(self, net):
         self.net = net
         self.dev = net.device
-        self.scratch = self.main_scratch = torch.empty(4 << 20, dtype=torch.float32, device=self.dev)
+        self.scratch = torch.empty(4 << 20, dtype=torch.float32, device=self.dev)
         self.red_scratch = None     # split sums of a backward pass's deferred weight-gradient reductions (batch sizes; allocated on first use)
         self.param_grads = True     # False: skip the weight-gradient GEMMs (stage-2 sampler training keeps this net frozen)
-        # The step is written as segments (forward_segments / backward_segments); optionally the future trunk's segments run on a side
-        # stream with its own split-k scratch (_use_streams: off by default).
-        self.side = None            # [stream, stream], created on first use
-        self.side_scratch = None
-        self.multi = False
-        self._hold = []
-        self.fused_trunk = os.environ.get('STTODE_TRUNK_FUSED', '1') != '0'   # scene batches: a trunk's forward + tape in one launch
+        # scene batches: a trunk's forward + tape in one launch.  False -- layer by layer, the only form for T > 12 and D != 64 -- is otherwise
+        # a test reference only (tests/test_gpu_parity.py::test_fused_trunk_forward_writes_the_layer_by_layer_tape sets it)
+        self.fused_trunk = True
         # dimensions (train.py:37-40 --zdim / --hidden_dim / --num_decompose; 8 heads, ff 1024, conv 32 and GRU 96 are fixed in the reference:
         # model/STTODE.py:23-26,188-189): D model width, HD head width, ZD latent width, PFW = width of past_feature = cat(ftraj_input, ode),
         # ST = column of the GRU state in a decompose block's input cat(pf, z, state), IN = its width
@@ -101,63 +89,22 @@ class Engine:
         self.HD, self.PFW = self.D // 8, 2 * self.D
         self.ST = self.PFW + self.ZD
         self.IN = self.ST + 96
-        self.ZS = self.ZD + 96                    # width of a trajectory's own layer-1 input [z | state] (layer-1 split)
-        self.split = False                        # set per decoder pass (decoder_fwd) from the pass's trajectory count
 
-    # ---------------------------------------------------------------- streams
-    def _use_streams(self, n):
-        """The future trunk's segments on a side stream (STTODE_TRAIN_STREAMS=1; default off).  Measured on one-scene steps: in the eager form
-        the host enqueues too slowly for two streams to overlap (and holding every temporary alive costs more than it buys: 6.5 vs 4.0 ms),
-        in the captured form hipGraphLaunch feeds kernels at the rate one queue executes them (see _GraphedStep._capture)."""
-        on = os.environ.get('STTODE_TRAIN_STREAMS', '0') not in ('', '0') and n * 20 <= 32768
-        if on and self.side is None:
-            self.side = [torch.cuda.Stream(device=self.dev), torch.cuda.Stream(device=self.dev)]
-            self.side_scratch = [torch.empty(4 << 20, dtype=torch.float32, device=self.dev) for _ in self.side]
-        return on
+    def begin(self):
+        """Start a pass on the engine: the parameters by name as they are now, and the launches bound to the caller's stream."""
+        self.P = dict(self.net.named_parameters())
+        self._enter()
 
-    def _enter(self, idx):
-        """Bind the launch state to the stream a segment runs on (idx -1: the caller's stream, 0 / 1: side streams)."""
+    def _enter(self):
+        """Bind the launches to the caller's current stream (again inside a capture: torch.cuda.graph switches the stream)."""
         self.st = capi.stream_ptr()
-        self.scratch = self.main_scratch if idx < 0 else self.side_scratch[idx]
-
-    def run_segments(self, segs, launch=None):
-        """A step is a list of segments (stream, waits, fn): fn enqueues a chain of kernels on its stream; a side-stream segment starts
-        after everything enqueued so far on the caller's stream, a caller's-stream segment after the side streams named in ``waits``.
-        ``launch(i)`` replaces fn (replay of the segment's captured hipGraph).  With streams off everything runs in list order."""
-        main = torch.cuda.current_stream()
-        used = set()
-        for i, (stream, waits, fn) in enumerate(segs):
-            if not self.multi or stream < 0:
-                if self.multi:
-                    for w in waits:
-                        main.wait_stream(self.side[w])
-                        used.discard(w)
-                self._enter(-1)
-                fn() if launch is None else launch(i)
-            else:
-                sd = self.side[stream]
-                sd.wait_stream(main)
-                used.add(stream)
-                with torch.cuda.stream(sd):
-                    self._enter(stream)
-                    fn() if launch is None else launch(i)
-        for w in used:                       # the caller's stream ends behind every side stream
-            main.wait_stream(self.side[w])
-        self._enter(-1)
-
-    def hold(self, t):
-        """Keeps a tensor that crosses streams alive until the step's last kernel is enqueued AND the next step begins: the caching
-        allocator would otherwise hand its block to a later allocation of the allocating stream while another stream still uses it."""
-        if self.multi:
-            self._hold.append(t)
-        return t
 
     # ---------------------------------------------------------------- primitives
     def new(self, *shape):
-        return self.hold(torch.empty(*shape, dtype=torch.float32, device=self.dev))
+        return torch.empty(*shape, dtype=torch.float32, device=self.dev)
 
     def zeros(self, *shape):
-        return self.hold(torch.zeros(*shape, dtype=torch.float32, device=self.dev))
+        return torch.zeros(*shape, dtype=torch.float32, device=self.dev)
 
     def lin(self, X, W, b, act=None, xdiv=1, out=None, cols=None):
         """out[c] = act(W X[c / xdiv] + b); X [rows, J] (row stride free), W [I, J] row-major view."""
@@ -166,15 +113,6 @@ class Engine:
         assert X.shape[1] == J
         out = self.new(cols, I) if out is None else out
         capi.call('sttode_tlinear', X, _ld(X), xdiv, W, _ld(W), 0, b, None, 0, out, _ld(out), cols, J, I, ACT[act], 0, self.st)
-        return out
-
-    def lin_tab(self, X, W, tab, tdiv, act=None):
-        """out[c] = act(W X[c] + tab[c / tdiv]) (sttode_tlinear_tab: the decoder MLPs' layer 1 with its per-agent part as a table)."""
-        cols = X.shape[0]
-        I, J = W.shape
-        assert X.shape[1] == J and tab.shape[1] == I and tab.shape[0] * tdiv == cols
-        out = self.new(cols, I)
-        capi.call('sttode_tlinear_tab', X, _ld(X), W, _ld(W), None, tab, _ld(tab), tdiv, out, _ld(out), cols, J, I, ACT[act], self.st)
         return out
 
     def lin_dx(self, dY, W, mask=None, out=None, accumulate=False, in_features=None):
@@ -343,7 +281,7 @@ class Engine:
                     self.ew(EW_MUL, s['tp'], s['tp'], s['drop'])
         for s in S:
             s['h3in'] = self.zeros(s['n'], D + 4)
-            s['h3in'][:, D + 2] = self.hold(s['last'].to(torch.float32))   # add_category: [0, 0, 1] for the last agent (model/STTODE.py:199-210)
+            s['h3in'][:, D + 2] = s['last'].to(torch.float32)   # add_category: [0, 0, 1] for the last agent (model/STTODE.py:199-210)
         with self.group():
             for s in S:
                 self.lin(s['tp'].view(s['n'], s['T'] * D), P[s['pre'] + 'input_fc2.weight'], P[s['pre'] + 'input_fc2.bias'], out=s['h3in'][:, :D])
@@ -353,7 +291,6 @@ class Engine:
                 self.lin(s['h3in'][:, :D + 3], P[s['pre'] + 'input_fc3.weight'], P[s['pre'] + 'input_fc3.bias'], out=s['x'])
 
     def _trunk_launch(self, src, n, T, feat, phase):
-        import ctypes
         tbl = (ctypes.c_void_p * len(capi.TRUNK_PTRS))(*[(src[k].data_ptr() if src.get(k) is not None else None) for k in capi.TRUNK_PTRS])
         capi.call('sttode_ttrunk_fwd', tbl, len(capi.TRUNK_PTRS), n, T, feat.stride(0), float(self.net.ODE_TIME), phase, self.st)
 
@@ -361,7 +298,6 @@ class Engine:
         """The same forward and the same tape in ONE launch (csrc/train_trunk.hip, attention length 1): the step is bound by the number of
         launches, and a trunk is 21 of them layer by layer.  ``phase=1``: only up to the in-projection (attention over the forward-call batch:
         the caller runs the attention and then phase 2 through _trunk_launch); returns (tape, pointer sources) then."""
-        import ctypes
         P, net = self.P, self.net
         pre, n, T = t['pre'], t['n'], t['T']
         a = pre + _ATT
@@ -764,7 +700,7 @@ class Engine:
         def vjp(j, kb, close):
             c1 = nst - ((nst - 1 - j) // C) * C
             c0 = max(0, c1 - C)
-            if j == c1 - 1:                                     # the chunk's first (highest) stage: its column buffers (one stream: not held)
+            if j == c1 - 1:                                     # the chunk's first (highest) stage: its column buffers
                 K[:] = [{k: torch.empty((c1 - c0) * s['n'], width[k], dtype=torch.float32, device=self.dev) for k in nm} for s, nm in zip(S, names)]
             keep = [{k: v[(j - c0) * s['n']:(j - c0 + 1) * s['n']] for k, v in kk.items()} for s, kk in zip(S, K)]
             if fused:
@@ -786,42 +722,14 @@ class Engine:
         self._trunk_bwd_pre(S)
 
     # ---------------------------------------------------------------- decoder (Decoder.forward, model/STTODE.py:320-347)
-    def l1_fwd(self, pre, inp, tab, K):
-        """Layer 1 of a decoder MLP: plain, or -- layer-1 split -- from the agent's table and the trajectory's own [z | state] columns."""
+    def mlp_fwd(self, pre, inp):
         P = self.P
-        if tab is None:
-            return self.lin(inp, P[pre + 'layers.0.weight'], P[pre + 'layers.0.bias'], act='relu')
-        return self.lin_tab(inp[:, self.PFW:], P[pre + 'layers.0.weight'][:, self.PFW:], tab, K, act='relu')
-
-    def l1_tables(self, pres, pf):
-        """The per-agent tables W1[:, pf] pf + b1 of the given MLPs (one grouped launch)."""
-        P = self.P
-        with self.group():
-            return [self.lin(pf, P[pre + 'layers.0.weight'][:, :self.PFW], P[pre + 'layers.0.bias']) for pre in pres]
-
-    def l1_bwd(self, pre, da, inp, din, accumulate, pf, dpf, K):
-        """Backward of layer 1: plain (din [m, IN]), or -- layer-1 split -- the trajectory part into din [m, ZS] and the agent part from the
-        K-summed gradient rows into dpf [n, 2 D] (accumulated)."""
-        P, g = self.P, self.grad
-        W, gW, gb = P[pre + 'layers.0.weight'], g(pre + 'layers.0.weight'), g(pre + 'layers.0.bias')
-        if pf is None:
-            self.lin_bwd(da, W, inp, gW, gb, out=din, accumulate=accumulate)
-            return
-        PFW = self.PFW
-        self.lin_bwd(da, W[:, PFW:], inp[:, PFW:], gW[:, PFW:], gb, out=din, accumulate=accumulate)   # (gb: the whole bias gradient = sum over all columns)
-        n = pf.shape[0]
-        dA = self.new(n, da.shape[1])
-        capi.call('sttode_rows_reduce', dA, _ld(dA), da, _ld(da), n, da.shape[1], K, 0, self.st)
-        self.lin_bwd(dA, W[:, :PFW], pf, gW[:, :PFW], None, out=dpf, accumulate=True)
-
-    def mlp_fwd(self, pre, inp, tab=None, K=1):
-        P = self.P
-        a1 = self.l1_fwd(pre, inp, tab, K)
+        a1 = self.lin(inp, P[pre + 'layers.0.weight'], P[pre + 'layers.0.bias'], act='relu')
         a2 = self.lin(a1, P[pre + 'layers.1.weight'], P[pre + 'layers.1.bias'], act='relu')
         out = self.lin(a2, P[pre + 'layers.2.weight'], P[pre + 'layers.2.bias'])
         return out, (a1, a2)
 
-    def mlp_fwd_pair(self, pre_a, pre_b, inp, tabs=(None, None), K=1):
+    def mlp_fwd_pair(self, pre_a, pre_b, inp):
         """decoder_y and decoder_x of a block (same input, separate weights, model/STTODE.py:71-77) layer by layer: at batch sizes the two
         products of a layer leave as one launch (sttode_tgemm_group)."""
         P = self.P
@@ -829,37 +737,29 @@ class Engine:
         xa = xb = inp
         for li, act in ((0, 'relu'), (1, 'relu'), (2, None)):
             with self.group():
-                if li == 0:
-                    xa, xb = self.l1_fwd(pre_a, inp, tabs[0], K), self.l1_fwd(pre_b, inp, tabs[1], K)
-                else:
-                    xa = self.lin(xa, P[f'{pre_a}layers.{li}.weight'], P[f'{pre_a}layers.{li}.bias'], act=act)
-                    xb = self.lin(xb, P[f'{pre_b}layers.{li}.weight'], P[f'{pre_b}layers.{li}.bias'], act=act)
+                xa = self.lin(xa, P[f'{pre_a}layers.{li}.weight'], P[f'{pre_a}layers.{li}.bias'], act=act)
+                xb = self.lin(xb, P[f'{pre_b}layers.{li}.weight'], P[f'{pre_b}layers.{li}.bias'], act=act)
             acts.append((xa, xb))
         return (acts[2][0], (acts[0][0], acts[1][0])), (acts[2][1], (acts[0][1], acts[1][1]))
 
-    def mlp_bwd_pair(self, pre_a, pre_b, inp, saved_a, saved_b, dout_a, dout_b, din, pf=None, dpf=None, K=1):
+    def mlp_bwd_pair(self, pre_a, pre_b, inp, saved_a, saved_b, dout_a, dout_b, din):
         """Backward of the pair: layers 2 and 1 of both MLPs side by side (four products per launch at batch sizes); their layer-0 input
         gradients add into the same ``din``, so those two stay launches of their own, in order."""
         P, g = self.P, self.grad
         da, db_ = dout_a, dout_b
         for li, (sa, sb) in ((2, (saved_a[1], saved_b[1])), (1, (saved_a[0], saved_b[0]))):
-            capi.call('sttode_tgemm_group', 1)
-            try:
+            with self.group():
                 da = self.lin_bwd(da, P[f'{pre_a}layers.{li}.weight'], sa, g(f'{pre_a}layers.{li}.weight'), g(f'{pre_a}layers.{li}.bias'), mask=sa)
                 db_ = self.lin_bwd(db_, P[f'{pre_b}layers.{li}.weight'], sb, g(f'{pre_b}layers.{li}.weight'), g(f'{pre_b}layers.{li}.bias'), mask=sb)
-            except BaseException:
-                capi.call('sttode_tgemm_group', -1)
-                raise
-            capi.call('sttode_tgemm_group', 0)
-        self.l1_bwd(pre_a, da, inp, din, False, pf, dpf, K)
-        self.l1_bwd(pre_b, db_, inp, din, True, pf, dpf, K)
+        self.lin_bwd(da, P[pre_a + 'layers.0.weight'], inp, g(pre_a + 'layers.0.weight'), g(pre_a + 'layers.0.bias'), out=din)
+        self.lin_bwd(db_, P[pre_b + 'layers.0.weight'], inp, g(pre_b + 'layers.0.weight'), g(pre_b + 'layers.0.bias'), out=din, accumulate=True)
 
-    def mlp_bwd(self, pre, inp, saved, dout, din, accumulate, pf=None, dpf=None, K=1):
+    def mlp_bwd(self, pre, inp, saved, dout, din):
         P, g = self.P, self.grad
         a1, a2 = saved
         da2 = self.lin_bwd(dout, P[pre + 'layers.2.weight'], a2, g(pre + 'layers.2.weight'), g(pre + 'layers.2.bias'), mask=a2)
         da1 = self.lin_bwd(da2, P[pre + 'layers.1.weight'], a1, g(pre + 'layers.1.weight'), g(pre + 'layers.1.bias'), mask=a1)
-        self.l1_bwd(pre, da1, inp, din, accumulate, pf, dpf, K)
+        self.lin_bwd(da1, P[pre + 'layers.0.weight'], inp, g(pre + 'layers.0.weight'), g(pre + 'layers.0.bias'), out=din)
 
     def block_fwd(self, i, past, K, xhat_prev, pf, z, want_x, inp=None):
         P = self.P
@@ -889,39 +789,30 @@ class Engine:
             capi.call('sttode_gru_seq_fwd', gi, P[pre + 'encoder_past.weight_hh_l0'], P[pre + 'encoder_past.bias_hh_l0'], H, tapes,
                       inp[:, ST:], IN, m, Tp, self.st)                                                   # all Tp steps, one launch
         if prefix:
-            if not self.split:                                                                           # (layer-1 split: the pf columns of inp are never read)
-                capi.call('sttode_rows_copy', inp, IN, pf, _ld(pf), m, PFW, K, n, self.st)
+            capi.call('sttode_rows_copy', inp, IN, pf, _ld(pf), m, PFW, K, n, self.st)
             capi.call('sttode_rows_copy', inp[:, PFW:], IN, z, _ld(z), m, ZD, 1, m, self.st)
-        tabs = (None, None)
-        if self.split:
-            tabs = self.l1_tables([pre + 'decoder_y.'] + ([pre + 'decoder_x.'] if want_x else []), pf) + [None]
-        if want_x and _PAIRED:
-            (yh, sy), (xh, sx) = self.mlp_fwd_pair(pre + 'decoder_y.', pre + 'decoder_x.', inp, tabs, K)
+        if want_x:
+            (yh, sy), (xh, sx) = self.mlp_fwd_pair(pre + 'decoder_y.', pre + 'decoder_x.', inp)
         else:
-            yh, sy = self.mlp_fwd(pre + 'decoder_y.', inp, tabs[0], K)
-            xh, sx = self.mlp_fwd(pre + 'decoder_x.', inp, tabs[1], K) if want_x else (None, None)
-        return dict(pre=pre, m=m, Tp=Tp, K=K, x=x, e=e, H=H, tapes=tapes, inp=inp, yh=yh, sy=sy, xh=xh, sx=sx, pf=pf if self.split else None, agent=agent)
+            (yh, sy), (xh, sx) = self.mlp_fwd(pre + 'decoder_y.', inp), (None, None)
+        return dict(pre=pre, m=m, Tp=Tp, K=K, x=x, e=e, H=H, tapes=tapes, inp=inp, yh=yh, sy=sy, xh=xh, sx=sx, agent=agent)
 
-    def block_bwd(self, b, dyh, dxh, need_dx, dpf=None):
-        """Returns (din [m, IN] -- layer-1 split: [m, ZS], the trajectory's own columns [z | state]; the pf part went into dpf -- , dx [m,Tp,2] | None)."""
+    def block_bwd(self, b, dyh, dxh, need_dx):
+        """Returns (din [m, IN], dx [m,Tp,2] | None)."""
         P, g = self.P, self.grad
-        pre, m, Tp = b['pre'], b['m'], b['Tp']
-        pf, K = b.get('pf'), b['K']
-        split = pf is not None
-        LD, SO = (self.ZS, self.ZD) if split else (self.IN, self.ST)          # row length of din, column of the GRU state in it
-        din = self.new(m, LD)
-        if dxh is not None and _PAIRED:
-            self.mlp_bwd_pair(pre + 'decoder_y.', pre + 'decoder_x.', b['inp'], b['sy'], b['sx'], dyh, dxh, din, pf, dpf, K)
+        pre, m, Tp, K = b['pre'], b['m'], b['Tp'], b['K']
+        IN, ST = self.IN, self.ST
+        din = self.new(m, IN)
+        if dxh is not None:
+            self.mlp_bwd_pair(pre + 'decoder_y.', pre + 'decoder_x.', b['inp'], b['sy'], b['sx'], dyh, dxh, din)
         else:
-            self.mlp_bwd(pre + 'decoder_y.', b['inp'], b['sy'], dyh, din, False, pf, dpf, K)
-            if dxh is not None:
-                self.mlp_bwd(pre + 'decoder_x.', b['inp'], b['sx'], dxh, din, True, pf, dpf, K)
-        dstate, lds, mg = din[:, SO:], LD, m
+            self.mlp_bwd(pre + 'decoder_y.', b['inp'], b['sy'], dyh, din)
+        dstate, lds, mg = din[:, ST:], IN, m
         if b.get('agent'):                                          # conv + GRU ran once per agent: its state gradient is the sum over the agent's columns
             assert not need_dx
             mg = m // K
             dstate, lds = self.new(mg, 96), 96
-            capi.call('sttode_rows_reduce', dstate, 96, din[:, SO:], LD, mg, 96, K, 0, self.st)
+            capi.call('sttode_rows_reduce', dstate, 96, din[:, ST:], IN, mg, 96, K, 0, self.st)
         dgi = self.new(mg * Tp, 288)
         dgh = self.new(Tp, mg, 288)
         capi.call('sttode_gru_seq_bwd', dstate, lds, b['tapes'], b['H'], P[pre + 'encoder_past.weight_hh_l0'], dgi, dgh, mg, Tp, self.st)
@@ -942,18 +833,12 @@ class Engine:
         Tf = self.net.args.future_length
         m = n * K
         nb = self.NBLK
-        self.split = m >= _L1SPLIT_MIN_COLS
         inps = [None] * nb
         if qz_eps is not None:
             inps = [self.new(m, self.IN) for _ in range(nb)]
-            if self.split:        # only z is written, at its usual columns (the pf prefix is replaced by the per-agent tables)
-                capi.call('sttode_decoder_inputs', inps[0][:, self.PFW:], inps[1][:, self.PFW:] if nb > 1 else None, self.IN, pf, _ld(pf), qz_eps[0], qz_eps[1],
-                          n, K, 0, self.ZD, self.st)
-            else:
-                capi.call('sttode_decoder_inputs', inps[0], inps[1] if nb > 1 else None, self.IN, pf, _ld(pf), qz_eps[0], qz_eps[1], n, K, self.PFW, self.ZD, self.st)
+            capi.call('sttode_decoder_inputs', inps[0], inps[1] if nb > 1 else None, self.IN, pf, _ld(pf), qz_eps[0], qz_eps[1], n, K, self.PFW, self.ZD, self.st)
             for i in range(2, nb):                                  # (further blocks: the same prefix)
-                o, w = (self.PFW, self.ZD) if self.split else (0, self.ST)
-                capi.call('sttode_rows_copy', inps[i][:, o:], self.IN, inps[0][:, o:], self.IN, m, w, 1, m, self.st)
+                capi.call('sttode_rows_copy', inps[i], self.IN, inps[0], self.IN, m, self.ST, 1, m, self.st)
         blocks, xprev = [], None
         for i in range(nb):
             b = self.block_fwd(i, past, K, xprev, pf, z, want_recover or i + 1 < nb, inp=inps[i])
@@ -978,7 +863,7 @@ class Engine:
             if want_recover:
                 rec = self.new(m, 2 * Tp)
                 self.ew(EW_SUM_CUR, rec, xsum, blocks[-1]['xh'] if nb > 1 else self.zeros(m, 2 * Tp), None, i0=2 * Tp, f0=K)
-        return dict(blocks=blocks, b0=blocks[0], b1=blocks[-1], n=n, K=K, m=m, pred=pred, rec=rec, split=self.split)
+        return dict(blocks=blocks, b0=blocks[0], b1=blocks[-1], n=n, K=K, m=m, pred=pred, rec=rec)
 
     def decoder_live(self, d, best):
         """The decoder's tape reduced to the columns that carry a gradient.  forward() decodes 1 + 20 samples per agent, but the objective
@@ -999,7 +884,7 @@ class Engine:
             return dst
         for b in d['blocks']:
             Tp = b['Tp']
-            nb = dict(pre=b['pre'], m=m2, Tp=Tp, K=2, pf=b['pf'], agent=b.get('agent', False))
+            nb = dict(pre=b['pre'], m=m2, Tp=Tp, K=2, agent=b.get('agent', False))
             if nb['agent']:                                          # conv + GRU ran per agent: their tape has no column dimension
                 nb.update(x=b['x'], e=b['e'], H=b['H'], tapes=b['tapes'])
             else:
@@ -1015,20 +900,17 @@ class Engine:
             chunk = items[i:i + _GATHER_MAX]
             table = (_GatherItem * len(chunk))(*chunk)              # (a named object: it must outlive the call that reads it)
             capi.call('sttode_live_rows_gather', table, len(chunk), best, n, K1, self.st)
-        return dict(blocks=blocks, b0=blocks[0], b1=blocks[-1], n=n, K=2, m=m2, split=d.get('split', False))
+        return dict(blocks=blocks, b0=blocks[0], b1=blocks[-1], n=n, K=2, m=m2)
 
     def decoder_bwd(self, d, dpred, drec, dpf, dz, dpf_accumulate=True):
         """Accumulates dpf [n, 2 D] (+=; ``dpf_accumulate=False``: writes it); writes dz [m, zd] if not None.  Returns the gradient of the
         blocks' summed layer-1 input [m, IN] = cat(d pf_rep | d z | d state) (its columns 2 D .. 2 D + zd - 1 are dz)."""
         n, K, m = d['n'], d['K'], d['m']
         blocks = d['blocks']
-        split = d.get('split', False)
-        if split and not dpf_accumulate:
-            self.ew(EW_FILL, dpf, f0=0.0)                          # (layer-1 split: every MLP adds its agent part into dpf)
         # x_{i+1} = x_true - x_hat_i  =>  d x_hat_i = (d recover) - d x_{i+1}; the last block's x_hat only feeds the reconstruction
         dxh, din_sum = drec, None
         for i in range(len(blocks) - 1, -1, -1):
-            din, dx = self.block_bwd(blocks[i], dpred, dxh, i > 0, dpf)
+            din, dx = self.block_bwd(blocks[i], dpred, dxh, i > 0)
             if din_sum is None:
                 din_sum = din
             else:
@@ -1037,175 +919,134 @@ class Engine:
             if i > 0:
                 dxh = dx.view(m, -1)
                 self.ew(EW_SCALE_ADD, dxh, drec, f0=-1.0)           # d x_hat_{i-1} = -dx_i (+ drec)
-        if split:                                                  # din_sum [m, ZS] = cat(d z | d state); dpf is complete
-            if dz is not None:
-                dz.copy_(din_sum[:, :self.ZD])
-            return din_sum
         capi.call('sttode_rows_reduce', dpf, _ld(dpf), din_sum, self.IN, n, self.PFW, K, int(dpf_accumulate), self.st)
         if dz is not None:
             dz.copy_(din_sum[:, self.PFW:self.ST])
         return din_sum
 
     # ---------------------------------------------------------------- the objective (model/STTODE.py:553-568)
-    def forward_segments(self, eps_q, eps20, drop_past=None, drop_future=None, streams=None):
-        """The forward pass as segments (see run_segments): future trunk on side 1 beside the past trunk; then the q-net and ONE decoder
-        pass over 1 + 20 samples per agent -- sample 0 decoded from the posterior draw (pred_traj / recover_traj, model/STTODE.py:
-        553-560), samples 1..20 from the prior draws (diverse_pred_traj, :562-566): the two passes of the reference share every
-        weight, so one pass over 21 columns per agent halves the launches of the decoder's forward and backward."""
-        net, a = self.net, self.net.args
-        self.P = {k: v for k, v in net.named_parameters()}
-        P = self.P
-        self._hold = []
-        self.multi = self._use_streams(net._past.shape[0]) if streams is None else bool(streams)
-        for t_in in (eps_q, eps20, drop_past, drop_future):       # the caller may drop them while a side stream still reads them
-            if t_in is not None:
-                self.hold(t_in)
+    def prepare_forward(self):
+        """The host side of a forward pass, BEFORE a capture begins (_GraphedStep._capture): the parameters by name, and at batch sizes the
+        room for a backward pass's deferred split sums -- the engine's own buffer, which must not come from a graph's private pool."""
+        self.begin()
+        net = self.net
+        if net._past.shape[0] * _K1 * net.args.past_length > _TGEMM_MIN_COLS_BWD and self.red_scratch is None:
+            self.red_scratch = torch.empty(_SCRATCH_BATCH, dtype=torch.float32, device=self.dev)
+
+    def enqueue_forward(self, eps_q, eps20, drop_past=None, drop_future=None):
+        """Enqueues the forward pass (after prepare_forward): the frontend, both trunks together, then the q-net and ONE decoder pass over
+        1 + 20 samples per agent -- sample 0 decoded from the posterior draw (pred_traj / recover_traj, model/STTODE.py:553-560),
+        samples 1..20 from the prior draws (diverse_pred_traj, :562-566): the two passes of the reference share every weight, so one
+        pass over 21 columns per agent halves the launches of the decoder's forward and backward.  Returns the loss values [5]."""
+        self._enter()
+        net, a, P = self.net, self.net.args, self.P
         B = net.batch_size if net._mode == 'nba' else 1
         N = net.agent_num
         n, Tp, Tf, zd = net._past.shape[0], a.past_length, a.future_length, a.zdim
         mode = 0 if net._mode == 'scenes' else 1
-        K1 = 21
-        if n * K1 * Tp > _TGEMM_MIN_COLS_BWD and self.red_scratch is None:         # batch sizes: room for a backward pass's deferred split sums
-            self.red_scratch = torch.empty(_SCRATCH_BATCH, dtype=torch.float32, device=self.dev)
-        V = self.V = {}
-
-        PFW = self.PFW
-
-        def f_front():
-            V['ws'] = ws = net._frontend(vel_from_norm=0)
-            V['past'] = ws['xpad'][:, :2 * Tp].reshape(n, Tp, 2).contiguous()
-            V['fut'] = (net._future - ws['orig'][:, None, :]).contiguous()
-            V['hcat'] = self.new(n, 2 * PFW)
-            V['lastpos'] = self.hold(net._past[:, -1].contiguous())
-
-        def f_future():
-            ws, hcat = V['ws'], V['hcat']
-            enc_f = self.new(n, Tf, 4)
-            capi.call('sttode_frontend_future', net._future, V['lastpos'], n, Tf, mode, net._N or 1, ws.get('scene_orig'),
-                      ws.get('agent_scene'), net._scene_ptr if mode == 0 else None, enc_f, self.st)
-            if _PAIRED and not self.multi:
-                V['enc_f'] = enc_f                                   # one stream: the two trunks' forward as ONE launch (f_past)
-            else:
-                V['tf'] = self.trunk_fwd('future_encoder.', enc_f, ws['last'], hcat[:, PFW:], drop_future)
-
-        def f_past():
-            ws, hcat = V['ws'], V['hcat']
-            if _PAIRED and not self.multi:                           # one stream: both trunks together (grouped launches)
-                V['tf'], V['tp'] = self.trunk_fwd_multi([('future_encoder.', V['enc_f'], ws['last'], hcat[:, PFW:], drop_future),
-                                                         ('past_encoder.', ws['enc_in'], ws['last'], hcat[:, :PFW], drop_past)])
-            else:
-                V['tp'] = self.trunk_fwd('past_encoder.', ws['enc_in'], ws['last'], hcat[:, :PFW], drop_past)
-
-        def f_dec():
-            ws, hcat, fut, past = V['ws'], V['hcat'], V['fut'], V['past']
-            hq = self.lin(hcat, P['future_encoder.out_mlp.affine_layers.0.weight'], P['future_encoder.out_mlp.affine_layers.0.bias'], act='relu')
-            qzp = self.lin(hq, P['future_encoder.qz_layer.weight'], P['future_encoder.qz_layer.bias'])
-            qz = self.new(n, zd)
-            self.ew(EW_RSAMPLE, qz, qzp, eps_q, i0=zd)
-            # z per (agent, sample): sample 0 = the posterior draw, samples 1..20 = the prior draws -- read where they are by the launch that
-            # fills both blocks' input prefix
-            assert zd % 4 == 0 and eps20.is_contiguous() and qz.is_contiguous()
-            d = self.decoder_fwd(hcat[:, :PFW], None, K1, past, ws['cur'], True, qz_eps=(qz, eps20))
-            losses = self.new(5)                                    # the four terms and their sum
-            live = _LIVE_COLUMNS
-            KG = 2 if live else K1                                  # columns per agent that carry a gradient (see decoder_live)
-            dpred, drec, dqzp = self.new(n * KG, 2 * Tf), self.new(n * KG, 2 * Tp), self.new(n, 2 * zd)
-            best = self.hold(torch.empty(n, dtype=torch.int32, device=self.dev)) if live else None
-            # several independent scenes in one step (set_scene_batch): the objective is the SUM of the per-scene objectives, i.e. the
-            # gradient equals what S reference steps would accumulate (per-scene KL clamp and per-scene mean of the best-of-20 term)
-            seg = net._mode == 'scenes' and net._S > 1
-            sp, ags, S = (net._scene_ptr, ws['agent_scene'], net._S) if seg else (None, None, 0)
-            if live:
-                capi.call('sttode_loss_objective_live', d['pred'], d['rec'], fut, past, qzp, sp, ags, S, n, K1, 2 * Tf, 2 * Tp, zd, 1.0 / (B * Tf),
-                          1.0 / (B * Tp), float(B * N), float(a.min_clip), losses, dpred, drec, dqzp, best, self.scratch, self.scratch.numel(), self.st)
-            else:
-                capi.call('sttode_loss_objective', d['pred'], d['rec'], fut, past, qzp, sp, ags, S, n, K1, 2 * Tf, 2 * Tp, zd, 1.0 / (B * Tf),
-                          1.0 / (B * Tp), float(B * N), float(a.min_clip), losses, dpred, drec, dqzp, self.scratch, self.scratch.numel(), self.st)
-            if getattr(self, 'publish', None) is not None:         # a step being captured: the values reach the host from HERE (see _GraphedStep)
-                capi.call('sttode_publish_values', losses, 5, *self.publish, self.st)
-            self.step_id = getattr(self, 'step_id', 0) + 1
-            self.tape = dict(step_id=self.step_id, tp=V['tp'], tf=V['tf'], hcat=hcat, hq=hq, qzp=qzp, eps_q=eps_q, d=d, dpred=dpred,
-                             drec=drec, dqzp=dqzp, n=n, zd=zd, K1=K1, best=best)
-            V['losses'] = losses
-            # attributes the reference sets (read by callers)
-            pr = d['pred'].view(n, K1, Tf, 2)
-            net.past_feature = hcat[:, :PFW]
-            net.qz_param = qzp
-            net.qz_sampled = qz
-            net.pred_traj = pr[:, 0]
-            net.recover_traj = d['rec'].view(n, K1, Tp, 2)[:, 0]
-            net.diverse_pred_traj = pr[:, 1:]
-            net.past_traj, net.future_traj, net.cur_location = past, fut, past[:, -1:]
-
-        return [(-1, (), f_front), (1, (), f_future), (-1, (), f_past), (-1, (1,), f_dec)]
+        K1, PFW = _K1, self.PFW
+        ws = net._frontend(vel_from_norm=0)
+        past = ws['xpad'][:, :2 * Tp].reshape(n, Tp, 2).contiguous()
+        fut = (net._future - ws['orig'][:, None, :]).contiguous()
+        hcat = self.new(n, 2 * PFW)
+        lastpos = net._past[:, -1].contiguous()
+        enc_f = self.new(n, Tf, 4)
+        capi.call('sttode_frontend_future', net._future, lastpos, n, Tf, mode, net._N or 1, ws.get('scene_orig'),
+                  ws.get('agent_scene'), net._scene_ptr if mode == 0 else None, enc_f, self.st)
+        tf, tp = self.trunk_fwd_multi([('future_encoder.', enc_f, ws['last'], hcat[:, PFW:], drop_future),    # both trunks together (grouped launches)
+                                       ('past_encoder.', ws['enc_in'], ws['last'], hcat[:, :PFW], drop_past)])
+        hq = self.lin(hcat, P['future_encoder.out_mlp.affine_layers.0.weight'], P['future_encoder.out_mlp.affine_layers.0.bias'], act='relu')
+        qzp = self.lin(hq, P['future_encoder.qz_layer.weight'], P['future_encoder.qz_layer.bias'])
+        qz = self.new(n, zd)
+        self.ew(EW_RSAMPLE, qz, qzp, eps_q, i0=zd)
+        # z per (agent, sample): sample 0 = the posterior draw, samples 1..20 = the prior draws -- read where they are by the launch that
+        # fills both blocks' input prefix
+        assert zd % 4 == 0 and eps20.is_contiguous() and qz.is_contiguous()
+        d = self.decoder_fwd(hcat[:, :PFW], None, K1, past, ws['cur'], True, qz_eps=(qz, eps20))
+        losses = self.new(5)                                    # the four terms and their sum
+        live = _LIVE_COLUMNS
+        KG = 2 if live else K1                                  # columns per agent that carry a gradient (see decoder_live)
+        dpred, drec, dqzp = self.new(n * KG, 2 * Tf), self.new(n * KG, 2 * Tp), self.new(n, 2 * zd)
+        best = torch.empty(n, dtype=torch.int32, device=self.dev) if live else None
+        # several independent scenes in one step (set_scene_batch): the objective is the SUM of the per-scene objectives, i.e. the
+        # gradient equals what S reference steps would accumulate (per-scene KL clamp and per-scene mean of the best-of-20 term)
+        seg = net._mode == 'scenes' and net._S > 1
+        sp, ags, S = (net._scene_ptr, ws['agent_scene'], net._S) if seg else (None, None, 0)
+        if live:
+            capi.call('sttode_loss_objective_live', d['pred'], d['rec'], fut, past, qzp, sp, ags, S, n, K1, 2 * Tf, 2 * Tp, zd, 1.0 / (B * Tf),
+                      1.0 / (B * Tp), float(B * N), float(a.min_clip), losses, dpred, drec, dqzp, best, self.scratch, self.scratch.numel(), self.st)
+        else:
+            capi.call('sttode_loss_objective', d['pred'], d['rec'], fut, past, qzp, sp, ags, S, n, K1, 2 * Tf, 2 * Tp, zd, 1.0 / (B * Tf),
+                      1.0 / (B * Tp), float(B * N), float(a.min_clip), losses, dpred, drec, dqzp, self.scratch, self.scratch.numel(), self.st)
+        if getattr(self, 'publish', None) is not None:         # a step being captured: the values reach the host from HERE (see _GraphedStep)
+            capi.call('sttode_publish_values', losses, 5, *self.publish, self.st)
+        self.step_id = getattr(self, 'step_id', 0) + 1
+        self.tape = dict(step_id=self.step_id, tp=tp, tf=tf, hcat=hcat, hq=hq, qzp=qzp, eps_q=eps_q, d=d, dpred=dpred,
+                         drec=drec, dqzp=dqzp, n=n, zd=zd, K1=K1, best=best)
+        # the forward pass's own buffers (a captured step keeps them: _GraphedStep.keep)
+        self.V = dict(ws=ws, past=past, fut=fut, hcat=hcat, lastpos=lastpos, enc_f=enc_f, tf=tf, tp=tp, losses=losses)
+        # attributes the reference sets (read by callers)
+        pr = d['pred'].view(n, K1, Tf, 2)
+        net.past_feature = hcat[:, :PFW]
+        net.qz_param = qzp
+        net.qz_sampled = qz
+        net.pred_traj = pr[:, 0]
+        net.recover_traj = d['rec'].view(n, K1, Tp, 2)[:, 0]
+        net.diverse_pred_traj = pr[:, 1:]
+        net.past_traj, net.future_traj, net.cur_location = past, fut, past[:, -1:]
+        return losses
 
     def run_forward(self, eps_q, eps20, drop_past=None, drop_future=None):
-        self.run_segments(self.forward_segments(eps_q, eps20, drop_past, drop_future))
-        return self.V['losses']
+        self.prepare_forward()
+        return self.enqueue_forward(eps_q, eps20, drop_past, drop_future)
 
-    def backward_segments(self):
-        """The backward pass as segments: decoder pass + q-net on the caller's stream, then the future trunk on side 1 beside the past
-        trunk (disjoint parameters)."""
+    def enqueue_backward(self):
+        """Enqueues the backward pass of the most recent forward: the decoder and the q-net, then both trunks together (disjoint parameters).
+        A failure on the way drops the weight-gradient reductions that were deferred so far."""
+        try:
+            self._enqueue_backward()
+        except BaseException:
+            capi.call('sttode_twgrad_defer', -1, None, 0)
+            raise
+
+    def _enqueue_backward(self):
         T = self.tape
         # The tape (and the flat gradient buffer it fills) belongs to the MOST RECENT eager forward().  backward() of an older loss, or
         # a second backward() of the same loss, would silently differentiate the wrong step: refuse instead.
         if T is None:
             raise SttodeError('training backward: the tape of this forward() was already consumed (backward() called twice, or '
                               'retain_graph reuse); run forward() again')
+        self._enter()
         n, zd, K1 = T['n'], T['zd'], T['K1']
-        P, g = self.P, self.grad
-        W = {}
-
-        def b_dec():
-            self._grad_views()
-            if self.red_scratch is not None:                            # batch sizes: the split weight gradients' reductions as one launch per 16
-                capi.call('sttode_twgrad_defer', 1, self.red_scratch, self.red_scratch.numel())
-            W['dpf'] = dpf = self.new(n, self.PFW)
-            d, KG = T['d'], K1
-            if T.get('best') is not None:                               # backward over the two columns per agent that carry a gradient
-                d, KG = self.decoder_live(T['d'], T['best']), 2
-            din = self.decoder_bwd(d, T['dpred'], T['drec'], dpf, None, dpf_accumulate=False)
-            dqz = self.new(n, zd)                                       # gradient of the posterior draw = sample 0 of every agent: dz of row a KG
-            if d.get('split'):
-                capi.call('sttode_rows_copy', dqz, zd, din, KG * self.ZS, n, zd, 1, n, self.st)
-            else:
-                capi.call('sttode_rows_copy', dqz, zd, din[:, self.PFW:], KG * self.IN, n, zd, 1, n, self.st)
-            dqzp = T['dqzp']                                            # starts as the KL gradient
-            self.ew(EW_RSAMPLE_BWD, dqz, T['qzp'], T['eps_q'], dqzp, i0=zd)
-            dhq = self.lin_bwd(dqzp, P['future_encoder.qz_layer.weight'], T['hq'], g('future_encoder.qz_layer.weight'),
-                               g('future_encoder.qz_layer.bias'), mask=T['hq'])
-            W['dhcat'] = self.hold(self.lin_bwd(dhq, P['future_encoder.out_mlp.affine_layers.0.weight'], T['hcat'],
-                                                g('future_encoder.out_mlp.affine_layers.0.weight'),
-                                                g('future_encoder.out_mlp.affine_layers.0.bias')))
-
-        def b_future():
-            if not (_PAIRED and not self.multi):
-                self.trunk_bwd(T['tf'], W['dhcat'][:, self.PFW:])
-
-        def b_past():
-            dpf = W['dpf']
-            dh = W['dhcat']
-            assert dh.stride(1) == 1 and dh.stride(0) < 65536
-            self.ew(EW_AXPY_ROWS, dpf, dh, i0=(dh.stride(0) << 16) | self.PFW, f0=1.0, count=n * self.PFW)   # dpf += dhcat[:, :2 D] (read where it is)
-            if _PAIRED and not self.multi:                              # one stream: both trunks layer by layer, grouped launches
-                self.trunk_bwd_multi([(T['tf'], W['dhcat'][:, self.PFW:]), (T['tp'], dpf)])
-            else:
-                self.trunk_bwd(T['tp'], dpf)
-            capi.call('sttode_twgrad_defer', 0, None, 0)                # the pending reductions run here, behind the last gradient
-            self.tape = None
-
-        return [(-1, (), b_dec), (1, (), b_future), (-1, (), b_past)]
+        P, g, PFW = self.P, self.grad, self.PFW
+        self._grad_views()
+        if self.red_scratch is not None:                            # batch sizes: the split weight gradients' reductions as one launch per 16
+            capi.call('sttode_twgrad_defer', 1, self.red_scratch, self.red_scratch.numel())
+        dpf = self.new(n, PFW)
+        d, KG = T['d'], K1
+        if T.get('best') is not None:                               # backward over the two columns per agent that carry a gradient
+            d, KG = self.decoder_live(T['d'], T['best']), 2
+        din = self.decoder_bwd(d, T['dpred'], T['drec'], dpf, None, dpf_accumulate=False)
+        dqz = self.new(n, zd)                                       # gradient of the posterior draw = sample 0 of every agent: dz of row a KG
+        capi.call('sttode_rows_copy', dqz, zd, din[:, PFW:], KG * self.IN, n, zd, 1, n, self.st)
+        dqzp = T['dqzp']                                            # starts as the KL gradient
+        self.ew(EW_RSAMPLE_BWD, dqz, T['qzp'], T['eps_q'], dqzp, i0=zd)
+        dhq = self.lin_bwd(dqzp, P['future_encoder.qz_layer.weight'], T['hq'], g('future_encoder.qz_layer.weight'),
+                           g('future_encoder.qz_layer.bias'), mask=T['hq'])
+        dh = self.lin_bwd(dhq, P['future_encoder.out_mlp.affine_layers.0.weight'], T['hcat'], g('future_encoder.out_mlp.affine_layers.0.weight'),
+                          g('future_encoder.out_mlp.affine_layers.0.bias'))
+        assert dh.stride(1) == 1 and dh.stride(0) < 65536
+        self.ew(EW_AXPY_ROWS, dpf, dh, i0=(dh.stride(0) << 16) | PFW, f0=1.0, count=n * PFW)   # dpf += dhcat[:, :2 D] (read where it is)
+        self.trunk_bwd_multi([(T['tf'], dh[:, PFW:]), (T['tp'], dpf)])    # both trunks layer by layer, grouped launches
+        capi.call('sttode_twgrad_defer', 0, None, 0)                # the pending reductions run here, behind the last gradient
+        self.tape = None
 
     def run_backward(self, gout=None, step_id=None):
         T = self.tape
         if T is not None and step_id is not None and T.get('step_id') != step_id:
             raise SttodeError('training backward: this loss belongs to an earlier forward(); only the most recent forward() of a model '
                               'can be differentiated (its tape was overwritten by the newer forward())')
-        try:
-            self.run_segments(self.backward_segments())
-        except BaseException:
-            capi.call('sttode_twgrad_defer', -1, None, 0)
-            raise
+        self.enqueue_backward()
         if gout is not None:
             self.Gflat.mul_(gout)
         return {k: self.G[k] for k in self.touched}
@@ -1319,12 +1160,12 @@ class _GraphedStep:
             net._scene_ptr = st['scene_ptr']
 
     def _capture(self):
-        """The whole step (forward with tape + backward) as ONE hipGraph on one stream.  Measured alternatives: the future trunk's
-        segments as branches of the same graph, or every segment as its own graph replayed on two streams -- hipGraphLaunch feeds a
+        """The whole step (forward with tape + backward) as ONE hipGraph on one stream.  Measured alternatives: the future trunk as a
+        branch of the same graph, or pieces of the step as graphs of their own replayed on two streams -- hipGraphLaunch feeds a
         graph's kernels at about the rate a queue executes small dependent kernels (~5 us each), so neither ran the trunks
         concurrently, and every graph boundary cost 20-60 us of idle queue (7 graphs: ~0.15 ms per step)."""
         eng, st = self.eng, self.static
-        segs = eng.forward_segments(st['eps_q'], st['eps20'], st['drop_past'], st['drop_future'], streams=False)
+        eng.prepare_forward()                                       # host side, and the engine's own buffers: outside the capture
         torch.cuda.synchronize()
         # The loss values leave for the host in the MIDDLE of the graph (after the forward half): forward() returns them as Python floats
         # (model/STTODE.py:568), and reading them off the end of the queue (`.tolist()`) left the GPU idle for the whole host side of
@@ -1352,18 +1193,13 @@ class _GraphedStep:
                         st[k].bernoulli_(_DROP_KEEP).div_(_DROP_KEEP)
                     else:
                         st[k].normal_()
-                eng.run_segments(segs)
-                try:
-                    eng.run_segments(eng.backward_segments())
-                except BaseException:
-                    capi.call('sttode_twgrad_defer', -1, None, 0)
-                    raise
+                eng.enqueue_forward(st['eps_q'], st['eps20'], st['drop_past'], st['drop_future'])
+                eng.enqueue_backward()
         finally:
             eng.publish = None
             if gc_was_on:
                 gc.enable()
-        self.keep = (eng._hold, eng.V, eng.G, eng.main_scratch, eng.red_scratch)        # static buffers of the graph
-        eng._hold = []
+        self.keep = (eng.V, eng.G, eng.scratch, eng.red_scratch)        # static buffers of the graph
         self.out = (eng.V['losses'], eng.Gflat, {k: eng.G[k] for k in eng.touched})
 
     def run(self, inputs):
