@@ -492,6 +492,36 @@ int sttode_delta_workspace(int T, int n, long* floats);
 int sttode_delta_hyp(const float* dist, int T, int n, long dist_floats, int symmetric, float* ws, long ws_floats, float* delta, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Oversample and reduce: Lloyd k-means of M sampled futures per agent to K representatives.  Added WITHIN ABI version 14:
+ * one new export, nothing else changed, so a binding built for 14 keeps working.
+ * ------------------------------------------------------------------------------------------------ */
+/* pred [R,n,K_in,Tf,2] fp32, round-major: R stacked outputs [n,K_in,Tf,2] of inference.  Sample m = r K_in + k of agent a starts at
+ * (((r n + a) K_in + k) Tf) 2; M = R K_in; R = 1 is the familiar [n,M,Tf,2].  With x[m] agent a's sample m, a point of R^(2 Tf), and
+ * t0 = from_frame:
+ *     c_0 = init
+ *     for i = 1 .. iters:
+ *         label_i[m] = argmin_k sum_{t >= t0} |x[m,t] - c_{i-1}[k,t]|^2        (the lowest k on exact ties)
+ *         c_i[k]     = mean of x[m] over {m : label_i[m] = k}, ALL frames       (c_{i-1}[k] if that set is empty)
+ *     centroids [n,K,Tf,2] fp32 = c_iters, labels [n,M] int32 = label_iters, counts [n,K] int32: counts[k] = |{m : label_iters[m] = k}|
+ * from_frame = 0 clusters whole trajectories, from_frame = Tf - 1 endpoints; the representatives are full mean trajectories either way, and
+ * counts / M are their weights.  This is scipy.cluster.vq.kmeans2(x[:, sliced], init[:, sliced], iter=iters, minit='matrix') for the labels
+ * and the sliced code book, including the rule that an empty cluster keeps its centroid.
+ * init_mode 0 ('first'): the agent's samples 0 .. K-1 (i.i.d. draws: Forgy initialisation); 1 ('maximin'): sample 0, then K-1 times the
+ * sample whose squared distance (same frame slice) to its nearest chosen sample is largest, the lowest index on ties; 2: the caller's
+ * init [n,K,Tf,2].  init is non-NULL exactly in mode 2.
+ * Arithmetic: fp32 throughout; distances are direct sums of squared differences over the slice in coordinate order (never the expanded
+ * |x|^2 - 2 x.c + |c|^2 form); a cluster's members are added in sample order and the sum is divided by the count; no floating-point
+ * atomics.  Two runs give the same bits, and an agent's result depends on its own samples only (the same bits alone or inside any batch).
+ * The loop ends early once an iteration changes no label (further iterations would reproduce the same bits).  Non-finite inputs: outputs
+ * unspecified, labels still in [0, K), nothing read or written out of bounds.
+ * One workgroup per agent; the agent's samples are staged in LDS when they fit (about 4 (2 Tf) (M + 2 K) + 5 M bytes within 160 KiB: M = 1000
+ * at Tf = 12 does), otherwise every pass re-reads them from global memory / L2 with the same result.
+ * Limits, refused before anything is launched or written: n >= 1, 1 <= K <= 64, K <= M <= 4096, 1 <= Tf <= 200, 0 <= from_frame < Tf,
+ * 1 <= iters <= 1000, init_mode in {0, 1, 2}. */
+int sttode_reduce_samples(const float* pred, int n, int R, int K_in, int Tf, int K, int iters, int from_frame, int init_mode,
+                          const float* init, float* centroids, int* labels, int* counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Native forward pipeline: one call enqueues STTODENet.inference (model/STTODE.py:574-623) end to end.
  * ------------------------------------------------------------------------------------------------ */
 typedef struct SttodeModel SttodeModel;

@@ -90,6 +90,8 @@ SIGNATURES = {
     'sttode_delta_dist': [_P, _I, _I, _P, _I, _I, _P, _L, _P, _P],
     'sttode_delta_workspace': [_I, _I, ctypes.POINTER(ctypes.c_long)],
     'sttode_delta_hyp': [_P, _I, _I, _L, _I, _P, _L, _P, _P],
+    # oversample and reduce (csrc/reduce.hip; added within ABI version 14)
+    'sttode_reduce_samples': [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     # native pipeline (csrc/pipeline.hip)
     'sttode_model_create': [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), _I, _I, _I, _I, _I, _I],
     'sttode_model_destroy': [_P],

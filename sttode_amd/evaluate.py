@@ -8,6 +8,8 @@
   eval_scenes_report / eval_sampler_report / eval_nba_report: the same loops returning an EvalReport -- global ADE / FDE and miss rate,
                   per-scene (per NBA batch) ADE / FDE / miss count, the best sample of every agent (utils/metrics.py:29-48); on request
                   the scene-level metrics of DESIGN.md 4l: joint min ADE / FDE, collision rates, KDE NLL.
+  eval_scenes_reduced  oversample and reduce: `rounds` calls per scene batch, k-means of the rounds * sample_k futures of every
+                  agent to K representatives on the device, then the selection of eval_scenes_report on the representatives.
   embedding_delta  how tree-like the encoder's past features (or the observed tracks) of a dataset are: delta / diam of hyptorch/delta.py's
                    batched_delta_hyp over all agents.
 """
@@ -333,6 +335,56 @@ def eval_scenes_report(model, dataset, traj_scale=1.0, scenes_per_call=512, z_fn
     return _scenes_report(model, dataset, scenes_per_call, pipelined, traj_scale, miss_threshold, gather,
                           lambda sb: model.inference_async(z=latents(sb), metrics_gt=model._future, metrics_scale=traj_scale),
                           lambda sb: model.inference(None, z=latents(sb)), joint, kde, collision_radius)
+
+
+@torch.no_grad()
+def eval_scenes_reduced(model, dataset, rounds, K=None, iters=10, from_frame=0, init='first', traj_scale=1.0, scenes_per_call=512, z_fn=None,
+                        pipelined=True, miss_threshold=1.0):
+    """Oversample and reduce as an evaluation loop: per scene batch ``rounds`` inference calls -- M = rounds * sample_k futures
+    per agent -- reduced to ``K`` (default sample_k) representatives per agent by ``metrics.reduce_samples`` (``iters``, ``from_frame``,
+    ``init`` as there), and the best-of-K selection of eval_scenes_report on the representatives.  Returns an ``EvalReport``.
+    ``z_fn(rows)`` is asked once per round, in round order.  ``pipelined`` (default): the rounds go through ``inference_async``, never more
+    in flight than ``async_depth`` allows; each is waited for and copied into the round buffer before its slot is taken again.  The reduction
+    and the selection run on the caller's stream.  The two forms' samples differ by fp32 rounding (as inference_async and inference do), so
+    with rounds > 1 a near-tied label may legitimately differ between them."""
+    from . import metrics
+    rounds = int(rounds)
+    if rounds < 1:
+        raise ValueError(f'eval_scenes_reduced needs rounds >= 1, got {rounds}')
+    Ks, zd = model.args.sample_k, model.args.zdim
+    K = Ks if K is None else int(K)
+    acc = _ReportAcc(miss_threshold, K=K)
+    depth = max(2, min(8, int(model.async_depth)))
+    for s0 in range(0, len(dataset), scenes_per_call):
+        sb = dataset.scene_batch(range(s0, min(s0 + scenes_per_call, len(dataset))))
+        model.set_scene_batch(sb.past, sb.future, sb.scene_ptr)
+        rows = sb.n_agents * Ks
+        buf = model._round_buffer(rounds, sb.n_agents)
+        if pipelined:
+            new = sum((sb.n_agents, model._S, s) not in model._async_bufs for s in range(depth))
+            if len(model._async_bufs) + new > 16:                         # batches of ever new sizes: per-shape slot buffers are dropped in time
+                model.reset_async()                                       # (nothing is in flight between batches)
+            pend = []
+
+            def finish(item):
+                r, h = item
+                buf[r].copy_(model.wait(h).permute(1, 0, 2, 3))             # [n, sample_k, Tf, 2], on the caller's stream: in front of the slot's next call
+            for r in range(rounds):
+                if len(pend) >= depth - 1:
+                    finish(pend.pop(0))
+                z = z_fn(rows) if z_fn is not None else torch.randn(rows, zd, device=model.device)
+                pend.append((r, model.inference_async(z=z)))
+            while pend:
+                finish(pend.pop(0))
+        else:
+            for r in range(rounds):
+                z = z_fn(rows) if z_fn is not None else torch.randn(rows, zd, device=model.device)
+                buf[r].copy_(model.inference(None, z=z).permute(1, 0, 2, 3))
+        red = metrics.reduce_samples(buf, K, iters=iters, from_frame=from_frame, init=init)
+        acc.add(model.select_best_of_k(red.centroids, scale=traj_scale, miss_threshold=miss_threshold, seg_ptr=model._scene_ptr), sb.scene_ptr)
+    if pipelined:
+        model.reset_async()
+    return acc.report(False)
 
 
 @torch.no_grad()

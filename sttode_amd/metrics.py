@@ -2,7 +2,8 @@
 sttode_best_of_k_select).
 
 ``joint_select`` and ``kde_nll`` (csrc/metrics.hip) are the scene-level metrics the reference does not compute: joint min ADE / FDE
-and collision counts per segment, and the KDE NLL per agent.
+and collision counts per segment, and the KDE NLL per agent.  ``reduce_samples`` (csrc/reduce.hip) clusters M sampled futures
+per agent to K representatives.
 
 ``select`` is the kernel call: per agent the min-over-K ADE / FDE, the index of the best sample by ADE and by final displacement
 (``get_best_idx``), the miss flag (``count_miss_samples``) and optionally the best trajectory; per CSR segment (a scene, an NBA batch) the
@@ -178,6 +179,66 @@ def kde_nll(pred_nk, gt, scale=1.0):
     out = torch.empty(n, dtype=torch.float64, device=pred_nk.device)
     with torch.cuda.device(pred_nk.device):
         capi.call('sttode_kde_nll', pred_nk, gt, n, K, Tf, float(scale), out, capi.stream_ptr())
+    return out
+
+
+# ----- oversample and reduce (csrc/reduce.hip: sttode_reduce_samples) ------------------------------------------------------
+
+class Reduction:
+    """Outputs of one reduction (device tensors): ``centroids`` [n, K, Tf, 2] float32 (full mean trajectories), ``labels`` [n, M] int32 (the
+    cluster of every sample), ``counts`` [n, K] int32 (cluster sizes) and ``weights`` [n, K] float32 = counts / M."""
+    __slots__ = ('centroids', 'labels', 'counts', 'M', '_weights')
+
+    def __init__(self, n, M, K, Tf, device):
+        self.centroids = torch.empty(n, K, Tf, 2, dtype=torch.float32, device=device)
+        i = torch.empty(n * M + n * K, dtype=torch.int32, device=device)
+        self.labels, self.counts = i[:n * M].view(n, M), i[n * M:].view(n, K)
+        self.M = M
+        self._weights = None
+
+    @property
+    def weights(self):
+        if self._weights is None:
+            self._weights = self.counts.to(torch.float32) / float(self.M)
+        return self._weights
+
+
+REDUCE_INIT = {'first': 0, 'maximin': 1}
+
+
+@torch.no_grad()
+def reduce_samples(pred, K, iters=10, from_frame=0, init='first'):
+    """Lloyd k-means of every agent's M sampled futures to K representatives, on the current stream (include/sttode_hip.h
+    sttode_reduce_samples states the iteration).  ``pred``: [n, M, Tf, 2], or [R, n, K_in, Tf, 2] -- R stacked outputs of inference,
+    M = R K_in, sample m = r K_in + k.  ``from_frame``: the first frame the distances look at (0: whole trajectories; -1: endpoints; negative
+    values count from the end); the representatives are full mean trajectories either way.  ``init``: 'first' (samples 0 .. K-1), 'maximin'
+    (farthest-point, deterministic) or a tensor [n, K, Tf, 2].  K <= 64, K <= M <= 4096.  Returns a ``Reduction``."""
+    if not (isinstance(pred, torch.Tensor) and pred.is_cuda):
+        raise capi.SttodeError('sample reduction runs on a HIP device only (no CPU fallback): pass device tensors')
+    if pred.dim() == 4:
+        pred = pred.unsqueeze(0)
+    if pred.dim() != 5 or pred.shape[4] != 2 or 0 in pred.shape:
+        raise ValueError(f'pred must be [n, M, Tf, 2] or [R, n, K_in, Tf, 2] with no empty dimension, got {tuple(pred.shape)}')
+    dev = pred.device
+    pred = pred.to(torch.float32).contiguous()
+    R, n, K_in, Tf = pred.shape[:4]
+    K, iters, from_frame = int(K), int(iters), int(from_frame)
+    if not -Tf <= from_frame < Tf:
+        raise ValueError(f'from_frame must be in [-{Tf}, {Tf}), got {from_frame}')
+    if isinstance(init, str):
+        if init not in REDUCE_INIT:
+            raise ValueError(f"init must be 'first', 'maximin' or a tensor [n, K, Tf, 2], got {init!r}")
+        mode, init_t = REDUCE_INIT[init], None
+    else:
+        mode, init_t = 2, torch.as_tensor(init, dtype=torch.float32).to(dev).contiguous()
+        if tuple(init_t.shape) != (n, K, Tf, 2):
+            raise ValueError(f'init must be [{n}, {K}, {Tf}, 2], got {tuple(init_t.shape)}')
+    if not 1 <= K <= 64 or not K <= R * K_in <= 4096:
+        raise ValueError(f'sample reduction needs 1 <= K <= 64 and K <= M <= 4096, got K = {K}, M = {R * K_in}')
+    out = Reduction(n, R * K_in, K, Tf, dev)
+    with torch.cuda.device(dev):
+        capi.call('sttode_reduce_samples', pred, n, R, K_in, Tf, K, iters, from_frame % Tf, mode, init_t, out.centroids, out.labels,
+                  out.counts, capi.stream_ptr())
     return out
 
 

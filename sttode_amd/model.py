@@ -779,6 +779,42 @@ class STTODENet(nn.Module):
         self.diverse_pred = pred
         return pred.permute(1, 0, 2, 3)
 
+    def _round_buffer(self, rounds, n):
+        """[rounds, n, sample_k, Tf, 2] on the device: the stacked outputs of `rounds` inference calls, one buffer per shape."""
+        bufs = self.__dict__.setdefault('_reduce_bufs', {})
+        key = (int(rounds), int(n), self.args.sample_k, self.args.future_length)
+        if key not in bufs:
+            if len(bufs) > 8:
+                bufs.clear()
+            bufs[key] = torch.empty(*key, 2, dtype=torch.float32, device=self.device)
+        return bufs[key]
+
+    @torch.no_grad()
+    def inference_reduced(self, rounds, K=None, iters=10, from_frame=0, init='first', z=None):
+        """Oversample and reduce: ``rounds`` inference() calls on the data that set_data / set_scene_batch / set_data_nba
+        set -- M = rounds * sample_k futures per agent -- clustered to ``K`` (default sample_k) representatives per agent by
+        ``metrics.reduce_samples`` (``iters``, ``from_frame``, ``init`` as there).  ``z``: None or [rounds, n * sample_k, zdim], one slice per
+        call.  Sets ``diverse_pred`` to the centroids [n, K, Tf, 2] and ``reduction`` to the ``metrics.Reduction`` (labels, counts, weights);
+        returns the [K, n, Tf, 2] permuted view, like inference()."""
+        from . import metrics
+        self._require_gpu()
+        rounds = int(rounds)
+        if rounds < 1:
+            raise ValueError(f'inference_reduced needs rounds >= 1, got {rounds}')
+        if self._mode is None:
+            raise capi.SttodeError('call set_data / set_data_nba / set_scene_batch before inference_reduced()')
+        if z is not None and (getattr(z, 'ndim', 0) != 3 or z.shape[0] != rounds):
+            raise ValueError(f'z must be [rounds = {rounds}, n * sample_k, zdim], got {tuple(getattr(z, "shape", ()))}')
+        K = self.args.sample_k if K is None else int(K)
+        buf = self._round_buffer(rounds, self._past.shape[0])
+        for r in range(rounds):
+            self.inference(None, z=None if z is None else z[r])
+            buf[r].copy_(self.diverse_pred)
+        red = metrics.reduce_samples(buf, K, iters=iters, from_frame=from_frame, init=init)
+        self.__dict__['reduction'] = red
+        self.diverse_pred = red.centroids
+        return red.centroids.permute(1, 0, 2, 3)
+
     @torch.no_grad()
     def inference_nba_sharded(self, data_local, z=None, gather=None):
         """NBA path with ONE attention group spanning ranks (SURVEY.md §8e, config 5 read literally): this rank holds
