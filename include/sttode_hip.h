@@ -76,6 +76,25 @@ int sttode_mhgsa_attn(const float* R, const float* C, const float* V, float* out
 int sttode_mhgsa_attn_groups(const float* R, const float* C, const float* V, float* out, int groups, long gs_r, long gs_c, long gs_v, long gs_o,
                              int rows, int cols, int Nb, long rs_seq, long rs_b, long cs_seq, long cs_b, long vs_seq, long vs_b, long os_seq,
                              long os_b, float rscale, float cscale, int head_dim, void* stream);
+/* Attention core with a running maximum (csrc/attention.hip; added within ABI version 14): operands and strides as sttode_mhgsa_attn,
+ * 8 heads x 8 dims.  mode 0: the geodesic scores above (hyptransformerlib.py:251-300); mode 1: dot-product scores
+ * s_ij = <rscale R_i, cscale C_j>, no normalisation, no clamp (transformerlib.py:251-282: R = q, rscale = hd^-0.5).  mask: NULL, or an fp32
+ * [rows, cols] additive mask with row stride ld_mask >= cols floats, shared by every slot and head: mask[i * ld_mask + j] is added to score
+ * (row i, column j) before the softmax (hyptransformerlib.py:290-292, transformerlib.py:276-279); -inf and +inf entries are allowed, NaN
+ * entries are unspecified.  A row that is -inf over all columns yields a NaN output row and NaN weights (torch's softmax does); other
+ * rows of the call are unaffected.  wmax / wsum [Nb,8,rows] (both or neither): the softmax's per-(slot, head, row) maximum and sum of
+ * exp(s - max); wout [Nb,rows,cols] (head-averaged weights) needs them.  Deterministic bit for bit; no host synchronisation and no
+ * allocation (safe under stream capture). */
+int sttode_attn_core(const float* R, const float* C, const float* V, const float* mask, long ld_mask, float* out, float* wmax, float* wsum,
+                     float* wout, int rows, int cols, int Nb, long rs_seq, long rs_b, long cs_seq, long cs_b, long vs_seq, long vs_b,
+                     long os_seq, long os_b, float rscale, float cscale, int mode, void* stream);
+/* Backward of sttode_attn_core: dO laid out like `out` (strides os_*) -> dR, dC, dV in the layouts of R, C, V (overwritten, not
+ * accumulated).  Mode 0: through the clamp (torch.clamp, bounds inclusive), both normalisations and both scales; mode 1: through both
+ * scales.  Positions masked with -inf have probability 0 and contribute nothing; the mask gets no gradient.  One workgroup per
+ * (slot, head), deterministic; rows (2 head_dim + 3) + cols 2 head_dim floats of LDS must fit 64 KiB (rows = cols <= 468). */
+int sttode_attn_core_bwd(const float* R, const float* C, const float* V, const float* mask, long ld_mask, const float* dO, float* dR,
+                         float* dC, float* dV, int rows, int cols, int Nb, long rs_seq, long rs_b, long cs_seq, long cs_b, long vs_seq,
+                         long vs_b, long os_seq, long os_b, float rscale, float cscale, int mode, void* stream);
 
 /* out_proj (hyptransformerlib.py:305) -> Hypattention gate tanh(info)*sigmoid(gate) (hypertransformer.py:81-83)
  * -> TransformerEncoderLayer post-LN + FFN (hypertransformer.py:148-152) -> ODEG_Encoder: one explicit Euler step of

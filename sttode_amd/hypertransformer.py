@@ -11,6 +11,11 @@ file the model never instantiates -- the decoder-side stack with cross-attention
 
 d_model = 64, nhead = 8 (the kernels' build); dropout must be 0 (the only value the repo passes); attention / padding masks
 and ``seq_mask`` are accepted and ignored exactly as Hypattention.forward ignores them (:69-72 builds a mask nobody reads).
+(The stand-alone attention modules that DO apply ``attn_mask`` are in attention.py.)
+
+``euclidean=True`` (keyword-only, on Hypattention and the two layers) swaps the attention core for dot-product attention (ops.mha, the
+transformerlib.MultiheadAttention computation with the same parameters): the geodesic-versus-Euclidean ablation on the device.  Rows then
+follow the queries for every L, S; gate, FFN, LayerNorms and the ODEG stacks are unchanged.  The default is today's code bit for bit.
 
 By default every forward computes values only: outputs carry no graph, whatever grad mode says.  ``trainable(module)`` switches
 autograd on for every drop-in inside ``module`` (the flag survives ``copy.deepcopy``, so ODEG / ODEG_Encoder clones keep it).  A graph is
@@ -26,7 +31,8 @@ from torch import nn
 from torch.autograd.function import once_differentiable
 
 from . import capi
-from .ops import linear_bwd, linear_cols, mhgsa, scratch
+from .attention import Hyp_mhsa, MultiheadAttention
+from .ops import linear_bwd, linear_cols, mha, mhgsa, scratch
 from .model import _HypMHSA
 
 
@@ -100,11 +106,12 @@ class _Gate(torch.autograd.Function):
 
 
 class Hypattention(nn.Module):
-    def __init__(self, d_model, nhead, dropout=0., motion_only=True, cross_range=0, num_conv_layer=3):
+    def __init__(self, d_model, nhead, dropout=0., motion_only=True, cross_range=0, num_conv_layer=3, *, euclidean=False):
         super().__init__()
         if d_model != 64 or nhead != 8 or dropout != 0.:
             raise NotImplementedError('HIP attention is built for d_model=64, nhead=8, dropout=0')
         self.model_dim = d_model
+        self.euclidean = bool(euclidean)          # the attention core is ops.mha (dot product, rows = queries) instead of ops.mhgsa
         self.temporal_attention_before = _HypMHSA(d_model, nhead)
         self.temporal_info = nn.Linear(d_model, d_model)
         self.temporal_gate = nn.Linear(d_model, d_model)
@@ -123,8 +130,9 @@ class Hypattention(nn.Module):
             q3 = query.reshape(Lq, A * Sn, D)
             k3 = q3 if key is query else key.reshape(Lk, A * Sn, D)
             v3 = k3 if value is key else (q3 if value is query else value.reshape(Lk, A * Sn, D))
-            out, w = mhgsa(q3, k3, v3, m.in_proj_weight, m.in_proj_bias, m.out_proj.weight, m.out_proj.bias, need_weights=True,
-                           differentiable=grad)
+            op = mha if getattr(self, 'euclidean', False) else mhgsa
+            out, w = op(q3, k3, v3, m.in_proj_weight, m.in_proj_bias, m.out_proj.weight, m.out_proj.bias, need_weights=True,
+                        differentiable=grad)
             o2 = out.reshape(out.shape[0] * out.shape[1], D)
             if grad:
                 ti, tg = self.temporal_info, self.temporal_gate
@@ -132,7 +140,7 @@ class Hypattention(nn.Module):
             else:
                 g = _gate_fwd(o2, self.temporal_info, self.temporal_gate)[0]
             # NB with L == S the reference's untransposed scores make the output rows follow the KEYS (hyptransformerlib.py:261-265);
-            # mhgsa returns [rows, A*Sn, D] accordingly and rows == Lq in every case
+            # mhgsa returns [rows, A*Sn, D] accordingly and rows == Lq in every case (mha: rows follow the queries, always)
             return g.view(out.shape[0], A, Sn, D), w
 
 
@@ -168,11 +176,11 @@ def _graph(mod, *inputs):
 
 
 class TransformerEncoderLayer(nn.Module):
-    def __init__(self, d_model, nhead, dim_feedforward=2048, dropout=0., activation='relu'):
+    def __init__(self, d_model, nhead, dim_feedforward=2048, dropout=0., activation='relu', *, euclidean=False):
         super().__init__()
         if activation != 'relu' or dim_feedforward % 16:
             raise NotImplementedError('relu FFN with a hidden width that is a multiple of 16')
-        self.self_attn = Hypattention(d_model, nhead, dropout=dropout)
+        self.self_attn = Hypattention(d_model, nhead, dropout=dropout, euclidean=euclidean)
         self.linear1, self.linear2 = nn.Linear(d_model, dim_feedforward), nn.Linear(dim_feedforward, d_model)
         self.norm1, self.norm2 = nn.LayerNorm(d_model), nn.LayerNorm(d_model)
         self._trainable = False
@@ -185,12 +193,12 @@ class TransformerEncoderLayer(nn.Module):
 
 
 class TransformerDecoderLayer(nn.Module):
-    def __init__(self, d_model, nhead, dim_feedforward=2048, dropout=0., activation='relu', cross_motion_only=False):
+    def __init__(self, d_model, nhead, dim_feedforward=2048, dropout=0., activation='relu', cross_motion_only=False, *, euclidean=False):
         super().__init__()
         if activation != 'relu' or dim_feedforward % 16:
             raise NotImplementedError('relu FFN with a hidden width that is a multiple of 16')
-        self.self_attn = Hypattention(d_model, nhead, dropout=dropout)
-        self.cross_attn = Hypattention(d_model, nhead, dropout=dropout)
+        self.self_attn = Hypattention(d_model, nhead, dropout=dropout, euclidean=euclidean)
+        self.cross_attn = Hypattention(d_model, nhead, dropout=dropout, euclidean=euclidean)
         self.linear1, self.linear2 = nn.Linear(d_model, dim_feedforward), nn.Linear(dim_feedforward, d_model)
         self.norm1, self.norm2, self.norm3 = nn.LayerNorm(d_model), nn.LayerNorm(d_model), nn.LayerNorm(d_model)
         self.cross_motion_only = cross_motion_only
@@ -362,7 +370,7 @@ class ODEG_Encoder(nn.Module):
             return _relu_(ode_integrate(self._rhs, src, self.time, self.method, self.steps, grad=grad), grad)
 
 
-_DROPINS = (Hypattention, TransformerEncoderLayer, TransformerDecoderLayer, ODEG, ODEG_Encoder)
+_DROPINS = (Hypattention, TransformerEncoderLayer, TransformerDecoderLayer, ODEG, ODEG_Encoder, Hyp_mhsa, MultiheadAttention)
 
 
 def trainable(module, on=True):
