@@ -238,7 +238,7 @@ int sttode_sampler_loss_bwd(const float* mu, const float* logvar, const float* p
                             float* dlogvar, float* dmotion, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Training step (csrc/train.hip): forward-with-tape + backward of STTODENet.forward() (model/STTODE.py:553-568; losses
+ * Training step (csrc/train*.hip, one file per kernel family: index in train.hip): forward-with-tape + backward of STTODENet.forward() (model/STTODE.py:553-568; losses
  * :372-395; what train.py:81-87 drives through total_loss.backward()).  Generic kernels over row-major nn.Parameter storage;
  * gradients are ACCUMULATED into the caller's .grad buffers.  All matrices row-major with explicit leading dimensions.
  * ------------------------------------------------------------------------------------------------ */

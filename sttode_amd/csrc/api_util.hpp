@@ -79,7 +79,6 @@ struct LagGroups {
 };
 int stt_chain_lagged(const float* const* W, const LagRoles& r, const LagGroups& g, int K, int Tp, int Tf, int prog_len, int b3, void* stream);
 bool stt_chain_lagged_covers(int Tp);
-int stt_trunk_group(int on);   // train_trunk.hip: the trunk-forward half of sttode_tgemm_group (train.hip)
 // chain32.hip: the stage-2 sampler's Q-net (struct SttodeSamplerPlan of include/sttode_hip.h).  stt_sampler_plan_check: nullptr if the
 // plan can be streamed for K samples per agent, else why not; stt_sampler_qnet: pf [n][128] -> z [n K][32] on `stream` (plan checked).
 struct SttodeSamplerPlan;

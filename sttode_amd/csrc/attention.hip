@@ -194,7 +194,7 @@ __global__ __launch_bounds__(256) void attn_core_weights_kernel(const float* __r
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Backward, on the plan of train.hip's attn_rc_bwd_kernel: one workgroup per (slot, head) owns all rows and columns, operands in LDS, no
+// Backward, on the plan of train_attn.hip's attn_rc_bwd_kernel: one workgroup per (slot, head) owns all rows and columns, operands in LDS, no
 // atomics, fixed summation order; the outputs are overwritten.  rho = rscale R[r], gam = cscale C[c];
 //   P = softmax_c(s + mask), dP = dO[r] . V[c], dS = P (dP - sum_c' P dP), dV[c] = sum_r P dO[r];
 //   mode 1: s = rho . gam,               dR[r] = rscale sum_c dS gam_c,  dC[c] = cscale sum_r dS rho_r

@@ -12,6 +12,7 @@
 #include "chain.hpp"
 #include "ode_body.hpp"
 #include "api_util.hpp"
+#include "train_group.hpp"
 #include "../../include/sttode_hip.h"
 
 struct TrunkArgs {
@@ -312,7 +313,7 @@ __global__ __launch_bounds__(256) void ttrunk_fwd2_kernel(TrunkArgs a0, TrunkArg
 }
 
 // group mode (sttode_tgemm_group -> stt_trunk_group): a trunk launch waits for a second one of the same group
-static thread_local struct { TrunkArgs a; size_t lds; void* stream; bool have, on; } g_tq = {};   // (per host thread, like the group state of train.hip)
+static thread_local struct { TrunkArgs a; size_t lds; void* stream; bool have, on; } g_tq = {};   // (per host thread, like the group state of train_gemm.hip)
 static std::mutex g_tq_mu;
 static void tq_flush_locked() {
     if (!g_tq.have) return;

@@ -3,7 +3,7 @@
 
 The fused forms of csrc/ (chain launch, lagged roles, one-launch scene form, packed fragment streams) are built for the reference's DEFAULT
 widths -- hidden_dim 64, zdim 32, two decompose blocks, 2 Tp <= 32, 2 Tf <= 96 -- because their register / LDS budgets are tuned to those
-tiles.  A model constructed with anything else takes this form instead: the same HIP kernels the training step runs (csrc/train.hip:
+tiles.  A model constructed with anything else takes this form instead: the same HIP kernels the training step runs (csrc/train*.hip:
 sttode_tlinear MFMA GEMMs over the row-major nn.Parameter storage, conv / GRU-sequence / LayerNorm / geodesic-attention kernels templated
 on the model width), layer by layer, driven by sttode_amd.training.Engine.  Results are held to the imported reference at the same 1e-4
 (tests/golden/dims.npz); PERFORMANCE CAVEAT: one launch per layer and activations through HBM -- roughly the training forward's rate, far

@@ -662,7 +662,7 @@ class STTODENet(nn.Module):
 
     def forward(self, eps_q=None, eps_p=None, eps20=None, drop_past=None, drop_future=None):
         """Training objective (model/STTODE.py:553-568, losses :372-395): (total_loss, loss_pred, loss_recover, loss_kl,
-        loss_diverse).  With autograd enabled (the train.py case) the step runs on the training kernels of csrc/train.hip and
+        loss_diverse).  With autograd enabled (the train.py case) the step runs on the training kernels of csrc/train*.hip and
         ``total_loss.backward()`` fills ``.grad`` of every parameter (sttode_amd/training.py); under ``torch.no_grad()`` the
         same values come from the fused inference kernels.  ``eps_*`` / ``drop_*`` inject the noises / dropout masks the
         reference draws from torch's generator (Normal.rsample, nn.Dropout(0.1) of the positional encoders)."""

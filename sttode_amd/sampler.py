@@ -51,7 +51,7 @@ class Sampler(nn.Module):
 
     def forward(self, net, mean=True, need_weights=False, eps=None):
         """With autograd enabled (trainsampler.py:134-150,171-185) the outputs carry a graph to the sampler's parameters (backward
-        on csrc/train.hip + csrc/sampler.hip kernels, see ``_SamplerFn``); otherwise plain values.  See ``_forward_values``."""
+        on csrc/train*.hip + csrc/sampler.hip kernels, see ``_SamplerFn``); otherwise plain values.  See ``_forward_values``."""
         if self.device.type != 'cuda':
             raise capi.SttodeError('Sampler runs only on a HIP device (no CPU fallback): call set_device(cuda) first')
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):

@@ -6,7 +6,7 @@ format (train.py:208-213), without the argparse / dataset-path plumbing.
     for epoch in range(args.num_epochs):
         train_epoch(args, epoch, model, optimizer, scheduler, loader)
 
-``model.forward()`` runs forward + (lazily, inside ``total_loss.backward()``) backward on csrc/train.hip kernels; the
+``model.forward()`` runs forward + (lazily, inside ``total_loss.backward()``) backward on csrc/train*.hip kernels; the
 optimizer is torch's (element-wise parameter update on device tensors).
 """
 import torch
@@ -46,7 +46,7 @@ def train_epoch(args, epoch, model, optimizer, scheduler, train_loader, log=prin
 
 def train_sampler_epoch(args, epoch, model, sampler, optimizer, scheduler, train_loader, div_cfg, log=print, max_iters=None):
     """One epoch of stage 2, trainsampler.py:124-194: the prediction model stays frozen, ``optimizer`` steps the sampler's parameters
-    (trainsampler.py:283) on compute_sampler_loss (samplerloss.py:41-73) through Sampler.forward's autograd path (csrc/train.hip +
+    (trainsampler.py:283) on compute_sampler_loss (samplerloss.py:41-73) through Sampler.forward's autograd path (csrc/train*.hip +
     csrc/sampler.hip).  NBA: loader yields seq_collate dicts; otherwise the per-scene tuples of TrajectoryDataset / SDD_Dataset wrapped by
     DataLoader(batch_size=1).  Returns the list of total losses."""
     from . import samplerloss

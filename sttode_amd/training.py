@@ -4,7 +4,7 @@ Reference: model/STTODE.py:553-568 (objective), :372-395 (losses), :214-236 / :2
 (decoder), hypertransformer.py:134-153 + hyptransformerlib.py:191-300 (encoder layer / geodesic attention),
 ode_demo.py:188,228 (one Euler step of size 12 + relu); what ``train.py:81-87`` drives through ``total_loss.backward()``.
 
-Every network evaluation, loss and gradient runs in ``csrc/train.hip`` kernels (generic MFMA linear / weight-gradient
+Every network evaluation, loss and gradient runs in ``csrc/train*.hip`` kernels (generic MFMA linear / weight-gradient
 kernels over the row-major nn.Parameter storage, plus the element-wise pieces).  PyTorch only allocates buffers and, via
 one ``autograd.Function``, hands the finished gradients to ``.grad`` so that ``optimizer.step()`` works unchanged.
 There is no eager / CPU fallback.
@@ -40,7 +40,7 @@ class _OdeStageBwd(ctypes.Structure):                # include/sttode_hip.h Stto
                [(k, ctypes.c_void_p) for k in ('attn', 'ao', 'h', 'f1', 'dsum2', 'df1', 'du', 'dv', 'dao', 'dattn', 'ln')] + [('n', ctypes.c_int)]
 
 
-class _GatherItem(ctypes.Structure):                 # csrc/train.hip GatherItem (include/sttode_hip.h sttode_live_rows_gather)
+class _GatherItem(ctypes.Structure):                 # csrc/train_ewise.hip GatherItem (include/sttode_hip.h sttode_live_rows_gather)
     _fields_ = [('src', ctypes.c_void_p), ('dst', ctypes.c_void_p), ('src_plane', ctypes.c_long),
                 ('dst_plane', ctypes.c_long), ('row', ctypes.c_int), ('outer', ctypes.c_int)]
 
@@ -54,7 +54,7 @@ _ATT = 'ODE_Encoder.odeblock.odefunc.layers.0.'
 # the first block's conv + GRU once per agent.  False -- per trajectory column -- is a test reference only (the same test); part of the graph key
 _AGENT_GRU = True
 _SCRATCH_BATCH = 32 << 20     # floats (128 MB): split sums of one backward pass at batch sizes (more than 2048 GEMM columns)
-_TGEMM_MIN_COLS_BWD = 600     # == TGEMM_MIN_COLS_BWD of csrc/train.hip: backward products above it take the LDS-tiled GEMM (split sums)
+_TGEMM_MIN_COLS_BWD = 600     # == TGEMM_MIN_COLS_BWD of csrc/train_gemm.hip: backward products above it take the LDS-tiled GEMM (split sums)
 # non-default encoder integrators: cap of the per-stage activation and gradient columns the deferred weight-gradient pass holds at once
 _ODE_DW_CAP = int(os.environ.get('STTODE_ODE_DW_CAP_MB', '256')) << 20      # bytes
 
@@ -871,7 +871,7 @@ class Engine:
         the prior samples per agent; the decoder treats trajectory columns independently (conv, GRU and MLPs per column,
         model/STTODE.py:50-77), so the backward pass of the other 19 columns is exactly zero in every layer and contributes nothing to
         any parameter gradient.  The reference's autograd multiplies through those zeros; here the tape rows of the two live columns per
-        agent are gathered (ONE launch, csrc/train.hip live_rows_gather_kernel) and the backward pass runs over 2 n columns instead of
+        agent are gathered (ONE launch, csrc/train_ewise.hip live_rows_gather_kernel) and the backward pass runs over 2 n columns instead of
         21 n -- the same gradient (the reference's own backward() digests: tests/test_gpu_parity.py::test_training_step_vs_reference_*)."""
         n, K1, m2 = d['n'], d['K'], 2 * d['n']
         items, blocks = [], []

@@ -1,4 +1,4 @@
-"""Direct float64 tests of the training-step entry points of csrc/train.hip, called through capi.call at the shapes, strides and size
+"""Direct float64 tests of the training-step entry points of csrc/train*.hip, called through capi.call at the shapes, strides and size
 thresholds where their code paths change, plus the Adam drop-in against torch.optim.Adam.
 
 Yardstick (tests/train_ref.py): |hip - f64| <= max(4 |torch_fp32 - f64|, atol + rtol |f64|) per element, with f64 the same operation in
@@ -336,7 +336,7 @@ def test_layernorm_backward_is_deterministic_and_refusals_write_nothing():
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # sttode_tlinear_tab: every form tlinear_impl can reach, with a per-group table as the accumulate source
 # ---------------------------------------------------------------------------------------------------------------------------------------
-TGEMM_MIN_COLS, TLIN_MEDIUM_BELOW = 2048, 4096
+TGEMM_MIN_COLS, TGEMM_MIN_COLS_BWD, TLIN_MEDIUM_BELOW = 2048, 600, 4096
 
 
 def _tlin_form(cols, I):
@@ -512,6 +512,127 @@ def test_train_ewise_grouped_is_bitwise_the_same_and_bad_op_is_refused():
             capi.call('sttode_train_ewise', op, buf, buf, buf, buf, buf, 300, 0, 1.0, st)
     torch.cuda.synchronize()
     assert (buf == SENT).all()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# group mode across its queues (LDS-tiled products, scene-size products, element-wise pieces, deferred split sums) and its error paths
+# ---------------------------------------------------------------------------------------------------------------------------------------
+GROUP_MULTI_MAX = 4                      # TG_MULTI_MAX == TS_MULTI_MAX == EW_MULTI_MAX
+BIG = (TGEMM_MIN_COLS + 1, 16, 16)       # cols, J, I: the first column count on the LDS-tiled forward kernel
+SMALL = (17, 33, 20)                     # a scene-size product (latency mode)
+RS_ROWS, RS_ZD = 8, 12                   # the reparameterisation (op 5): count 96
+BWD = (TGEMM_MIN_COLS_BWD + 1, 8, 8)     # cols, N, K: the first column count whose backward products are LDS-tiled (split sums: S = 5)
+
+
+def _group_inputs(dev, rng, reps):
+    t = lambda *s: torch.from_numpy(rng.standard_normal(s).astype(np.float32)).to(dev)
+    cols, N, K = BWD
+    return dict(big=[(t(BIG[0], BIG[1]), t(BIG[2], BIG[1]), t(BIG[2])) for _ in range(reps)],
+                small=[(t(SMALL[0], SMALL[1]), t(SMALL[2], SMALL[1]), t(SMALL[2])) for _ in range(reps)],
+                ew=[(t(RS_ROWS, 2 * RS_ZD), t(RS_ROWS, RS_ZD)) for _ in range(reps)],
+                bwd=(t(cols, N), t(N, K), t(cols, K)))
+
+
+def _sent(dev, rows, width):
+    """A sentinel-filled output of `width` logical columns in rows of width + 4 floats."""
+    return torch.full((rows, width + 4), SENT, device=dev)
+
+
+def _group_issue(capi, dev, st, inp, with_bwd=True):
+    """Issues the calls of ``inp`` in turn (one of each kind, then the next of each) and returns {label: (output buffer, logical width)}."""
+    outs = {}
+    for i, ((Xb, Wb, bb), (Xs, Ws, bs), (prm, eps)) in enumerate(zip(inp['big'], inp['small'], inp['ew'])):
+        for tag, (cols, J, I), X, W, b in (('big', BIG, Xb, Wb, bb), ('small', SMALL, Xs, Ws, bs)):
+            Y = _sent(dev, cols, I)
+            capi.call('sttode_tlinear', X, J, 1, W, J, 0, b, None, 0, Y, Y.stride(0), cols, J, I, 2, 0, st)
+            outs[f'{tag} {i}'] = (Y, I)
+        z = _sent(dev, 1, RS_ROWS * RS_ZD)
+        capi.call('sttode_train_ewise', R.EW_OPS['RSAMPLE'], z, prm, eps, None, None, RS_ROWS * RS_ZD, RS_ZD, 0.0, st)
+        outs[f'ew {i}'] = (z, RS_ROWS * RS_ZD)
+    if with_bwd:
+        cols, N, K = BWD
+        dY, W, X = inp['bwd']
+        dX, dW, db = _sent(dev, cols, K), _sent(dev, N, K), _sent(dev, 1, N)
+        scratch = torch.zeros(64 * N * (K + 1), device=dev)
+        capi.call('sttode_tlinear_bwd', dY, N, W, K, None, 0, dX, dX.stride(0), K, 0, X, K, 1, dW, dW.stride(0), db, cols, N, K,
+                  scratch, scratch.numel(), st)
+        outs.update({'bwd dX': (dX, K), 'bwd dW': (dW, K), 'bwd db': (db, N)})
+        outs['_scratch'] = (scratch, scratch.numel())          # (kept alive until the launches have run)
+    return outs
+
+
+def test_one_group_across_every_queue_is_bitwise_the_ungrouped_calls():
+    """Five LDS-tiled forward products, five scene-size products, five element-wise pieces (one more than each queue holds: every queue
+    takes its overflow flush) and one LDS-tiled layer backward (a weight gradient with split sums) in ONE group on one stream: every
+    output equals the same call made outside a group bit for bit, and nothing beyond an output's logical width is written."""
+    capi, dev = _capi(), _gpu()
+    st = capi.stream_ptr()
+    inp = _group_inputs(dev, np.random.default_rng(23), GROUP_MULTI_MAX + 1)
+    plain = _group_issue(capi, dev, st, inp)
+    torch.cuda.synchronize()
+    capi.call('sttode_tgemm_group', 1)
+    try:
+        grouped = _group_issue(capi, dev, st, inp)
+    finally:
+        capi.call('sttode_tgemm_group', 0)
+    torch.cuda.synchronize()
+    assert len(plain) == 3 * (GROUP_MULTI_MAX + 1) + 4
+    for label, (p, width) in plain.items():
+        if label.startswith('_'):
+            continue
+        g = grouped[label][0]
+        assert not (p[:, :width] == SENT).any(), f'{label}: the ungrouped call left part of its output unwritten'
+        assert torch.equal(p[:, :width], g[:, :width]), f'{label}: the grouped call differs from the ungrouped one'
+        assert (p[:, width:] == SENT).all() and (g[:, width:] == SENT).all(), f'{label}: written beyond its logical width'
+
+
+def test_group_and_deferred_reduction_error_paths_forget_what_is_queued():
+    """sttode_tgemm_group(-1): whatever the open group has queued, in each of its queues, is never launched, and the group is closed.
+    sttode_twgrad_defer(-1, ..): a split weight gradient whose reduction was deferred has written its partial sums to the deferral buffer;
+    the pending reduction is forgotten, so dW and db stay untouched (observed on the library before and after the kernels moved to one
+    file per family).  The next sttode_twgrad, without deferral, runs its own reduction and gives the float64 gradient."""
+    capi, dev = _capi(), _gpu()
+    st = capi.stream_ptr()
+    rng = np.random.default_rng(24)
+    inp = _group_inputs(dev, rng, 1)
+    try:
+        capi.call('sttode_tgemm_group', 1)
+        queued = _group_issue(capi, dev, st, inp, with_bwd=False)
+        capi.call('sttode_tgemm_group', -1)
+        torch.cuda.synchronize()
+        assert len(queued) == 3
+        for label, (y, _) in queued.items():
+            assert (y == SENT).all(), f'{label}: launched although the group was abandoned'
+        (cols, J, I), (X, W, b) = SMALL, inp['small'][0]
+        Y = _sent(dev, cols, I)
+        capi.call('sttode_tlinear', X, J, 1, W, J, 0, b, None, 0, Y, Y.stride(0), cols, J, I, 2, 0, st)   # no group call in between
+        torch.cuda.synchronize()
+        assert not (Y[:, :I] == SENT).any(), 'a call after sttode_tgemm_group(-1) was queued: the group is still open'
+        assert (Y[:, I:] == SENT).all()
+        a32 = [X.cpu(), W.cpu(), b.cpu(), torch.zeros(cols, I)]
+        _close(Y[:, :I], R.tlinear_tab(*[v.double() for v in a32], 1, 2), R.tlinear_tab(*a32, 1, 2), 'tlinear after an abandoned group')
+
+        cols, N, K = BWD
+        dY, _, X = inp['bwd']
+        buf, scratch = torch.zeros(4096, device=dev), torch.zeros(64 * N * (K + 1), device=dev)
+        dW, db = _sent(dev, N, K), _sent(dev, 1, N)
+        capi.call('sttode_twgrad_defer', 1, buf, buf.numel())
+        capi.call('sttode_twgrad', dY, N, X, K, 1, dW, dW.stride(0), db, cols, N, K, scratch, scratch.numel(), st)
+        capi.call('sttode_twgrad_defer', -1, None, 0)
+        torch.cuda.synchronize()
+        assert (buf != 0).any() and (scratch == 0).all(), 'the split sums of a deferred gradient go to the deferral buffer'
+        assert (dW == SENT).all() and (db == SENT).all(), 'the forgotten reduction ran'
+        dW, db = torch.zeros(N, K + 4, device=dev), torch.zeros(1, N + 4, device=dev)
+        capi.call('sttode_twgrad', dY, N, X, K, 1, dW, dW.stride(0), db, cols, N, K, scratch, scratch.numel(), st)
+        torch.cuda.synchronize()
+        assert (dW[:, K:] == 0).all() and (db[:, N:] == 0).all()
+        dYc, Xc = dY.cpu(), X.cpu()
+        w = max(_close(dW[:, :K], dYc.double().T @ Xc.double(), dYc.T @ Xc, 'twgrad dW after a forgotten reduction'),
+                _close(db[0, :N], dYc.double().sum(0), dYc.sum(0), 'twgrad db after a forgotten reduction'))
+        _worst('twgrad after the error paths', w)
+    finally:                                                   # (a failure above must not leave its queue to the next test's group)
+        capi.call('sttode_tgemm_group', -1)
+        capi.call('sttode_twgrad_defer', -1, None, 0)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------

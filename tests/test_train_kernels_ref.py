@@ -127,7 +127,7 @@ def _ew(op, p, count, i0=0, f0=0.0):
 
 
 def test_ewise_restatements_on_worked_cases():
-    """Hand-worked values of every op code (the comments of the EW_* enum of csrc/train.hip)."""
+    """Hand-worked values of every op code (the comments of the EW_* enum of csrc/train_ewise.hip)."""
     a, b = np.array([1.0, -2.0, 3.0]), np.array([4.0, 5.0, -6.0])
     assert np.array_equal(_ew('MUL', [np.zeros(3), a, b, None, None], 3)[0][0], [4.0, -10.0, -18.0])
     assert np.array_equal(_ew('AXPY', [a, b, None, None, None], 3, f0=0.5)[0][0], [3.0, 0.5, 0.0])

@@ -1,4 +1,4 @@
-"""Plain restatements of the training-step kernels of csrc/train.hip, for tests/test_train_kernels_*.py.
+"""Plain restatements of the training-step kernels of csrc/train*.hip, for tests/test_train_kernels_*.py.
 
 Each reference runs in the dtype of its inputs: float64 is the rounding-free yardstick, float32 is torch's own fp32 evaluation of the same
 operation (how far a correct fp32 implementation may sit from float64).  Layouts are the kernels' (training.py block_fwd / block_bwd).
