@@ -344,6 +344,34 @@ int sttode_mhgsa_attn_rc_bwd(const float* R, const float* C, const float* V, con
  * beta2^t) + eps); weight_decay adds weight_decay * p to g first (torch's L2 form).  amsgrad / maximize: not built (the caller falls back). */
 int sttode_adam_step(const void* items, int n, long chunks, const float* gbase, double lr, double beta1, double beta2, double eps,
                      double weight_decay, long step, void* stream);
+/* Global-norm gradient clipping (torch.nn.utils.clip_grad_norm_, norm_type 2) and a non-finite guard in front of the optimizer step
+ * (train.py:64-66,85-87: backward, then optimizer.step(); the reference carries a detect_grad_nan, core/utils.py:268-272, and never calls
+ * it), on the device with no host round trip.  Added within ABI version 14.
+ * One param group: the table of sttode_adam_step (the p / m / v pointers are read by sttode_adam_step_guarded only) and the group's Adam
+ * hyper-parameters; step = the t the group's next update would have had no step ever been skipped (0: no Adam scalars wanted). */
+typedef struct SttodeGradGroup {
+    const void* items; int n; long chunks; const float* gbase;
+    double lr, beta1, beta2; long step;
+} SttodeGradGroup;
+#define STTODE_GRAD_MAX_GROUPS 16
+/* The device state block: STTODE_GRAD_STATE_WORDS 32-bit words owned by the caller, zeroed once (or with `applied` preset).
+ *   [0] total_norm (float)  [1] coef (float)  [2] apply (int)  [3] applied (int)  [4] skipped (int)  [5..7] reserved
+ *   [8 + 2 g], [9 + 2 g]: lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t) of group g (float), t = step - skipped */
+#define STTODE_GRAD_STATE_WORDS 40
+/* groups: HOST array of ngroups <= STTODE_GRAD_MAX_GROUPS records.  One launch per group writes the sum of squares of each 1024-element
+ * chunk to partials (DEVICE, partials_len >= the groups' chunks together; fixed summation order, no atomics: repeatable bit for bit, NaN /
+ * Inf propagate); one workgroup then sums them in double and writes the state block: total_norm, coef = min(1, max_norm / (total_norm +
+ * 1e-6)) (max_norm > 0; 0 = no clipping: coef 1), apply = 0 when skip_nonfinite and the norm is NaN / Inf (then `skipped` counts the step,
+ * else `applied`), and each group's two scalars: sttode_adam_step's own values for t = step while nothing was ever skipped, else
+ * recomputed on the device for t = step - skipped. */
+int sttode_grad_norm(const SttodeGradGroup* groups, int ngroups, float* partials, long partials_len, double max_norm, int skip_nonfinite,
+                     void* state, void* stream);
+/* sttode_adam_step on g * coef, with coef, apply and the two scalars of slot `group` read from the state block sttode_grad_norm wrote in
+ * front of it on the stream; apply == 0: nothing is stored.  coef == 1 and nothing skipped: sttode_adam_step's result bit for bit. */
+int sttode_adam_step_guarded(const void* items, int n, long chunks, const float* gbase, double beta1, double beta2, double eps,
+                             double weight_decay, const void* state, int group, void* stream);
+/* g *= coef in place for every tensor of the table (the second half of a stand-alone clip_grad_norm_); coef == 1: nothing is stored. */
+int sttode_grad_scale(const void* items, int n, long chunks, float* gbase, const void* state, void* stream);
 /* out[0] = scale * sum (pred - target)^2 (calculate_loss_pred / _recover, :372-376,384-388); dpred optional. */
 int sttode_loss_sqerr(const float* pred, const float* target, long count, float scale, float* out, float* dpred, void* stream);
 /* KL term (:378-382, utils/dist.py:26-29), params [rows,2*zd].  scene_ptr NULL: out[0] = clamp_min(sum KL / denom, min_clip).

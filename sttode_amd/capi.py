@@ -70,6 +70,10 @@ SIGNATURES = {
     'sttode_mhgsa_attn_bwd': [_P, _P, _P, _I, _I, _I, _P],
     'sttode_mhgsa_attn_rc_bwd': [_P] * 7 + [_I, _I, _I] + [_L] * 8 + [_F, _F, _P],
     'sttode_adam_step': [_P, _I, _L, _P, _D, _D, _D, _D, _D, _L, _P],
+    # global-norm clipping and the non-finite guard in front of the optimizer step (csrc/train_optim.hip; added within ABI version 14)
+    'sttode_grad_norm': [_P, _I, _P, _L, _D, _I, _P, _P],
+    'sttode_adam_step_guarded': [_P, _I, _L, _P, _D, _D, _D, _D, _P, _I, _P],
+    'sttode_grad_scale': [_P, _I, _L, _P, _P, _P],
     'sttode_loss_sqerr': [_P, _P, _L, _F, _P, _P, _P],
     'sttode_loss_kl': [_P, _P, _I, _I, _I, _F, _F, _P, _P, _P, _P],
     'sttode_loss_diverse': [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
@@ -162,6 +166,16 @@ class AsyncOpts(ctypes.Structure):
     """struct SttodeAsyncOpts of include/sttode_hip.h: everything an asynchronous call needs travels with the call."""
     _fields_ = [('device_latents', ctypes.c_int), ('zkey', ctypes.c_ulonglong), ('metrics_gt', ctypes.c_void_p), ('ade', ctypes.c_void_p),
                 ('fde', ctypes.c_void_p), ('metrics_scale', ctypes.c_float), ('nba_groups', ctypes.c_int), ('sampler', ctypes.c_void_p)]
+
+
+class GradGroup(ctypes.Structure):
+    """struct SttodeGradGroup of include/sttode_hip.h: one param group's tensor table and Adam hyper-parameters for sttode_grad_norm."""
+    _fields_ = [('items', ctypes.c_void_p), ('n', ctypes.c_int), ('chunks', ctypes.c_long), ('gbase', ctypes.c_void_p),
+                ('lr', ctypes.c_double), ('beta1', ctypes.c_double), ('beta2', ctypes.c_double), ('step', ctypes.c_long)]
+
+
+GRAD_MAX_GROUPS = 16       # STTODE_GRAD_MAX_GROUPS
+GRAD_STATE_WORDS = 40      # STTODE_GRAD_STATE_WORDS: [0] total_norm [1] coef [2] apply [3] applied [4] skipped [8 + 2 g, 9 + 2 g] group scalars
 
 
 class SamplerPlan(ctypes.Structure):

@@ -4,18 +4,52 @@ Drop-in: same constructor, same ``state`` layout (``step`` / ``exp_avg`` / ``exp
 ``load_state_dict()`` round-trip with torch's class and the reference's checkpoints (train.py:188-213) load.  torch's own implementations
 walk the model's 88 small tensors -- foreach: ~0.3 ms of host time and a dozen launches per step, fused: three multi_tensor_apply launches
 of 41-44 us -- which is 6 % of an NBA-size step and 13 % of a one-scene step of this model (profiles/r05/); the update itself moves 26 MB.
-``csrc/train.hip adam_step_kernel`` does it in one launch from a device table of the tensors.  Options the kernel does not implement
+``csrc/train_optim.hip adam_step_kernel`` does it in one launch from a device table of the tensors.  Options the kernel does not implement
 (amsgrad, maximize, capturable, differentiable, sparse or non-fp32 / non-contiguous / CPU tensors) take torch's own step.
+
+Opt-in, for the deep unrolled training paths (RK4 / multi-step Euler encoders, GRU BPTT): ``Adam(..., max_grad_norm=c)`` clips the
+gradients to the global 2-norm c (torch.nn.utils.clip_grad_norm_'s formula) and ``skip_nonfinite=True`` leaves parameters and moments
+untouched by a step whose gradient norm is NaN / Inf (the reference's unused detect_grad_nan, core/utils.py:268-272, superseded).  Both
+run on the device over the same table -- per-chunk sums of squares, one workgroup that writes the norm, the clip coefficient, the apply
+flag and the step counters to a small state block, and the update reading them -- with no host round trip: torch's clip walks the 88
+tensors again with foreach launches, which is the cost this file exists to remove.  A skipped step does not count towards the bias
+corrections (as a step a GradScaler skipped).  ``clip_grad_norm_`` below is the stand-alone drop-in for torch's function.
 """
+import ctypes
+import math
+
 import torch
 
 from . import capi
 
+_NORM, _APPLIED, _SKIPPED = 0, 3, 4      # words of the device state block (include/sttode_hip.h: STTODE_GRAD_STATE_WORDS)
+
+
+def _chunk_rows(ptrs, offs, numels):
+    """Rows of the device tensor table (struct AdamItem of csrc/train_optim.hip) and their total of 1024-element chunks."""
+    rows, chunk = [], 0
+    for (p, m, v), off, n in zip(ptrs, offs, numels):
+        rows.append((p, m, v, off // 4, n, chunk))
+        chunk += (n + 1023) // 1024
+    return rows, chunk
+
 
 class Adam(torch.optim.Adam):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, **kw):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, max_grad_norm=None, skip_nonfinite=False, **kw):
         kw.pop('fused', None)
         kw.pop('foreach', None)
+        if max_grad_norm is not None:
+            if isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, (int, float)) or not 0 < max_grad_norm < math.inf:
+                raise ValueError(f'max_grad_norm must be a positive finite number or None, got {max_grad_norm!r}')
+            max_grad_norm = float(max_grad_norm)
+        # plain attributes, not entries of param_groups: state_dict() stays interchangeable with torch's class
+        self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
+        self._gstate = None       # the device state block of the guarded step (norm, coef, apply, counters, per-group scalars); None: never used
+        self._guard = None        # (plans it was made for, partials, the host array of SttodeGradGroup, total chunks)
+        self._skipped_host = 0    # skipped steps already taken out of _t (the device word counts the ones since)
+        self._applied0 = 0        # what the device's `applied` word starts from (load_state_dict: the loaded step)
+        self._unfolded = False    # a guarded step ran since the device's count of skipped steps was last read
+        self._last_norm = None
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, **kw)
         self._plans = None        # per group: (group, params, device table, chunks, rows, gradient offsets from the first one) -- None: (re)build
         self._t = {}              # group index -> steps taken (the per-parameter ``step`` tensors of torch's state are written on demand)
@@ -53,14 +87,11 @@ class Adam(torch.optim.Adam):
                 return None                                       # parameters at different step counts (a hand-made state): torch's own step
             self._t.setdefault(gi, steps.pop())
             g0 = ps[0].grad.data_ptr()
-            rows, chunk, offs = [], 0, []
-            for p in ps:
-                st, g = self.state[p], p.grad.data_ptr()
-                if (g - g0) % 4:
-                    return None
-                offs.append(g - g0)
-                rows.append((p.data_ptr(), st['exp_avg'].data_ptr(), st['exp_avg_sq'].data_ptr(), (g - g0) // 4, p.numel(), chunk))
-                chunk += (p.numel() + 1023) // 1024
+            offs = [p.grad.data_ptr() - g0 for p in ps]
+            if any(o % 4 for o in offs):
+                return None
+            rows, chunk = _chunk_rows([(p.data_ptr(), self.state[p]['exp_avg'].data_ptr(), self.state[p]['exp_avg_sq'].data_ptr()) for p in ps],
+                                      offs, [p.numel() for p in ps])
             plans.append((gi, group, ps, torch.tensor(rows, dtype=torch.int64).to(ps[0].device), chunk, len(rows), offs,
                           [p.data_ptr() for p in ps]))
         return plans
@@ -68,7 +99,18 @@ class Adam(torch.optim.Adam):
     def _grad_counts(self):
         return [sum(p.grad is not None for p in group['params']) for group in self.param_groups]
 
+    def _fold_skips(self):
+        """Take the steps the device skipped out of the host's counts (reads the device word: synchronises)."""
+        if self._unfolded:
+            self._unfolded = False
+            sk = int(self._gstate.view(torch.int32)[_SKIPPED])
+            if sk:
+                self._t = {gi: t - sk for gi, t in self._t.items()}
+                self._skipped_host += sk
+                self._gstate[_SKIPPED].zero_()
+
     def _sync_steps(self):
+        self._fold_skips()                                        # step = applied: a skipped step does not count
         for gi, group, ps, *_ in (self._plans or ()):
             t = float(self._t.get(gi, 0))
             for p in ps:
@@ -80,11 +122,46 @@ class Adam(torch.optim.Adam):
 
     def load_state_dict(self, sd):
         super().load_state_dict(sd)
-        self._plans, self._t = None, {}
+        self._plans, self._t, self._guard = None, {}, None
+        steps = [int(st['step']) for st in self.state.values() if 'step' in st]
+        self._skipped_host, self._applied0, self._unfolded = 0, (steps[0] if steps else 0), False     # the counters start again from the loaded step
+        if self._gstate is not None:
+            self._gstate.zero_()
+            self._gstate.view(torch.int32)[_APPLIED] = self._applied0
 
     def add_param_group(self, group):
         super().add_param_group(group)
         self._plans = None
+
+    def _guard_buffers(self, plans):
+        """What the guarded step needs besides the plans: the state block (made once, it carries the counters), the partial sums and the
+        host array of group records.  None: more groups than the finish kernel takes, or groups on several devices."""
+        dev = plans[0][2][0].device
+        if len(plans) > capi.GRAD_MAX_GROUPS or any(pl[2][0].device != dev for pl in plans):
+            return None
+        if self._gstate is None or self._gstate.device != dev:
+            self._gstate = torch.zeros(capi.GRAD_STATE_WORDS, dtype=torch.float32, device=dev)
+            self._gstate.view(torch.int32)[_APPLIED] = self._applied0
+        total = sum(pl[4] for pl in plans)
+        arr = (capi.GradGroup * len(plans))()
+        for r, (gi, group, ps, table, chunks, nrows, offs, pptrs) in zip(arr, plans):
+            r.items, r.n, r.chunks = table.data_ptr(), nrows, chunks
+        return plans, torch.empty(total, dtype=torch.float32, device=dev), arr, total
+
+    def _step_fallback_guarded(self):
+        """The same semantics with torch's own pieces (amsgrad, CPU tensors, ...): clip, then skip the step if the norm is not finite."""
+        params = [p for group in self.param_groups for p in group['params'] if p.grad is not None]
+        if not params:
+            return
+        if self.max_grad_norm is not None:
+            norm = torch.nn.utils.clip_grad_norm_(params, self.max_grad_norm)
+        else:
+            norm = torch.linalg.vector_norm(torch.stack([torch.linalg.vector_norm(p.grad) for p in params]))
+        self._last_norm = norm
+        if self.skip_nonfinite and not bool(torch.isfinite(norm)):
+            self._skipped_host += 1
+        else:
+            super().step()
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -109,14 +186,40 @@ class Adam(torch.optim.Adam):
                         break
             except AttributeError:                                # a gradient is None this step
                 plans = None
+        guarded = self.max_grad_norm is not None or self.skip_nonfinite
         if plans is None:
             self._sync_steps()
             plans = self._plans = self._build()
-            if plans is None:                                     # an option the kernel does not implement: torch's own step throughout
+            self._guard = None
+        if guarded and plans and (self._guard is None or self._guard[0] is not plans):
+            self._guard = self._guard_buffers(plans)
+            if self._guard is None:
+                self._sync_steps()
+                plans = self._plans = None
+        if plans is None:                                         # an option the kernel does not implement: torch's own step throughout
+            if guarded:
+                self._step_fallback_guarded()
+            else:
                 super().step()
-                self._t = {}                                      # torch advanced the state's step tensors: the next plans read them again
-                return loss
+            self._t = {}                                          # torch advanced the state's step tensors: the next plans read them again
+            return loss
         L, st = capi.lib(), capi.stream_ptr()
+        if guarded and plans:
+            # norm, coefficient and the apply flag on the device, the update reading them: all on the current stream, nothing synchronises
+            _, partials, arr, total = self._guard
+            state = self._gstate.data_ptr()
+            for r, (gi, group, ps, *_) in zip(arr, plans):
+                r.gbase, r.lr, (r.beta1, r.beta2) = ps[0].grad.data_ptr(), group['lr'], group['betas']
+                r.step = self._t[gi] = self._t.get(gi, 0) + 1     # (the device takes its count of skipped steps off)
+            if L.sttode_grad_norm(arr, len(arr), partials.data_ptr(), total, self.max_grad_norm or 0.0, int(self.skip_nonfinite), state, st):
+                raise capi.SttodeError('sttode_grad_norm failed: ' + L.sttode_last_error().decode())
+            for i, (gi, group, ps, table, chunks, nrows, offs, pptrs) in enumerate(plans):
+                b1, b2 = group['betas']
+                if L.sttode_adam_step_guarded(table.data_ptr(), nrows, chunks, ps[0].grad.data_ptr(), b1, b2, group['eps'], group['weight_decay'], state, i, st):
+                    raise capi.SttodeError('sttode_adam_step_guarded failed: ' + L.sttode_last_error().decode())
+            self._last_norm, self._unfolded = self._gstate[_NORM], True
+            return loss
+        self._fold_skips()                                        # (only after guarded steps, when the options were switched off again)
         for gi, group, ps, table, chunks, nrows, offs, pptrs in plans:
             t = self._t[gi] = self._t.get(gi, 0) + 1
             b1, b2 = group['betas']
@@ -126,4 +229,70 @@ class Adam(torch.optim.Adam):
 
     @property
     def steps_taken(self):
+        self._fold_skips()
         return dict(self._t)
+
+    @property
+    def last_grad_norm(self):
+        """The global gradient norm of the last guarded step: a 0-dim tensor on the parameters' device (a view of the state block, read
+        without synchronising; the next step overwrites it).  None before the first such step."""
+        return self._last_norm
+
+    @property
+    def skipped_steps(self):
+        """How many steps the non-finite guard has skipped (reads the device word: synchronises)."""
+        return self._skipped_host + (int(self._gstate.view(torch.int32)[_SKIPPED]) if self._gstate is not None else 0)
+
+
+_CLIP_PLANS = {}         # gradient layout (device, offsets from the first gradient, sizes) -> uploaded table, partials, state block
+_CLIP_PLANS_MAX = 8
+
+
+def _clip_plan(grads):
+    dev = grads[0].device
+    if dev.type != 'cuda' or not all(g.device == dev and g.dtype == torch.float32 and not g.is_sparse and g.is_contiguous() for g in grads):
+        return None
+    g0 = grads[0].data_ptr()
+    offs, numels = tuple(g.data_ptr() - g0 for g in grads), tuple(g.numel() for g in grads)
+    if any(o % 4 for o in offs) or not all(numels):
+        return None
+    key = (dev, offs, numels)
+    plan = _CLIP_PLANS.get(key)
+    if plan is None:
+        rows, chunks = _chunk_rows([(0, 0, 0)] * len(grads), offs, numels)
+        arr = (capi.GradGroup * 1)()
+        table = torch.tensor(rows, dtype=torch.int64).to(dev)
+        arr[0].items, arr[0].n, arr[0].chunks = table.data_ptr(), len(rows), chunks
+        plan = (table, arr, torch.empty(chunks, dtype=torch.float32, device=dev), torch.zeros(capi.GRAD_STATE_WORDS, dtype=torch.float32, device=dev))
+        while len(_CLIP_PLANS) >= _CLIP_PLANS_MAX:
+            _CLIP_PLANS.pop(next(iter(_CLIP_PLANS)))
+        _CLIP_PLANS[key] = plan
+    return plan
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None):
+    """torch.nn.utils.clip_grad_norm_ (same signature, same return value: the total norm, on the device) as two HIP launches plus the
+    one-workgroup finish over one table of all gradients, instead of a walk over every tensor.  Kernel path: norm_type 2, fp32 contiguous
+    CUDA gradients, 0 < max_norm < inf; anything else is torch's own function.  A NaN norm turns the gradients NaN, as in torch."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    parameters = list(parameters)
+    grads = [p.grad for p in parameters if p.grad is not None]
+    max_norm = float(max_norm)
+    plan = _clip_plan(grads) if grads and float(norm_type) == 2.0 and 0 < max_norm < math.inf else None
+    if plan is None:
+        return torch.nn.utils.clip_grad_norm_(parameters, max_norm, norm_type, error_if_nonfinite, foreach)
+    table, arr, partials, state = plan
+    arr[0].gbase = grads[0].data_ptr()
+    with torch.cuda.device(grads[0].device):
+        L, st = capi.lib(), capi.stream_ptr()
+        if L.sttode_grad_norm(arr, 1, partials.data_ptr(), arr[0].chunks, max_norm, 0, state.data_ptr(), st):
+            raise capi.SttodeError('sttode_grad_norm failed: ' + L.sttode_last_error().decode())
+        norm = state[_NORM].clone()
+        if error_if_nonfinite and not bool(torch.isfinite(norm)):
+            raise RuntimeError(f'The total norm of order {norm_type} for gradients from `parameters` is non-finite, so it cannot be clipped. '
+                               'To disable this error and scale the gradients by the non-finite norm anyway, set `error_if_nonfinite=False`')
+        if L.sttode_grad_scale(table.data_ptr(), arr[0].n, arr[0].chunks, grads[0].data_ptr(), state.data_ptr(), st):
+            raise capi.SttodeError('sttode_grad_scale failed: ' + L.sttode_last_error().decode())
+    return norm

@@ -12,9 +12,11 @@ optimizer is torch's (element-wise parameter update on device tensors).
 import torch
 
 
-def train_epoch(args, epoch, model, optimizer, scheduler, train_loader, log=print, max_iters=None):
+def train_epoch(args, epoch, model, optimizer, scheduler, train_loader, log=print, max_iters=None, log_grad_norm=False):
     """One epoch.  NBA: loader yields seq_collate dicts (train.py:59-71); otherwise the per-scene 10-tuples of
-    TrajectoryDataset / SDD_Dataset wrapped by DataLoader(batch_size=1) (train.py:72-95).  Returns the list of total losses."""
+    TrajectoryDataset / SDD_Dataset wrapped by DataLoader(batch_size=1) (train.py:72-95).  Returns the list of total losses.
+    log_grad_norm: with an optimizer that has ``last_grad_norm`` (sttode_amd.optim.Adam with max_grad_norm / skip_nonfinite), the printed
+    lines also carry the last step's global gradient norm and the number of steps the non-finite guard skipped."""
     model.train()
     total_iter_num = len(train_loader)
     losses = []
@@ -35,9 +37,12 @@ def train_epoch(args, epoch, model, optimizer, scheduler, train_loader, log=prin
         optimizer.step()
         losses.append(float(total_loss.detach()))
         if log is not None and iter_num % getattr(args, 'iternum_print', 100) == 0:
-            log('Epochs: {:02d}/{:02d}| It: {:04d}/{:04d} | Total loss: {:03f}| Loss_pred: {:03f}| Loss_recover: {:03f}| Loss_kl: {:03f}| '
-                'Loss_diverse: {:03f}'.format(epoch, getattr(args, 'num_epochs', 1), iter_num, total_iter_num, losses[-1], loss_pred,
-                                              loss_recover, loss_kl, loss_diverse))
+            line = ('Epochs: {:02d}/{:02d}| It: {:04d}/{:04d} | Total loss: {:03f}| Loss_pred: {:03f}| Loss_recover: {:03f}| Loss_kl: {:03f}| '
+                    'Loss_diverse: {:03f}'.format(epoch, getattr(args, 'num_epochs', 1), iter_num, total_iter_num, losses[-1], loss_pred,
+                                                  loss_recover, loss_kl, loss_diverse))
+            if log_grad_norm and getattr(optimizer, 'last_grad_norm', None) is not None:
+                line += '| Grad norm: {:03f}| Skipped steps: {:d}'.format(float(optimizer.last_grad_norm), optimizer.skipped_steps)
+            log(line)
     if scheduler is not None:
         scheduler.step()
     model.step_annealer()
