@@ -2,7 +2,6 @@
 // reductions, the element-wise op codes with their group-mode queue (stt_ew_group, train_group.hpp), LayerNorm forward / backward and
 // the gather of the tape rows that carry a gradient.
 #include "api_util.hpp"
-#include <mutex>
 #include "chain.hpp"
 #include "train_group.hpp"
 
@@ -177,17 +176,16 @@ __global__ void ewise_multi_kernel(EwMulti M) {
     }
 }
 // group mode (sttode_tgemm_group -> stt_ew_group): pieces queued in an open group leave as ONE ewise_multi_kernel launch
-static thread_local struct { EwMulti M; void* stream; bool on; } g_ewq = {};   // (per host thread, like every queue of a group)
-static std::mutex g_ew_mu;
-static void ew_group_launch_locked() {
+// (g_ewq belongs to the calling host thread, like every queue of a group: another thread's calls neither see it nor wait for it)
+static thread_local struct { EwMulti M; void* stream; bool on; } g_ewq = {};
+static void ew_group_launch() {
     if (g_ewq.M.n == 0) return;
     hipLaunchKernelGGL(ewise_multi_kernel, dim3((unsigned)g_ewq.M.blocks), dim3(256), 0, (hipStream_t)g_ewq.stream, g_ewq.M);
     g_ewq.M.n = 0; g_ewq.M.blocks = 0;
 }
 int stt_ew_group(int on) {
-    std::lock_guard<std::mutex> lk(g_ew_mu);
     if (on < 0) { g_ewq.M.n = 0; g_ewq.M.blocks = 0; }   // error paths: forget what is queued
-    ew_group_launch_locked();
+    ew_group_launch();
     g_ewq.on = on > 0;
     STT_HIP(hipGetLastError());
     return 0;
@@ -197,9 +195,8 @@ extern "C" int sttode_train_ewise(int op, float* p0, const float* p1, const floa
                                   float f0, void* stream) {
     STT_REQUIRE(op >= 0 && op <= EW_AXPY_ROWS && p0 && count > 0, "sttode_train_ewise: bad argument");
     if (g_ewq.on && count <= (1L << 24)) {   // an open group: queued, leaves with the group's other pieces
-        std::lock_guard<std::mutex> lk(g_ew_mu);
         EwMulti& M = g_ewq.M;
-        if (M.n == EW_MULTI_MAX || (M.n > 0 && g_ewq.stream != stream)) ew_group_launch_locked();
+        if (M.n == EW_MULTI_MAX || (M.n > 0 && g_ewq.stream != stream)) ew_group_launch();
         EwProb& e = M.p[M.n++];
         e.p0 = p0; e.p1 = p1; e.p2 = p2; e.p3 = p3; e.p4 = p4; e.count = count; e.op = op; e.i0 = i0; e.f0 = f0; e.blk0 = M.blocks;
         M.blocks += (int)((count + 255) / 256);

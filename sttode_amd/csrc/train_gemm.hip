@@ -6,7 +6,6 @@
 // Device code first, then the host state of group mode (the queues g_red, g_grp, g_ts), their submit functions and the entry points.
 // sttode_tgemm_group here is the one function that knows every queue of a group (train_group.hpp).
 #include "api_util.hpp"
-#include <mutex>
 #include "chain.hpp"
 #include "train_group.hpp"
 
@@ -571,7 +570,7 @@ __global__ __launch_bounds__(256) void tgemm_reduce_kernel(TGRed r) {
 struct TWg {
     const float* dY; const float* X; float* dW; float* db; float* scratch;
     long ldy, ldx, ldw;
-    int cols, N, K, xdiv, S, chunks_per_split;
+    int cols, N, K, xdiv, S, chunks_per_split;   // S: 1 from every caller but the one named at sttode_twgrad's reduction launch
 };
 
 static __device__ __forceinline__ void twgrad_body(const TWg& a, int bx, int by, int bz, float (*red)[32][33]) {
@@ -693,6 +692,30 @@ __global__ __launch_bounds__(256) void tsmall_multi_kernel(TSMulti M) {
 // yardsticks on the known ill-conditioned rows move from 0.8 to 1.05-1.8 of their bounds, for no gain at one scene per step).
 static constexpr int TGEMM_MIN_COLS = 2048, TGEMM_MIN_COLS_BWD = 600;
 static inline int aligned16(const void* p, long ld) { return (((size_t)p) % 16 == 0) && (ld % 4 == 0); }
+
+// ---- the descriptors: one function fills each, starting from zeros (the kernels declare them without an initial value and copy them
+// whole out of the kernel arguments, so the structs themselves stay plain: no default member initialisers) ---------------------------------
+// A linear product as its caller states it: Y[c] = epi(Wop X[c / xdiv]), `accumulate` adding row (c / adiv) of asrc.
+// evec: a layer's input gradient (sttode_tlinear_bwd) passes asrc = Y = dX and ldas = ldy, so its accumulate term repeats the yvec term
+// and its absent bias drops out: the backward case needs no expression of its own.
+static TLin tlin_fill(const float* X, long ldx, int xdiv, const float* W, long ldw, int trans, const float* bias, const float* mask, long ldm,
+                      float* Y, long ldy, int cols, int J, int I, int act, int accumulate, const float* asrc, long ldas, int adiv) {
+    TLin a{};
+    a.X = X; a.W = W; a.bias = bias; a.mask = mask; a.Y = Y;
+    a.ldx = ldx; a.ldw = ldw; a.ldy = ldy; a.ldm = ldm;
+    a.cols = cols; a.J = J; a.I = I; a.trans = trans; a.act = act; a.accumulate = accumulate; a.xdiv = xdiv;
+    a.asrc = asrc; a.ldas = ldas; a.adiv = adiv;
+    a.xvec = aligned16(X, ldx); a.wvec = aligned16(W, ldw); a.yvec = aligned16(Y, ldy);
+    a.evec = I % 4 == 0 && a.yvec && (!bias || aligned16(bias, 4)) && (!mask || aligned16(mask, ldm)) && (!accumulate || aligned16(asrc, ldas));
+    return a;
+}
+// latency mode: one 16 x 16 block per WG, reduction split over up to 4 waves (128 indices per round trip and wave)
+struct TLatPlan { int ksplit, gx, gy; };
+static TLatPlan tlin_latency_plan(int cols, int J, int I) {
+    const int ksplit = J > 256 ? 4 : (J > 128 ? 2 : 1);
+    const int blocks_per_wg = 4 / ksplit;
+    return {ksplit, (cols + 15) / 16, ((I + 15) / 16 + blocks_per_wg - 1) / blocks_per_wg};
+}
 // tg_fetch_fast: aligned operands without broadcast rows; the contiguous index of each operand (k, or the row index of a transposed one)
 // a multiple of 4 and at least 4; every split of the reduction a multiple of 4 long
 static inline int tg_fast(const TG& g, bool AT, bool BT) {
@@ -702,25 +725,53 @@ static inline int tg_fast(const TG& g, bool AT, bool BT) {
     if (BT ? (brows % 4 != 0 || brows < 4) : g.Kt % 4 != 0) return 0;
     return 1;
 }
+// g_tg_dbg: a plain global, shared by every host thread: written only by this diagnostic and read once per stand-alone launch
 static long long* g_tg_dbg = nullptr;
 extern "C" int sttode_tgemm_debug_buffer(void* p) { g_tg_dbg = (long long*)p; return 0; }   // diagnostic: >= grid * 4 int64 (NULL: off); stand-alone launches only
-static inline int tg_evec(const TG& g) {
-    return g.N % 4 == 0 && aligned16(g.C, g.ldc) && (!g.bias || aligned16(g.bias, 4)) && (!g.mask || aligned16(g.mask, g.ldm)) &&
-           (!g.accumulate || aligned16(g.asrc, g.ldas));
+// the linear product `a` (forward, or with a.trans an input gradient) on the LDS-tiled kernel: mode 0.  dbg: g_tg_dbg for a product that
+// is a launch (or a group member) of its own, null for one that shares tgemm_bwd_kernel's launch
+static TG tg_linear(const TLin& a, long long* dbg) {
+    TG g{};
+    g.A = a.X; g.lda = a.ldx; g.B = a.W; g.ldb = a.ldw; g.C = a.Y; g.ldc = a.ldy;
+    g.M = a.cols; g.N = a.I; g.Kt = a.J; g.adiv = a.xdiv; g.bkdiv = 1; g.ones_row = -1; g.S = 1;
+    g.avec = a.xvec; g.bvec = a.wvec; g.cvec = a.yvec; g.evec = a.evec;
+    g.bias = a.bias; g.mask = a.mask; g.ldm = a.ldm; g.act = a.act; g.accumulate = a.accumulate; g.asrc = a.asrc; g.ldas = a.ldas; g.acdiv = a.adiv;
+    g.fast = tg_fast(g, false, a.trans != 0); g.dbg = dbg;
+    return g;
+}
+// the generic weight gradient: fills w and returns its grid (32 x 32 blocks of [dW | db] x column splits)
+static inline dim3 twg_grid(const TWg& w) { return dim3((w.N + 31) / 32, (w.K + 1 + 31) / 32, w.S); }
+static dim3 twg_fill(TWg& w, const float* dY, long ldy, const float* X, long ldx, int xdiv, float* dW, long ldw, float* db, int cols, int N, int K,
+                     float* scratch, long scratch_floats) {
+    w = TWg{};
+    w.dY = dY; w.X = X; w.dW = dW; w.db = db; w.scratch = scratch;
+    w.ldy = ldy; w.ldx = ldx; w.ldw = ldw; w.cols = cols; w.N = N; w.K = K; w.xdiv = xdiv;
+    const int chunks = (cols + 15) / 16;
+    const long per = (long)N * (K + 1);
+    int S = chunks <= 64 ? 1 : (chunks + 31) / 32;    // >= 512 columns per split; up to 1024 columns one workgroup per tile (no reduce launch)
+    if (S > 64) S = 64;
+    if (!scratch || per * S > scratch_floats) S = scratch && scratch_floats >= 2 * per ? (int)(scratch_floats / per) : 1;
+    if (S < 1) S = 1;
+    w.S = S;
+    w.chunks_per_split = (chunks + S - 1) / S;
+    return twg_grid(w);
 }
 
-// ---- split weight gradients of the LDS-tiled kernel: where the partial sums go and when they are added up --------------------------------
+// ---- group mode and the deferred reductions: host-side state of the CALLING THREAD --------------------------------------------------------
+// g_red, g_grp and g_ts are thread_local, and nothing else is touched between an entry point's checks and its launches: a group, and a
+// bracket of deferred reductions, belong to the host thread that opened them (a training step -- its group brackets, its backward pass
+// with the deferred reductions -- is issued by one thread).  Another thread's calls neither see them nor wait for them: they launch at
+// once on their own stream, and no lock is taken anywhere.
+//
+// Split weight gradients of the LDS-tiled kernel: where the partial sums go and when they are added up.
 // Default: each weight gradient is followed by its own reduction launch (partial sums in the call's scratch).  Between
 // sttode_twgrad_defer(1, buf, floats) and sttode_twgrad_defer(0, ..) (the training engine brackets a backward pass with them) the partial
 // sums are bump-allocated from `buf` instead -- a buffer nothing else writes -- and the reductions run as ONE launch per TG_RED_MAX
 // gradients, or earlier: buf full, a destination that is already pending, another stream.  Host-side state only; inside a hipGraph capture
 // the flush is captured like any other launch.
-static std::mutex g_red_mu;
-// (per HOST THREAD: a training step -- its group brackets, its backward pass with the deferred reductions -- is issued by one thread; two
-// threads that train two models must not see each other's open group)
 static thread_local struct { TGRed r; int blocks; long used; float* buf; long cap; void* stream; bool defer; } g_red = {{}, 0, 0, nullptr, 0, nullptr, false};
 
-static void tg_red_flush_locked() {
+static void tg_red_flush() {
     if (g_red.r.n > 0) hipLaunchKernelGGL(tgemm_reduce_kernel, dim3((unsigned)g_red.blocks), dim3(256), 0, (hipStream_t)g_red.stream, g_red.r);
     g_red.r.n = 0; g_red.blocks = 0; g_red.used = 0;
 }
@@ -728,12 +779,12 @@ static void tg_red_flush_locked() {
 static void tg_wgrad_done(const TG& g, float* dW, long ldw, float* db) {
     if (g.S <= 1) return;
     const long per = (long)g.M * g.N;
-    if (g_red.r.n == TG_RED_MAX) tg_red_flush_locked();
+    if (g_red.r.n == TG_RED_MAX) tg_red_flush();
     TGRedItem& t = g_red.r.it[g_red.r.n++];
     t.part = g.scratch; t.dW = dW; t.db = db; t.ldw = ldw; t.per = per; t.K1 = g.N; t.S = g.S; t.blk0 = g_red.blocks;
     g_red.blocks += (int)((per + 255) / 256);
     const bool in_buf = g_red.buf && g.scratch >= g_red.buf && g.scratch < g_red.buf + g_red.cap;
-    if (!g_red.defer || !in_buf) tg_red_flush_locked();
+    if (!g_red.defer || !in_buf) tg_red_flush();
 }
 
 // ---- grouped launches (sttode_tgemm_group): batch-size products queued between group(1) and group(0) leave as ONE tgemm_multi_kernel launch ----
@@ -742,7 +793,7 @@ static thread_local struct {
     struct { float* dW; long ldw; float* db; } post[TG_MULTI_MAX];   // weight gradients: their split sums are queued for reduction AFTER the launch
     void* stream; bool on;
 } g_grp = {};
-static void tg_group_launch_locked() {
+static void tg_group_launch() {
     TGMulti& M = g_grp.M;
     if (M.n == 0) return;
     hipLaunchKernelGGL(tgemm_multi_kernel, dim3((unsigned)M.blk0[M.n]), dim3(256), 0, (hipStream_t)g_grp.stream, M);
@@ -751,11 +802,13 @@ static void tg_group_launch_locked() {
     for (int i = 0; i < n; ++i)
         if (M.kind[i] == 2) tg_wgrad_done(M.g[i], g_grp.post[i].dW, g_grp.post[i].ldw, g_grp.post[i].db);
 }
+// the queued LDS-tiled products, then every pending reduction behind them
+static void tg_flush_all() { tg_group_launch(); tg_red_flush(); }
 
 // ---- the scene-size queue: layers of at most 1024 columns queued in an open group leave as ONE tsmall_multi_kernel launch ----
 static thread_local struct { TSMulti M; void* stream; } g_ts = {};
 static void ts_group_forget() { g_ts.M.n = 0; }
-static void ts_group_launch_locked() {
+static void ts_group_launch() {
     if (g_ts.M.n == 0) return;
     hipLaunchKernelGGL(tsmall_multi_kernel, dim3((unsigned)g_ts.M.blk0[g_ts.M.n]), dim3(256), 0, (hipStream_t)g_ts.stream, g_ts.M);
     g_ts.M.n = 0;
@@ -765,7 +818,7 @@ static void ts_group_launch_locked() {
 static void tg_submit(const TG& g, int kind, int gx, int gy, int gz, void* stream, float* dW = nullptr, long ldw = 0, float* db = nullptr) {
     if (g_grp.on) {
         TGMulti& M = g_grp.M;
-        if (M.n == TG_MULTI_MAX || (M.n > 0 && g_grp.stream != stream)) tg_group_launch_locked();
+        if (M.n == TG_MULTI_MAX || (M.n > 0 && g_grp.stream != stream)) tg_group_launch();
         const int i = M.n++;
         if (i == 0) M.blk0[0] = 0;
         M.g[i] = g; M.g[i].dbg = nullptr; M.kind[i] = kind; M.gx[i] = gx; M.gy[i] = gy; g_grp.gz[i] = gz;
@@ -782,18 +835,26 @@ static void tg_submit(const TG& g, int kind, int gx, int gy, int gz, void* strea
         tg_wgrad_done(g, dW, ldw, db);
     }
 }
-static void ts_submit(const TLin& a, const TWg* w, int ksplit, int gxA, int nA, int gxW, int gyW, int nB, void* stream) {
+// queue a scene-size layer of the open group: a forward (a), a weight gradient alone (w: a layer backward without input-gradient blocks)
+// or a whole layer backward (both; w unsplit: at most 1024 columns)
+static void ts_submit(const TLin* a, const TWg* w, void* stream) {
     TSMulti& M = g_ts.M;
-    if (M.n == TS_MULTI_MAX || (M.n > 0 && g_ts.stream != stream)) ts_group_launch_locked();
+    if (M.n == TS_MULTI_MAX || (M.n > 0 && g_ts.stream != stream)) ts_group_launch();
     const int i = M.n++;
     if (i == 0) M.blk0[0] = 0;
     TSProb& P = M.p[i];
-    P.a = a; P.ksplit = ksplit; P.gxA = gxA; P.nA = nA; P.gxW = gxW; P.gyW = gyW; P.kind = w ? 1 : 0;
-    if (w) P.w = *w; else P.w = TWg{};
-    M.blk0[i + 1] = M.blk0[i] + nA + nB;
+    const TLatPlan lp = a ? tlin_latency_plan(a->cols, a->J, a->I) : TLatPlan{1, 1, 0};
+    const dim3 gw = w ? twg_grid(*w) : dim3(0, 0, 0);
+    P.a = a ? *a : TLin{}; P.w = w ? *w : TWg{};
+    P.ksplit = lp.ksplit; P.gxA = lp.gx; P.nA = lp.gx * lp.gy; P.gxW = (int)gw.x; P.gyW = (int)gw.y; P.kind = w ? 1 : 0;
+    M.blk0[i + 1] = M.blk0[i] + P.nA + (int)(gw.x * gw.y * gw.z);
     g_ts.stream = stream;
 }
 
+// does a gradient into N rows (of ldw) at dW, and db, write what a gradient into `rows` rows (of ld) at lo, and db2, writes?
+static inline bool tg_dest_overlap(const float* dW, long N, long ldw, const float* db, const float* lo, long rows, long ld, const float* db2) {
+    return (dW < lo + rows * ld && lo < dW + N * ldw) || (db && db == db2);
+}
 // fills g for dW (+)= dY^T [X | 1] with the reduction over the columns split S ways (about want_blocks workgroups); false: no room for partial sums
 static bool tg_wgrad_fill(TG& g, const float* dY, long ldy, const float* X, long ldx, int xdiv, float* dW, long ldw, float* db, int cols, int N,
                           int K, float* scratch, long scratch_floats, int want_blocks, void* stream) {
@@ -803,40 +864,34 @@ static bool tg_wgrad_fill(TG& g, const float* dY, long ldy, const float* X, long
     if (S > 64) S = 64;
     if (S > (cols + 127) / 128) S = (cols + 127) / 128;      // >= 128 columns per split
     if (S < 1) S = 1;
-    if (g_red.r.n > 0 && (g_red.stream != stream || !g_red.defer)) { tg_group_launch_locked(); tg_red_flush_locked(); }
+    if (g_red.r.n > 0 && (g_red.stream != stream || !g_red.defer)) tg_flush_all();
     const bool defer = g_red.defer && g_red.buf && g_red.cap >= 2 * per;
-    if (defer && g_red.r.n > 0) {
+    if (defer && (g_red.r.n > 0 || g_grp.M.n > 0)) {
+        // one launch adds every pending gradient: none of them may share a destination, and the queued, not yet launched gradients of the
+        // open group count as pending destinations too (also in front of an unsplit gradient to a pending destination: it adds into dW itself)
         bool again = g_red.r.n == TG_RED_MAX || (S > 1 && g_red.used + per * S > g_red.cap);
-        for (int i = 0; i < g_red.r.n && !again; ++i) {   // one launch adds every pending gradient: none of them may share a destination
+        for (int i = 0; i < g_red.r.n && !again; ++i) {
             const TGRedItem& t = g_red.r.it[i];
-            const float* lo = t.dW; const float* hi = t.dW + (t.per / t.K1) * t.ldw;
-            again = (dW < hi && lo < dW + (long)N * ldw) || (db && db == t.db);
+            again = tg_dest_overlap(dW, N, ldw, db, t.dW, t.per / t.K1, t.ldw, t.db);
         }
-        if (again) { tg_group_launch_locked(); tg_red_flush_locked(); }   // (also in front of an unsplit gradient to a pending destination: it adds into dW itself)
-    }
-    if (defer && g_grp.M.n > 0) {         // queued, not yet launched gradients of the open group count as pending destinations too
-        bool again = S > 1 && g_red.used + per * S > g_red.cap;
         for (int i = 0; i < g_grp.M.n && !again; ++i)
-            if (g_grp.M.kind[i] == 2) {
-                const float* lo = g_grp.post[i].dW; const float* hi = lo + (long)g_grp.M.g[i].M * g_grp.post[i].ldw;
-                again = (dW < hi && lo < dW + (long)N * ldw) || (db && db == g_grp.post[i].db);
-            }
-        if (again) { tg_group_launch_locked(); tg_red_flush_locked(); }
+            if (g_grp.M.kind[i] == 2) again = tg_dest_overlap(dW, N, ldw, db, g_grp.post[i].dW, g_grp.M.g[i].M, g_grp.post[i].ldw, g_grp.post[i].db);
+        if (again) tg_flush_all();
     }
     if (!defer && g_grp.M.n > 0) {        // without a buffer of its own every split gradient uses the call's scratch: one per launch
         for (int i = 0; i < g_grp.M.n; ++i)
-            if (g_grp.M.kind[i] == 2) { tg_group_launch_locked(); break; }
+            if (g_grp.M.kind[i] == 2) { tg_group_launch(); break; }
     }
     float* part = defer ? g_red.buf + g_red.used : scratch;
     const long room = defer ? g_red.cap - g_red.used : scratch_floats;
     if (S > 1 && (!part || per * S > room)) S = part ? (int)(room / per) : 1;
     if (S < 1) return false;
     g_red.stream = stream;
+    g = TG{};
     g.A = dY; g.lda = ldy; g.B = X; g.ldb = ldx; g.C = dW; g.ldc = ldw;
-    g.M = N; g.N = K + 1; g.Kt = cols; g.adiv = 1; g.bkdiv = xdiv; g.ones_row = K;
-    g.avec = aligned16(dY, ldy); g.bvec = aligned16(X, ldx); g.cvec = 0;
-    g.bias = nullptr; g.mask = nullptr; g.ldm = 0; g.act = 0; g.accumulate = 0; g.asrc = nullptr; g.ldas = 0; g.acdiv = 1;
-    g.db = db; g.scratch = part; g.S = S; g.mode = 1; g.evec = 0; g.fast = tg_fast(g, true, true); g.dbg = nullptr;
+    g.M = N; g.N = K + 1; g.Kt = cols; g.adiv = 1; g.bkdiv = xdiv; g.ones_row = K; g.acdiv = 1;
+    g.avec = aligned16(dY, ldy); g.bvec = aligned16(X, ldx);
+    g.db = db; g.scratch = part; g.S = S; g.mode = 1; g.fast = tg_fast(g, true, true);
     if (defer && S > 1) g_red.used += per * S;     // reserved now: a second gradient of the same group must not get the same piece
     g.kchunk = ((cols + S - 1) / S + 31) / 32 * 32;
     return true;
@@ -844,72 +899,42 @@ static bool tg_wgrad_fill(TG& g, const float* dY, long ldy, const float* X, long
 
 // The one place that lists a group's queues, in the order a closing group flushes them: LDS-tiled, scene-size, element-wise, trunk.
 extern "C" int sttode_tgemm_group(int on) {
-    std::lock_guard<std::mutex> lk(g_red_mu);
     if (on < 0) { g_grp.M.n = 0; ts_group_forget(); }   // error paths: forget what is queued
-    tg_group_launch_locked();
-    ts_group_launch_locked();
+    tg_group_launch();
+    ts_group_launch();
     g_grp.on = on > 0;
     const int rc_ew = stt_ew_group(on), rc_trunk = stt_trunk_group(on);   // (both run: no queue stays open behind another's error)
     if (rc_ew || rc_trunk) return rc_ew ? rc_ew : rc_trunk;
-    STT_HIP(hipGetLastError());
-    return 0;
+    STT_HIP(hipGetLastError()); return 0;
 }
 extern "C" int sttode_twgrad_defer(int on, float* buf, long floats) {
-    std::lock_guard<std::mutex> lk(g_red_mu);
     if (on < 0) { g_red.r.n = 0; g_red.blocks = 0; g_red.used = 0; }      // error paths: forget what is pending
-    tg_red_flush_locked();
+    tg_red_flush();
     g_red.defer = on > 0 && buf && floats > 0;
     g_red.buf = g_red.defer ? buf : nullptr; g_red.cap = g_red.defer ? floats : 0;
-    STT_HIP(hipGetLastError());
-    return 0;
+    STT_HIP(hipGetLastError()); return 0;
 }
 extern "C" int sttode_twgrad_flush(void) {
-    std::lock_guard<std::mutex> lk(g_red_mu);
-    tg_red_flush_locked();
-    STT_HIP(hipGetLastError());
-    return 0;
+    tg_red_flush();
+    STT_HIP(hipGetLastError()); return 0;
 }
 
-static int tlinear_impl(const float* X, long ldx, int xdiv, const float* W, long ldw, int trans, const float* bias, const float* mask, long ldm,
-                        float* Y, long ldy, int cols, int J, int I, int act, int accumulate, const float* asrc, long ldas, int adiv, void* stream) {
-    STT_REQUIRE(X && W && Y, "sttode_tlinear: null pointer");
-    STT_REQUIRE(cols > 0 && J > 0 && I > 0 && xdiv > 0, "sttode_tlinear: cols, J, I, xdiv must be positive");
-    STT_REQUIRE(act >= 0 && act <= 3, "sttode_tlinear: act must be 0 none | 1 relu | 2 tanh | 3 sigmoid");
-    STT_REQUIRE(ldx >= J && ldy >= I && ldw >= (trans ? I : J), "sttode_tlinear: leading dimension smaller than the row length");
-    TLin a;
-    a.X = X; a.W = W; a.bias = bias; a.mask = mask; a.Y = Y;
-    a.ldx = ldx; a.ldw = ldw; a.ldy = ldy; a.ldm = ldm;
-    a.cols = cols; a.J = J; a.I = I; a.trans = trans; a.act = act; a.accumulate = accumulate; a.xdiv = xdiv;
-    a.asrc = asrc; a.ldas = ldas; a.adiv = adiv;
-    a.xvec = aligned16(X, ldx); a.wvec = aligned16(W, ldw); a.yvec = aligned16(Y, ldy);
-    a.evec = I % 4 == 0 && a.yvec && (!bias || aligned16(bias, 4)) && (!mask || aligned16(mask, ldm)) && (!accumulate || aligned16(asrc, ldas));
+static int tlinear_impl(const TLin& a, void* stream) {
+    const int cols = a.cols, J = a.J, I = a.I, trans = a.trans;
+    STT_REQUIRE(a.X && a.W && a.Y, "sttode_tlinear: null pointer");
+    STT_REQUIRE(cols > 0 && J > 0 && I > 0 && a.xdiv > 0, "sttode_tlinear: cols, J, I, xdiv must be positive");
+    STT_REQUIRE(a.act >= 0 && a.act <= 3, "sttode_tlinear: act must be 0 none | 1 relu | 2 tanh | 3 sigmoid");
+    STT_REQUIRE(a.ldx >= J && a.ldy >= I && a.ldw >= (trans ? I : J), "sttode_tlinear: leading dimension smaller than the row length");
     if (cols > (trans ? TGEMM_MIN_COLS_BWD : TGEMM_MIN_COLS)) {   // batch sizes: the LDS-tiled kernel (trans: an input gradient)
-        TG g;
-        g.A = X; g.lda = ldx; g.B = W; g.ldb = ldw; g.C = Y; g.ldc = ldy;
-        g.M = cols; g.N = I; g.Kt = J; g.adiv = xdiv; g.bkdiv = 1; g.ones_row = -1;
-        g.avec = a.xvec; g.bvec = a.wvec; g.cvec = a.yvec;
-        g.bias = bias; g.mask = mask; g.ldm = ldm; g.act = act; g.accumulate = accumulate; g.asrc = asrc; g.ldas = ldas; g.acdiv = adiv;
-        g.db = nullptr; g.scratch = nullptr; g.S = 1; g.kchunk = 0; g.mode = 0;
-        g.evec = tg_evec(g); g.fast = tg_fast(g, false, trans != 0); g.dbg = g_tg_dbg;
         // (NB = 2, 64 x 128 tiles, measured SLOWER at the NBA step's shapes -- 36-38 us against 19-25 us per product: 55 KB of LDS leave two
         // workgroups per CU to hide the panel loads instead of four -- and is not instantiated)
-        std::lock_guard<std::mutex> lk(g_red_mu);
-        tg_submit(g, trans ? 1 : 0, (cols + 63) / 64, (I + 63) / 64, 1, stream);
-        STT_HIP(hipGetLastError());
-        return 0;
-    }
-    if (cols <= 1024) {
-        // latency mode: one 16 x 16 block per WG, reduction split over up to 4 waves (128 indices per round trip and wave)
-        const int ksplit = J > 256 ? 4 : (J > 128 ? 2 : 1);
-        const int blocks_per_wg = 4 / ksplit;
-        dim3 grid((cols + 15) / 16, ((I + 15) / 16 + blocks_per_wg - 1) / blocks_per_wg);
-        if (g_grp.on) {   // an open group: queued, leaves with the group's other scene-size layers as one launch
-            std::lock_guard<std::mutex> lk(g_red_mu);
-            ts_submit(a, nullptr, ksplit, (int)grid.x, (int)(grid.x * grid.y), 0, 0, 0, stream);
-            STT_HIP(hipGetLastError());
-            return 0;
+        tg_submit(tg_linear(a, g_tg_dbg), trans ? 1 : 0, (cols + 63) / 64, (I + 63) / 64, 1, stream);
+    } else if (cols <= 1024) {
+        if (g_grp.on) ts_submit(&a, nullptr, stream);   // an open group: queued, leaves with the group's other scene-size layers as one launch
+        else {
+            const TLatPlan lp = tlin_latency_plan(cols, J, I);
+            hipLaunchKernelGGL((tlinear_kernel<1, 1, 8>), dim3(lp.gx, lp.gy), dim3(256), 0, (hipStream_t)stream, a, lp.ksplit);
         }
-        hipLaunchKernelGGL((tlinear_kernel<1, 1, 8>), grid, dim3(256), 0, (hipStream_t)stream, a, ksplit);
     } else if ((long)((cols + 63) / 64) * ((I + 63) / 64) < TLIN_MEDIUM_BELOW) {
         // medium mode: 32 columns x 32 outputs per wave -- 4x the waves of the throughput tiling, for launches that would
         // otherwise leave most SIMDs empty (e.g. 7040 columns x 512 outputs = 880 throughput-mode waves on 1024 SIMDs)
@@ -923,13 +948,12 @@ static int tlinear_impl(const float* X, long ldx, int xdiv, const float* W, long
         dim3 grid((cols + 63) / 64, (I + outs_per_wg - 1) / outs_per_wg);
         hipLaunchKernelGGL((tlinear_kernel<4, 4, 2>), grid, dim3(256), 0, (hipStream_t)stream, a, ksplit);
     }
-    STT_HIP(hipGetLastError());
-    return 0;
+    STT_HIP(hipGetLastError()); return 0;
 }
 extern "C" int sttode_tlinear(const float* X, long ldx, int xdiv, const float* W, long ldw, int trans, const float* bias,
                               const float* mask, long ldm, float* Y, long ldy, int cols, int J, int I, int act, int accumulate,
                               void* stream) {
-    return tlinear_impl(X, ldx, xdiv, W, ldw, trans, bias, mask, ldm, Y, ldy, cols, J, I, act, accumulate, Y, ldy, 1, stream);
+    return tlinear_impl(tlin_fill(X, ldx, xdiv, W, ldw, trans, bias, mask, ldm, Y, ldy, cols, J, I, act, accumulate, Y, ldy, 1), stream);
 }
 // Y[c] = act(W X[c] + tab[c / tdiv] (+ bias)): nn.Linear whose input is cat(shared, own) with the shared part's product -- the same for tdiv
 // consecutive columns -- precomputed as a table (the decoder MLPs' layer 1, model/utils.py:86-95 on cat(past_feature_rep, z, state),
@@ -937,7 +961,7 @@ extern "C" int sttode_tlinear(const float* X, long ldx, int xdiv, const float* W
 extern "C" int sttode_tlinear_tab(const float* X, long ldx, const float* W, long ldw, const float* bias, const float* tab, long ldt, int tdiv,
                                   float* Y, long ldy, int cols, int J, int I, int act, void* stream) {
     STT_REQUIRE(tab && tdiv > 0 && ldt >= I, "sttode_tlinear_tab: bad table");
-    return tlinear_impl(X, ldx, 1, W, ldw, 0, bias, nullptr, 0, Y, ldy, cols, J, I, act, 1, tab, ldt, tdiv, stream);
+    return tlinear_impl(tlin_fill(X, ldx, 1, W, ldw, 0, bias, nullptr, 0, Y, ldy, cols, J, I, act, 1, tab, ldt, tdiv), stream);
 }
 
 extern "C" int sttode_twgrad(const float* dY, long ldy, const float* X, long ldx, int xdiv, float* dW, long ldw, float* db,
@@ -945,37 +969,29 @@ extern "C" int sttode_twgrad(const float* dY, long ldy, const float* X, long ldx
     STT_REQUIRE(dY && X && dW, "sttode_twgrad: null pointer");
     STT_REQUIRE(cols > 0 && N > 0 && K > 0 && xdiv > 0, "sttode_twgrad: cols, N, K, xdiv must be positive");
     STT_REQUIRE(ldy >= N && ldx >= K && ldw >= K, "sttode_twgrad: leading dimension smaller than the row length");
-    TWg a;
-    a.dY = dY; a.X = X; a.dW = dW; a.db = db; a.scratch = scratch;
-    a.ldy = ldy; a.ldx = ldx; a.ldw = ldw; a.cols = cols; a.N = N; a.K = K; a.xdiv = xdiv;
-    const int chunks = (cols + 15) / 16;
-    const long per = (long)N * (K + 1);
     if (cols > TGEMM_MIN_COLS_BWD) {   // batch sizes: the LDS-tiled kernel, reduction over the columns split so that the chip is full
-        std::lock_guard<std::mutex> lk(g_red_mu);
         TG g;
         if (tg_wgrad_fill(g, dY, ldy, X, ldx, xdiv, dW, ldw, db, cols, N, K, scratch, scratch_floats, 480, stream)) {
             tg_submit(g, 2, (N + 63) / 64, (K + 1 + 63) / 64, g.S, stream, dW, ldw, db);
-            STT_HIP(hipGetLastError());
-            return 0;
+            STT_HIP(hipGetLastError()); return 0;
         }
     }
-    int S = chunks <= 64 ? 1 : (chunks + 31) / 32;    // >= 512 columns per split; up to 1024 columns one workgroup per tile (no reduce launch)
-    if (S > 64) S = 64;
-    if (!scratch || per * S > scratch_floats) S = scratch && scratch_floats >= 2 * per ? (int)(scratch_floats / per) : 1;
-    if (S < 1) S = 1;
-    a.S = S;
-    a.chunks_per_split = (chunks + S - 1) / S;
-    dim3 grid((N + 31) / 32, (K + 1 + 31) / 32, S);
-    if (g_grp.on && S == 1 && cols <= 1024) {   // an open group: a weight gradient alone is a layer backward without input-gradient blocks
-        std::lock_guard<std::mutex> lk(g_red_mu);
-        ts_submit(TLin{}, &a, 1, 1, 0, (int)grid.x, (int)grid.y, (int)(grid.x * grid.y), stream);
-        STT_HIP(hipGetLastError());
-        return 0;
+    TWg w;
+    const dim3 grid = twg_fill(w, dY, ldy, X, ldx, xdiv, dW, ldw, db, cols, N, K, scratch, scratch_floats);
+    if (g_grp.on && cols <= 1024) {   // an open group: a weight gradient alone is a layer backward without input-gradient blocks
+        ts_submit(nullptr, &w, stream);
+        STT_HIP(hipGetLastError()); return 0;
     }
-    hipLaunchKernelGGL(twgrad_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
-    if (S > 1) hipLaunchKernelGGL(twgrad_reduce_kernel, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-    STT_HIP(hipGetLastError());
-    return 0;
+    hipLaunchKernelGGL(twgrad_kernel, grid, dim3(256), 0, (hipStream_t)stream, w);
+    // The generic kernel's own split, S > 1, is left with ONE case.  Up to 600 columns there are at most 38 chunks of 16 and one split; above,
+    // this line is reached only when tg_wgrad_fill found no room for one gradient's partial sums.  Without deferral that room is the call's
+    // scratch, and twg_fill's test of the same scratch gives S = 1.  With deferral it is the deferral buffer, which is out of room with
+    // nothing pending or queued to flush only after sttode_tgemm_group(-1) forgot a group's split gradients (their pieces stay reserved
+    // until the bracket ends or is abandoned); a gradient of more than 1024 columns issued in that state splits over the call's scratch.
+    // The training engine never gets here: it follows group(-1) with sttode_twgrad_defer(-1), which frees the pieces.  Only a caller of
+    // the C entry points that goes on inside the bracket does.
+    if (w.S > 1) hipLaunchKernelGGL(twgrad_reduce_kernel, dim3((unsigned)(((long)N * (K + 1) + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w);
+    STT_HIP(hipGetLastError()); return 0;
 }
 
 // Backward of one nn.Linear in (at most) two launches: dX = mask(dY W[:, :Kdx] (+ dX)) and dW += dY^T X, db += sum dY.
@@ -985,66 +1001,39 @@ extern "C" int sttode_tlinear_bwd(const float* dY, long ldy, const float* W, lon
                                   float* db, int cols, int N, int K, float* scratch, long scratch_floats, void* stream) {
     STT_REQUIRE(dY && W && dX && X && dW, "sttode_tlinear_bwd: null pointer");
     STT_REQUIRE(cols > 0 && N > 0 && K > 0 && Kdx > 0 && Kdx <= K && xdiv > 0, "sttode_tlinear_bwd: bad sizes");
-    if (cols > TGEMM_MIN_COLS_BWD && xdiv == 1) {   // batch sizes: both products of the layer's backward in ONE launch
+    if (xdiv == 1) {   // (broadcast rows: the two stand-alone entry points, with their own checks)
         STT_REQUIRE(ldy >= N && ldx >= K && ldgw >= K && ldw >= K && lddx >= Kdx, "sttode_tlinear_bwd: leading dimension smaller than the row length");
-        std::lock_guard<std::mutex> lk(g_red_mu);
-        TG gx;
-        gx.A = dY; gx.lda = ldy; gx.B = W; gx.ldb = ldw; gx.C = dX; gx.ldc = lddx;
-        gx.M = cols; gx.N = Kdx; gx.Kt = N; gx.adiv = 1; gx.bkdiv = 1; gx.ones_row = -1;
-        gx.avec = aligned16(dY, ldy); gx.bvec = aligned16(W, ldw); gx.cvec = aligned16(dX, lddx);
-        gx.bias = nullptr; gx.mask = mask; gx.ldm = ldm; gx.act = 0; gx.accumulate = accumulate; gx.asrc = dX; gx.ldas = lddx; gx.acdiv = 1;
-        gx.db = nullptr; gx.scratch = nullptr; gx.S = 1; gx.kchunk = 0; gx.mode = 0;
-        gx.evec = tg_evec(gx); gx.fast = tg_fast(gx, false, true); gx.dbg = nullptr;
-        const int gxx = (cols + 63) / 64, nx = gxx * ((Kdx + 63) / 64);
-        TG gw;
-        if (tg_wgrad_fill(gw, dY, ldy, X, ldx, 1, dW, ldgw, db, cols, N, K, scratch, scratch_floats,
-                          g_grp.on ? 400 : (nx < 680 ? 1000 - nx : 320), stream)) {
-            const int gxw = (N + 63) / 64, gyw = (K + 1 + 63) / 64, nw = gxw * gyw * gw.S;
-            if (g_grp.on) {   // (an open group: the two products join it as two of its problems)
-                tg_submit(gw, 2, gxw, gyw, gw.S, stream, dW, ldgw, db);
-                tg_submit(gx, 1, gxx, (Kdx + 63) / 64, 1, stream);
-            } else {
-                hipLaunchKernelGGL(tgemm_bwd_kernel, dim3(nw + nx), dim3(256), 0, (hipStream_t)stream, gw, gxw, gyw, nw, gx, gxx);
-                tg_wgrad_done(gw, dW, ldgw, db);
+        const TLin a = tlin_fill(dY, ldy, 1, W, ldw, 1, nullptr, mask, ldm, dX, lddx, cols, N, Kdx, 0, accumulate, dX, lddx, 1);   // the input gradient
+        if (cols > TGEMM_MIN_COLS_BWD) {   // batch sizes: both products of the layer's backward in ONE launch
+            const TG gx = tg_linear(a, nullptr);
+            TG gw;
+            const int gxx = (cols + 63) / 64, gyx = (Kdx + 63) / 64, nx = gxx * gyx;
+            if (tg_wgrad_fill(gw, dY, ldy, X, ldx, 1, dW, ldgw, db, cols, N, K, scratch, scratch_floats,
+                              g_grp.on ? 400 : (nx < 680 ? 1000 - nx : 320), stream)) {
+                const int gxw = (N + 63) / 64, gyw = (K + 1 + 63) / 64, nw = gxw * gyw * gw.S;
+                if (g_grp.on) {   // (an open group: the two products join it as two of its problems)
+                    tg_submit(gw, 2, gxw, gyw, gw.S, stream, dW, ldgw, db);
+                    tg_submit(gx, 1, gxx, gyx, 1, stream);
+                } else {
+                    hipLaunchKernelGGL(tgemm_bwd_kernel, dim3(nw + nx), dim3(256), 0, (hipStream_t)stream, gw, gxw, gyw, nw, gx, gxx);
+                    tg_wgrad_done(gw, dW, ldgw, db);
+                }
+                STT_HIP(hipGetLastError()); return 0;
             }
-            STT_HIP(hipGetLastError());
-            return 0;
+        }
+        if (cols <= 1024) {   // scene sizes: input-gradient blocks, then weight-gradient blocks (one split: at most 64 chunks of 16 columns)
+            TWg w;
+            const dim3 gridW = twg_fill(w, dY, ldy, X, ldx, 1, dW, ldgw, db, cols, N, K, scratch, scratch_floats);
+            if (g_grp.on) ts_submit(&a, &w, stream);
+            else {
+                const TLatPlan lp = tlin_latency_plan(cols, N, Kdx);
+                const int nA = lp.gx * lp.gy;
+                hipLaunchKernelGGL(tbwd_kernel, dim3(nA + gridW.x * gridW.y), dim3(256), 0, (hipStream_t)stream, a, lp.ksplit, lp.gx, nA, w,
+                                   (int)gridW.x, (int)gridW.y);
+            }
+            STT_HIP(hipGetLastError()); return 0;
         }
     }
-    if (cols > 1024 || xdiv != 1) {
-        if (int rc = sttode_tlinear(dY, ldy, 1, W, ldw, 1, nullptr, mask, ldm, dX, lddx, cols, N, Kdx, 0, accumulate, stream)) return rc;
-        return sttode_twgrad(dY, ldy, X, ldx, xdiv, dW, ldgw, db, cols, N, K, scratch, scratch_floats, stream);
-    }
-    STT_REQUIRE(ldy >= N && ldx >= K && ldgw >= K && ldw >= K && lddx >= Kdx, "sttode_tlinear_bwd: leading dimension smaller than the row length");
-    TLin a;
-    a.X = dY; a.W = W; a.bias = nullptr; a.mask = mask; a.Y = dX;
-    a.ldx = ldy; a.ldw = ldw; a.ldy = lddx; a.ldm = ldm;
-    a.cols = cols; a.J = N; a.I = Kdx; a.trans = 1; a.act = 0; a.accumulate = accumulate; a.xdiv = 1; a.asrc = dX; a.ldas = lddx; a.adiv = 1;
-    a.xvec = aligned16(dY, ldy); a.wvec = aligned16(W, ldw); a.yvec = aligned16(dX, lddx);
-    a.evec = Kdx % 4 == 0 && a.yvec && (!mask || aligned16(mask, ldm));
-    const int ksplit = N > 256 ? 4 : (N > 128 ? 2 : 1);
-    const int blocks_per_wg = 4 / ksplit;
-    const int gxA = (cols + 15) / 16, gyA = ((Kdx + 15) / 16 + blocks_per_wg - 1) / blocks_per_wg;
-    TWg w;
-    w.dY = dY; w.X = X; w.dW = dW; w.db = db; w.scratch = scratch;
-    w.ldy = ldy; w.ldx = ldx; w.ldw = ldgw; w.cols = cols; w.N = N; w.K = K; w.xdiv = 1;
-    const int chunks = (cols + 15) / 16;
-    const long per = (long)N * (K + 1);
-    int S = chunks <= 64 ? 1 : (chunks + 31) / 32;
-    if (!scratch || per * S > scratch_floats) S = scratch && scratch_floats >= 2 * per ? (int)(scratch_floats / per) : 1;
-    if (S < 1) S = 1;
-    w.S = S;
-    w.chunks_per_split = (chunks + S - 1) / S;
-    const int gxW = (N + 31) / 32, gyW = (K + 1 + 31) / 32;
-    const int nA = gxA * gyA, nB = gxW * gyW * S;
-    if (g_grp.on && S == 1) {
-        std::lock_guard<std::mutex> lk(g_red_mu);
-        ts_submit(a, &w, ksplit, gxA, nA, gxW, gyW, nB, stream);
-        STT_HIP(hipGetLastError());
-        return 0;
-    }
-    hipLaunchKernelGGL(tbwd_kernel, dim3(nA + nB), dim3(256), 0, (hipStream_t)stream, a, ksplit, gxA, nA, w, gxW, gyW);
-    if (S > 1) hipLaunchKernelGGL(twgrad_reduce_kernel, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w);
-    STT_HIP(hipGetLastError());
-    return 0;
+    if (int rc = sttode_tlinear(dY, ldy, 1, W, ldw, 1, nullptr, mask, ldm, dX, lddx, cols, N, Kdx, 0, accumulate, stream)) return rc;
+    return sttode_twgrad(dY, ldy, X, ldx, xdiv, dW, ldgw, db, cols, N, K, scratch, scratch_floats, stream);
 }

@@ -8,7 +8,6 @@
 // bound by the NUMBER of launches.  Here one workgroup (4 waves) owns a 16-agent tile, wave w computes output row tile w of
 // every layer from the row-major nn.Parameter storage (an A fragment of v_mfma_f32_16x16x4_f32 is a float4 of a weight row), tiles are
 // exchanged through LDS, and every tensor the backward pass needs is written on the way -- the same tape trunk_bwd reads.
-#include <mutex>
 #include "chain.hpp"
 #include "ode_body.hpp"
 #include "api_util.hpp"
@@ -313,17 +312,16 @@ __global__ __launch_bounds__(256) void ttrunk_fwd2_kernel(TrunkArgs a0, TrunkArg
 }
 
 // group mode (sttode_tgemm_group -> stt_trunk_group): a trunk launch waits for a second one of the same group
-static thread_local struct { TrunkArgs a; size_t lds; void* stream; bool have, on; } g_tq = {};   // (per host thread, like the group state of train_gemm.hip)
-static std::mutex g_tq_mu;
-static void tq_flush_locked() {
+// (g_tq belongs to the calling host thread, like the group state of train_gemm.hip: another thread's calls neither see it nor wait for it)
+static thread_local struct { TrunkArgs a; size_t lds; void* stream; bool have, on; } g_tq = {};
+static void tq_flush() {
     if (!g_tq.have) return;
     g_tq.have = false;
     hipLaunchKernelGGL(ttrunk_fwd_kernel, dim3((g_tq.a.n + 15) / 16), dim3(256), g_tq.lds, (hipStream_t)g_tq.stream, g_tq.a);
 }
 int stt_trunk_group(int on) {
-    std::lock_guard<std::mutex> lk(g_tq_mu);
     if (on < 0) g_tq.have = false;
-    tq_flush_locked();
+    tq_flush();
     g_tq.on = on > 0;
     STT_HIP(hipGetLastError());
     return 0;
@@ -340,7 +338,6 @@ extern "C" int sttode_ttrunk_fwd(const void* const* ptrs, int count, int n, int 
         STT_REQUIRE(a.p[i] || i == STT_TT_DROP || i == STT_TT_LAST || (i == STT_TT_ATTN && phase != 2), "sttode_ttrunk_fwd: null pointer in the table");
     }
     a.n = n; a.T = T; a.ld_feat = ld_feat; a.ode_time = ode_time; a.phase = phase;
-    std::lock_guard<std::mutex> lk(g_tq_mu);
     if (g_tq.on && g_tq.have && g_tq.stream == stream) {   // the group's second trunk: both in one launch
         g_tq.have = false;
         const int n0 = (g_tq.a.n + 15) / 16;
@@ -349,7 +346,7 @@ extern "C" int sttode_ttrunk_fwd(const void* const* ptrs, int count, int n, int 
         STT_HIP(hipGetLastError());
         return 0;
     }
-    tq_flush_locked();
+    tq_flush();
     if (g_tq.on) { g_tq.a = a; g_tq.lds = lds; g_tq.stream = stream; g_tq.have = true; return 0; }
     hipLaunchKernelGGL(ttrunk_fwd_kernel, dim3((n + 15) / 16), dim3(256), lds, (hipStream_t)stream, a);
     STT_HIP(hipGetLastError());
@@ -441,10 +438,7 @@ extern "C" int sttode_ttrunk_ode_fwd(const void* const* ptrs, int count, int tru
         if (k == 0) a.tiles0 = (n[k] + 15) / 16;
         tiles += (n[k] + 15) / 16;
     }
-    {
-        std::lock_guard<std::mutex> lk(g_tq_mu);
-        tq_flush_locked();                                   // (a fused trunk queued by an open group runs first)
-    }
+    tq_flush();                                              // (a fused trunk queued by an open group runs first)
     if (a.p.stages == 1) hipLaunchKernelGGL(ttrunk_ode_fwd_kernel<1>, dim3(tiles), dim3(256), lds, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(ttrunk_ode_fwd_kernel<4>, dim3(tiles), dim3(256), lds, (hipStream_t)stream, a);
     STT_HIP(hipGetLastError());

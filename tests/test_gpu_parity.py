@@ -2048,6 +2048,40 @@ def test_sampler_loss_kernel_general_prior_and_scales():
         assert_close(div.cpu().numpy(), ref_d.numpy(), rtol=1e-4, atol=1e-6, what='div ' + ds)
 
 
+def _twgrad_generic_split_case(capi, dev, rng, scratch, st, cols, N, K):
+    """The one case in which the GENERIC weight gradient still splits its columns (sttode_twgrad's reduction launch; 3001 columns: 188
+    chunks of 16, 6 splits): an abandoned group's split gradient keeps the whole deferral buffer reserved, nothing is pending or queued
+    that a flush could free, and the next gradient finds no room there and splits over the call's scratch."""
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+    S = ((cols + 15) // 16 + 31) // 32
+    per = N * (K + 1)
+    assert cols > 1024 and S > 1 and S * per < scratch.numel()
+    dY, Xw = rng.standard_normal((cols, N)).astype(np.float32), rng.standard_normal((cols, K + 5)).astype(np.float32)
+    gW0, gb0 = rng.standard_normal((N, K)).astype(np.float32), rng.standard_normal(N).astype(np.float32)
+    X = t(Xw)[:, :K]
+    buf = torch.zeros(2 * per, device=dev)
+    gWa, gba, gW, gb = t(gW0), t(gb0), t(gW0), t(gb0)
+    scratch.zero_()
+    try:
+        capi.call('sttode_twgrad_defer', 1, buf, buf.numel())
+        capi.call('sttode_tgemm_group', 1)
+        capi.call('sttode_twgrad', t(dY), N, X, X.stride(0), 1, gWa, K, gba, cols, N, K, scratch, scratch.numel(), st)   # queued, 2 splits reserved
+        capi.call('sttode_tgemm_group', -1)
+        capi.call('sttode_twgrad', t(dY), N, X, X.stride(0), 1, gW, K, gb, cols, N, K, scratch, scratch.numel(), st)
+        capi.call('sttode_twgrad_defer', 0, None, 0)
+        torch.cuda.synchronize()
+    finally:
+        capi.call('sttode_tgemm_group', -1)
+        capi.call('sttode_twgrad_defer', -1, None, 0)
+    assert (buf == 0).all() and (scratch[(S - 1) * per:S * per] != 0).any() and (scratch[S * per:] == 0).all(), \
+        f'not the generic kernel with {S} column splits in the call\'s scratch'
+    assert np.array_equal(gWa.cpu().numpy(), gW0) and np.array_equal(gba.cpu().numpy(), gb0), 'the abandoned gradient ran'
+    tol = 1e-5 * max(1.0, np.sqrt(cols))
+    assert_close(gW.cpu().numpy(), dY.astype(np.float64).T @ Xw[:, :K].astype(np.float64) + gW0, rtol=1e-5, atol=tol,
+                 what='twgrad dW, generic kernel with split columns')
+    assert_close(gb.cpu().numpy(), dY.astype(np.float64).sum(0) + gb0, rtol=1e-5, atol=tol, what='twgrad db, generic kernel with split columns')
+
+
 def test_tlinear_and_twgrad_vs_torch():
     """Generic training kernels: forward / input-gradient / weight-gradient of nn.Linear at the model's awkward shapes
     (K = 4, 67; N = 24; ragged columns; broadcast rows; strided views; relu mask; accumulation; >1 column split)."""
@@ -2090,6 +2124,7 @@ def test_tlinear_and_twgrad_vs_torch():
         tol = 1e-5 * max(1.0, np.sqrt(cols))
         assert_close(gW.cpu().numpy(), refW, rtol=1e-5, atol=tol, what=f'twgrad dW {cols}')
         assert_close(gb.cpu().numpy(), refb, rtol=1e-5, atol=tol, what=f'twgrad db {cols}')
+    _twgrad_generic_split_case(capi, dev, rng, scratch, st, cols=3001, N=70, K=67)
 
 
 @pytest.mark.gpu

@@ -635,6 +635,51 @@ def test_group_and_deferred_reduction_error_paths_forget_what_is_queued():
         capi.call('sttode_twgrad_defer', -1, None, 0)
 
 
+def test_an_open_group_belongs_to_the_host_thread_that_opened_it():
+    """The queues of a group are per host thread and nothing locks them: while the main thread's group is open with one scene-size product
+    queued, the same product and an element-wise fill issued by ANOTHER thread run at once on that thread's current stream -- they are not
+    queued behind the main thread's group, do not launch what it queued and do not wait for it.  Closing the group then runs the queued
+    product, bit for bit the other thread's."""
+    import threading
+    capi, dev = _capi(), _gpu()
+    rng = np.random.default_rng(25)
+    cols, J, I, n_fill = 37, 67, 64, 1283
+    Xb = torch.from_numpy(rng.standard_normal((cols, J + 3)).astype(np.float32)).to(dev)
+    X = Xb[:, :J]                                                                                  # a strided view (ld J + 3)
+    W = torch.from_numpy((rng.standard_normal((I, J)) / np.sqrt(J)).astype(np.float32)).to(dev)
+    b = torch.from_numpy((0.5 * rng.standard_normal(I)).astype(np.float32)).to(dev)
+    Y1, Y2 = _sent(dev, cols, I), _sent(dev, cols, I)
+    fill = torch.full((n_fill + 5,), SENT, device=dev)
+    tlinear = lambda Y: capi.call('sttode_tlinear', X, X.stride(0), 1, W, J, 0, b, None, 0, Y, Y.stride(0), cols, J, I, 2, 0, capi.stream_ptr())
+    failed = []
+
+    def other():
+        try:
+            tlinear(Y2)
+            capi.call('sttode_train_ewise', R.EW_OPS['FILL'], fill, None, None, None, None, n_fill, 0, 2.5, capi.stream_ptr())
+            torch.cuda.synchronize()
+        except BaseException as e:                         # (reported by the main thread)
+            failed.append(e)
+
+    capi.call('sttode_tgemm_group', 1)
+    try:
+        tlinear(Y1)                                        # queued
+        th = threading.Thread(target=other)
+        th.start()
+        th.join()
+        assert not failed, failed
+        a32 = [X.cpu(), W.cpu(), b.cpu(), torch.zeros(cols, I)]
+        _worst('tlinear from a second host thread', _close(Y2[:, :I], R.tlinear_tab(*[v.double() for v in a32], 1, 2), R.tlinear_tab(*a32, 1, 2),
+                                                           'tlinear from a thread without a group'))
+        assert (Y2[:, I:] == SENT).all()
+        assert (fill[:n_fill] == 2.5).all() and (fill[n_fill:] == SENT).all(), 'the other thread\'s fill was queued, or wrote past its count'
+        assert (Y1 == SENT).all(), 'the other thread launched (or the open group did not queue) the main thread\'s product'
+    finally:
+        capi.call('sttode_tgemm_group', 0)
+        torch.cuda.synchronize()
+    assert torch.equal(Y1, Y2)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # row shuffles: bitwise
 # ---------------------------------------------------------------------------------------------------------------------------------------
