@@ -519,6 +519,23 @@ int sttode_pmath_pair(int which, const float* x, const float* y, const float* A,
                       void* stream);
 /* poincare_mean over dim 0 (pmath.py:472-479): x [rows,d] -> out [d]; workspaces yl_ws [rows,d], lam_ws [rows]. */
 int sttode_pmath_mean(const float* x, float* yl_ws, float* lam_ws, float* out, int rows, int d, float c, void* stream);
+/* Backward passes (csrc/pmath_grad.hip; added within ABI version 14).  Gradients are WRITTEN, not accumulated.
+ * Row ops 0..11: g is the upstream gradient, [rows,d] for vector results and [rows] for the scalar results (lambda_x, dist, dist0,
+ * lorenz_factor); gx [rows,d]; gy [rows,d] is required exactly for the four two-operand ops (mobius_add, dist, expmap, logmap) and must be
+ * NULL otherwise.  Op 12 (Oblique.proj) and the internal codes 13/14 are refused.  One launch, no workspace; only x, y, g are read. */
+int sttode_pmath_rowop_bwd(int op, const float* x, const float* y, const float* g, float* gx, float* gy, int rows, int d, float c, void* stream);
+/* mobius_matvec backward: m [O,d], x [rows,d], g [rows,O] -> gx [rows,d], gm [O,d] (zeroed here first).  Workspaces mx_ws [rows,O] (x m^T is
+ * recomputed into it by sttode_tlinear; afterwards it holds the split sums of sttode_twgrad), gmx_ws [rows,O] (gradient with respect to
+ * x m^T).  gxn_ws [rows] is not a workspace of the computation but an unused OUTPUT: the gradient with respect to |x| per row is written to
+ * it once and read by nothing (the row kernel puts that term into gx itself); it must not be NULL.  _project's branch is chosen by a float64
+ * test on the recomputed x m^T and can differ from the forward kernel's fp32 choice for a row within fp32 rounding of the maximal norm.  gx = gmx m + gxn x / |x| (sttode_tlinear, trans = 1), gm = gmx^T x (sttode_twgrad).
+ * Not inside a sttode_tgemm_group bracket.  DEVIATION from the reference: a row with x m^T == 0 gets a zero gradient (the reference: NaN). */
+int sttode_pmath_matvec_bwd(const float* m, const float* x, const float* g, float* mx_ws, float* gmx_ws, float* gxn_ws, float* gx, float* gm,
+                            int rows, int d, int O, float c, void* stream);
+/* dist_matrix backward: x [P,d], y [R,d], g [P,R] -> gx [P,d], gy [R,d].  Two launches (one wave per x row, one wave per y row), sums in a
+ * fixed order: bitwise repeatable, no atomics. */
+int sttode_pmath_dist_matrix_bwd(const float* x, const float* y, const float* g, float* gx, float* gy, int P, int R, int d, float c,
+                                 void* stream);
 /* Oblique.dist (core/manifolds/oblique.py:36-43): p1 [nb,n1,d], p2 [nb,n2,d] -> acos(clamp(p2 p1^T)) [nb,n2,n1]. */
 int sttode_oblique_dist(const float* p1, const float* p2, float* out, int nb, int n1, int n2, int d, void* stream);
 

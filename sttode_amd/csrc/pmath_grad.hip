@@ -1,0 +1,304 @@
+// Backward passes of the Poincare-ball primitives of pmath.hip (hyptorch/pmath.py): one fused kernel per operation, against the few dozen
+// autograd nodes -- and their live intermediates -- that the reference builds per call.
+//
+// Every row-op result is out = alpha x + beta y with alpha, beta functions of the row scalars p = (|x|^2, |y|^2, <x,y>) and c (dist / logmap:
+// |(-x) (+) y|^2 = A^2 p1 - 2 A B p3 + B^2 p2 is itself a closed form in p), or a scalar s(p).  The vector-Jacobian product is therefore
+//     gx = alpha g + 2 x L1 + y L3,   gy = beta g + 2 y L2 + x L3,   L_k = d alpha/d p_k <g,x> + d beta/d p_k <g,y>
+// (scalar results: g ds/dp_k in place of L_k, no alpha g / beta g term): ONE WAVE PER ROW, four rows per 256-thread block, as the forward
+// kernel.  Pass 1 forms the five dot products in one sweep (float64 accumulators, wavefront xor-shuffles), the per-row scalar stage runs
+// redundantly on all lanes, pass 2 writes gx and gy with coalesced stores.  No atomics, no LDS, no workspace; only x, y, g are read.
+//
+// The scalar stage is float64 forward-mode arithmetic (struct D3: a value and its three partials d/dp_k): 1 - c |x|^2, 1 - u^2 under artanh
+// and the Moebius denominator cancel near the ball boundary (pmath.hip's pair kernel and OP_PMEAN_PREP use float64 for the same reason).
+// The stage is a few hundred float64 operations per row, tanh / log1p / sqrt among them, redundantly on 64 lanes (dist_matrix: once per
+// pair); it is EXPECTED to stay below the row's memory traffic, and has not been timed.
+// The primitives carry the derivative that the reference's autograd gives, not the textbook one:
+//   * norm: 0 at a zero row (torch's subgradient), so a zero row of expmap0 / logmap0 gets g times the constant factor;
+//   * clamp_min(1e-5) / tanh's clamp at 15: the gradient passes where the argument is inside (bounds included), else 0;
+//   * artanh: value at the clamped argument, derivative 1 / (1 - x_clamped^2) (Artanh.backward, pmath.py:25-27) -- NOT zero outside the clamp;
+//   * project: the clipped branch gets the gradient of maxnorm x / |x|; the branch is chosen by the forward kernel's own fp32 test;
+//   * the + 1e-5 of the Moebius denominator.
+#include "api_util.hpp"
+#include "train_group.hpp"
+
+extern "C" int sttode_tlinear(const float* X, long ldx, int xdiv, const float* W, long ldw, int trans, const float* bias, const float* mask,
+                              long ldm, float* Y, long ldy, int cols, int J, int I, int act, int accumulate, void* stream);
+extern "C" int sttode_twgrad(const float* dY, long ldy, const float* X, long ldx, int xdiv, float* dW, long ldw, float* db, int cols, int N,
+                             int K, float* scratch, long scratch_floats, void* stream);
+extern "C" int sttode_twgrad_flush(void);
+
+namespace {
+
+enum { OPB_PROJECT = 0, OPB_LAMBDA_X, OPB_MOBIUS_ADD, OPB_DIST, OPB_DIST0, OPB_EXPMAP, OPB_EXPMAP0, OPB_LOGMAP, OPB_LOGMAP0, OPB_P2K, OPB_K2P,
+       OPB_LORENZ, OPB_COUNT };   // == the first twelve codes of pmath.hip's PmathOp (include/sttode_hip.h)
+
+constexpr double EPS5 = (double)1e-5f;   // the reference's 1e-5, as the forward kernels round it
+
+// value + partials with respect to the three row scalars
+struct D3 { double v, d[3]; };
+__device__ __forceinline__ D3 var(double v, int k) { D3 r{v, {0., 0., 0.}}; r.d[k] = 1.; return r; }
+__device__ __forceinline__ D3 cst(double v) { return D3{v, {0., 0., 0.}}; }
+__device__ __forceinline__ D3 operator+(const D3& a, const D3& b) { return D3{a.v + b.v, {a.d[0] + b.d[0], a.d[1] + b.d[1], a.d[2] + b.d[2]}}; }
+__device__ __forceinline__ D3 operator-(const D3& a, const D3& b) { return D3{a.v - b.v, {a.d[0] - b.d[0], a.d[1] - b.d[1], a.d[2] - b.d[2]}}; }
+__device__ __forceinline__ D3 operator*(const D3& a, const D3& b) {
+    return D3{a.v * b.v, {a.d[0] * b.v + a.v * b.d[0], a.d[1] * b.v + a.v * b.d[1], a.d[2] * b.v + a.v * b.d[2]}};
+}
+__device__ __forceinline__ D3 operator/(const D3& a, const D3& b) {
+    const double q = a.v / b.v, ib = 1.0 / b.v;
+    return D3{q, {(a.d[0] - q * b.d[0]) * ib, (a.d[1] - q * b.d[1]) * ib, (a.d[2] - q * b.d[2]) * ib}};
+}
+__device__ __forceinline__ D3 operator+(double a, const D3& b) { return D3{a + b.v, {b.d[0], b.d[1], b.d[2]}}; }
+__device__ __forceinline__ D3 operator-(double a, const D3& b) { return D3{a - b.v, {-b.d[0], -b.d[1], -b.d[2]}}; }
+__device__ __forceinline__ D3 operator*(double a, const D3& b) { return D3{a * b.v, {a * b.d[0], a * b.d[1], a * b.d[2]}}; }
+__device__ __forceinline__ D3 operator/(double a, const D3& b) { return cst(a) / b; }
+__device__ __forceinline__ D3 operator*(const D3& a, double b) { return b * a; }
+__device__ __forceinline__ D3 operator/(const D3& a, double b) { return (1.0 / b) * a; }
+__device__ __forceinline__ D3 chain(double v, double dv, const D3& a) { return D3{v, {dv * a.d[0], dv * a.d[1], dv * a.d[2]}}; }
+// x.norm(): sqrt of a sum of squares, derivative 0 at a zero row
+__device__ __forceinline__ D3 norm_of(const D3& sq) { const double n = sqrt(sq.v); return chain(n, n > 0. ? 0.5 / n : 0., sq); }
+__device__ __forceinline__ D3 sqrt_(const D3& a) { const double n = sqrt(a.v); return chain(n, 0.5 / n, a); }
+__device__ __forceinline__ D3 clamp_min_(const D3& a, double lo) { return a.v >= lo ? a : cst(lo); }
+__device__ __forceinline__ D3 tanh_clamped_(const D3& a) {   // pmath.py:11-12
+    const bool in = a.v >= -15.0 && a.v <= 15.0;
+    const double t = tanh(fmin(fmax(a.v, -15.0), 15.0));
+    return chain(t, in ? 1.0 - t * t : 0., a);
+}
+__device__ __forceinline__ D3 artanh_d(const D3& a) {        // pmath.py:16-27
+    const double xc = fmin(fmax(a.v, -1.0 + EPS5), 1.0 - EPS5);
+    return chain(0.5 * (log1p(xc) - log1p(-xc)), 1.0 / (1.0 - xc * xc), a);
+}
+
+__device__ __forceinline__ double wsum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ float wsumf(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// _mobius_add(a, b) = (ca a + cb b) / den from the row scalars of its operands (pmath.py:171-177)
+struct MobD { D3 ca, cb; };
+__device__ __forceinline__ MobD mob_d(const D3& a2, const D3& b2, const D3& ab, double c) {
+    const D3 den = 1.0 + 2.0 * c * ab + (c * c) * (a2 * b2) + cst(EPS5);
+    return MobD{(1.0 + 2.0 * c * ab + c * b2) / den, (1.0 - c * a2) / den};
+}
+// (-x) (+) y = A (-x) + B y and its norm (pmath.py:207, :335-336)
+struct SubD { D3 A, B, sn; };
+__device__ __forceinline__ SubD sub_d(const D3& p1, const D3& p2, const D3& p3, double c) {
+    const MobD m = mob_d(p1, p2, -1.0 * p3, c);
+    return SubD{m.ca, m.cb, norm_of(m.ca * m.ca * p1 - 2.0 * (m.ca * m.cb * p3) + m.cb * m.cb * p2)};
+}
+// dist(x, y) (pmath.py:205-208) as a function of p = (|x|^2, |y|^2, <x,y>)
+__device__ __forceinline__ D3 dist_d(double x2, double y2, double xy, double c) {
+    const double sc = sqrt(c);
+    const SubD s = sub_d(var(x2, 0), var(y2, 1), var(xy, 2), c);
+    return (2.0 / sc) * artanh_d(sc * s.sn);
+}
+
+// ---- row ops --------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void pmath_row_bwd_kernel(int op, const float* __restrict__ x, const float* __restrict__ y,
+                                                            const float* __restrict__ g, float* __restrict__ gx, float* __restrict__ gy,
+                                                            int rows, int d, float cf) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const bool scalar = op == OPB_LAMBDA_X || op == OPB_DIST || op == OPB_DIST0 || op == OPB_LORENZ;
+    const float* xr = x + (size_t)r * d;
+    const float* yr = y ? y + (size_t)r * d : nullptr;
+    const float* gr = scalar ? nullptr : g + (size_t)r * d;
+    double x2 = 0., y2 = 0., xy = 0., gxd = 0., gyd = 0.;
+    float x2f = 0.f;   // project's branch: the forward kernel's own fp32 sum, same order
+    for (int i = lane; i < d; i += 64) {
+        const float af = xr[i];
+        const double a = af, gi = gr ? (double)gr[i] : 0.;
+        x2f += af * af;
+        x2 += a * a; gxd += gi * a;
+        if (yr) { const double b = yr[i]; y2 += b * b; xy += a * b; gyd += gi * b; }
+    }
+    x2 = wsum(x2); y2 = wsum(y2); xy = wsum(xy); gxd = wsum(gxd); gyd = wsum(gyd); x2f = wsumf(x2f);
+    const double c = cf, sc = sqrt(c);
+    const D3 p1 = var(x2, 0), p2 = var(y2, 1), p3 = var(xy, 2);
+    D3 al = cst(0.), be = cst(0.);   // vector results: alpha, beta; scalar results: al = s
+    switch (op) {
+        case OPB_PROJECT: {  // pmath.py:98-103
+            const float normf = fmaxf(sqrtf(x2f), 1e-5f), maxnormf = (1.0f - 1e-3f) / sqrtf(cf);
+            const D3 norm = clamp_min_(norm_of(p1), EPS5);
+            al = normf > maxnormf ? ((1.0 - 1e-3) / sc) / norm : cst(1.0);
+        } break;
+        case OPB_LAMBDA_X: al = 2.0 / (1.0 - c * p1); break;   // pmath.py:128-129
+        case OPB_MOBIUS_ADD: { const MobD m = mob_d(p1, p2, p3, c); al = m.ca; be = m.cb; } break;
+        case OPB_DIST: al = dist_d(x2, y2, xy, c); break;
+        case OPB_LOGMAP: {   // pmath.py:334-339 : 2 / sqrt_c / lambda_x * artanh(sqrt_c |sub|) * sub / |sub|
+            const SubD s = sub_d(p1, p2, p3, c);
+            const D3 k = (1.0 - c * p1) / sc * artanh_d(sc * s.sn) / s.sn;
+            al = -1.0 * (k * s.A); be = k * s.B;
+        } break;
+        case OPB_DIST0: al = (2.0 / sc) * artanh_d(sc * norm_of(p1)); break;   // pmath.py:231-234
+        case OPB_EXPMAP: {   // pmath.py:268-277, y = u
+            const D3 un = clamp_min_(norm_of(p2), EPS5);
+            const D3 lam = 2.0 / (1.0 - c * p1);
+            const D3 s = tanh_clamped_((sc / 2.0) * lam * un) / (sc * un);   // second_term = s u
+            const MobD m = mob_d(p1, s * s * p2, s * p3, c);
+            al = m.ca; be = m.cb * s;
+        } break;
+        case OPB_EXPMAP0: {  // pmath.py:300-304
+            const D3 un = clamp_min_(norm_of(p1), EPS5);
+            al = tanh_clamped_(sc * un) / (sc * un);
+        } break;
+        case OPB_LOGMAP0: {  // pmath.py:365-368
+            const D3 yn = clamp_min_(norm_of(p1), EPS5);
+            al = 1.0 / yn / sc * artanh_d(sc * yn);
+        } break;
+        case OPB_P2K: al = 2.0 / (1.0 + c * p1); break;                  // pmath.py:440-442
+        case OPB_K2P: al = 1.0 / (1.0 + sqrt_(1.0 - c * p1)); break;     // pmath.py:445-447
+        case OPB_LORENZ: al = 1.0 / sqrt_(1.0 - c * p1); break;          // pmath.py:450-469
+    }
+    // gx = ag g + ax x + ay y ; gy = bg g + by y + bx x
+    double ag, ax, ay, bg, by, bx;
+    if (scalar) {
+        const double gs = g[r];
+        ag = 0.; ax = 2.0 * gs * al.d[0]; ay = gs * al.d[2];
+        bg = 0.; by = 2.0 * gs * al.d[1]; bx = ay;
+    } else {
+        const double L1 = al.d[0] * gxd + be.d[0] * gyd, L2 = al.d[1] * gxd + be.d[1] * gyd, L3 = al.d[2] * gxd + be.d[2] * gyd;
+        ag = al.v; ax = 2.0 * L1; ay = L3;
+        bg = be.v; by = 2.0 * L2; bx = L3;
+    }
+    float* gxr = gx + (size_t)r * d;
+    float* gyr = yr ? gy + (size_t)r * d : nullptr;
+    for (int i = lane; i < d; i += 64) {
+        const double a = xr[i], b = yr ? (double)yr[i] : 0., gi = gr ? (double)gr[i] : 0.;
+        gxr[i] = (float)(ag * gi + ax * a + ay * b);
+        if (gyr) gyr[i] = (float)(bg * gi + by * b + bx * a);
+    }
+}
+
+// ---- mobius_matvec (pmath.py:399-408) back through _project, the tanh(|mx| / |x| artanh(sqrt_c |x|)) mx / (|mx| sqrt_c) factor and the
+// mx == 0 branch: out = alpha(q) mx with q = (|mx|^2, |x|).  One wave per row: gmx = alpha g + 2 mx d alpha/d q1 <g,mx>, and
+// gxn = dL/d|x| = d alpha/d q2 <g,mx>; the row of gx is started as gxn x / |x| (0 at a zero row), the GEMM adds gmx m to it.  gxn is also
+// written to gxn_ws, an output nothing here reads.
+// _project's branch is chosen here by a float64 test on the recomputed mx; the forward kernel (pmath.hip OP_MATVEC_FIN) chose it with fp32
+// norms of ITS mx (a sequential fp32 dot product, where this one comes from the training GEMM), so its test cannot be repeated bit for
+// bit: a row whose |res| is within fp32 rounding of maxnorm may get the gradient of the other branch than its forward value came from.
+__global__ __launch_bounds__(256) void pmath_matvec_bwd_kernel(const float* __restrict__ mx, const float* __restrict__ x, const float* __restrict__ g,
+                                                               float* __restrict__ gmx, float* __restrict__ gxn, float* __restrict__ gx, int rows,
+                                                               int d, int O, float cf) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const float* mr = mx + (size_t)r * O;
+    const float* gr = g + (size_t)r * O;
+    const float* xr = x + (size_t)r * d;
+    double m2 = 0., gm = 0., x2 = 0.;
+    for (int i = lane; i < O; i += 64) { const double a = mr[i]; m2 += a * a; gm += (double)gr[i] * a; }
+    for (int i = lane; i < d; i += 64) { const double a = xr[i]; x2 += a * a; }
+    m2 = wsum(m2); gm = wsum(gm); x2 = wsum(x2);
+    const double c = cf, sc = sqrt(c), xnv = sqrt(x2);
+    double a0 = 0., c1 = 0., dn = 0.;   // mx == 0: zero gradient (the reference's 0/0 behind torch.where gives NaN)
+    if (m2 > 0.) {
+        const D3 q1 = var(m2, 0), xn = clamp_min_(var(xnv, 1), EPS5);
+        const D3 mxn = norm_of(q1);
+        const D3 ga = tanh_clamped_(mxn / xn * artanh_d(sc * xn)) / (mxn * sc);   // res = ga mx
+        const D3 norm = clamp_min_(norm_of(ga * ga * q1), EPS5);                 // _project, pmath.py:98-103
+        const double maxnorm = (1.0 - 1e-3) / sc;
+        const D3 al = norm.v > maxnorm ? ga * (maxnorm / norm) : ga;
+        a0 = al.v; c1 = 2.0 * al.d[0] * gm; dn = al.d[1] * gm;
+    }
+    float* go = gmx + (size_t)r * O;
+    for (int i = lane; i < O; i += 64) go[i] = (float)(a0 * (double)gr[i] + c1 * (double)mr[i]);
+    if (lane == 0) gxn[r] = (float)dn;
+    const double kx = xnv > 0. ? dn / xnv : 0.;
+    float* gxr = gx + (size_t)r * d;
+    for (int i = lane; i < d; i += 64) gxr[i] = (float)(kx * (double)xr[i]);
+}
+
+// ---- dist_matrix (pmath.py:482-493): out[p, q] = dist(x_p, y_q).  side 0: one wave per x row sums g[p, q] (2 x_p ds/dp1 + y_q ds/dp3) over
+// its R partners -> gx; side 1: one wave per y row sums g[p, q] (2 y_q ds/dp2 + x_p ds/dp3) over its P partners -> gy.  Partners in index
+// order, every sum in a fixed order: bitwise repeatable, no atomics.  Scalars in float64 as in the forward pair kernel.  Each lane keeps
+// four elements of the row's sum; a row longer than 256 takes one sweep over the partners per 256 elements.
+__global__ __launch_bounds__(256) void pmath_dist_matrix_bwd_kernel(int side, const float* __restrict__ x, const float* __restrict__ y,
+                                                                    const float* __restrict__ g, float* __restrict__ gout, int P, int R, int d,
+                                                                    float cf) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int n_self = side ? R : P, n_part = side ? P : R;
+    if (r >= n_self) return;
+    const float* self = (side ? y : x) + (size_t)r * d;
+    const float* part = side ? x : y;
+    const double c = cf;
+    double s2 = 0.;
+    for (int i = lane; i < d; i += 64) { const double a = self[i]; s2 += a * a; }
+    s2 = wsum(s2);
+    for (int base = 0; base < d; base += 256) {
+        double acc[4] = {0., 0., 0., 0.}, ks = 0.;
+        for (int q = 0; q < n_part; ++q) {
+            const float* pr = part + (size_t)q * d;
+            double q2 = 0., sq = 0.;
+            for (int i = lane; i < d; i += 64) { const double a = self[i], b = pr[i]; q2 += b * b; sq += a * b; }
+            q2 = wsum(q2); sq = wsum(sq);
+            const D3 s = side ? dist_d(q2, s2, sq, c) : dist_d(s2, q2, sq, c);
+            const double gv = side ? g[(size_t)q * R + r] : g[(size_t)r * R + q];
+            ks += 2.0 * gv * s.d[side ? 1 : 0];
+            const double kp = gv * s.d[2];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { const int i = base + lane + 64 * j; if (i < d) acc[j] += kp * (double)pr[i]; }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { const int i = base + lane + 64 * j; if (i < d) gout[(size_t)r * d + i] = (float)(ks * (double)self[i] + acc[j]); }
+    }
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------
+extern "C" int sttode_pmath_rowop_bwd(int op, const float* x, const float* y, const float* g, float* gx, float* gy, int rows, int d, float c,
+                                      void* stream) {
+    STT_REQUIRE(op != 12, "sttode_pmath_rowop_bwd: Oblique.proj has no backward pass here");
+    STT_REQUIRE(op != 13 && op != 14, "sttode_pmath_rowop_bwd: the internal halves of mobius_matvec / poincare_mean have no backward pass here");
+    STT_REQUIRE(op >= 0 && op < OPB_COUNT, "sttode_pmath_rowop_bwd: unknown op");
+    STT_REQUIRE(x && g && gx && rows > 0 && d > 0, "sttode_pmath_rowop_bwd: null pointer or empty shape");
+    const bool needs_y = op == OPB_MOBIUS_ADD || op == OPB_DIST || op == OPB_LOGMAP || op == OPB_EXPMAP;
+    STT_REQUIRE(!needs_y || (y && gy), "sttode_pmath_rowop_bwd: this op needs a second operand and its gradient buffer gy");
+    STT_REQUIRE(needs_y || !gy, "sttode_pmath_rowop_bwd: gy given for an op with one operand");
+    STT_REQUIRE(c > 0.f, "sttode_pmath_rowop_bwd: curvature c must be positive");
+    hipLaunchKernelGGL(pmath_row_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, op, x, needs_y ? y : nullptr, g, gx,
+                       needs_y ? gy : nullptr, rows, d, c);
+    STT_HIP(hipGetLastError());
+    return 0;
+}
+
+// mobius_matvec backward.  gxn_ws [rows] receives dL/d|x| per row: an OUTPUT that no later launch reads (the row kernel puts that term
+// into gx itself); it must not be NULL.  mx = x m^T is recomputed into mx_ws by the training GEMM (the autograd function saves only m and x); after the
+// row kernel has read it, mx_ws holds the split sums of the weight gradient.  gx = gmx m + gxn x / |x| (sttode_tlinear, trans = 1, adding to
+// the rows the row kernel started); gm = gmx^T x (sttode_twgrad, which accumulates: gm is zeroed first).
+// DEVIATION from the reference: a row with mx == 0 (a zero x row) gets a zero gradient; the reference's 0/0 behind torch.where gives NaN.
+extern "C" int sttode_pmath_matvec_bwd(const float* m, const float* x, const float* g, float* mx_ws, float* gmx_ws, float* gxn_ws, float* gx,
+                                       float* gm, int rows, int d, int O, float c, void* stream) {
+    STT_REQUIRE(m && x && g && mx_ws && gmx_ws && gxn_ws && gx && gm, "sttode_pmath_matvec_bwd: null pointer");
+    STT_REQUIRE(rows > 0 && d > 0 && O > 0, "sttode_pmath_matvec_bwd: rows, d, O must be positive");
+    STT_REQUIRE(c > 0.f, "sttode_pmath_matvec_bwd: curvature c must be positive");
+    STT_REQUIRE(!stt_tgemm_group_open(), "sttode_pmath_matvec_bwd: not inside a sttode_tgemm_group bracket (its products depend on each other)");
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = sttode_tlinear(x, d, 1, m, d, 0, nullptr, nullptr, 0, mx_ws, O, rows, d, O, 0, 0, stream)) return rc;
+    hipLaunchKernelGGL(pmath_matvec_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, (const float*)mx_ws, x, g, gmx_ws, gxn_ws, gx, rows, d, O, c);
+    STT_HIP(hipGetLastError());
+    if (int rc = sttode_tlinear(gmx_ws, O, 1, m, d, 1, nullptr, nullptr, 0, gx, d, rows, O, d, 0, 1, stream)) return rc;
+    STT_HIP(hipMemsetAsync(gm, 0, sizeof(float) * (size_t)O * d, s));
+    if (int rc = sttode_twgrad(gmx_ws, O, x, d, 1, gm, d, nullptr, rows, O, d, mx_ws, (long)rows * O, stream)) return rc;
+    return sttode_twgrad_flush();   // (inside a sttode_twgrad_defer bracket the split sums would otherwise be added later)
+}
+
+extern "C" int sttode_pmath_dist_matrix_bwd(const float* x, const float* y, const float* g, float* gx, float* gy, int P, int R, int d, float c,
+                                            void* stream) {
+    STT_REQUIRE(x && y && g && gx && gy, "sttode_pmath_dist_matrix_bwd: null pointer");
+    STT_REQUIRE(P > 0 && R > 0 && d > 0, "sttode_pmath_dist_matrix_bwd: P, R, d must be positive");
+    STT_REQUIRE(c > 0.f, "sttode_pmath_dist_matrix_bwd: curvature c must be positive");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(pmath_dist_matrix_bwd_kernel, dim3((P + 3) / 4), dim3(256), 0, s, 0, x, y, g, gx, P, R, d, c);
+    hipLaunchKernelGGL(pmath_dist_matrix_bwd_kernel, dim3((R + 3) / 4), dim3(256), 0, s, 1, x, y, g, gy, P, R, d, c);
+    STT_HIP(hipGetLastError());
+    return 0;
+}

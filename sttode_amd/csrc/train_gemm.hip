@@ -907,6 +907,7 @@ extern "C" int sttode_tgemm_group(int on) {
     if (rc_ew || rc_trunk) return rc_ew ? rc_ew : rc_trunk;
     STT_HIP(hipGetLastError()); return 0;
 }
+bool stt_tgemm_group_open() { return g_grp.on; }
 extern "C" int sttode_twgrad_defer(int on, float* buf, long floats) {
     if (on < 0) { g_red.r.n = 0; g_red.blocks = 0; g_red.used = 0; }      // error paths: forget what is pending
     tg_red_flush();

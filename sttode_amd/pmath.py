@@ -1,10 +1,20 @@
-"""Poincare-ball math on HIP: same function names / argument meaning as hyptorch/pmath.py (forward values only).
+"""Poincare-ball math on HIP: same function names / argument meaning as hyptorch/pmath.py, forward values and gradients.
 
 Every function takes CUDA(HIP) fp32 tensors and raises on CPU tensors (no fallback).  Leading dims are flattened to
 rows; the last dim is the feature dim.  ``auto_select_c`` is host arithmetic (scipy gamma, pmath.py:496-505).
+
+Gradients: ``project, lambda_x, mobius_add, dist, dist0, expmap, expmap0, logmap, logmap0, p2k, k2p, lorenz_factor``,
+``mobius_matvec`` and ``dist_matrix`` are differentiable with respect to their tensor arguments (``artanh``, ``arsinh`` and
+``RiemannianGradient`` always were): one fused backward kernel per operation (csrc/pmath_grad.hip), first order only
+(``once_differentiable``).  A function takes that path only when grad mode is on and an input requires grad; otherwise it makes exactly
+the calls of the forward-only path, and the forward values of the two paths are bitwise equal.  ``c`` is a Python float and gets no
+gradient.  ``mobius_matvec`` deviates from the reference in one place: a row with ``x m^T == 0`` gets a zero gradient (the reference: NaN).
+``_mobius_addition_batch``, ``_hyperbolic_softmax``, ``poincare_mean`` and the Oblique ops stay FORWARD-ONLY: their results are cut off
+from the graph.
 """
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import capi
 
@@ -18,10 +28,21 @@ def _prep(x):
     return x.to(torch.float32).contiguous()
 
 
+def _wants_grad(*ts):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
+
+
 def _row(op, x, y=None, c=1.0, scalar=False, keepdim=False):
     x = _prep(x)
     if y is not None:
         y = _prep(y)
+    if op != 'oblique_proj' and _wants_grad(x, y):
+        return _RowOp.apply(x, y, op, float(c), scalar, keepdim)
+    return _row_fwd(op, x, y, c, scalar, keepdim)
+
+
+def _row_fwd(op, x, y, c, scalar, keepdim):
+    if y is not None:
         x, y = torch.broadcast_tensors(x, y)
         x, y = x.contiguous(), y.contiguous()
     d = x.shape[-1]
@@ -31,6 +52,34 @@ def _row(op, x, y=None, c=1.0, scalar=False, keepdim=False):
     if scalar:
         return out.view(*x.shape[:-1], 1) if keepdim else out.view(*x.shape[:-1])
     return out.view(x.shape)
+
+
+class _RowOp(torch.autograd.Function):
+    """A row op and its fused backward kernel (sttode_pmath_rowop_bwd).  Saves only its inputs; a broadcast operand's gradient is
+    summed back to the operand's shape."""
+
+    @staticmethod
+    def forward(ctx, x, y, op, c, scalar, keepdim):
+        ctx.save_for_backward(x, y)
+        ctx.op, ctx.c, ctx.scalar = op, c, scalar
+        return _row_fwd(op, x, y, c, scalar, keepdim)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, y = ctx.saved_tensors
+        xb, yb = x, y
+        if y is not None:
+            xb, yb = torch.broadcast_tensors(x, y)
+            xb, yb = xb.contiguous(), yb.contiguous()
+        d = xb.shape[-1]
+        rows = xb.numel() // d
+        g = _prep(g)
+        assert g.numel() == (rows if ctx.scalar else rows * d)
+        gx = torch.empty_like(xb)
+        gy = torch.empty_like(yb) if y is not None else None
+        capi.call('sttode_pmath_rowop_bwd', _OPS[ctx.op], xb, yb, g, gx, gy, rows, d, ctx.c, capi.stream_ptr())
+        return gx.sum_to_size(x.shape), (gy.sum_to_size(y.shape) if y is not None else None), None, None, None, None
 
 
 def _scalar(which, x):
@@ -159,6 +208,12 @@ def lorenz_factor(x, *, c=1.0, dim=-1, keepdim=False):
 
 def mobius_matvec(m, x, *, c=1.0):
     m, x = _prep(m), _prep(x)
+    if _wants_grad(m, x):
+        return _MatVec.apply(m, x, float(c))
+    return _matvec_fwd(m, x, c)
+
+
+def _matvec_fwd(m, x, c):
     O, d = m.shape
     rows = x.numel() // d
     mx = torch.empty(rows, O, dtype=torch.float32, device=x.device)
@@ -166,6 +221,47 @@ def mobius_matvec(m, x, *, c=1.0):
     out = torch.empty(rows, O, dtype=torch.float32, device=x.device)
     capi.call('sttode_pmath_matvec', m, x, mx, xn, out, rows, d, O, float(c), capi.stream_ptr())
     return out.view(*x.shape[:-1], O)
+
+
+class _MatVec(torch.autograd.Function):
+    """mobius_matvec and its backward (sttode_pmath_matvec_bwd: a row kernel + the training GEMMs).  Saves only m and x."""
+
+    @staticmethod
+    def forward(ctx, m, x, c):
+        ctx.save_for_backward(m, x)
+        ctx.c = c
+        return _matvec_fwd(m, x, c)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        m, x = ctx.saved_tensors
+        O, d = m.shape
+        rows = x.numel() // d
+        g = _prep(g)
+        f = dict(dtype=torch.float32, device=x.device)
+        mx, gmx, gxn = torch.empty(rows, O, **f), torch.empty(rows, O, **f), torch.empty(rows, **f)   # gxn: an output the entry point requires; unused
+        gx, gm = torch.empty_like(x), torch.empty_like(m)
+        capi.call('sttode_pmath_matvec_bwd', m, x, g, mx, gmx, gxn, gx, gm, rows, d, O, ctx.c, capi.stream_ptr())
+        return gm, gx, None
+
+
+class _DistMatrix(torch.autograd.Function):
+    """dist_matrix and its backward (sttode_pmath_dist_matrix_bwd).  Saves only x and y."""
+
+    @staticmethod
+    def forward(ctx, x, y, c):
+        ctx.save_for_backward(x, y)
+        ctx.c = c
+        return _pair(0, x, y, None, c, (x.shape[0], y.shape[0]))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, y = ctx.saved_tensors
+        gx, gy = torch.empty_like(x), torch.empty_like(y)
+        capi.call('sttode_pmath_dist_matrix_bwd', x, y, _prep(g), gx, gy, x.shape[0], y.shape[0], x.shape[1], ctx.c, capi.stream_ptr())
+        return gx, gy, None
 
 
 def _pair(which, x, y, A, c, shape):
@@ -177,6 +273,9 @@ def _pair(which, x, y, A, c, shape):
 
 
 def dist_matrix(x, y, c=1.0):
+    x, y = _prep(x), _prep(y)
+    if _wants_grad(x, y):
+        return _DistMatrix.apply(x, y, float(c))
     return _pair(0, x, y, None, c, (x.shape[0], y.shape[0]))
 
 

@@ -1,0 +1,90 @@
+"""CPU tests of the pmath backward passes: the three entry points exist in the library, the header and the ctypes table, and the
+fixtures tests/golden/pmath_vjp.npz and pmath_vjp_rows.npz are ones the reference itself handles (its own fp32 gradients within the
+bound of its float64 ones)."""
+import ctypes
+import os
+
+import numpy as np
+
+from pmath_vjp_cases import BOUND, COMPOSITIONS, CS, DIMS, DIST_MATRIX, LOGMAP0_ZERO_ROW, MATVEC, ROW_OPS, ROW_SHAPES, ROWS, cases, err
+from test_capi_symbols import header_functions
+
+NEW = {'sttode_pmath_rowop_bwd': 10, 'sttode_pmath_matvec_bwd': 13, 'sttode_pmath_dist_matrix_bwd': 10}
+
+
+def test_library_header_and_table_agree_on_the_new_entry_points():
+    from sttode_amd import capi
+    if not os.path.exists(capi.LIB_PATH):
+        import __graft_entry__ as g
+        g.build()
+    L = ctypes.CDLL(capi.LIB_PATH)
+    fns = header_functions()
+    for name, nargs in NEW.items():
+        assert hasattr(L, name), name + ' is not exported'
+        assert name in fns and len(fns[name]) == nargs, (name, fns.get(name))
+        assert len(capi.SIGNATURES[name]) == nargs
+        for ct, decl in zip(capi.SIGNATURES[name], fns[name]):
+            assert (ct is ctypes.c_int and decl.startswith('int ')) or (ct is ctypes.c_float and decl.startswith('float ')) or \
+                (ct is ctypes.c_void_p and '*' in decl), (name, decl)
+    assert L.sttode_abi_version() == capi.ABI_VERSION == 14
+
+
+def test_new_entry_points_refuse_by_name_without_a_launch():
+    """Argument checks come first and name the entry point (host only: nothing is launched, no GPU needed)."""
+    from sttode_amd import capi
+    L = capi.lib()
+    one = ctypes.c_void_p(8)          # never dereferenced: every call below fails its checks
+    for op, gy, c, word in ((12, None, 1.0, 'Oblique'), (13, None, 1.0, 'internal'), (14, None, 1.0, 'internal'), (99, None, 1.0, 'unknown op'),
+                            (-1, None, 1.0, 'unknown op'), (2, None, 1.0, 'gy'), (0, one, 1.0, 'gy'), (0, None, 0.0, 'curvature'),
+                            (3, one, -1.0, 'curvature')):
+        assert L.sttode_pmath_rowop_bwd(op, one, one, one, one, gy, 4, 4, c, None) != 0, (op, c)
+        msg = L.sttode_last_error().decode()
+        assert 'sttode_pmath_rowop_bwd' in msg and word in msg, msg
+    assert L.sttode_pmath_matvec_bwd(one, one, one, one, one, one, one, one, 4, 4, 4, 0.0, None) != 0
+    assert 'sttode_pmath_matvec_bwd' in L.sttode_last_error().decode()
+    assert L.sttode_pmath_dist_matrix_bwd(one, one, one, one, one, 4, 4, 4, 0.0, None) != 0
+    assert 'sttode_pmath_dist_matrix_bwd' in L.sttode_last_error().decode()
+
+
+def test_fixture_holds_the_cases_and_the_reference_handles_them(golden):
+    z, zr = golden('pmath_vjp'), golden('pmath_vjp_rows')
+    cs = cases(z, zr)
+    names = {c['name'] for c in cs}
+    for op in ROW_OPS:                                   # the whole product: every op at every d, both row counts, both curvatures
+        for d in DIMS:
+            for n in ROWS:
+                for c in CS:
+                    assert 'row.%s.d%d.n%d.c%s' % (op, d, n, c) in names
+    assert len([n for n in names if n.startswith('row.')]) == 12 * 20
+    assert all('mv.' + t in names for t in MATVEC) and all('dm.P%dR%dd%d' % s in names for s in DIST_MATRIX)
+    assert z['mv.big.x'].shape == (2100, 8) and not z['mv.zero.x'][int(z['mv.zero.row'])].any()
+    for c in CS:                                         # the clipped branch of project: sqrt(c) |x| = 1.2
+        np.testing.assert_allclose(np.sqrt(c) * np.linalg.norm(z['clip.project.c%s.x' % c], axis=-1), 1.2, rtol=1e-6)
+    assert not z['zero.expmap0.x'][4].any() and not z['zero.logmap0.x'][4].any() and not z['zero.expmap.y'][4].any()
+    for d, n, c in ROW_SHAPES:                           # the domain: sqrt(c) |x| in [0.05, 0.9] for x, y and u
+        r = np.sqrt(c) * np.linalg.norm(zr['in.d%d.n%d.c%s' % (d, n, c)][:3], axis=-1)
+        assert r.shape == (3, n) and (r > 0.0499).all() and (r < 0.9001).all()
+    worst = {}
+    for case in cs:
+        for k, g64, g32 in case['grads']:
+            assert np.isfinite(g64).all(), k
+            if case['name'] == LOGMAP0_ZERO_ROW[0]:
+                # The ONE exemption.  On logmap0's all-zero row the gradient is g artanh(1e-5 sqrt_c) / (1e-5 sqrt_c), and the reference's
+                # fp32 artanh -- a difference of two logs of 1 +- 1e-5 rounded to fp32 -- is 5e-4 relative off: the reference's own fp32
+                # entry misses the bound on that row (and is shown to: the row is in the fixture because it misses).  The row stays in the
+                # fixture with its upstream gradient at full size, and the kernel is held to the float64 value there like everywhere else.
+                row = LOGMAP0_ZERO_ROW[1]
+                assert err(g32[row], g64[row]) > BOUND, 'the exemption is no longer needed: remove it'
+                keep = np.arange(len(g64)) != row
+                g64, g32 = g64[keep], g32[keep]
+            e = err(g32, g64)
+            worst[case['op']] = max(worst.get(case['op'], 0.0), e)
+            assert e <= BOUND, (k, e)
+    for name, ins in COMPOSITIONS.items():
+        for i in ins:
+            e = err(z['%s.g%s32' % (name, i)], z['%s.g%s64' % (name, i)])
+            worst[name] = max(worst.get(name, 0.0), e)
+            assert e <= BOUND, (name, i, e)
+    print('reference fp32 against its float64, worst per op: ' + ', '.join('%s %.1e' % kv for kv in sorted(worst.items())))
+    here = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
+    assert all(os.path.getsize(os.path.join(here, f)) < (1 << 20) for f in ('pmath_vjp.npz', 'pmath_vjp_rows.npz'))
