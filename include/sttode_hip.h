@@ -536,6 +536,16 @@ int sttode_pmath_matvec_bwd(const float* m, const float* x, const float* g, floa
  * fixed order: bitwise repeatable, no atomics. */
 int sttode_pmath_dist_matrix_bwd(const float* x, const float* y, const float* g, float* gx, float* gy, int P, int R, int d, float c,
                                  void* stream);
+/* _hyperbolic_softmax backward (added within ABI version 14): X [B,d], A [C,d], P [C,d], g [B,C] -> gX [B,d], gA [C,d],
+ * gP [C,d], all written.  coef_ws holds 6 B C doubles: g times the partial of the logit with respect to each of the pair's six scalars,
+ * written once per pair and then read by one wave per X row and one wave per class row, partners in index order: bitwise repeatable, no
+ * atomics.  A zero row of A is outside the domain (the reference gives NaN). */
+int sttode_pmath_hsoftmax_bwd(const float* X, const float* A, const float* P, const float* g, double* coef_ws, float* gX, float* gA, float* gP,
+                              int B, int C, int d, float c, void* stream);
+/* Feature clipping of hyptorch/nn.py's ToPoincare(clip_r=r): out = x min(1, r / (|x| + 1e-5)) over rows of x [rows,d], and its backward
+ * pass g [rows,d] -> gx [rows,d]; r > 0. */
+int sttode_pmath_clip(const float* x, float* out, int rows, int d, float r, void* stream);
+int sttode_pmath_clip_bwd(const float* x, const float* g, float* gx, int rows, int d, float r, void* stream);
 /* Oblique.dist (core/manifolds/oblique.py:36-43): p1 [nb,n1,d], p2 [nb,n2,d] -> acos(clamp(p2 p1^T)) [nb,n2,n1]. */
 int sttode_oblique_dist(const float* p1, const float* p2, float* out, int nb, int n1, int n2, int d, void* stream);
 

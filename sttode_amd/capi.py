@@ -94,6 +94,10 @@ SIGNATURES = {
     'sttode_pmath_rowop_bwd': [_I, _P, _P, _P, _P, _P, _I, _I, _F, _P],
     'sttode_pmath_matvec_bwd': [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P],
     'sttode_pmath_dist_matrix_bwd': [_P, _P, _P, _P, _P, _I, _I, _I, _F, _P],
+    # _hyperbolic_softmax backward and the feature-clip row op (csrc/pmath_grad.hip; added within ABI version 14)
+    'sttode_pmath_hsoftmax_bwd': [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P],
+    'sttode_pmath_clip': [_P, _P, _I, _I, _F, _P],
+    'sttode_pmath_clip_bwd': [_P, _P, _P, _I, _I, _F, _P],
     # Gromov delta-hyperbolicity (csrc/delta.hip)
     'sttode_delta_dist': [_P, _I, _I, _P, _I, _I, _P, _L, _P, _P],
     'sttode_delta_workspace': [_I, _I, ctypes.POINTER(ctypes.c_long)],

@@ -8,7 +8,7 @@
 // kernel.  Pass 1 forms the five dot products in one sweep (float64 accumulators, wavefront xor-shuffles), the per-row scalar stage runs
 // redundantly on all lanes, pass 2 writes gx and gy with coalesced stores.  No atomics, no LDS, no workspace; only x, y, g are read.
 //
-// The scalar stage is float64 forward-mode arithmetic (struct D3: a value and its three partials d/dp_k): 1 - c |x|^2, 1 - u^2 under artanh
+// The scalar stage is float64 forward-mode arithmetic (struct DN<N>: a value and N partials; D3: the three partials d/dp_k): 1 - c |x|^2, 1 - u^2 under artanh
 // and the Moebius denominator cancel near the ball boundary (pmath.hip's pair kernel and OP_PMEAN_PREP use float64 for the same reason).
 // The stage is a few hundred float64 operations per row, tanh / log1p / sqrt among them, redundantly on 64 lanes (dist_matrix: once per
 // pair); it is EXPECTED to stay below the row's memory traffic, and has not been timed.
@@ -18,6 +18,8 @@
 //   * artanh: value at the clamped argument, derivative 1 / (1 - x_clamped^2) (Artanh.backward, pmath.py:25-27) -- NOT zero outside the clamp;
 //   * project: the clipped branch gets the gradient of maxnorm x / |x|; the branch is chosen by the forward kernel's own fp32 test;
 //   * the + 1e-5 of the Moebius denominator.
+// _hyperbolic_softmax's backward (per-pair coefficients, then row sums) and the feature clip of ToPoincare follow the same rules; their
+// forms are described where they stand below.
 #include "api_util.hpp"
 #include "train_group.hpp"
 
@@ -34,38 +36,52 @@ enum { OPB_PROJECT = 0, OPB_LAMBDA_X, OPB_MOBIUS_ADD, OPB_DIST, OPB_DIST0, OPB_E
 
 constexpr double EPS5 = (double)1e-5f;   // the reference's 1e-5, as the forward kernels round it
 
-// value + partials with respect to the three row scalars
-struct D3 { double v, d[3]; };
-__device__ __forceinline__ D3 var(double v, int k) { D3 r{v, {0., 0., 0.}}; r.d[k] = 1.; return r; }
-__device__ __forceinline__ D3 cst(double v) { return D3{v, {0., 0., 0.}}; }
-__device__ __forceinline__ D3 operator+(const D3& a, const D3& b) { return D3{a.v + b.v, {a.d[0] + b.d[0], a.d[1] + b.d[1], a.d[2] + b.d[2]}}; }
-__device__ __forceinline__ D3 operator-(const D3& a, const D3& b) { return D3{a.v - b.v, {a.d[0] - b.d[0], a.d[1] - b.d[1], a.d[2] - b.d[2]}}; }
-__device__ __forceinline__ D3 operator*(const D3& a, const D3& b) {
-    return D3{a.v * b.v, {a.d[0] * b.v + a.v * b.d[0], a.d[1] * b.v + a.v * b.d[1], a.d[2] * b.v + a.v * b.d[2]}};
+// value + partials with respect to N scalars (D3: the three row scalars; D6: the six pair scalars of _hyperbolic_softmax)
+template <int N> struct DN { double v, d[N]; };
+using D3 = DN<3>;
+using D6 = DN<6>;
+// the value v with partials d[k] = f(k)
+template <int N, class F> __device__ __forceinline__ DN<N> dn(double v, F f) {
+    DN<N> r; r.v = v;
+#pragma unroll
+    for (int k = 0; k < N; ++k) r.d[k] = f(k);
+    return r;
 }
-__device__ __forceinline__ D3 operator/(const D3& a, const D3& b) {
+template <int N> __device__ __forceinline__ DN<N> cst(double v) { return dn<N>(v, [](int) { return 0.; }); }
+template <int N> __device__ __forceinline__ DN<N> var(double v, int i) { return dn<N>(v, [i](int k) { return k == i ? 1. : 0.; }); }
+template <int N> __device__ __forceinline__ DN<N> operator+(const DN<N>& a, const DN<N>& b) { return dn<N>(a.v + b.v, [&](int k) { return a.d[k] + b.d[k]; }); }
+template <int N> __device__ __forceinline__ DN<N> operator-(const DN<N>& a, const DN<N>& b) { return dn<N>(a.v - b.v, [&](int k) { return a.d[k] - b.d[k]; }); }
+template <int N> __device__ __forceinline__ DN<N> operator*(const DN<N>& a, const DN<N>& b) {
+    return dn<N>(a.v * b.v, [&](int k) { return a.d[k] * b.v + a.v * b.d[k]; });
+}
+template <int N> __device__ __forceinline__ DN<N> operator/(const DN<N>& a, const DN<N>& b) {
     const double q = a.v / b.v, ib = 1.0 / b.v;
-    return D3{q, {(a.d[0] - q * b.d[0]) * ib, (a.d[1] - q * b.d[1]) * ib, (a.d[2] - q * b.d[2]) * ib}};
+    return dn<N>(q, [&](int k) { return (a.d[k] - q * b.d[k]) * ib; });
 }
-__device__ __forceinline__ D3 operator+(double a, const D3& b) { return D3{a + b.v, {b.d[0], b.d[1], b.d[2]}}; }
-__device__ __forceinline__ D3 operator-(double a, const D3& b) { return D3{a - b.v, {-b.d[0], -b.d[1], -b.d[2]}}; }
-__device__ __forceinline__ D3 operator*(double a, const D3& b) { return D3{a * b.v, {a * b.d[0], a * b.d[1], a * b.d[2]}}; }
-__device__ __forceinline__ D3 operator/(double a, const D3& b) { return cst(a) / b; }
-__device__ __forceinline__ D3 operator*(const D3& a, double b) { return b * a; }
-__device__ __forceinline__ D3 operator/(const D3& a, double b) { return (1.0 / b) * a; }
-__device__ __forceinline__ D3 chain(double v, double dv, const D3& a) { return D3{v, {dv * a.d[0], dv * a.d[1], dv * a.d[2]}}; }
+template <int N> __device__ __forceinline__ DN<N> operator+(double a, const DN<N>& b) { return dn<N>(a + b.v, [&](int k) { return b.d[k]; }); }
+template <int N> __device__ __forceinline__ DN<N> operator-(double a, const DN<N>& b) { return dn<N>(a - b.v, [&](int k) { return -b.d[k]; }); }
+template <int N> __device__ __forceinline__ DN<N> operator*(double a, const DN<N>& b) { return dn<N>(a * b.v, [&](int k) { return a * b.d[k]; }); }
+template <int N> __device__ __forceinline__ DN<N> operator/(double a, const DN<N>& b) { return cst<N>(a) / b; }
+template <int N> __device__ __forceinline__ DN<N> operator*(const DN<N>& a, double b) { return b * a; }
+template <int N> __device__ __forceinline__ DN<N> operator/(const DN<N>& a, double b) { return (1.0 / b) * a; }
+template <int N> __device__ __forceinline__ DN<N> chain(double v, double dv, const DN<N>& a) { return dn<N>(v, [&](int k) { return dv * a.d[k]; }); }
 // x.norm(): sqrt of a sum of squares, derivative 0 at a zero row
-__device__ __forceinline__ D3 norm_of(const D3& sq) { const double n = sqrt(sq.v); return chain(n, n > 0. ? 0.5 / n : 0., sq); }
-__device__ __forceinline__ D3 sqrt_(const D3& a) { const double n = sqrt(a.v); return chain(n, 0.5 / n, a); }
-__device__ __forceinline__ D3 clamp_min_(const D3& a, double lo) { return a.v >= lo ? a : cst(lo); }
-__device__ __forceinline__ D3 tanh_clamped_(const D3& a) {   // pmath.py:11-12
+template <int N> __device__ __forceinline__ DN<N> norm_of(const DN<N>& sq) { const double n = sqrt(sq.v); return chain(n, n > 0. ? 0.5 / n : 0., sq); }
+template <int N> __device__ __forceinline__ DN<N> sqrt_(const DN<N>& a) { const double n = sqrt(a.v); return chain(n, 0.5 / n, a); }
+template <int N> __device__ __forceinline__ DN<N> clamp_min_(const DN<N>& a, double lo) { return a.v >= lo ? a : cst<N>(lo); }
+template <int N> __device__ __forceinline__ DN<N> tanh_clamped_(const DN<N>& a) {   // pmath.py:11-12
     const bool in = a.v >= -15.0 && a.v <= 15.0;
     const double t = tanh(fmin(fmax(a.v, -15.0), 15.0));
     return chain(t, in ? 1.0 - t * t : 0., a);
 }
-__device__ __forceinline__ D3 artanh_d(const D3& a) {        // pmath.py:16-27
+template <int N> __device__ __forceinline__ DN<N> artanh_d(const DN<N>& a) {        // pmath.py:16-27
     const double xc = fmin(fmax(a.v, -1.0 + EPS5), 1.0 - EPS5);
     return chain(0.5 * (log1p(xc) - log1p(-xc)), 1.0 / (1.0 - xc * xc), a);
+}
+// arsinh (pmath.py:51-60): log of the clamped x + sqrt(1 + x^2); the derivative Arsinh.backward gives, 1 / sqrt(1 + x^2), whatever the clamp
+template <int N> __device__ __forceinline__ DN<N> arsinh_d(const DN<N>& a) {
+    const double h = sqrt(1.0 + a.v * a.v);
+    return chain(log(fmax(a.v + h, EPS5)), 1.0 / h, a);
 }
 
 __device__ __forceinline__ double wsum(double v) {
@@ -82,7 +98,7 @@ __device__ __forceinline__ float wsumf(float v) {
 // _mobius_add(a, b) = (ca a + cb b) / den from the row scalars of its operands (pmath.py:171-177)
 struct MobD { D3 ca, cb; };
 __device__ __forceinline__ MobD mob_d(const D3& a2, const D3& b2, const D3& ab, double c) {
-    const D3 den = 1.0 + 2.0 * c * ab + (c * c) * (a2 * b2) + cst(EPS5);
+    const D3 den = 1.0 + 2.0 * c * ab + (c * c) * (a2 * b2) + cst<3>(EPS5);
     return MobD{(1.0 + 2.0 * c * ab + c * b2) / den, (1.0 - c * a2) / den};
 }
 // (-x) (+) y = A (-x) + B y and its norm (pmath.py:207, :335-336)
@@ -94,7 +110,7 @@ __device__ __forceinline__ SubD sub_d(const D3& p1, const D3& p2, const D3& p3, 
 // dist(x, y) (pmath.py:205-208) as a function of p = (|x|^2, |y|^2, <x,y>)
 __device__ __forceinline__ D3 dist_d(double x2, double y2, double xy, double c) {
     const double sc = sqrt(c);
-    const SubD s = sub_d(var(x2, 0), var(y2, 1), var(xy, 2), c);
+    const SubD s = sub_d(var<3>(x2, 0), var<3>(y2, 1), var<3>(xy, 2), c);
     return (2.0 / sc) * artanh_d(sc * s.sn);
 }
 
@@ -120,13 +136,13 @@ __global__ __launch_bounds__(256) void pmath_row_bwd_kernel(int op, const float*
     }
     x2 = wsum(x2); y2 = wsum(y2); xy = wsum(xy); gxd = wsum(gxd); gyd = wsum(gyd); x2f = wsumf(x2f);
     const double c = cf, sc = sqrt(c);
-    const D3 p1 = var(x2, 0), p2 = var(y2, 1), p3 = var(xy, 2);
-    D3 al = cst(0.), be = cst(0.);   // vector results: alpha, beta; scalar results: al = s
+    const D3 p1 = var<3>(x2, 0), p2 = var<3>(y2, 1), p3 = var<3>(xy, 2);
+    D3 al = cst<3>(0.), be = cst<3>(0.);   // vector results: alpha, beta; scalar results: al = s
     switch (op) {
         case OPB_PROJECT: {  // pmath.py:98-103
             const float normf = fmaxf(sqrtf(x2f), 1e-5f), maxnormf = (1.0f - 1e-3f) / sqrtf(cf);
             const D3 norm = clamp_min_(norm_of(p1), EPS5);
-            al = normf > maxnormf ? ((1.0 - 1e-3) / sc) / norm : cst(1.0);
+            al = normf > maxnormf ? ((1.0 - 1e-3) / sc) / norm : cst<3>(1.0);
         } break;
         case OPB_LAMBDA_X: al = 2.0 / (1.0 - c * p1); break;   // pmath.py:128-129
         case OPB_MOBIUS_ADD: { const MobD m = mob_d(p1, p2, p3, c); al = m.ca; be = m.cb; } break;
@@ -199,7 +215,7 @@ __global__ __launch_bounds__(256) void pmath_matvec_bwd_kernel(const float* __re
     const double c = cf, sc = sqrt(c), xnv = sqrt(x2);
     double a0 = 0., c1 = 0., dn = 0.;   // mx == 0: zero gradient (the reference's 0/0 behind torch.where gives NaN)
     if (m2 > 0.) {
-        const D3 q1 = var(m2, 0), xn = clamp_min_(var(xnv, 1), EPS5);
+        const D3 q1 = var<3>(m2, 0), xn = clamp_min_(var<3>(xnv, 1), EPS5);
         const D3 mxn = norm_of(q1);
         const D3 ga = tanh_clamped_(mxn / xn * artanh_d(sc * xn)) / (mxn * sc);   // res = ga mx
         const D3 norm = clamp_min_(norm_of(ga * ga * q1), EPS5);                 // _project, pmath.py:98-103
@@ -251,6 +267,120 @@ __global__ __launch_bounds__(256) void pmath_dist_matrix_bwd_kernel(int side, co
     }
 }
 
+// ---- _hyperbolic_softmax (pmath.py:430-437): logit[q, p] is a function of six scalars of the pair, z = (|P_p|^2, |X_q|^2, <P_p,X_q>,
+// |A_p|^2, <A_p,P_p>, <A_p,X_q>): with ca = 1 - 2c z2 + c z1, cb = 1 - c z0, den = 1 - 2c z2 + c^2 z0 z1 + 1e-5 the Moebius sum v = (-P) (+) X
+// has <v,A> = (cb z5 - ca z4) / den and |v|^2 = (ca^2 z0 - 2 ca cb z2 + cb^2 z1) / den^2, and
+//     logit = 2 / cb * sqrt(z3) / sqrt_c * arsinh(2 sqrt_c <v,A> / (sqrt(z3) (1 - c |v|^2))).
+// Every input gradient is then a sum of rows weighted by w_k[q, p] = g[q, p] d logit / d z_k:
+//     gX_q = 2 X_q sum_p w1 + sum_p w2 P_p + sum_p w5 A_p
+//     gP_p = 2 P_p sum_q w0 + A_p sum_q w4 + sum_q w2 X_q          gA_p = 2 A_p sum_q w3 + P_p sum_q w4 + sum_q w5 X_q
+// The coefficient kernel (one wave per pair) forms the six scalars in float64 -- as the forward pair kernel does, for the same cancellation in
+// cb and 1 - c |v|^2 -- and writes w [6,B,C] once per pair; the row-sum kernel (one wave per output row, partners in index order, each lane
+// four elements of the row, one sweep over the partners per 256 elements) adds the rows: no atomics, every sum in a fixed order.
+__device__ __forceinline__ D6 hsoftmax_d(double pi, double xi, double tau, double al, double be, double ga, double c) {
+    const double sc = sqrt(c);
+    const D6 p = var<6>(pi, 0), x = var<6>(xi, 1), t = var<6>(tau, 2), a = var<6>(al, 3), b = var<6>(be, 4), g = var<6>(ga, 5);
+    const D6 ca = 1.0 - 2.0 * c * t + c * x, cb = 1.0 - c * p;
+    const D6 den = 1.0 - 2.0 * c * t + (c * c) * (p * x) + cst<6>(EPS5);
+    const D6 va = (cb * g - ca * b) / den;
+    const D6 v2 = (ca * ca * p - 2.0 * (ca * cb * t) + cb * cb * x) / (den * den);
+    const D6 an = norm_of(a);
+    return (2.0 / sc) * an / cb * arsinh_d((2.0 * sc) * va / (an * (1.0 - c * v2)));
+}
+
+__global__ __launch_bounds__(256) void pmath_hsoftmax_coef_kernel(const float* __restrict__ X, const float* __restrict__ A, const float* __restrict__ P,
+                                                                  const float* __restrict__ g, double* __restrict__ w, int B, int C, int d,
+                                                                  float cf) {
+    const int lane = threadIdx.x & 63;
+    const long pair = (long)blockIdx.x * 4 + (threadIdx.x >> 6), BC = (long)B * C;
+    if (pair >= BC) return;
+    const float* xr = X + (size_t)(pair / C) * d;
+    const float* ar = A + (size_t)(pair % C) * d;
+    const float* pr = P + (size_t)(pair % C) * d;
+    double pi = 0., xi = 0., tau = 0., al = 0., be = 0., ga = 0.;
+    for (int i = lane; i < d; i += 64) {
+        const double pv = pr[i], xv = xr[i], av = ar[i];
+        pi += pv * pv; xi += xv * xv; tau += pv * xv; al += av * av; be += av * pv; ga += av * xv;
+    }
+    pi = wsum(pi); xi = wsum(xi); tau = wsum(tau); al = wsum(al); be = wsum(be); ga = wsum(ga);
+    const D6 L = hsoftmax_d(pi, xi, tau, al, be, ga, (double)cf);
+    if (lane == 0) {
+        const double gv = g[pair];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) w[(size_t)k * BC + pair] = gv * L.d[k];
+    }
+}
+
+// side 0: one wave per X row -> gX; side 1: one wave per class row -> gP and gA (both sum the same partners, the X rows)
+__global__ __launch_bounds__(256) void pmath_hsoftmax_rowsum_kernel(int side, const float* __restrict__ X, const float* __restrict__ A,
+                                                                    const float* __restrict__ P, const double* __restrict__ w,
+                                                                    float* __restrict__ gX, float* __restrict__ gA, float* __restrict__ gP, int B,
+                                                                    int C, int d) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int n_self = side ? C : B, n_part = side ? B : C;
+    if (r >= n_self) return;
+    const size_t BC = (size_t)B * C;
+    const float* trow = side ? X : P;   // the partner rows that w2 weights
+    const float* grow = side ? X : A;   // ... and w5
+    for (int base = 0; base < d; base += 256) {
+        double at[4] = {0., 0., 0., 0.}, ag[4] = {0., 0., 0., 0.}, s0 = 0., s3 = 0., s4 = 0.;
+        for (int j = 0; j < n_part; ++j) {
+            const size_t pair = side ? (size_t)j * C + r : (size_t)r * C + j;
+            const double wt = w[2 * BC + pair], wg = w[5 * BC + pair];
+            if (side) { s0 += w[pair]; s3 += w[3 * BC + pair]; s4 += w[4 * BC + pair]; }
+            else s0 += w[BC + pair];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int i = base + lane + 64 * k;
+                if (i < d) { at[k] += wt * (double)trow[(size_t)j * d + i]; ag[k] += wg * (double)grow[(size_t)j * d + i]; }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int i = base + lane + 64 * k;
+            if (i >= d) continue;
+            const size_t o = (size_t)r * d + i;
+            if (side) {
+                const double pv = P[o], av = A[o];
+                gP[o] = (float)(2.0 * s0 * pv + s4 * av + at[k]);
+                gA[o] = (float)(2.0 * s3 * av + s4 * pv + ag[k]);
+            } else {
+                gX[o] = (float)(2.0 * s0 * (double)X[o] + at[k] + ag[k]);
+            }
+        }
+    }
+}
+
+// ---- feature clipping (hyptorch/nn.py:154-160, ToPoincare(clip_r=r)): out = x min(1, r / (|x| + 1e-5)).  One wave per row, the norm in
+// float64.  Backward: an unclipped row passes g; a clipped one gets s g - x <g,x> s / ((|x| + 1e-5) |x|) with s = r / (|x| + 1e-5).
+__global__ __launch_bounds__(256) void pmath_clip_kernel(const float* __restrict__ x, float* __restrict__ out, int rows, int d, float rf) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const float* xr = x + (size_t)r * d;
+    double x2 = 0.;
+    for (int i = lane; i < d; i += 64) { const double a = xr[i]; x2 += a * a; }
+    const double s = fmin(1.0, (double)rf / (sqrt(wsum(x2)) + EPS5));
+    for (int i = lane; i < d; i += 64) out[(size_t)r * d + i] = (float)(s * (double)xr[i]);
+}
+
+__global__ __launch_bounds__(256) void pmath_clip_bwd_kernel(const float* __restrict__ x, const float* __restrict__ g, float* __restrict__ gx,
+                                                             int rows, int d, float rf) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const float* xr = x + (size_t)r * d;
+    const float* gr = g + (size_t)r * d;
+    double x2 = 0., gxd = 0.;
+    for (int i = lane; i < d; i += 64) { const double a = xr[i]; x2 += a * a; gxd += (double)gr[i] * a; }
+    x2 = wsum(x2); gxd = wsum(gxd);
+    const double n = sqrt(x2), s = (double)rf / (n + EPS5);
+    const bool clipped = s < 1.0;   // (then n > r - 1e-5 > 0 is not guaranteed for r <= 1e-5: a zero row is never divided by)
+    const double kg = clipped ? s : 1.0, kx = clipped && n > 0. ? -gxd * s / ((n + EPS5) * n) : 0.;
+    for (int i = lane; i < d; i += 64) gx[(size_t)r * d + i] = (float)(kg * (double)gr[i] + kx * (double)xr[i]);
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------
@@ -299,6 +429,40 @@ extern "C" int sttode_pmath_dist_matrix_bwd(const float* x, const float* y, cons
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(pmath_dist_matrix_bwd_kernel, dim3((P + 3) / 4), dim3(256), 0, s, 0, x, y, g, gx, P, R, d, c);
     hipLaunchKernelGGL(pmath_dist_matrix_bwd_kernel, dim3((R + 3) / 4), dim3(256), 0, s, 1, x, y, g, gy, P, R, d, c);
+    STT_HIP(hipGetLastError());
+    return 0;
+}
+
+// _hyperbolic_softmax backward: X [B,d], A [C,d], P [C,d], g [B,C] -> gX [B,d], gA [C,d], gP [C,d]; coef_ws [6,B,C] doubles.  Three launches
+// (coefficients once per pair, then one wave per X row and one wave per class row); bitwise repeatable.
+extern "C" int sttode_pmath_hsoftmax_bwd(const float* X, const float* A, const float* P, const float* g, double* coef_ws, float* gX, float* gA,
+                                         float* gP, int B, int C, int d, float c, void* stream) {
+    STT_REQUIRE(X && A && P && g && coef_ws && gX && gA && gP, "sttode_pmath_hsoftmax_bwd: null pointer");
+    STT_REQUIRE(B > 0 && C > 0 && d > 0, "sttode_pmath_hsoftmax_bwd: B, C, d must be positive");
+    STT_REQUIRE((long)B * C <= 0x7fffffffL, "sttode_pmath_hsoftmax_bwd: more than 2^31 - 1 pairs");
+    STT_REQUIRE(c > 0.f, "sttode_pmath_hsoftmax_bwd: curvature c must be positive");
+    hipStream_t s = (hipStream_t)stream;
+    const long BC = (long)B * C;
+    hipLaunchKernelGGL(pmath_hsoftmax_coef_kernel, dim3((unsigned)((BC + 3) / 4)), dim3(256), 0, s, X, A, P, g, coef_ws, B, C, d, c);
+    hipLaunchKernelGGL(pmath_hsoftmax_rowsum_kernel, dim3((B + 3) / 4), dim3(256), 0, s, 0, X, A, P, (const double*)coef_ws, gX, gA, gP, B, C, d);
+    hipLaunchKernelGGL(pmath_hsoftmax_rowsum_kernel, dim3((C + 3) / 4), dim3(256), 0, s, 1, X, A, P, (const double*)coef_ws, gX, gA, gP, B, C, d);
+    STT_HIP(hipGetLastError());
+    return 0;
+}
+
+// Feature clipping x min(1, r / (|x| + 1e-5)) over rows (ToPoincare(clip_r=r)) and its backward pass.
+extern "C" int sttode_pmath_clip(const float* x, float* out, int rows, int d, float r, void* stream) {
+    STT_REQUIRE(x && out && rows > 0 && d > 0, "sttode_pmath_clip: null pointer or empty shape");
+    STT_REQUIRE(r > 0.f, "sttode_pmath_clip: the clipping radius r must be positive");
+    hipLaunchKernelGGL(pmath_clip_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, out, rows, d, r);
+    STT_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sttode_pmath_clip_bwd(const float* x, const float* g, float* gx, int rows, int d, float r, void* stream) {
+    STT_REQUIRE(x && g && gx && rows > 0 && d > 0, "sttode_pmath_clip_bwd: null pointer or empty shape");
+    STT_REQUIRE(r > 0.f, "sttode_pmath_clip_bwd: the clipping radius r must be positive");
+    hipLaunchKernelGGL(pmath_clip_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, g, gx, rows, d, r);
     STT_HIP(hipGetLastError());
     return 0;
 }

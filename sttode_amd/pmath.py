@@ -4,13 +4,14 @@ Every function takes CUDA(HIP) fp32 tensors and raises on CPU tensors (no fallba
 rows; the last dim is the feature dim.  ``auto_select_c`` is host arithmetic (scipy gamma, pmath.py:496-505).
 
 Gradients: ``project, lambda_x, mobius_add, dist, dist0, expmap, expmap0, logmap, logmap0, p2k, k2p, lorenz_factor``,
-``mobius_matvec`` and ``dist_matrix`` are differentiable with respect to their tensor arguments (``artanh``, ``arsinh`` and
-``RiemannianGradient`` always were): one fused backward kernel per operation (csrc/pmath_grad.hip), first order only
-(``once_differentiable``).  A function takes that path only when grad mode is on and an input requires grad; otherwise it makes exactly
-the calls of the forward-only path, and the forward values of the two paths are bitwise equal.  ``c`` is a Python float and gets no
-gradient.  ``mobius_matvec`` deviates from the reference in one place: a row with ``x m^T == 0`` gets a zero gradient (the reference: NaN).
-``_mobius_addition_batch``, ``_hyperbolic_softmax``, ``poincare_mean`` and the Oblique ops stay FORWARD-ONLY: their results are cut off
-from the graph.
+``mobius_matvec``, ``dist_matrix``, ``_mobius_addition_batch``, ``_hyperbolic_softmax`` and ``feature_clip`` are differentiable with respect
+to their tensor arguments (``artanh``, ``arsinh`` and ``RiemannianGradient`` always were): fused backward kernels (csrc/pmath_grad.hip,
+DESIGN.md 4q and 4r), first order only (``once_differentiable``).  A function takes that path only when grad mode is on and an input requires
+grad; otherwise it makes exactly the calls of the forward-only path, and the forward values of the two paths are bitwise equal.  ``c`` is a
+Python float and gets no gradient.  ``mobius_matvec`` deviates from the reference in one place: a row with ``x m^T == 0`` gets a zero
+gradient (the reference: NaN).  ``_hyperbolic_softmax`` needs non-zero rows of ``A`` (the reference gives NaN for a zero row).
+``poincare_mean`` and the Oblique ops stay FORWARD-ONLY: their results are cut off from the graph.
+``feature_clip(x, r)`` is not a function of the reference's pmath.py: it is the clipping of hyptorch/nn.py's ``ToPoincare(clip_r=r)``.
 """
 import numpy as np
 import torch
@@ -279,12 +280,93 @@ def dist_matrix(x, y, c=1.0):
     return _pair(0, x, y, None, c, (x.shape[0], y.shape[0]))
 
 
+class _MobiusAdditionBatch(torch.autograd.Function):
+    """_mobius_addition_batch and its backward: the forward is the pair kernel's; the backward is mobius_add's row kernel
+    (sttode_pmath_rowop_bwd) on the broadcast operands, summed back to each operand's shape.  Saves only x and y."""
+
+    @staticmethod
+    def forward(ctx, x, y, c):
+        ctx.save_for_backward(x, y)
+        ctx.c = c
+        return _pair(1, x, y, None, c, (x.shape[0], y.shape[0], x.shape[1]))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, y = ctx.saved_tensors
+        shape = (x.shape[0], y.shape[0], x.shape[1])
+        xb, yb = x.unsqueeze(1).expand(shape).contiguous(), y.unsqueeze(0).expand(shape).contiguous()
+        gx, gy = torch.empty_like(xb), torch.empty_like(yb)
+        capi.call('sttode_pmath_rowop_bwd', _OPS['mobius_add'], xb, yb, _prep(g), gx, gy, shape[0] * shape[1], shape[2], ctx.c, capi.stream_ptr())
+        return gx.sum_to_size(x.unsqueeze(1).shape).view_as(x), gy.sum_to_size(y.unsqueeze(0).shape).view_as(y), None
+
+
 def _mobius_addition_batch(x, y, c):
+    x, y = _prep(x), _prep(y)
+    if _wants_grad(x, y):
+        return _MobiusAdditionBatch.apply(x, y, float(c))
     return _pair(1, x, y, None, float(c), (x.shape[0], y.shape[0], x.shape[1]))
 
 
+class _HyperbolicSoftmax(torch.autograd.Function):
+    """_hyperbolic_softmax and its backward (sttode_pmath_hsoftmax_bwd).  Saves only X, A and P."""
+
+    @staticmethod
+    def forward(ctx, X, A, P, c):
+        ctx.save_for_backward(X, A, P)
+        ctx.c = c
+        return _pair(2, P, X, A, c, (X.shape[0], P.shape[0]))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        X, A, P = ctx.saved_tensors
+        B, C, d = X.shape[0], P.shape[0], X.shape[1]
+        ws = torch.empty(6, B, C, dtype=torch.float64, device=X.device)
+        gX, gA, gP = torch.empty_like(X), torch.empty_like(A), torch.empty_like(P)
+        capi.call('sttode_pmath_hsoftmax_bwd', X, A, P, _prep(g), ws, gX, gA, gP, B, C, d, ctx.c, capi.stream_ptr())
+        return gX, gA, gP, None
+
+
 def _hyperbolic_softmax(X, A, P, c):
+    X, A, P = _prep(X), _prep(A), _prep(P)
+    if _wants_grad(X, A, P):
+        return _HyperbolicSoftmax.apply(X, A, P, float(c))
     return _pair(2, P, X, A, float(c), (X.shape[0], P.shape[0]))
+
+
+def _clip_fwd(x, r):
+    d = x.shape[-1]
+    out = torch.empty_like(x)
+    capi.call('sttode_pmath_clip', x, out, x.numel() // d, d, float(r), capi.stream_ptr())
+    return out
+
+
+class _FeatureClip(torch.autograd.Function):
+    """feature_clip and its backward (sttode_pmath_clip_bwd).  Saves only x."""
+
+    @staticmethod
+    def forward(ctx, x, r):
+        ctx.save_for_backward(x)
+        ctx.r = r
+        return _clip_fwd(x, r)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        d = x.shape[-1]
+        gx = torch.empty_like(x)
+        capi.call('sttode_pmath_clip_bwd', x, _prep(g), gx, x.numel() // d, d, ctx.r, capi.stream_ptr())
+        return gx, None
+
+
+def feature_clip(x, r):
+    """x min(1, r / (|x| + 1e-5)) over the last dim: the clipping of hyptorch/nn.py's ToPoincare(clip_r=r) (nn.py:154-160)."""
+    x = _prep(x)
+    if _wants_grad(x):
+        return _FeatureClip.apply(x, float(r))
+    return _clip_fwd(x, float(r))
 
 
 def poincare_mean(x, dim=0, c=1.0):
