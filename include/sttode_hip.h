@@ -220,6 +220,24 @@ int sttode_best_of_k_select(const float* pred, const float* gt, int n, int K, in
 int sttode_joint_select(const float* pred, const float* gt, int n, int K, int Tf, float scale, const int* seg_ptr, int S, float radius,
                         float* seg_jade, float* seg_jfde, int* seg_jade_idx, int* seg_jfde_idx, int* seg_col, int* seg_gt_col, void* stream);
 int sttode_kde_nll(const float* pred, const float* gt, int n, int K, int Tf, float scale, double* nll, void* stream);
+/* Spread of the K sampled futures of every agent among themselves; the reference has only the DLow term, as a training loss
+ * (samplerloss.py:12-20).  pred [n,K,Tf,2] float32, gt [n,Tf,2] float32 or NULL; n >= 1, 2 <= K <= 64, Tf >= 1, div_scale > 0 and finite.
+ * Coordinates are x = (double)(x * scale), the product in float32 as sttode_kde_nll; everything after that is float64.  For the pairs
+ * i < j of an agent's samples, in F.pdist order, frames summed in frame order and pairs in pair order:
+ *   d_traj(i,j) = sqrt(sum_t |x_i,t - x_j,t|^2),  d_ade(i,j) = (1/Tf) sum_t |x_i,t - x_j,t|,  d_fde(i,j) = |x_i,Tf-1 - x_j,Tf-1|.
+ * Per agent, float64 [n] (required):
+ *   apd  = mean over the K(K-1)/2 pairs of d_traj (DLow's APD: pdist of the flattened trajectories);  fpd = mean of d_fde;
+ *   pade = mean of d_ade;  dlow = mean of exp(-d_traj^2 / div_scale): the per-agent term of diversity_loss, dlow.sum() / n its
+ *   loss_unweighted.
+ * With gt (each may be NULL; all must be NULL when gt is NULL):
+ *   es_ade [n] = (1/K) sum_k D_ade(x_k, y) - ((K-1)/(2K)) pade,  es_fde [n] = (1/K) sum_k D_fde(x_k, y) - ((K-1)/(2K)) fpd: the energy
+ *   score E|X - y| - E|X - X'|/2 of the ensemble with the 1/K^2 double sum, D_ade / D_fde the same float64 distances to the ground truth.
+ *   ade_at_k / fde_at_k [n,K] float32: column k-1 = the minimum over the first k samples of ADE(a, .) / FDE(a, .), the float32 values of
+ *   bok_select_kernel (NaN samples skipped): column K-1 is sttode_best_of_k_select's ade / fde bit for bit, and column k-1 what it gives
+ *   for the first k samples (+inf if all of them are NaN and k < 64, as there).
+ * Refused before any launch or write, naming the entry.  No atomics, every sum in a fixed order: the same bits on every run. */
+int sttode_sample_spread(const float* pred, const float* gt, int n, int K, int Tf, float scale, double div_scale, double* apd, double* fpd,
+                         double* pade, double* dlow, double* es_ade, double* es_fde, float* ade_at_k, float* fde_at_k, void* stream);
 
 /* Stage-2 latent sampler (sampler.py:47-54): z = b (eps_mode 0) or A*eps + b with eps shared [nz] (1, share_eps) or per agent
  * [n,nz] (2); logvar = log(A^2 + 1e-8).  A, b, z, logvar [n*K, nz] (row = agent*K + k). */
@@ -816,6 +834,11 @@ int sttode_async_joint_select(SttodeModel* m, int slot, const float* pred, const
                               const int* seg_ptr, int S, float radius, float* seg_jade, float* seg_jfde, int* seg_jade_idx, int* seg_jfde_idx,
                               int* seg_col, int* seg_gt_col);
 int sttode_async_kde_nll(SttodeModel* m, int slot, const float* pred, const float* gt, int n, int K, int Tf, float scale, double* nll);
+/* sttode_sample_spread of an asynchronous call's predictions, on the call's pipeline stream behind its outstanding groups, the slot's
+ * completion event re-recorded behind it (as sttode_async_kde_nll). */
+int sttode_async_sample_spread(SttodeModel* m, int slot, const float* pred, const float* gt, int n, int K, int Tf, float scale,
+                               double div_scale, double* apd, double* fpd, double* pade, double* dlow, double* es_ade, double* es_fde,
+                               float* ade_at_k, float* fde_at_k);
 int sttode_wait(SttodeModel* m, int slot, void* stream);
 /* Zero-copy futures (lagged form): the trajectory groups of a lagged call only WRITE `pred` (block 0's y_hat0 waits in the workspace), so
  * `pred` may be pinned host memory addressed by its host pointer: the futures reach the host with the launch itself, no D2H copy

@@ -42,6 +42,7 @@ SIGNATURES = {
     'sttode_best_of_k_select': [_P, _P, _I, _I, _I, _F, _F, _P, _I] + [_P] * 10,
     'sttode_joint_select': [_P, _P, _I, _I, _I, _F, _P, _I, _F] + [_P] * 7,
     'sttode_kde_nll': [_P, _P, _I, _I, _I, _F, _P, _P],
+    'sttode_sample_spread': [_P, _P, _I, _I, _I, _F, _D] + [_P] * 9,
     # stage-2 sampler (csrc/sampler.hip)
     'sttode_sampler_latent': [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P],
     'sttode_sampler_loss': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P],
@@ -141,6 +142,7 @@ SIGNATURES = {
     'sttode_async_best_of_k_select': [_P, _I, _P, _P, _I, _I, _I, _F, _F, _P, _I] + [_P] * 9,
     'sttode_async_joint_select': [_P, _I, _P, _P, _I, _I, _I, _F, _P, _I, _F] + [_P] * 6,
     'sttode_async_kde_nll': [_P, _I, _P, _P, _I, _I, _I, _F, _P],
+    'sttode_async_sample_spread': [_P, _I, _P, _P, _I, _I, _I, _F, _D] + [_P] * 8,
     'sttode_wait': [_P, _I, _P],
     'sttode_async_is_lagged': [_P, _I],
     'sttode_wait_host': [_P, _I],

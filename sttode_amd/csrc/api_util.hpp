@@ -84,9 +84,12 @@ bool stt_chain_lagged_covers(int Tp);
 struct SttodeSamplerPlan;
 const char* stt_sampler_plan_check(const SttodeSamplerPlan* plan, int K);
 int stt_sampler_qnet(const SttodeSamplerPlan* plan, const float* pf, int n, float* z, void* stream);
-// metrics.hip: argument checks of sttode_joint_select / sttode_kde_nll, shared with their asynchronous forms (0, or 1 with the error set,
+// metrics.hip: argument checks of sttode_joint_select / sttode_kde_nll / sttode_sample_spread, shared with their asynchronous forms (0, or 1 with the error set,
 // naming `who`)
 int stt_joint_check(const char* who, const float* pred, const float* gt, int n, int K, int Tf, const int* seg_ptr, int S, float radius,
                     const float* seg_jade, const float* seg_jfde, const int* seg_jade_idx, const int* seg_jfde_idx, const int* seg_col,
                     const int* seg_gt_col);
 int stt_kde_check(const char* who, const float* pred, const float* gt, int n, int K, int Tf, const double* nll);
+int stt_spread_check(const char* who, const float* pred, const float* gt, int n, int K, int Tf, double div_scale, const double* apd,
+                     const double* fpd, const double* pade, const double* dlow, const double* es_ade, const double* es_fde,
+                     const float* ade_at_k, const float* fde_at_k);

@@ -6,7 +6,10 @@
 //   joint_collision_kernel  one workgroup per segment: per sample (and the ground truth) the agents that come closer than r to another agent
 //                           of the segment at some frame; positions staged in LDS in tiles of 64 agents x 8 frames.
 //   kde_nll_kernel          one wave per agent, frames on lanes, everything in float64; samples staged in LDS in tiles of frames.
+//   sample_spread_kernel    one workgroup per agent: the K (K-1) / 2 sample pairs dealt to the threads, float64 (sttode_sample_spread, 4s).
 // No atomics: every sum has a fixed order, so runs give the same bits.
+#include <cmath>
+
 #include "api_util.hpp"
 #include "frontend_body.hpp"
 #include "../../include/sttode_hip.h"
@@ -236,6 +239,152 @@ __global__ __launch_bounds__(256) void kde_nll_kernel(const float* __restrict__ 
     if (lane == 0) nll[a] = any_bad ? (double)NAN : -acc / Tf;
 }
 
+constexpr int SS_FT = 32;             // frames per LDS tile of the spread pass
+constexpr int SS_STRIDE = SS_FT + 1;  // row stride in float2: odd, so that lanes on different samples at one frame fall on different banks
+constexpr int SS_K1 = 23;             // the largest K with one pair per thread at most: 23 * 22 / 2 = 253 <= 256
+
+// Spread of agent a's K samples among themselves (include/sttode_hip.h sttode_sample_spread), one workgroup per agent.
+// Coordinates are (double)(x * scale) with the product in fp32, everything after that float64.  The samples go through LDS in tiles of SS_FT
+// frames (raw float2, rows of SS_STRIDE).  Pair p (F.pdist order: (0,1), (0,2), ... (K-2,K-1)) belongs to thread p mod 256; a thread keeps, per
+// pair, the running sum of squared distances, the running sum of distances and the last frame's distance, frames in frame order.  After the
+// last tile it finishes its pairs in pair order (sqrt, exp) into four partial sums; those go through LDS, wave 0 adds the four of lane l,
+// l + 64, l + 128, l + 192 in that order and the 64 lanes by a fixed xor tree.  No atomics.
+// R = pairs per thread, KM = the largest K.  <8, 64> takes any K (2016 pairs <= 8 * 256); <1, SS_K1> is the same code for K <= 23, where the
+// registers of seven more pairs and the LDS of 41 more samples would halve the workgroups a CU holds: the kernel waits on latency.
+// With gt: wave 3 (the one with the fewest pairs), lane = sample, sums the float64 distances to the ground truth for the energy scores and, in
+// fp32 with bok_dist in frame order, bok_select_kernel's ADE(a, k) / FDE(a, k); an inclusive prefix minimum over the lanes (fminf: NaN
+// skipped) gives the *_at_k rows.  A prefix of k < 64 samples that are all NaN gives +inf (k = 64: NaN), as the selection of those k samples.
+template <int R, int KM>
+__global__ __launch_bounds__(256) void sample_spread_kernel(const float* __restrict__ pred, const float* __restrict__ gt, int K, int Tf,
+                                                            float scale, double div_scale, double* __restrict__ apd, double* __restrict__ fpd,
+                                                            double* __restrict__ pade, double* __restrict__ dlow, double* __restrict__ es_ade,
+                                                            double* __restrict__ es_fde, float* __restrict__ ade_at_k,
+                                                            float* __restrict__ fde_at_k) {
+    __shared__ float2 sx[KM * SS_STRIDE];
+    __shared__ float2 sg[SS_FT];
+    __shared__ double red[4][256];
+    __shared__ double gsum[2];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int a = blockIdx.x;
+    const int P = K * (K - 1) / 2;
+    const float2* p = reinterpret_cast<const float2*>(pred + (size_t)a * K * Tf * 2);
+    const float2* g = gt ? reinterpret_cast<const float2*>(gt + (size_t)a * Tf * 2) : nullptr;
+    int ij[R];                                   // (i, j) of the thread's r-th pair as i | j << 8
+    double s2[R], s1[R], dl[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        int q = tid + 256 * r, i = 0;
+        if (q < P)
+            while (q >= K - 1 - i) {
+                q -= K - 1 - i;
+                ++i;
+            }
+        ij[r] = i | (i + 1 + q) << 8;
+        s2[r] = s1[r] = dl[r] = 0.0;
+    }
+    const bool gw = g != nullptr && w == 3;
+    double ga = 0.0, gl = 0.0;                            // wave 3, lane k: sum over frames of |x_k - y| and the last frame's, float64
+    float fa = 0.f, fl = 0.f;                             // the same with bok_dist in fp32
+    for (int t0 = 0; t0 < Tf; t0 += SS_FT) {
+        const int ft = min(SS_FT, Tf - t0);
+        for (int i = tid; i < K * ft; i += 256) {
+            const int k = i / ft, tl = i - k * ft;
+            sx[k * SS_STRIDE + tl] = p[k * Tf + t0 + tl];
+        }
+        if (g && tid < ft) sg[tid] = g[t0 + tid];
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            if (tid + 256 * r < P) {
+                const float2* xi = sx + (ij[r] & 255) * SS_STRIDE;
+                const float2* xj = sx + (ij[r] >> 8) * SS_STRIDE;
+                for (int tl = 0; tl < ft; ++tl) {
+                    const float2 u = xi[tl], v = xj[tl];
+                    const double dx = (double)(u.x * scale) - (double)(v.x * scale), dy = (double)(u.y * scale) - (double)(v.y * scale);
+                    const double d2 = dx * dx + dy * dy;
+                    dl[r] = sqrt(d2);
+                    s2[r] += d2;
+                    s1[r] += dl[r];
+                }
+            }
+        }
+        if (gw && lane < K) {
+            for (int tl = 0; tl < ft; ++tl) {
+                const float2 v = sx[lane * SS_STRIDE + tl], y = sg[tl];
+                const double dx = (double)(v.x * scale) - (double)(y.x * scale), dy = (double)(v.y * scale) - (double)(y.y * scale);
+                gl = sqrt(dx * dx + dy * dy);
+                ga += gl;
+                fl = bok_dist(v.x, v.y, y.x, y.y, scale);
+                fa += fl;
+            }
+        }
+        __syncthreads();   // (the next tile overwrites sx and sg)
+    }
+    double t_apd = 0.0, t_fpd = 0.0, t_pade = 0.0, t_dlow = 0.0;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        if (tid + 256 * r < P) {
+            t_apd += sqrt(s2[r]);
+            t_fpd += dl[r];
+            t_pade += s1[r] / Tf;
+            t_dlow += exp(-s2[r] / div_scale);
+        }
+    }
+    red[0][tid] = t_apd;
+    red[1][tid] = t_fpd;
+    red[2][tid] = t_pade;
+    red[3][tid] = t_dlow;
+    if (gw) {
+        double da = lane < K ? ga / Tf : 0.0, df = lane < K ? gl : 0.0;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            da += __shfl_xor(da, o, 64);
+            df += __shfl_xor(df, o, 64);
+        }
+        if (lane == 0) {
+            gsum[0] = da;
+            gsum[1] = df;
+        }
+        if (ade_at_k || fde_at_k) {
+            float va = lane < K ? fa / (float)Tf : INFINITY, vf = lane < K ? fl : INFINITY;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const float ua = __shfl_up(va, o, 64), uf = __shfl_up(vf, o, 64);
+                if (lane >= o) {
+                    va = fminf(va, ua);
+                    vf = fminf(vf, uf);
+                }
+            }
+            if (lane < 63) {                              // (the selection of k < 64 samples takes its minimum with the idle lanes' +inf)
+                va = fminf(va, INFINITY);
+                vf = fminf(vf, INFINITY);
+            }
+            if (lane < K) {
+                if (ade_at_k) ade_at_k[(size_t)a * K + lane] = va;
+                if (fde_at_k) fde_at_k[(size_t)a * K + lane] = vf;
+            }
+        }
+    }
+    __syncthreads();
+    if (w != 0) return;
+    double v[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        v[q] = ((red[q][lane] + red[q][lane + 64]) + red[q][lane + 128]) + red[q][lane + 192];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v[q] += __shfl_xor(v[q], o, 64);
+    }
+    if (lane == 0) {
+        const double np = (double)P, c = (double)(K - 1) / (2.0 * K);
+        apd[a] = v[0] / np;
+        fpd[a] = v[1] / np;
+        pade[a] = v[2] / np;
+        dlow[a] = v[3] / np;
+        if (es_ade) es_ade[a] = gsum[0] / K - c * (v[2] / np);
+        if (es_fde) es_fde[a] = gsum[1] / K - c * (v[1] / np);
+    }
+}
+
 }  // namespace
 
 // Argument checks of the joint pass, shared with sttode_async_joint_select (pipeline.hip): 0, or 1 with the error set naming `who`.
@@ -273,6 +422,27 @@ int stt_kde_check(const char* who, const float* pred, const float* gt, int n, in
     return 1;
 }
 
+int stt_spread_check(const char* who, const float* pred, const float* gt, int n, int K, int Tf, double div_scale, const double* apd,
+                     const double* fpd, const double* pade, const double* dlow, const double* es_ade, const double* es_fde,
+                     const float* ade_at_k, const float* fde_at_k) {
+    char b[256];
+    const char* why = nullptr;
+    if (!(pred && apd && fpd && pade && dlow))
+        why = "null pointer (pred, apd, fpd, pade and dlow are required)";
+    else if (!gt && (es_ade || es_fde || ade_at_k || fde_at_k))
+        why = "es_ade, es_fde, ade_at_k and fde_at_k need gt (pass them as NULL without it)";
+    else if (!(n > 0 && Tf > 0))
+        why = "n and Tf must be positive";
+    else if (K < 2 || K > 64)
+        why = "needs 2 <= K <= 64 (K < 2: no pair; K > 64: one lane per sample)";
+    else if (!(div_scale > 0.0) || std::isinf(div_scale))
+        why = "div_scale must be positive and finite";
+    if (!why) return 0;
+    snprintf(b, sizeof(b), "%s: %s", who, why);
+    stt_set_error(b);
+    return 1;
+}
+
 extern "C" int sttode_joint_select(const float* pred, const float* gt, int n, int K, int Tf, float scale, const int* seg_ptr, int S, float radius,
                                    float* seg_jade, float* seg_jfde, int* seg_jade_idx, int* seg_jfde_idx, int* seg_col, int* seg_gt_col,
                                    void* stream) {
@@ -292,6 +462,21 @@ extern "C" int sttode_joint_select(const float* pred, const float* gt, int n, in
 extern "C" int sttode_kde_nll(const float* pred, const float* gt, int n, int K, int Tf, float scale, double* nll, void* stream) {
     if (stt_kde_check("sttode_kde_nll", pred, gt, n, K, Tf, nll)) return 1;
     hipLaunchKernelGGL(kde_nll_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, pred, gt, n, K, Tf, scale, nll);
+    STT_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sttode_sample_spread(const float* pred, const float* gt, int n, int K, int Tf, float scale, double div_scale, double* apd,
+                                    double* fpd, double* pade, double* dlow, double* es_ade, double* es_fde, float* ade_at_k, float* fde_at_k,
+                                    void* stream) {
+    if (stt_spread_check("sttode_sample_spread", pred, gt, n, K, Tf, div_scale, apd, fpd, pade, dlow, es_ade, es_fde, ade_at_k, fde_at_k))
+        return 1;
+    if (K <= SS_K1)
+        hipLaunchKernelGGL((sample_spread_kernel<1, SS_K1>), dim3(n), dim3(256), 0, (hipStream_t)stream, pred, gt, K, Tf, scale, div_scale, apd,
+                           fpd, pade, dlow, es_ade, es_fde, ade_at_k, fde_at_k);
+    else
+        hipLaunchKernelGGL((sample_spread_kernel<8, 64>), dim3(n), dim3(256), 0, (hipStream_t)stream, pred, gt, K, Tf, scale, div_scale, apd, fpd,
+                           pade, dlow, es_ade, es_fde, ade_at_k, fde_at_k);
     STT_HIP(hipGetLastError());
     return 0;
 }

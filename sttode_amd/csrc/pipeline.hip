@@ -843,7 +843,7 @@ extern "C" int sttode_async_best_of_k_select(SttodeModel* m, int slot, const flo
     return 0;
 }
 
-// Scene-level metrics (joint min ADE / FDE and collisions; KDE NLL: metrics.hip) of an asynchronous call's predictions, on the call's own
+// Scene-level metrics (joint min ADE / FDE and collisions; KDE NLL; sample spread: metrics.hip) of an asynchronous call's predictions, on the call's own
 // pipeline stream like sttode_async_best_of_k_select.  The arguments are checked before the slot's groups are enqueued.
 extern "C" int sttode_async_joint_select(SttodeModel* m, int slot, const float* pred, const float* gt, int n, int K, int Tf, float scale,
                                          const int* seg_ptr, int S, float radius, float* seg_jade, float* seg_jfde, int* seg_jade_idx,
@@ -869,6 +869,22 @@ extern "C" int sttode_async_kde_nll(SttodeModel* m, int slot, const float* pred,
     STT_REQUIRE(m->slot_stream[slot] != nullptr, "sttode_async_kde_nll: no asynchronous call has used this slot");
     if (int rc = lag_flush(m, slot)) return rc;
     if (int rc = sttode_kde_nll(pred, gt, n, K, Tf, scale, nll, m->slot_stream[slot])) return rc;
+    STT_HIP(hipEventRecord(m->evB_done[slot], m->slot_stream[slot]));
+    return 0;
+}
+
+extern "C" int sttode_async_sample_spread(SttodeModel* m, int slot, const float* pred, const float* gt, int n, int K, int Tf, float scale,
+                                          double div_scale, double* apd, double* fpd, double* pade, double* dlow, double* es_ade,
+                                          double* es_fde, float* ade_at_k, float* fde_at_k) {
+    STT_REQUIRE(m && slot >= 0 && slot < STT_MAX_SLOTS, "sttode_async_sample_spread: bad model / slot");
+    if (stt_spread_check("sttode_async_sample_spread", pred, gt, n, K, Tf, div_scale, apd, fpd, pade, dlow, es_ade, es_fde, ade_at_k, fde_at_k))
+        return 1;
+    std::lock_guard<std::mutex> lk(m->mu);
+    STT_REQUIRE(m->slot_stream[slot] != nullptr, "sttode_async_sample_spread: no asynchronous call has used this slot");
+    if (int rc = lag_flush(m, slot)) return rc;
+    if (int rc = sttode_sample_spread(pred, gt, n, K, Tf, scale, div_scale, apd, fpd, pade, dlow, es_ade, es_fde, ade_at_k, fde_at_k,
+                                      m->slot_stream[slot]))
+        return rc;
     STT_HIP(hipEventRecord(m->evB_done[slot], m->slot_stream[slot]));
     return 0;
 }

@@ -7,7 +7,8 @@
                   1..future_length (the reference prints every 0.4 s step), weighted by batch size.
   eval_scenes_report / eval_sampler_report / eval_nba_report: the same loops returning an EvalReport -- global ADE / FDE and miss rate,
                   per-scene (per NBA batch) ADE / FDE / miss count, the best sample of every agent (utils/metrics.py:29-48); on request
-                  the scene-level metrics of DESIGN.md 4l: joint min ADE / FDE, collision rates, KDE NLL.
+                  the scene-level metrics of DESIGN.md 4l: joint min ADE / FDE, collision rates, KDE NLL; and the spread of the samples
+                  among themselves of DESIGN.md 4s: APD / FPD, the DLow kernel value, energy scores, best-of-k.
   eval_scenes_reduced  oversample and reduce: `rounds` calls per scene batch, k-means of the rounds * sample_k futures of every
                   agent to K representatives on the device, then the selection of eval_scenes_report on the representatives.
   embedding_delta  how tree-like the encoder's past features (or the observed tracks) of a dataset are: delta / diam of hyptorch/delta.py's
@@ -195,7 +196,13 @@ class EvalReport:
     ``collision_rate`` (colliding agent-samples / (K n)), ``gt_collision_rate`` (colliding agents of the ground truth / n) and
     ``scene_collision`` [S, 2] (per segment: colliding agent-samples, colliding ground-truth agents).  ``kde=True``: ``kde_nll`` (mean over
     the agents whose NLL is finite), ``kde_nll_agents`` [n] float64 (NaN where the samples' covariance is singular) and ``kde_invalid`` (the
-    number of NaN agents)."""
+    number of NaN agents).
+
+    Spread of the samples among themselves, None unless ``spread=True``: ``apd`` / ``fpd`` / ``pade`` (mean over agents of the
+    mean pairwise trajectory / final-frame / per-frame distance), ``dlow`` (mean over agents of the DLow kernel value at ``div_scale``:
+    diversity_loss's loss_unweighted), ``energy_ade`` / ``energy_fde`` (mean energy score), all float64 sums over agents in dataset order;
+    ``spread_agents`` [n, 6] float64 (the six values per agent, in that order); ``ade_at_k`` / ``fde_at_k``: a dict k -> mean over agents of
+    the min ADE / FDE over the first k samples, for each k <= K of ``ks``."""
     ade: float
     fde: float
     n_agents: int
@@ -221,27 +228,52 @@ class EvalReport:
     kde_nll: float = None
     kde_nll_agents: np.ndarray = None
     kde_invalid: int = None
+    apd: float = None
+    fpd: float = None
+    pade: float = None
+    dlow: float = None
+    energy_ade: float = None
+    energy_fde: float = None
+    spread_agents: np.ndarray = None
+    ade_at_k: dict = None
+    fde_at_k: dict = None
 
 
 class _ReportAcc:
     """Host side of a report loop: per call, the same double sums eval_scenes forms (so the global ADE / FDE agree bit for bit), and the
     small per-scene / per-agent arrays."""
 
-    def __init__(self, miss_threshold, joint=False, kde=False, collision_radius=None, K=None):
-        from .metrics import check_radius
+    def __init__(self, miss_threshold, joint=False, kde=False, collision_radius=None, K=None, spread=False, div_scale=None, ks=(1, 5, 10),
+                 dataset=None):
+        from .metrics import check_radius, check_spread
         self.thr = float(miss_threshold)
         self.tot_a = self.tot_f = 0.0
         self.n = 0
         self.parts = []
         self.joint, self.kde, self.radius, self.K = bool(joint), bool(kde), check_radius(collision_radius), K
         self.jparts, self.kparts = [], []
+        self.spread = bool(spread)
+        if self.spread:
+            if div_scale is None:
+                from .samplerloss import get_diversity_config
+                div_scale = get_diversity_config(dataset)['scale'] if dataset is not None else 1.0
+            self.div_scale = check_spread(K, div_scale)
+            self.ks = [int(k) for k in ks if 1 <= int(k) <= K]
+            self.sparts = []
 
     @property
     def scene_metrics(self):
         """Whether a joint pass runs (for the joint values, the collision counts or both)."""
         return self.joint or self.radius is not None
 
-    def add_scene_metrics(self, js, kd):
+    def add_spread(self, ss):
+        cols = torch.tensor([k - 1 for k in self.ks], dtype=torch.long, device=ss.apd.device)
+        self.sparts.append((torch.stack([ss.apd, ss.fpd, ss.pade, ss.dlow, ss.es_ade, ss.es_fde], dim=1).cpu().numpy(),
+                            ss.ade_at_k[:, cols].cpu().numpy(), ss.fde_at_k[:, cols].cpu().numpy()))
+
+    def add_scene_metrics(self, js, kd, ss=None):
+        if ss is not None:
+            self.add_spread(ss)
         if js is not None:
             self.jparts.append((js.seg_jade.cpu().numpy(), js.seg_jfde.cpu().numpy(), js.seg_jade_idx.cpu().numpy(),
                                 None if js.seg_col is None else torch.stack([js.seg_col, js.seg_gt_col], dim=1).cpu().numpy()))
@@ -276,19 +308,26 @@ class _ReportAcc:
             ok = np.isfinite(v)
             rep.kde_nll_agents, rep.kde_invalid = v, int((~ok).sum())
             rep.kde_nll = float(v[ok].mean()) if ok.any() else float('nan')
+        if self.spread:
+            v, ak, fk = (np.concatenate([p[i] for p in self.sparts]) for i in range(3))
+            rep.spread_agents = v
+            rep.apd, rep.fpd, rep.pade, rep.dlow, rep.energy_ade, rep.energy_fde = (float(x) for x in v.sum(axis=0) / v.shape[0])
+            rep.ade_at_k = {k: float(ak[:, i].astype(np.float64).sum() / ak.shape[0]) for i, k in enumerate(self.ks)}
+            rep.fde_at_k = {k: float(fk[:, i].astype(np.float64).sum() / fk.shape[0]) for i, k in enumerate(self.ks)}
         return rep
 
 
 def _scenes_report(model, dataset, scenes_per_call, pipelined, traj_scale, miss_threshold, gather, launch, serial, joint, kde,
-                   collision_radius):
-    acc = _ReportAcc(miss_threshold, joint, kde, collision_radius, model.args.sample_k)
+                   collision_radius, spread=False, div_scale=None, ks=(1, 5, 10)):
+    acc = _ReportAcc(miss_threshold, joint, kde, collision_radius, model.args.sample_k, spread, div_scale, ks,
+                     getattr(model.args, 'dataset', None))
     pend = []
 
     def finish(item):
-        h, sel, sp, js, kd = item
+        h, sel, sp, js, kd, ss = item
         model.wait(h)
         acc.add(sel, sp)
-        acc.add_scene_metrics(js, kd)
+        acc.add_scene_metrics(js, kd, ss)
     for s0 in range(0, len(dataset), scenes_per_call):
         sb = dataset.scene_batch(range(s0, min(s0 + scenes_per_call, len(dataset))))
         model.set_scene_batch(sb.past, sb.future, sb.scene_ptr)
@@ -301,7 +340,8 @@ def _scenes_report(model, dataset, scenes_per_call, pipelined, traj_scale, miss_
             sel = model.select_best_of_k_async(h, scale=traj_scale, miss_threshold=miss_threshold, seg_ptr='scenes', gather=gather)
             js = model.select_joint_async(h, seg_ptr='scenes', scale=traj_scale, collision_radius=acc.radius) if acc.scene_metrics else None
             kd = model.kde_nll_async(h, scale=traj_scale) if kde else None
-            pend.append((h, sel, sb.scene_ptr, js, kd))
+            ss = model.sample_spread_async(h, scale=traj_scale, div_scale=acc.div_scale) if spread else None
+            pend.append((h, sel, sb.scene_ptr, js, kd, ss))
             if len(pend) > 4:
                 finish(pend.pop(0))
             continue
@@ -309,10 +349,11 @@ def _scenes_report(model, dataset, scenes_per_call, pipelined, traj_scale, miss_
         sel = model.select_best_of_k(pred.permute(1, 0, 2, 3), scale=traj_scale, miss_threshold=miss_threshold, seg_ptr=model._scene_ptr,
                                      gather=gather)
         acc.add(sel, sb.scene_ptr)
-        if acc.scene_metrics or kde:
+        if acc.scene_metrics or kde or spread:
             pnk = pred.permute(1, 0, 2, 3).contiguous()
             acc.add_scene_metrics(model.select_joint(pnk, seg_ptr=model._scene_ptr, scale=traj_scale, collision_radius=acc.radius)
-                                  if acc.scene_metrics else None, model.kde_nll(pnk, scale=traj_scale) if kde else None)
+                                  if acc.scene_metrics else None, model.kde_nll(pnk, scale=traj_scale) if kde else None,
+                                  model.sample_spread(pnk, scale=traj_scale, div_scale=acc.div_scale) if spread else None)
     while pend:
         finish(pend.pop(0))
     if pipelined:
@@ -322,11 +363,13 @@ def _scenes_report(model, dataset, scenes_per_call, pipelined, traj_scale, miss_
 
 @torch.no_grad()
 def eval_scenes_report(model, dataset, traj_scale=1.0, scenes_per_call=512, z_fn=None, pipelined=True, miss_threshold=1.0, gather=False,
-                       joint=False, kde=False, collision_radius=None):
+                       joint=False, kde=False, collision_radius=None, spread=False, div_scale=None, ks=(1, 5, 10)):
     """eval_scenes with the per-scene breakdown, the best sample of every agent and the miss rate (an ``EvalReport``).  The same calls, latents
     and global ADE / FDE as eval_scenes; each call adds one selection pass on its own pipeline stream (``select_best_of_k_async``).
     ``joint`` / ``collision_radius`` / ``kde`` add the scene-level passes (``select_joint_async``, ``kde_nll_async``; after the serial call
-    with ``pipelined=False``); every other field is the same with them on or off."""
+    with ``pipelined=False``); every other field is the same with them on or off.  ``spread`` adds the spread pass (``sample_spread_async``:
+    APD / FPD, the DLow kernel value at ``div_scale`` -- default: the scale of samplerloss.get_diversity_config for the model's dataset -- the
+    energy scores and best-of-k for each k of ``ks``) in the same way."""
     K, zd = model.args.sample_k, model.args.zdim
 
     def latents(sb):
@@ -334,26 +377,27 @@ def eval_scenes_report(model, dataset, traj_scale=1.0, scenes_per_call=512, z_fn
         return z_fn(rows) if z_fn is not None else torch.randn(rows, zd, device=model.device)
     return _scenes_report(model, dataset, scenes_per_call, pipelined, traj_scale, miss_threshold, gather,
                           lambda sb: model.inference_async(z=latents(sb), metrics_gt=model._future, metrics_scale=traj_scale),
-                          lambda sb: model.inference(None, z=latents(sb)), joint, kde, collision_radius)
+                          lambda sb: model.inference(None, z=latents(sb)), joint, kde, collision_radius, spread, div_scale, ks)
 
 
 @torch.no_grad()
 def eval_scenes_reduced(model, dataset, rounds, K=None, iters=10, from_frame=0, init='first', traj_scale=1.0, scenes_per_call=512, z_fn=None,
-                        pipelined=True, miss_threshold=1.0):
+                        pipelined=True, miss_threshold=1.0, spread=False, div_scale=None, ks=(1, 5, 10)):
     """Oversample and reduce as an evaluation loop: per scene batch ``rounds`` inference calls -- M = rounds * sample_k futures
     per agent -- reduced to ``K`` (default sample_k) representatives per agent by ``metrics.reduce_samples`` (``iters``, ``from_frame``,
     ``init`` as there), and the best-of-K selection of eval_scenes_report on the representatives.  Returns an ``EvalReport``.
     ``z_fn(rows)`` is asked once per round, in round order.  ``pipelined`` (default): the rounds go through ``inference_async``, never more
     in flight than ``async_depth`` allows; each is waited for and copied into the round buffer before its slot is taken again.  The reduction
     and the selection run on the caller's stream.  The two forms' samples differ by fp32 rounding (as inference_async and inference do), so
-    with rounds > 1 a near-tied label may legitimately differ between them."""
+    with rounds > 1 a near-tied label may legitimately differ between them.  ``spread`` / ``div_scale`` / ``ks`` as eval_scenes_report, on the
+    representatives: what the reduction does to the diversity of the set."""
     from . import metrics
     rounds = int(rounds)
     if rounds < 1:
         raise ValueError(f'eval_scenes_reduced needs rounds >= 1, got {rounds}')
     Ks, zd = model.args.sample_k, model.args.zdim
     K = Ks if K is None else int(K)
-    acc = _ReportAcc(miss_threshold, K=K)
+    acc = _ReportAcc(miss_threshold, K=K, spread=spread, div_scale=div_scale, ks=ks, dataset=getattr(model.args, 'dataset', None))
     depth = max(2, min(8, int(model.async_depth)))
     for s0 in range(0, len(dataset), scenes_per_call):
         sb = dataset.scene_batch(range(s0, min(s0 + scenes_per_call, len(dataset))))
@@ -382,6 +426,8 @@ def eval_scenes_reduced(model, dataset, rounds, K=None, iters=10, from_frame=0, 
                 buf[r].copy_(model.inference(None, z=z).permute(1, 0, 2, 3))
         red = metrics.reduce_samples(buf, K, iters=iters, from_frame=from_frame, init=init)
         acc.add(model.select_best_of_k(red.centroids, scale=traj_scale, miss_threshold=miss_threshold, seg_ptr=model._scene_ptr), sb.scene_ptr)
+        if spread:
+            acc.add_spread(model.sample_spread(red.centroids, scale=traj_scale, div_scale=acc.div_scale))
     if pipelined:
         model.reset_async()
     return acc.report(False)
@@ -389,27 +435,30 @@ def eval_scenes_reduced(model, dataset, rounds, K=None, iters=10, from_frame=0, 
 
 @torch.no_grad()
 def eval_sampler_report(model, sampler, dataset, traj_scale=1.0, scenes_per_call=512, mean=True, eps_fn=None, pipelined=True,
-                        miss_threshold=1.0, gather=False, joint=False, kde=False, collision_radius=None):
+                        miss_threshold=1.0, gather=False, joint=False, kde=False, collision_radius=None, spread=False, div_scale=None,
+                        ks=(1, 5, 10)):
     """eval_sampler with the per-scene breakdown, the best sample of every agent and the miss rate (an ``EvalReport``; test_sampler.py:214-217
-    asks count_miss_samples of the same loop).  ``joint`` / ``collision_radius`` / ``kde`` as eval_scenes_report."""
+    asks count_miss_samples of the same loop).  ``joint`` / ``collision_radius`` / ``kde`` / ``spread`` / ``div_scale`` / ``ks`` as
+    eval_scenes_report."""
     def eps_of(sb):
         return eps_fn(1 if sampler.share_eps else sb.n_agents) if (not mean and eps_fn is not None) else None
     return _scenes_report(model, dataset, scenes_per_call, pipelined, traj_scale, miss_threshold, gather,
                           lambda sb: sampler.inference_async(model, mean=mean, eps=eps_of(sb), metrics_gt=model._future,
                                                              metrics_scale=traj_scale),
-                          lambda sb: sampler.inference(model, mean=mean, eps=eps_of(sb)), joint, kde, collision_radius)
+                          lambda sb: sampler.inference(model, mean=mean, eps=eps_of(sb)), joint, kde, collision_radius, spread, div_scale, ks)
 
 
 @torch.no_grad()
 def eval_nba_report(model, loader, traj_scale=1.0, z_fn=None, pipelined=True, groups_per_call=16, miss_threshold=1.0, gather=False,
-                    joint=False, kde=False, collision_radius=None):
+                    joint=False, kde=False, collision_radius=None, spread=False, div_scale=None, ks=(1, 5, 10)):
     """NBA evaluation (test.py:495-552) as an ``EvalReport``: ADE / FDE over the whole horizon (the last horizon of eval_nba), the miss rate,
     per loader batch its ADE / FDE / miss count, the best sample of every agent.  Calls as eval_nba: up to ``groups_per_call`` loader batches
     of one shape per call, several in flight, the selection on each call's pipeline stream with one segment per loader batch.
-    ``joint`` / ``collision_radius`` / ``kde`` as eval_scenes_report; the joint and collision segments are games (N players each)."""
+    ``joint`` / ``collision_radius`` / ``kde`` / ``spread`` / ``div_scale`` / ``ks`` as eval_scenes_report; the joint and collision segments
+    are games (N players each)."""
     Tf, K = model.args.future_length, model.args.sample_k
     dev = model.device
-    acc = _ReportAcc(miss_threshold, joint, kde, collision_radius, K)
+    acc = _ReportAcc(miss_threshold, joint, kde, collision_radius, K, spread, div_scale, ks, getattr(model.args, 'dataset', 'nba'))
     if not pipelined:
         for data in loader:
             model.set_data_nba(data)
@@ -419,21 +468,22 @@ def eval_nba_report(model, loader, traj_scale=1.0, z_fn=None, pipelined=True, gr
             sp = np.array([0, n], dtype=np.int32)
             acc.add(model.select_best_of_k(pred.permute(1, 0, 2, 3), scale=traj_scale, miss_threshold=miss_threshold, seg_ptr=sp,
                                            gather=gather), sp)
-            if acc.scene_metrics or kde:
+            if acc.scene_metrics or kde or spread:
                 pnk = pred.permute(1, 0, 2, 3).contiguous()
                 games = np.arange(0, n + 1, data['past_traj'].shape[1], dtype=np.int32)
                 acc.add_scene_metrics(model.select_joint(pnk, seg_ptr=games, scale=traj_scale, collision_radius=acc.radius)
-                                      if acc.scene_metrics else None, model.kde_nll(pnk, scale=traj_scale) if kde else None)
+                                      if acc.scene_metrics else None, model.kde_nll(pnk, scale=traj_scale) if kde else None,
+                                      model.sample_spread(pnk, scale=traj_scale, div_scale=acc.div_scale) if spread else None)
         return acc.report(gather)
 
     pend = []
     seg_ptrs = {}
 
     def finish(item):
-        h, sel, sp, js, kd = item
+        h, sel, sp, js, kd, ss = item
         model.wait(h)
         acc.add(sel, sp)
-        acc.add_scene_metrics(js, kd)
+        acc.add_scene_metrics(js, kd, ss)
 
     def submit(group):
         B, N = group[0]['past_traj'].shape[:2]
@@ -458,7 +508,8 @@ def eval_nba_report(model, loader, traj_scale=1.0, z_fn=None, pipelined=True, gr
         js = (model.select_joint_async(h, gt=model._future, seg_ptr=seg_ptrs[('games', G * B, N)], scale=traj_scale, collision_radius=acc.radius)
               if acc.scene_metrics else None)
         kd = model.kde_nll_async(h, gt=model._future, scale=traj_scale) if kde else None
-        pend.append((h, sel, np.arange(0, n + 1, B * N), js, kd))
+        ss = model.sample_spread_async(h, gt=model._future, scale=traj_scale, div_scale=acc.div_scale) if spread else None
+        pend.append((h, sel, np.arange(0, n + 1, B * N), js, kd, ss))
         if len(pend) > 3:
             finish(pend.pop(0))
 

@@ -2,8 +2,9 @@
 sttode_best_of_k_select).
 
 ``joint_select`` and ``kde_nll`` (csrc/metrics.hip) are the scene-level metrics the reference does not compute: joint min ADE / FDE
-and collision counts per segment, and the KDE NLL per agent.  ``reduce_samples`` (csrc/reduce.hip) clusters M sampled futures
-per agent to K representatives.
+and collision counts per segment, and the KDE NLL per agent.  ``sample_spread`` compares an agent's samples with each other:
+pairwise distances, the DLow kernel value, energy scores and best-of-k for every k.  ``reduce_samples`` (csrc/reduce.hip)
+clusters M sampled futures per agent to K representatives.
 
 ``select`` is the kernel call: per agent the min-over-K ADE / FDE, the index of the best sample by ADE and by final displacement
 (``get_best_idx``), the miss flag (``count_miss_samples``) and optionally the best trajectory; per CSR segment (a scene, an NBA batch) the
@@ -124,7 +125,7 @@ def check_kde_k(K):
         raise ValueError(f'KDE NLL needs 2 <= K <= 64 samples (a covariance; one LDS tile per frame block), got K = {K}')
 
 
-def _inputs(pred_nk, gt, what):
+def _inputs(pred_nk, gt, what, need_gt=True):
     if not (isinstance(pred_nk, torch.Tensor) and pred_nk.is_cuda):
         raise capi.SttodeError(f'{what} runs on a HIP device only (no CPU fallback): pass device tensors')
     if pred_nk.dim() != 4 or pred_nk.shape[3] != 2 or 0 in pred_nk.shape:
@@ -132,6 +133,8 @@ def _inputs(pred_nk, gt, what):
     dev = pred_nk.device
     pred_nk = pred_nk.to(torch.float32).contiguous()
     n, K, Tf = pred_nk.shape[:3]
+    if gt is None and not need_gt:
+        return pred_nk, None, n, K, Tf
     gt = torch.as_tensor(gt, dtype=torch.float32).to(dev).contiguous()
     if tuple(gt.shape) != (n, Tf, 2):
         raise ValueError(f'gt must be [{n}, {Tf}, 2], got {tuple(gt.shape)}')
@@ -179,6 +182,69 @@ def kde_nll(pred_nk, gt, scale=1.0):
     out = torch.empty(n, dtype=torch.float64, device=pred_nk.device)
     with torch.cuda.device(pred_nk.device):
         capi.call('sttode_kde_nll', pred_nk, gt, n, K, Tf, float(scale), out, capi.stream_ptr())
+    return out
+
+
+# ----- spread of the samples among themselves (csrc/metrics.hip: sttode_sample_spread) --------------------------------------
+
+class SampleSpread:
+    """Outputs of one spread pass (device tensors), per agent.  float64 [n]: ``apd`` (mean over the sample pairs of the trajectory
+    distance: DLow's APD), ``fpd`` (of the final-frame distance), ``pade`` (of the mean per-frame distance), ``dlow`` (of
+    exp(-d_traj^2 / div_scale): the per-agent term of ``samplerloss.diversity_loss``); with a ground truth, else None: ``es_ade`` /
+    ``es_fde`` [n] float64 (energy scores on the ADE / FDE distance) and ``ade_at_k`` / ``fde_at_k`` [n, K] float32 (column k-1: min ADE /
+    FDE over the first k samples)."""
+    __slots__ = ('apd', 'fpd', 'pade', 'dlow', 'es_ade', 'es_fde', 'ade_at_k', 'fde_at_k', 'K', 'div_scale')
+
+    def __init__(self, n, K, device, div_scale, has_gt):
+        d = torch.empty((6 if has_gt else 4) * n, dtype=torch.float64, device=device)
+        self.apd, self.fpd, self.pade, self.dlow = d[:n], d[n:2 * n], d[2 * n:3 * n], d[3 * n:4 * n]
+        self.es_ade = d[4 * n:5 * n] if has_gt else None
+        self.es_fde = d[5 * n:] if has_gt else None
+        f = torch.empty(2 * n * K, dtype=torch.float32, device=device) if has_gt else None
+        self.ade_at_k = f[:n * K].view(n, K) if has_gt else None
+        self.fde_at_k = f[n * K:].view(n, K) if has_gt else None
+        self.K, self.div_scale = K, div_scale
+
+    def args(self):
+        """div_scale and output pointers in the order of sttode_sample_spread."""
+        return (float(self.div_scale), self.apd, self.fpd, self.pade, self.dlow, self.es_ade, self.es_fde, self.ade_at_k, self.fde_at_k)
+
+    def at(self, k):
+        """(min ADE, min FDE) [n] over the first ``k`` samples, 1 <= k <= K (needs a ground truth)."""
+        if self.ade_at_k is None:
+            raise ValueError('best-of-k columns need a ground truth (sample_spread was called without gt)')
+        k = int(k)
+        if not 1 <= k <= self.K:
+            raise ValueError(f'k must be in [1, {self.K}], got {k}')
+        return self.ade_at_k[:, k - 1], self.fde_at_k[:, k - 1]
+
+    def record_stream(self, stream):
+        for t in (self.apd, self.ade_at_k):   # (views: the record covers the whole allocation)
+            if t is not None:
+                t.record_stream(stream)
+
+
+def check_spread(K, div_scale):
+    """div_scale as a float, after the checks of sttode_sample_spread."""
+    if K < 2 or K > 64:
+        raise ValueError(f'sample spread needs 2 <= K <= 64 samples (a pair; one lane per sample), got K = {K}')
+    ds = float(div_scale)
+    if not (ds > 0.0 and ds != float('inf')):
+        raise ValueError(f'div_scale must be positive and finite, got {div_scale}')
+    return ds
+
+
+@torch.no_grad()
+def sample_spread(pred_nk, gt=None, scale=1.0, div_scale=1.0):
+    """How spread out the K samples of pred_nk [n, K, Tf, 2] are among themselves, per agent, in float64 on the current stream
+    (include/sttode_hip.h sttode_sample_spread states every value): average / final pairwise distance, the DLow kernel value at
+    ``div_scale``, and with gt [n, Tf, 2] the energy scores and the best-of-k minima for every k <= K.  2 <= K <= 64.  Returns a
+    ``SampleSpread``."""
+    pred_nk, gt, n, K, Tf = _inputs(pred_nk, gt, 'sample spread', need_gt=False)
+    ds = check_spread(K, div_scale)
+    out = SampleSpread(n, K, pred_nk.device, ds, gt is not None)
+    with torch.cuda.device(pred_nk.device):
+        capi.call('sttode_sample_spread', pred_nk, gt, n, K, Tf, float(scale), *out.args(), capi.stream_ptr())
     return out
 
 

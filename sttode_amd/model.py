@@ -1174,6 +1174,31 @@ class STTODENet(nn.Module):
         return out
 
     @torch.no_grad()
+    def sample_spread(self, pred_nk, gt=None, scale=1.0, div_scale=1.0):
+        """Spread of the K samples among themselves per agent on device: pred_nk [n,K,Tf,2], gt [n,Tf,2] (default: the
+        futures set with the batch) -> ``metrics.SampleSpread`` (average / final pairwise distance, the DLow kernel value at ``div_scale``,
+        energy scores, best-of-k minima for every k).  2 <= K <= 64."""
+        from . import metrics
+        gt = self._future if gt is None else _f32(gt, self.device)
+        return metrics.sample_spread(pred_nk, gt, scale=scale, div_scale=div_scale)
+
+    def sample_spread_async(self, handle, gt=None, scale=1.0, div_scale=1.0):
+        """sample_spread of an inference_async() call on the pipeline stream the call runs on, behind its trajectory groups (as
+        kde_nll_async).  Returns a ``metrics.SampleSpread`` whose tensors are valid after ``wait(handle)``; the handle keeps it alive."""
+        from . import metrics
+        if handle.get('generic'):
+            out = self.sample_spread(handle['pred'], gt=handle.get('gt_default') if gt is None else gt, scale=scale, div_scale=div_scale)
+            handle['spread'] = out
+            return out
+        pred, gt, n, K, Tf = self._async_metric_inputs(handle, gt, 'sample_spread_async')
+        out = metrics.SampleSpread(n, K, self.device, metrics.check_spread(K, div_scale), True)
+        capi.call('sttode_async_sample_spread', self.native().h, handle['slot'], pred, gt, n, K, Tf, float(scale), *out.args())
+        if handle.get('stream') is not None:
+            out.record_stream(handle['stream'])
+        handle['spread'] = out
+        return out
+
+    @torch.no_grad()
     def horizon_metrics(self, pred_nk, gt=None, scale=1.0):
         """The NBA evaluation's per-horizon metric (test.py:530-551) on device: pred_nk [n,K,Tf,2], gt [n,Tf,2] -> [n,Tf,2] with
         [a, h-1] = (min_k mean_{t<h} |scale (pred - gt)|, min_k |scale (pred_h - gt_h)|)."""
