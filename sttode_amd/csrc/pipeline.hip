@@ -811,40 +811,46 @@ extern "C" int sttode_inference_nba_async(SttodeModel* m, const float* past, int
     return run_async(m, past, nullptr, G * B * N, 0, G, B, N, z, workspace, pred, slot, opts, (hipStream_t)stream);
 }
 
-// Follow-up work of an asynchronous call ON THE CALL'S OWN pipeline stream: best-of-K metrics of its predictions (utils/metrics.py:7-26) run
-// the moment its launch drains -- in stream order, no event, no workgroup slots to fight for on a chip full of other calls' chains (on the
-// caller's stream that 8-us kernel sat 0.5 ms in the queue and held the next call's inputs behind it).  The slot's completion event is
-// re-recorded behind it: sttode_wait(slot) and the slot's next user wait for the metrics too.
-extern "C" int sttode_async_best_of_k(SttodeModel* m, int slot, const float* pred, const float* gt, int n, int K, int Tf, float scale,
-                                      float* ade, float* fde) {
-    STT_REQUIRE(m && slot >= 0 && slot < STT_MAX_SLOTS, "sttode_async_best_of_k: bad model / slot");
+// Follow-up work of an asynchronous call ON THE CALL'S OWN pipeline stream: a metric pass over its predictions (best-of-K and its selection,
+// utils/metrics.py:7-48; the per-horizon NBA metric, test.py:530-551; joint / collision, KDE NLL and sample spread, metrics.hip) runs the
+// moment the call's launch drains -- in stream order, no event, no workgroup slots to fight for on a chip full of other calls' chains (on
+// the caller's stream that 8-us kernel sat 0.5 ms in the queue and held the next call's inputs behind it).  Every such entry is this one
+// sequence: the slot's outstanding groups first (lagged form: nobody has enqueued them yet), then `launch`, the synchronous entry on the
+// slot's stream, then the slot's completion event re-recorded behind it: sttode_wait(slot) and the slot's next user wait for the pass too.
+// Passes that check their arguments themselves (stt_*_check) do so in front of this: a refused pass enqueues nothing.
+static int follow_up_refused(const char* who, const char* why) {
+    char b[128];
+    snprintf(b, sizeof(b), "%s: %s", who, why);
+    stt_set_error(b);
+    return 1;
+}
+template <class F>
+static int slot_follow_up(SttodeModel* m, int slot, const char* who, F&& launch) {
+    if (!(m && slot >= 0 && slot < STT_MAX_SLOTS)) return follow_up_refused(who, "bad model / slot");
     std::lock_guard<std::mutex> lk(m->mu);
-    STT_REQUIRE(m->slot_stream[slot] != nullptr, "sttode_async_best_of_k: no asynchronous call has used this slot");
-    if (int rc = lag_flush(m, slot)) return rc;   // (lagged form) nobody has enqueued this call's groups yet: they go first
-    if (int rc = sttode_best_of_k(pred, gt, n, K, Tf, scale, ade, fde, m->slot_stream[slot])) return rc;
+    if (!m->slot_stream[slot]) return follow_up_refused(who, "no asynchronous call has used this slot");
+    if (int rc = lag_flush(m, slot)) return rc;
+    if (int rc = launch(m->slot_stream[slot])) return rc;
     STT_HIP(hipEventRecord(m->evB_done[slot], m->slot_stream[slot]));
     return 0;
 }
 
-// Best-of-K selection (utils/metrics.py:7-48) of an asynchronous call's predictions, on the call's own pipeline stream like
-// sttode_async_best_of_k: the slot's outstanding groups first, then sttode_best_of_k_select, then the slot's completion event behind it.
+extern "C" int sttode_async_best_of_k(SttodeModel* m, int slot, const float* pred, const float* gt, int n, int K, int Tf, float scale,
+                                      float* ade, float* fde) {
+    return slot_follow_up(m, slot, "sttode_async_best_of_k",
+                          [&](hipStream_t s) { return sttode_best_of_k(pred, gt, n, K, Tf, scale, ade, fde, s); });
+}
+
 extern "C" int sttode_async_best_of_k_select(SttodeModel* m, int slot, const float* pred, const float* gt, int n, int K, int Tf, float scale,
                                              float miss_threshold, const int* seg_ptr, int S, float* ade, float* fde, int* best_ade_idx,
                                              int* best_fde_idx, unsigned char* miss, float* best, float* seg_ade, float* seg_fde,
                                              int* seg_miss) {
-    STT_REQUIRE(m && slot >= 0 && slot < STT_MAX_SLOTS, "sttode_async_best_of_k_select: bad model / slot");
-    std::lock_guard<std::mutex> lk(m->mu);
-    STT_REQUIRE(m->slot_stream[slot] != nullptr, "sttode_async_best_of_k_select: no asynchronous call has used this slot");
-    if (int rc = lag_flush(m, slot)) return rc;
-    if (int rc = sttode_best_of_k_select(pred, gt, n, K, Tf, scale, miss_threshold, seg_ptr, S, ade, fde, best_ade_idx, best_fde_idx, miss,
-                                         best, seg_ade, seg_fde, seg_miss, m->slot_stream[slot]))
-        return rc;
-    STT_HIP(hipEventRecord(m->evB_done[slot], m->slot_stream[slot]));
-    return 0;
+    return slot_follow_up(m, slot, "sttode_async_best_of_k_select", [&](hipStream_t s) {
+        return sttode_best_of_k_select(pred, gt, n, K, Tf, scale, miss_threshold, seg_ptr, S, ade, fde, best_ade_idx, best_fde_idx, miss, best,
+                                       seg_ade, seg_fde, seg_miss, s);
+    });
 }
 
-// Scene-level metrics (joint min ADE / FDE and collisions; KDE NLL; sample spread: metrics.hip) of an asynchronous call's predictions, on the call's own
-// pipeline stream like sttode_async_best_of_k_select.  The arguments are checked before the slot's groups are enqueued.
 extern "C" int sttode_async_joint_select(SttodeModel* m, int slot, const float* pred, const float* gt, int n, int K, int Tf, float scale,
                                          const int* seg_ptr, int S, float radius, float* seg_jade, float* seg_jfde, int* seg_jade_idx,
                                          int* seg_jfde_idx, int* seg_col, int* seg_gt_col) {
@@ -852,25 +858,16 @@ extern "C" int sttode_async_joint_select(SttodeModel* m, int slot, const float* 
     if (stt_joint_check("sttode_async_joint_select", pred, gt, n, K, Tf, seg_ptr, S, radius, seg_jade, seg_jfde, seg_jade_idx, seg_jfde_idx,
                         seg_col, seg_gt_col))
         return 1;
-    std::lock_guard<std::mutex> lk(m->mu);
-    STT_REQUIRE(m->slot_stream[slot] != nullptr, "sttode_async_joint_select: no asynchronous call has used this slot");
-    if (int rc = lag_flush(m, slot)) return rc;
-    if (int rc = sttode_joint_select(pred, gt, n, K, Tf, scale, seg_ptr, S, radius, seg_jade, seg_jfde, seg_jade_idx, seg_jfde_idx, seg_col,
-                                     seg_gt_col, m->slot_stream[slot]))
-        return rc;
-    STT_HIP(hipEventRecord(m->evB_done[slot], m->slot_stream[slot]));
-    return 0;
+    return slot_follow_up(m, slot, "sttode_async_joint_select", [&](hipStream_t s) {
+        return sttode_joint_select(pred, gt, n, K, Tf, scale, seg_ptr, S, radius, seg_jade, seg_jfde, seg_jade_idx, seg_jfde_idx, seg_col,
+                                   seg_gt_col, s);
+    });
 }
 
 extern "C" int sttode_async_kde_nll(SttodeModel* m, int slot, const float* pred, const float* gt, int n, int K, int Tf, float scale, double* nll) {
     STT_REQUIRE(m && slot >= 0 && slot < STT_MAX_SLOTS, "sttode_async_kde_nll: bad model / slot");
     if (stt_kde_check("sttode_async_kde_nll", pred, gt, n, K, Tf, nll)) return 1;
-    std::lock_guard<std::mutex> lk(m->mu);
-    STT_REQUIRE(m->slot_stream[slot] != nullptr, "sttode_async_kde_nll: no asynchronous call has used this slot");
-    if (int rc = lag_flush(m, slot)) return rc;
-    if (int rc = sttode_kde_nll(pred, gt, n, K, Tf, scale, nll, m->slot_stream[slot])) return rc;
-    STT_HIP(hipEventRecord(m->evB_done[slot], m->slot_stream[slot]));
-    return 0;
+    return slot_follow_up(m, slot, "sttode_async_kde_nll", [&](hipStream_t s) { return sttode_kde_nll(pred, gt, n, K, Tf, scale, nll, s); });
 }
 
 extern "C" int sttode_async_sample_spread(SttodeModel* m, int slot, const float* pred, const float* gt, int n, int K, int Tf, float scale,
@@ -879,28 +876,15 @@ extern "C" int sttode_async_sample_spread(SttodeModel* m, int slot, const float*
     STT_REQUIRE(m && slot >= 0 && slot < STT_MAX_SLOTS, "sttode_async_sample_spread: bad model / slot");
     if (stt_spread_check("sttode_async_sample_spread", pred, gt, n, K, Tf, div_scale, apd, fpd, pade, dlow, es_ade, es_fde, ade_at_k, fde_at_k))
         return 1;
-    std::lock_guard<std::mutex> lk(m->mu);
-    STT_REQUIRE(m->slot_stream[slot] != nullptr, "sttode_async_sample_spread: no asynchronous call has used this slot");
-    if (int rc = lag_flush(m, slot)) return rc;
-    if (int rc = sttode_sample_spread(pred, gt, n, K, Tf, scale, div_scale, apd, fpd, pade, dlow, es_ade, es_fde, ade_at_k, fde_at_k,
-                                      m->slot_stream[slot]))
-        return rc;
-    STT_HIP(hipEventRecord(m->evB_done[slot], m->slot_stream[slot]));
-    return 0;
+    return slot_follow_up(m, slot, "sttode_async_sample_spread", [&](hipStream_t s) {
+        return sttode_sample_spread(pred, gt, n, K, Tf, scale, div_scale, apd, fpd, pade, dlow, es_ade, es_fde, ade_at_k, fde_at_k, s);
+    });
 }
 
-// The NBA evaluation's per-horizon metric (test.py:530-551) of an asynchronous call, on the call's own pipeline stream like
-// sttode_async_best_of_k: out [n][Tf][2] = per agent and horizon h the min over K of (mean displacement over the first h frames, displacement
-// of frame h) -- sttode_horizon_metrics on the slot's predictions.
 extern "C" int sttode_async_horizon_metrics(SttodeModel* m, int slot, const float* pred, const float* gt, int n, int K, int Tf, float scale,
                                             float* out) {
-    STT_REQUIRE(m && slot >= 0 && slot < STT_MAX_SLOTS, "sttode_async_horizon_metrics: bad model / slot");
-    std::lock_guard<std::mutex> lk(m->mu);
-    STT_REQUIRE(m->slot_stream[slot] != nullptr, "sttode_async_horizon_metrics: no asynchronous call has used this slot");
-    if (int rc = lag_flush(m, slot)) return rc;
-    if (int rc = sttode_horizon_metrics(pred, gt, n, K, Tf, scale, out, m->slot_stream[slot])) return rc;
-    STT_HIP(hipEventRecord(m->evB_done[slot], m->slot_stream[slot]));
-    return 0;
+    return slot_follow_up(m, slot, "sttode_async_horizon_metrics",
+                          [&](hipStream_t s) { return sttode_horizon_metrics(pred, gt, n, K, Tf, scale, out, s); });
 }
 
 // The pipeline stream the NEXT asynchronous call of n agents will run on (lagged launches: one stream per call, three in rotation), or NULL

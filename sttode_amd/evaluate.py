@@ -14,11 +14,77 @@
   embedding_delta  how tree-like the encoder's past features (or the observed tracks) of a dataset are: delta / diam of hyptorch/delta.py's
                    batched_delta_hyp over all agents.
 """
+import collections
 import contextlib
 import dataclasses
 
 import numpy as np
 import torch
+
+
+def _latents(model, rows, z_fn):
+    return z_fn(rows) if z_fn is not None else torch.randn(rows, model.args.zdim, device=model.device)
+
+
+def _scene_loop(model, dataset, scenes_per_call, pipelined, launch, finish, serial):
+    """The loop over scene batches of every scene evaluation: ``scenes_per_call`` scenes per set_scene_batch.  Pipelined: ``launch(sb)``
+    enqueues the batch's call (and what follows it on the call's stream) and returns what ``finish`` takes once more than four calls are in
+    flight, and at the end.  Else ``serial(sb)`` does the whole batch."""
+    pend = []
+
+    def drain():
+        while pend:
+            finish(pend.pop(0))
+    for s0 in range(0, len(dataset), scenes_per_call):
+        sb = dataset.scene_batch(range(s0, min(s0 + scenes_per_call, len(dataset))))
+        model.set_scene_batch(sb.past, sb.future, sb.scene_ptr)
+        if not pipelined:
+            serial(sb)
+            continue
+        if model._async_shapes() > 12:                                    # batches of ever new sizes: per-shape slot buffers are dropped in time
+            drain()
+            model.reset_async()
+        pend.append(launch(sb))
+        if len(pend) > 4:
+            finish(pend.pop(0))
+    drain()
+    if pipelined:
+        model.reset_async()
+
+
+def _scenes_best_of_k(model, dataset, traj_scale, scenes_per_call, pipelined, launch, serial):
+    tot_a = tot_f = 0.0
+    tot_n = 0
+
+    def add(ade, fde):
+        nonlocal tot_a, tot_f, tot_n
+        tot_a += float(ade.double().sum())
+        tot_f += float(fde.double().sum())
+        tot_n += int(ade.numel())
+
+    def finish(h):
+        ade, fde = model.best_of_k_async(h, scale=traj_scale)
+        model.wait(h)
+        add(ade, fde)
+    _scene_loop(model, dataset, scenes_per_call, pipelined, launch, finish,
+                lambda sb: add(*model.best_of_k(serial(sb).permute(1, 0, 2, 3), scale=traj_scale)))     # serial(sb): [K, n, Tf, 2]
+    return tot_a / tot_n, tot_f / tot_n, tot_n
+
+
+def _scene_calls(model, traj_scale, z_fn):
+    """(launch, serial) of a scene batch on latents from z_fn / torch.randn."""
+    def z(sb):
+        return _latents(model, sb.n_agents * model.args.sample_k, z_fn)
+    return (lambda sb: model.inference_async(z=z(sb), metrics_gt=model._future, metrics_scale=traj_scale),
+            lambda sb: model.inference(None, z=z(sb)))
+
+
+def _sampler_calls(model, sampler, traj_scale, mean, eps_fn):
+    """(launch, serial) of a scene batch on the stage-2 sampler's latents."""
+    def eps(sb):
+        return eps_fn(1 if sampler.share_eps else sb.n_agents) if (not mean and eps_fn is not None) else None
+    return (lambda sb: sampler.inference_async(model, mean=mean, eps=eps(sb), metrics_gt=model._future, metrics_scale=traj_scale),
+            lambda sb: sampler.inference(model, mean=mean, eps=eps(sb)))
 
 
 @torch.no_grad()
@@ -27,41 +93,7 @@ def eval_scenes(model, dataset, traj_scale=1.0, scenes_per_call=512, z_fn=None, 
     Returns (ADE, FDE, n_agents).  ``z_fn(n_rows)`` may supply latents (tests); otherwise torch.randn like the reference.
     ``pipelined`` (default): the calls go through ``inference_async`` -- up to four in flight, best-of-K ADE / FDE computed by the calls' own
     trajectory groups (what bench.py times) -- instead of one serial ``inference()`` + ``best_of_k`` per batch."""
-    tot_a = tot_f = 0.0
-    tot_n = 0
-    K, zd = model.args.sample_k, model.args.zdim
-    pend = []
-
-    def finish(h):
-        nonlocal tot_a, tot_f
-        ade, fde = model.best_of_k_async(h, scale=traj_scale)
-        model.wait(h)
-        tot_a += float(ade.double().sum())
-        tot_f += float(fde.double().sum())
-    for s0 in range(0, len(dataset), scenes_per_call):
-        sb = dataset.scene_batch(range(s0, min(s0 + scenes_per_call, len(dataset))))
-        model.set_scene_batch(sb.past, sb.future, sb.scene_ptr)
-        rows = sb.n_agents * K
-        z = z_fn(rows) if z_fn is not None else torch.randn(rows, zd, device=model.device)
-        tot_n += sb.n_agents
-        if pipelined:
-            if len(model._async_bufs) > 12:                               # batches of ever new sizes: per-shape slot buffers are dropped in time
-                while pend:
-                    finish(pend.pop(0))
-                model.reset_async()
-            pend.append(model.inference_async(z=z, metrics_gt=model._future, metrics_scale=traj_scale))
-            if len(pend) > 4:
-                finish(pend.pop(0))
-            continue
-        pred = model.inference(None, z=z)                                  # [K, n, Tf, 2]
-        ade, fde = model.best_of_k(pred.permute(1, 0, 2, 3), scale=traj_scale)
-        tot_a += float(ade.double().sum())
-        tot_f += float(fde.double().sum())
-    while pend:
-        finish(pend.pop(0))
-    if pipelined:
-        model.reset_async()
-    return tot_a / tot_n, tot_f / tot_n, tot_n
+    return _scenes_best_of_k(model, dataset, traj_scale, scenes_per_call, pipelined, *_scene_calls(model, traj_scale, z_fn))
 
 
 @torch.no_grad()
@@ -71,41 +103,41 @@ def eval_sampler(model, sampler, dataset, traj_scale=1.0, scenes_per_call=512, m
     (``dataset.scene_batch``), and ``pipelined`` (default) runs the calls through ``sampler.inference_async`` -- several in flight, the metrics
     computed by the calls' own trajectory groups; ``pipelined=False``: one serial ``sampler.inference`` + ``best_of_k`` per batch.
     ``mean=False``: sampled latents, eps drawn like sampler.py:41-46 or by ``eps_fn(rows)`` (rows = 1 with share_eps, else the call's agents)."""
-    tot_a = tot_f = 0.0
-    tot_n = 0
+    return _scenes_best_of_k(model, dataset, traj_scale, scenes_per_call, pipelined, *_sampler_calls(model, sampler, traj_scale, mean, eps_fn))
+
+
+def _nba_loop(model, loader, z_fn, groups_per_call, follow, finish):
+    """The pipelined loop over an NBA loader: up to ``groups_per_call`` consecutive loader batches of equal shape travel as ONE call
+    (set_data_nba with [G,B,N,...]), staged on the pipeline stream the call will run on.  ``follow(h, G, B, N)`` enqueues what follows the
+    call on that stream and returns what ``finish`` takes once more than three calls are in flight, and at the end."""
+    K, dev = model.args.sample_k, model.device
     pend = []
 
-    def finish(h):
-        nonlocal tot_a, tot_f
-        ade, fde = model.best_of_k_async(h, scale=traj_scale)
-        model.wait(h)
-        tot_a += float(ade.double().sum())
-        tot_f += float(fde.double().sum())
-    for s0 in range(0, len(dataset), scenes_per_call):
-        sb = dataset.scene_batch(range(s0, min(s0 + scenes_per_call, len(dataset))))
-        model.set_scene_batch(sb.past, sb.future, sb.scene_ptr)
-        eps = None
-        if not mean and eps_fn is not None:
-            eps = eps_fn(1 if sampler.share_eps else sb.n_agents)
-        tot_n += sb.n_agents
-        if pipelined:
-            if len(model._async_bufs) > 12:                               # batches of ever new sizes: per-shape slot buffers are dropped in time
-                while pend:
-                    finish(pend.pop(0))
-                model.reset_async()
-            pend.append(sampler.inference_async(model, mean=mean, eps=eps, metrics_gt=model._future, metrics_scale=traj_scale))
-            if len(pend) > 4:
-                finish(pend.pop(0))
-            continue
-        pred = sampler.inference(model, mean=mean, eps=eps)                 # [K, n, Tf, 2]
-        ade, fde = model.best_of_k(pred.permute(1, 0, 2, 3), scale=traj_scale)
-        tot_a += float(ade.double().sum())
-        tot_f += float(fde.double().sum())
+    def submit(group):
+        B, N = group[0]['past_traj'].shape[:2]
+        past = torch.stack([torch.as_tensor(d['past_traj'], dtype=torch.float32) for d in group])
+        fut = torch.stack([torch.as_tensor(d['future_traj'], dtype=torch.float32) for d in group])
+        model.packed()
+        st = model.next_async_stream(len(group) * B * N)
+        with torch.cuda.stream(st) if st is not None else contextlib.nullcontext():
+            model.set_data_nba({'past_traj': past.to(dev, non_blocking=True), 'future_traj': fut.to(dev, non_blocking=True)})
+            # z_fn is asked once per LOADER batch (its rows: B N K), as the serial loop asks it; the call's latents are their concatenation
+            z = torch.cat([torch.as_tensor(z_fn(B * N * K)).to(dev) for _ in group]) if z_fn is not None else None
+            h = model.inference_async(z=z)
+        pend.append(follow(h, len(group), B, N))
+        if len(pend) > 3:
+            finish(pend.pop(0))
+    group = []
+    for data in loader:
+        if group and (group[0]['past_traj'].shape != data['past_traj'].shape or len(group) >= groups_per_call):
+            submit(group)
+            group = []
+        group.append(data)
+    if group:
+        submit(group)
     while pend:
         finish(pend.pop(0))
-    if pipelined:
-        model.reset_async()
-    return tot_a / tot_n, tot_f / tot_n, tot_n
+    model.reset_async()
 
 
 @torch.no_grad()
@@ -116,67 +148,39 @@ def eval_nba(model, loader, traj_scale=1.0, z_fn=None, pipelined=True, groups_pe
     [G,B,N,...]: the attention stays within each batch, exactly what the reference's one call per batch computes) through ``inference_async``
     -- several calls in flight -- and the per-horizon min-over-K metric is one HIP kernel on the call's own stream
     (``horizon_metrics_async``); the host only adds up [Tf, 2] sums.  ``pipelined=False``: one serial ``inference()`` per loader batch and
-    the metric as torch ops (the round-4 loop; kept as the cross-check of tests/test_gpu_parity.py)."""
+    the metric as torch ops (the plain per-batch loop; kept as the cross-check of tests/test_gpu_parity.py)."""
     Tf, K = model.args.future_length, model.args.sample_k
-    dev = model.device
-    acc = np.zeros((Tf, 2))
     count = 0
     if not pipelined:
+        acc = np.zeros((Tf, 2))
         for data in loader:
             model.set_data_nba(data)
-            n = data['past_traj'].shape[0] * data['past_traj'].shape[1]
+            B = data['past_traj'].shape[0]
+            n = B * data['past_traj'].shape[1]
             z = z_fn(n * K) if z_fn is not None else None
             pred = model.inference(data, z=z) * traj_scale                     # [K, n, Tf, 2]
             gt = torch.as_tensor(data['future_traj'], dtype=torch.float32).to(pred.device).reshape(n, Tf, 2) * traj_scale
             d = (pred - gt[None]).norm(dim=-1)                                 # [K, n, Tf]
             cum = d.cumsum(dim=2) / torch.arange(1, Tf + 1, device=d.device)   # mean over the first h frames
-            B = data['past_traj'].shape[0]
             acc[:, 0] += cum.min(dim=0)[0].mean(dim=0).double().cpu().numpy() * B
             acc[:, 1] += d.min(dim=0)[0].mean(dim=0).double().cpu().numpy() * B
             count += B
         acc /= count
-        return {h + 1: (float(acc[h, 0]), float(acc[h, 1])) for h in range(Tf)}
+    else:
+        totals = []
 
-    pend, totals = [], []
+        def follow(h, G, B, N):
+            nonlocal count
+            count += G * B
+            return h, model.horizon_metrics_async(h, gt=model._future, scale=traj_scale), N
 
-    def finish(item):
-        h, hm, B, N, G = item
-        model.wait(h)
-        # mean over the agents of a batch, times its batch size, summed over the call's batches == sum over all agents / N
-        totals.append(hm.double().sum(dim=0) / N)
-
-    def submit(group):
-        B, N = group[0]['past_traj'].shape[:2]
-        G = len(group)
-        past = torch.stack([torch.as_tensor(d['past_traj'], dtype=torch.float32) for d in group])
-        fut = torch.stack([torch.as_tensor(d['future_traj'], dtype=torch.float32) for d in group])
-        n = G * B * N
-        model.packed()
-        st = model.next_async_stream(n)
-        with torch.cuda.stream(st) if st is not None else contextlib.nullcontext():
-            model.set_data_nba({'past_traj': past.to(dev, non_blocking=True), 'future_traj': fut.to(dev, non_blocking=True)})
-            # z_fn is asked once per LOADER batch (its rows: B N K), as the serial loop asks it; the call's latents are their concatenation
-            z = torch.cat([torch.as_tensor(z_fn(B * N * K)).to(dev) for _ in group]) if z_fn is not None else None
-            h = model.inference_async(z=z)
-        hm = model.horizon_metrics_async(h, gt=model._future, scale=traj_scale)
-        pend.append((h, hm, B, N, G))
-        if len(pend) > 3:
-            finish(pend.pop(0))
-
-    group = []
-    for data in loader:
-        shape = tuple(data['past_traj'].shape)
-        if group and (tuple(group[0]['past_traj'].shape) != shape or len(group) >= groups_per_call):
-            submit(group)
-            group = []
-        group.append(data)
-        count += shape[0]
-    if group:
-        submit(group)
-    while pend:
-        finish(pend.pop(0))
-    model.reset_async()
-    acc = torch.stack(totals).sum(dim=0).cpu().numpy() / count
+        def finish(item):
+            h, hm, N = item
+            model.wait(h)
+            # mean over the agents of a batch, times its batch size, summed over the call's batches == sum over all agents / N
+            totals.append(hm.double().sum(dim=0) / N)
+        _nba_loop(model, loader, z_fn, groups_per_call, follow, finish)
+        acc = torch.stack(totals).sum(dim=0).cpu().numpy() / count
     return {h + 1: (float(acc[h, 0]), float(acc[h, 1])) for h in range(Tf)}
 
 
@@ -239,9 +243,13 @@ class EvalReport:
     fde_at_k: dict = None
 
 
+def _np(t):
+    return t.cpu().numpy() if isinstance(t, torch.Tensor) else t
+
+
 class _ReportAcc:
     """Host side of a report loop: per call, the same double sums eval_scenes forms (so the global ADE / FDE agree bit for bit), and the
-    small per-scene / per-agent arrays."""
+    small per-scene / per-agent arrays, kept per call under the name of the EvalReport field they become."""
 
     def __init__(self, miss_threshold, joint=False, kde=False, collision_radius=None, K=None, spread=False, div_scale=None, ks=(1, 5, 10),
                  dataset=None):
@@ -249,67 +257,74 @@ class _ReportAcc:
         self.thr = float(miss_threshold)
         self.tot_a = self.tot_f = 0.0
         self.n = 0
-        self.parts = []
+        self.parts = collections.defaultdict(list)
         self.joint, self.kde, self.radius, self.K = bool(joint), bool(kde), check_radius(collision_radius), K
-        self.jparts, self.kparts = [], []
-        self.spread = bool(spread)
+        self.spread, self.div_scale = bool(spread), None
         if self.spread:
             if div_scale is None:
                 from .samplerloss import get_diversity_config
                 div_scale = get_diversity_config(dataset)['scale'] if dataset is not None else 1.0
             self.div_scale = check_spread(K, div_scale)
             self.ks = [int(k) for k in ks if 1 <= int(k) <= K]
-            self.sparts = []
 
     @property
     def scene_metrics(self):
         """Whether a joint pass runs (for the joint values, the collision counts or both)."""
         return self.joint or self.radius is not None
 
+    def _put(self, **arrays):
+        for name, a in arrays.items():
+            self.parts[name].append(_np(a))
+
+    def _cat(self, name):
+        return np.concatenate(self.parts[name])
+
     def add_spread(self, ss):
         cols = torch.tensor([k - 1 for k in self.ks], dtype=torch.long, device=ss.apd.device)
-        self.sparts.append((torch.stack([ss.apd, ss.fpd, ss.pade, ss.dlow, ss.es_ade, ss.es_fde], dim=1).cpu().numpy(),
-                            ss.ade_at_k[:, cols].cpu().numpy(), ss.fde_at_k[:, cols].cpu().numpy()))
+        self._put(spread_agents=torch.stack([ss.apd, ss.fpd, ss.pade, ss.dlow, ss.es_ade, ss.es_fde], dim=1), ade_at_k=ss.ade_at_k[:, cols],
+                  fde_at_k=ss.fde_at_k[:, cols])
 
     def add_scene_metrics(self, js, kd, ss=None):
         if ss is not None:
             self.add_spread(ss)
         if js is not None:
-            self.jparts.append((js.seg_jade.cpu().numpy(), js.seg_jfde.cpu().numpy(), js.seg_jade_idx.cpu().numpy(),
-                                None if js.seg_col is None else torch.stack([js.seg_col, js.seg_gt_col], dim=1).cpu().numpy()))
+            self._put(scene_joint_ade=js.seg_jade, scene_joint_fde=js.seg_jfde, scene_joint_idx=js.seg_jade_idx)
+            if js.seg_col is not None:
+                self._put(scene_collision=torch.stack([js.seg_col, js.seg_gt_col], dim=1))
         if kd is not None:
-            self.kparts.append(kd.cpu().numpy())
+            self._put(kde_nll_agents=kd)
 
     def add(self, sel, seg_ptr):
         self.tot_a += float(sel.ade.double().sum())
         self.tot_f += float(sel.fde.double().sum())
         self.n += int(sel.ade.numel())
-        sp = seg_ptr.cpu().numpy() if isinstance(seg_ptr, torch.Tensor) else np.asarray(seg_ptr)
-        self.parts.append((sel.seg_ade.cpu().numpy(), sel.seg_fde.cpu().numpy(), sel.seg_miss.cpu().numpy(), np.diff(sp),
-                           sel.best_ade_idx.cpu().numpy(), sel.best_fde_idx.cpu().numpy(), None if sel.best is None else sel.best.cpu().numpy()))
+        self._put(scene_ade=sel.seg_ade, scene_fde=sel.seg_fde, scene_miss=sel.seg_miss, scene_agents=np.diff(_np(seg_ptr)),
+                  best_idx=sel.best_ade_idx, best_fde_idx=sel.best_fde_idx)
+        if sel.best is not None:
+            self._put(best=sel.best)
 
     def report(self, gather):
-        cat = [np.concatenate([p[i] for p in self.parts]) for i in range(6)]
-        miss = int(cat[2].sum())
+        miss = int(self._cat('scene_miss').sum())
         rep = EvalReport(ade=self.tot_a / self.n, fde=self.tot_f / self.n, n_agents=self.n, miss_count=miss, miss_rate=miss / self.n,
-                         miss_threshold=self.thr, scene_ade=cat[0], scene_fde=cat[1], scene_miss=cat[2], scene_agents=cat[3].astype(np.int64),
-                         best_idx=cat[4], best_fde_idx=cat[5], best=np.concatenate([p[6] for p in self.parts]) if gather else None)
+                         miss_threshold=self.thr, scene_agents=self._cat('scene_agents').astype(np.int64),
+                         best=self._cat('best') if gather else None,
+                         **{f: self._cat(f) for f in ('scene_ade', 'scene_fde', 'scene_miss', 'best_idx', 'best_fde_idx')})
         if self.joint:
-            rep.scene_joint_ade, rep.scene_joint_fde, rep.scene_joint_idx = (np.concatenate([p[i] for p in self.jparts]) for i in range(3))
+            rep.scene_joint_ade, rep.scene_joint_fde, rep.scene_joint_idx = (self._cat('scene_joint_' + f) for f in ('ade', 'fde', 'idx'))
             rep.joint_ade = float(rep.scene_joint_ade.astype(np.float64).mean())
             rep.joint_fde = float(rep.scene_joint_fde.astype(np.float64).mean())
         if self.radius is not None:
-            col = np.concatenate([p[3] for p in self.jparts]).astype(np.int64)
+            col = self._cat('scene_collision').astype(np.int64)
             rep.collision_radius, rep.scene_collision = self.radius, col
             rep.collision_rate = int(col[:, 0].sum()) / (self.K * self.n)
             rep.gt_collision_rate = int(col[:, 1].sum()) / self.n
         if self.kde:
-            v = np.concatenate(self.kparts)
+            v = self._cat('kde_nll_agents')
             ok = np.isfinite(v)
             rep.kde_nll_agents, rep.kde_invalid = v, int((~ok).sum())
             rep.kde_nll = float(v[ok].mean()) if ok.any() else float('nan')
         if self.spread:
-            v, ak, fk = (np.concatenate([p[i] for p in self.sparts]) for i in range(3))
+            v, ak, fk = (self._cat(f) for f in ('spread_agents', 'ade_at_k', 'fde_at_k'))
             rep.spread_agents = v
             rep.apd, rep.fpd, rep.pade, rep.dlow, rep.energy_ade, rep.energy_fde = (float(x) for x in v.sum(axis=0) / v.shape[0])
             rep.ade_at_k = {k: float(ak[:, i].astype(np.float64).sum() / ak.shape[0]) for i, k in enumerate(self.ks)}
@@ -317,48 +332,50 @@ class _ReportAcc:
         return rep
 
 
-def _scenes_report(model, dataset, scenes_per_call, pipelined, traj_scale, miss_threshold, gather, launch, serial, joint, kde,
-                   collision_radius, spread=False, div_scale=None, ks=(1, 5, 10)):
-    acc = _ReportAcc(miss_threshold, joint, kde, collision_radius, model.args.sample_k, spread, div_scale, ks,
-                     getattr(model.args, 'dataset', None))
-    pend = []
+class _ReportPasses:
+    """The metric passes of a report loop's calls, issued into a _ReportAcc (``options``: its arguments behind the threshold): ``follow`` behind
+    a pipelined call on its own stream (``finish`` once it is waited for), ``serial`` after a serial call."""
 
-    def finish(item):
-        h, sel, sp, js, kd, ss = item
-        model.wait(h)
-        acc.add(sel, sp)
-        acc.add_scene_metrics(js, kd, ss)
-    for s0 in range(0, len(dataset), scenes_per_call):
-        sb = dataset.scene_batch(range(s0, min(s0 + scenes_per_call, len(dataset))))
-        model.set_scene_batch(sb.past, sb.future, sb.scene_ptr)
-        if pipelined:
-            if len(model._async_bufs) > 12:                               # batches of ever new sizes: per-shape slot buffers are dropped in time
-                while pend:
-                    finish(pend.pop(0))
-                model.reset_async()
-            h = launch(sb)
-            sel = model.select_best_of_k_async(h, scale=traj_scale, miss_threshold=miss_threshold, seg_ptr='scenes', gather=gather)
-            js = model.select_joint_async(h, seg_ptr='scenes', scale=traj_scale, collision_radius=acc.radius) if acc.scene_metrics else None
-            kd = model.kde_nll_async(h, scale=traj_scale) if kde else None
-            ss = model.sample_spread_async(h, scale=traj_scale, div_scale=acc.div_scale) if spread else None
-            pend.append((h, sel, sb.scene_ptr, js, kd, ss))
-            if len(pend) > 4:
-                finish(pend.pop(0))
-            continue
-        pred = serial(sb)                                                  # [K, n, Tf, 2]
-        sel = model.select_best_of_k(pred.permute(1, 0, 2, 3), scale=traj_scale, miss_threshold=miss_threshold, seg_ptr=model._scene_ptr,
-                                     gather=gather)
-        acc.add(sel, sb.scene_ptr)
-        if acc.scene_metrics or kde or spread:
-            pnk = pred.permute(1, 0, 2, 3).contiguous()
-            acc.add_scene_metrics(model.select_joint(pnk, seg_ptr=model._scene_ptr, scale=traj_scale, collision_radius=acc.radius)
-                                  if acc.scene_metrics else None, model.kde_nll(pnk, scale=traj_scale) if kde else None,
-                                  model.sample_spread(pnk, scale=traj_scale, div_scale=acc.div_scale) if spread else None)
-    while pend:
-        finish(pend.pop(0))
-    if pipelined:
-        model.reset_async()
-    return acc.report(gather)
+    def __init__(self, model, traj_scale, miss_threshold, gather, *options):
+        self.model, self.scale, self.miss_threshold, self.gather = model, traj_scale, miss_threshold, gather
+        self.acc = _ReportAcc(miss_threshold, *options)
+
+    def follow(self, h, seg_ptr, joint_ptr, host_ptr, **gt):
+        """The passes of the pipelined call ``h`` on its own stream: the selection over ``seg_ptr``, the joint pass over ``joint_ptr``, KDE NLL
+        and spread as asked (``gt=``: as the passes take it).  Returns what ``finish`` takes; ``host_ptr``: seg_ptr on the host."""
+        m, acc = self.model, self.acc
+        sel = m.select_best_of_k_async(h, scale=self.scale, miss_threshold=self.miss_threshold, seg_ptr=seg_ptr, gather=self.gather, **gt)
+        js = m.select_joint_async(h, seg_ptr=joint_ptr, scale=self.scale, collision_radius=acc.radius, **gt) if acc.scene_metrics else None
+        kd = m.kde_nll_async(h, scale=self.scale, **gt) if acc.kde else None
+        ss = m.sample_spread_async(h, scale=self.scale, div_scale=acc.div_scale, **gt) if acc.spread else None
+        return h, sel, host_ptr, js, kd, ss
+
+    def finish(self, item):
+        h, sel, host_ptr, js, kd, ss = item
+        self.model.wait(h)
+        self.acc.add(sel, host_ptr)
+        self.acc.add_scene_metrics(js, kd, ss)
+
+    def serial(self, pred, seg_ptr, joint_ptr, host_ptr):
+        """The same passes on the predictions [K, n, Tf, 2] of a serial call, on the caller's stream."""
+        m, acc, pnk = self.model, self.acc, pred.permute(1, 0, 2, 3)
+        acc.add(m.select_best_of_k(pnk, scale=self.scale, miss_threshold=self.miss_threshold, seg_ptr=seg_ptr, gather=self.gather), host_ptr)
+        if acc.scene_metrics or acc.kde or acc.spread:
+            pnk = pnk.contiguous()
+            acc.add_scene_metrics(m.select_joint(pnk, seg_ptr=joint_ptr, scale=self.scale, collision_radius=acc.radius)
+                                   if acc.scene_metrics else None, m.kde_nll(pnk, scale=self.scale) if acc.kde else None,
+                                   m.sample_spread(pnk, scale=self.scale, div_scale=acc.div_scale) if acc.spread else None)
+
+    def report(self):
+        return self.acc.report(self.gather)
+
+
+def _scenes_report(model, dataset, scenes_per_call, pipelined, calls, traj_scale, miss_threshold, gather, *options):
+    launch, serial = calls
+    p = _ReportPasses(model, traj_scale, miss_threshold, gather, *options, getattr(model.args, 'dataset', None))
+    _scene_loop(model, dataset, scenes_per_call, pipelined, lambda sb: p.follow(launch(sb), 'scenes', 'scenes', sb.scene_ptr), p.finish,
+                lambda sb: p.serial(serial(sb), model._scene_ptr, model._scene_ptr, sb.scene_ptr))
+    return p.report()
 
 
 @torch.no_grad()
@@ -370,14 +387,8 @@ def eval_scenes_report(model, dataset, traj_scale=1.0, scenes_per_call=512, z_fn
     with ``pipelined=False``); every other field is the same with them on or off.  ``spread`` adds the spread pass (``sample_spread_async``:
     APD / FPD, the DLow kernel value at ``div_scale`` -- default: the scale of samplerloss.get_diversity_config for the model's dataset -- the
     energy scores and best-of-k for each k of ``ks``) in the same way."""
-    K, zd = model.args.sample_k, model.args.zdim
-
-    def latents(sb):
-        rows = sb.n_agents * K
-        return z_fn(rows) if z_fn is not None else torch.randn(rows, zd, device=model.device)
-    return _scenes_report(model, dataset, scenes_per_call, pipelined, traj_scale, miss_threshold, gather,
-                          lambda sb: model.inference_async(z=latents(sb), metrics_gt=model._future, metrics_scale=traj_scale),
-                          lambda sb: model.inference(None, z=latents(sb)), joint, kde, collision_radius, spread, div_scale, ks)
+    return _scenes_report(model, dataset, scenes_per_call, pipelined, _scene_calls(model, traj_scale, z_fn), traj_scale, miss_threshold, gather,
+                          joint, kde, collision_radius, model.args.sample_k, spread, div_scale, ks)
 
 
 @torch.no_grad()
@@ -395,7 +406,7 @@ def eval_scenes_reduced(model, dataset, rounds, K=None, iters=10, from_frame=0, 
     rounds = int(rounds)
     if rounds < 1:
         raise ValueError(f'eval_scenes_reduced needs rounds >= 1, got {rounds}')
-    Ks, zd = model.args.sample_k, model.args.zdim
+    Ks = model.args.sample_k
     K = Ks if K is None else int(K)
     acc = _ReportAcc(miss_threshold, K=K, spread=spread, div_scale=div_scale, ks=ks, dataset=getattr(model.args, 'dataset', None))
     depth = max(2, min(8, int(model.async_depth)))
@@ -405,8 +416,7 @@ def eval_scenes_reduced(model, dataset, rounds, K=None, iters=10, from_frame=0, 
         rows = sb.n_agents * Ks
         buf = model._round_buffer(rounds, sb.n_agents)
         if pipelined:
-            new = sum((sb.n_agents, model._S, s) not in model._async_bufs for s in range(depth))
-            if len(model._async_bufs) + new > 16:                         # batches of ever new sizes: per-shape slot buffers are dropped in time
+            if model._async_shapes(depth) > 16:                           # batches of ever new sizes: per-shape slot buffers are dropped in time
                 model.reset_async()                                       # (nothing is in flight between batches)
             pend = []
 
@@ -416,14 +426,12 @@ def eval_scenes_reduced(model, dataset, rounds, K=None, iters=10, from_frame=0, 
             for r in range(rounds):
                 if len(pend) >= depth - 1:
                     finish(pend.pop(0))
-                z = z_fn(rows) if z_fn is not None else torch.randn(rows, zd, device=model.device)
-                pend.append((r, model.inference_async(z=z)))
+                pend.append((r, model.inference_async(z=_latents(model, rows, z_fn))))
             while pend:
                 finish(pend.pop(0))
         else:
             for r in range(rounds):
-                z = z_fn(rows) if z_fn is not None else torch.randn(rows, zd, device=model.device)
-                buf[r].copy_(model.inference(None, z=z).permute(1, 0, 2, 3))
+                buf[r].copy_(model.inference(None, z=_latents(model, rows, z_fn)).permute(1, 0, 2, 3))
         red = metrics.reduce_samples(buf, K, iters=iters, from_frame=from_frame, init=init)
         acc.add(model.select_best_of_k(red.centroids, scale=traj_scale, miss_threshold=miss_threshold, seg_ptr=model._scene_ptr), sb.scene_ptr)
         if spread:
@@ -440,12 +448,8 @@ def eval_sampler_report(model, sampler, dataset, traj_scale=1.0, scenes_per_call
     """eval_sampler with the per-scene breakdown, the best sample of every agent and the miss rate (an ``EvalReport``; test_sampler.py:214-217
     asks count_miss_samples of the same loop).  ``joint`` / ``collision_radius`` / ``kde`` / ``spread`` / ``div_scale`` / ``ks`` as
     eval_scenes_report."""
-    def eps_of(sb):
-        return eps_fn(1 if sampler.share_eps else sb.n_agents) if (not mean and eps_fn is not None) else None
-    return _scenes_report(model, dataset, scenes_per_call, pipelined, traj_scale, miss_threshold, gather,
-                          lambda sb: sampler.inference_async(model, mean=mean, eps=eps_of(sb), metrics_gt=model._future,
-                                                             metrics_scale=traj_scale),
-                          lambda sb: sampler.inference(model, mean=mean, eps=eps_of(sb)), joint, kde, collision_radius, spread, div_scale, ks)
+    return _scenes_report(model, dataset, scenes_per_call, pipelined, _sampler_calls(model, sampler, traj_scale, mean, eps_fn), traj_scale, miss_threshold, gather,
+                          joint, kde, collision_radius, model.args.sample_k, spread, div_scale, ks)
 
 
 @torch.no_grad()
@@ -456,76 +460,30 @@ def eval_nba_report(model, loader, traj_scale=1.0, z_fn=None, pipelined=True, gr
     of one shape per call, several in flight, the selection on each call's pipeline stream with one segment per loader batch.
     ``joint`` / ``collision_radius`` / ``kde`` / ``spread`` / ``div_scale`` / ``ks`` as eval_scenes_report; the joint and collision segments
     are games (N players each)."""
-    Tf, K = model.args.future_length, model.args.sample_k
-    dev = model.device
-    acc = _ReportAcc(miss_threshold, joint, kde, collision_radius, K, spread, div_scale, ks, getattr(model.args, 'dataset', 'nba'))
+    K, dev = model.args.sample_k, model.device
+    p = _ReportPasses(model, traj_scale, miss_threshold, gather, joint, kde, collision_radius, K, spread, div_scale, ks,
+                      getattr(model.args, 'dataset', 'nba'))
     if not pipelined:
         for data in loader:
             model.set_data_nba(data)
-            n = data['past_traj'].shape[0] * data['past_traj'].shape[1]
-            z = z_fn(n * K) if z_fn is not None else None
-            pred = model.inference(data, z=z)                                   # [K, n, Tf, 2]
-            sp = np.array([0, n], dtype=np.int32)
-            acc.add(model.select_best_of_k(pred.permute(1, 0, 2, 3), scale=traj_scale, miss_threshold=miss_threshold, seg_ptr=sp,
-                                           gather=gather), sp)
-            if acc.scene_metrics or kde or spread:
-                pnk = pred.permute(1, 0, 2, 3).contiguous()
-                games = np.arange(0, n + 1, data['past_traj'].shape[1], dtype=np.int32)
-                acc.add_scene_metrics(model.select_joint(pnk, seg_ptr=games, scale=traj_scale, collision_radius=acc.radius)
-                                      if acc.scene_metrics else None, model.kde_nll(pnk, scale=traj_scale) if kde else None,
-                                      model.sample_spread(pnk, scale=traj_scale, div_scale=acc.div_scale) if spread else None)
-        return acc.report(gather)
-
-    pend = []
+            B, N = data['past_traj'].shape[:2]
+            z = z_fn(B * N * K) if z_fn is not None else None
+            sp = np.array([0, B * N], dtype=np.int32)
+            p.serial(model.inference(data, z=z), sp, np.arange(0, B * N + 1, N, dtype=np.int32), sp)
+        return p.report()
     seg_ptrs = {}
 
-    def finish(item):
-        h, sel, sp, js, kd, ss = item
-        model.wait(h)
-        acc.add(sel, sp)
-        acc.add_scene_metrics(js, kd, ss)
+    def csr(n, step):                                            # a device CSR of equal segments, complete before any stream reads it
+        if (n, step) not in seg_ptrs:
+            seg_ptrs[(n, step)] = torch.arange(0, n + 1, step, dtype=torch.int32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+        return seg_ptrs[(n, step)]
 
-    def submit(group):
-        B, N = group[0]['past_traj'].shape[:2]
-        G = len(group)
-        past = torch.stack([torch.as_tensor(d['past_traj'], dtype=torch.float32) for d in group])
-        fut = torch.stack([torch.as_tensor(d['future_traj'], dtype=torch.float32) for d in group])
+    def follow(h, G, B, N):                                      # one selection segment per loader batch, one joint segment per game
         n = G * B * N
-        if (G, B * N) not in seg_ptrs:                                     # one segment per loader batch, complete before any stream reads it
-            seg_ptrs[(G, B * N)] = torch.arange(0, n + 1, B * N, dtype=torch.int32, device=dev)
-            torch.cuda.current_stream(dev).synchronize()
-        sp = seg_ptrs[(G, B * N)]
-        if acc.scene_metrics and ('games', G * B, N) not in seg_ptrs:                # one segment per game
-            seg_ptrs[('games', G * B, N)] = torch.arange(0, n + 1, N, dtype=torch.int32, device=dev)
-            torch.cuda.current_stream(dev).synchronize()
-        model.packed()
-        st = model.next_async_stream(n)
-        with torch.cuda.stream(st) if st is not None else contextlib.nullcontext():
-            model.set_data_nba({'past_traj': past.to(dev, non_blocking=True), 'future_traj': fut.to(dev, non_blocking=True)})
-            z = torch.cat([torch.as_tensor(z_fn(B * N * K)).to(dev) for _ in group]) if z_fn is not None else None
-            h = model.inference_async(z=z)
-        sel = model.select_best_of_k_async(h, gt=model._future, scale=traj_scale, miss_threshold=miss_threshold, seg_ptr=sp, gather=gather)
-        js = (model.select_joint_async(h, gt=model._future, seg_ptr=seg_ptrs[('games', G * B, N)], scale=traj_scale, collision_radius=acc.radius)
-              if acc.scene_metrics else None)
-        kd = model.kde_nll_async(h, gt=model._future, scale=traj_scale) if kde else None
-        ss = model.sample_spread_async(h, gt=model._future, scale=traj_scale, div_scale=acc.div_scale) if spread else None
-        pend.append((h, sel, np.arange(0, n + 1, B * N), js, kd, ss))
-        if len(pend) > 3:
-            finish(pend.pop(0))
-
-    group = []
-    for data in loader:
-        shape = tuple(data['past_traj'].shape)
-        if group and (tuple(group[0]['past_traj'].shape) != shape or len(group) >= groups_per_call):
-            submit(group)
-            group = []
-        group.append(data)
-    if group:
-        submit(group)
-    while pend:
-        finish(pend.pop(0))
-    model.reset_async()
-    return acc.report(gather)
+        return p.follow(h, csr(n, B * N), csr(n, N) if p.acc.scene_metrics else None, np.arange(0, n + 1, B * N), gt=model._future)
+    _nba_loop(model, loader, z_fn, groups_per_call, follow, p.finish)
+    return p.report()
 
 
 @torch.no_grad()

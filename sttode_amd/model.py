@@ -1036,20 +1036,12 @@ class STTODENet(nn.Module):
         buffers, valid after ``wait(handle)`` and until the slot's next call.  ``gt`` [n, Tf, 2] must have been written before the
         inference_async() call (default: the futures set with the batch).  Further work on the call's results -- a D2H copy of its
         futures -- may follow on ``handle['stream']`` (stream order: no event; ``wait(handle)`` still covers the metrics only)."""
-        if handle.get('generic'):
-            return self.best_of_k(handle['pred'], gt=handle.get('gt_default') if gt is None else gt, scale=scale)
         fm = handle.get('fused_metrics')
         if fm is not None and (gt is None or gt.data_ptr() == fm[0].data_ptr()) and float(scale) == fm[1]:
             capi.call('sttode_async_enqueue', self.native().h, handle['slot'])   # the call's groups compute them: make sure they are enqueued
             return handle['metrics']
-        gt = handle.get('gt_default') if gt is None else gt
-        if not (isinstance(gt, torch.Tensor) and gt.is_cuda and gt.dtype == torch.float32 and gt.is_contiguous()):
-            raise ValueError('best_of_k_async needs a contiguous float32 device tensor gt [n, Tf, 2] that was written before the call')
-        pred = handle['pred']                                    # contiguous [n, K, Tf, 2]
-        n, K, Tf = pred.shape[:3]
-        mb = handle['metrics']
-        capi.call('sttode_async_best_of_k', self.native().h, handle['slot'], pred, gt, n, K, Tf, float(scale), mb[0], mb[1])
-        return mb[0], mb[1]
+        return self._follow_up(handle, 'sttode_async_best_of_k', self.best_of_k,
+                               lambda n, K, Tf, seg_ptr: (handle['metrics'],) * 2, gt, scale)
 
     @torch.no_grad()
     def select_best_of_k(self, pred_nk, gt=None, scale=1.0, miss_threshold=1.0, seg_ptr=None, gather=False):
@@ -1068,33 +1060,14 @@ class STTODENet(nn.Module):
         ``seg_ptr`` (a device int32 tensor, or 'scenes': the call's own scene_ptr) must have been written before the inference_async()
         call.  Returns a ``metrics.Selection`` whose tensors are valid after ``wait(handle)``; the handle keeps it alive."""
         from . import metrics
-        if isinstance(seg_ptr, str):
-            if seg_ptr != 'scenes' or handle['inputs'][1] is None:
-                raise ValueError("seg_ptr='scenes' needs a call made on a scene batch (set_scene_batch / set_data)")
-            seg_ptr = handle['inputs'][1]
-        gt = handle.get('gt_default') if gt is None else gt
-        if handle.get('generic'):
-            sel = self.select_best_of_k(handle['pred'], gt=gt, scale=scale, miss_threshold=miss_threshold, seg_ptr=seg_ptr, gather=gather)
-            handle['selection'] = sel
-            return sel
-        if not (isinstance(gt, torch.Tensor) and gt.is_cuda and gt.dtype == torch.float32 and gt.is_contiguous()):
-            raise ValueError('select_best_of_k_async needs a contiguous float32 device tensor gt [n, Tf, 2] that was written before the call')
-        if seg_ptr is not None and not (isinstance(seg_ptr, torch.Tensor) and seg_ptr.is_cuda and seg_ptr.dtype == torch.int32
-                                        and seg_ptr.is_contiguous()):
-            raise ValueError('select_best_of_k_async needs seg_ptr as a contiguous int32 device tensor written before the call')
-        pred = handle['pred']                                    # contiguous [n, K, Tf, 2]
-        n, K, Tf = pred.shape[:3]
-        metrics.check_k(K)
-        if tuple(gt.shape) != (n, Tf, 2):
-            raise ValueError(f'gt must be [{n}, {Tf}, 2], got {tuple(gt.shape)}')
-        S = int(seg_ptr.numel()) - 1 if seg_ptr is not None else 0
-        sel = metrics.Selection(n, S, Tf, self.device, gather)
-        capi.call('sttode_async_best_of_k_select', self.native().h, handle['slot'], pred, gt, n, K, Tf, float(scale), float(miss_threshold),
-                  seg_ptr, S, *sel.args())
-        if handle.get('stream') is not None:
-            sel.record_stream(handle['stream'])
-        handle['selection'] = sel
-        return sel
+
+        def outputs(n, K, Tf, seg_ptr):
+            metrics.check_k(K)
+            S = int(seg_ptr.numel()) - 1 if seg_ptr is not None else 0
+            sel = metrics.Selection(n, S, Tf, self.device, gather)
+            return sel, (float(miss_threshold), seg_ptr, S, *sel.args())
+        return self._follow_up(handle, 'sttode_async_best_of_k_select', self.select_best_of_k, outputs, gt, scale,
+                               'selection', seg_ptr, miss_threshold=miss_threshold, gather=gather)
 
     @torch.no_grad()
     def select_joint(self, pred_nk, gt=None, seg_ptr=None, scale=1.0, collision_radius=None):
@@ -1127,51 +1100,64 @@ class STTODENet(nn.Module):
             raise ValueError(f'gt must be [{n}, {Tf}, 2], got {tuple(gt.shape)}')
         return pred, gt, n, K, Tf
 
+    def _follow_up(self, handle, entry, serial, outputs, gt, scale, key=None, seg_ptr=False, **kw):
+        """The one path of the ``*_async`` metric passes: the C entry ``entry`` on the pipeline stream the call of ``handle`` runs on.
+        ``seg_ptr``: False for a pass without segments; 'scenes' is the call's own scene_ptr.  A handle of the generic form (it has no
+        pipeline) takes ``serial(pred, gt=, scale=, [seg_ptr=,] **kw)`` on the caller's stream.  Else ``gt`` (default: the futures set with
+        the batch) and ``seg_ptr`` are checked, ``outputs(n, K, Tf, seg_ptr)`` checks the rest and returns (the result, the entry's arguments
+        behind ``scale``) -- a refusal comes before anything is enqueued -- and the result is kept from reuse while that stream works on it.
+        ``key``: where the handle keeps the result alive."""
+        what = serial.__name__ + '_async'
+        if seg_ptr is not False:
+            if isinstance(seg_ptr, str):
+                if seg_ptr != 'scenes' or handle['inputs'][1] is None:
+                    raise ValueError("seg_ptr='scenes' needs a call made on a scene batch (set_scene_batch / set_data)")
+                seg_ptr = handle['inputs'][1]
+            kw['seg_ptr'] = seg_ptr
+        if handle.get('generic'):
+            out = serial(handle['pred'], gt=handle.get('gt_default') if gt is None else gt, scale=scale, **kw)
+        else:
+            if kw.get('seg_ptr') is not None and not (isinstance(seg_ptr, torch.Tensor) and seg_ptr.is_cuda and seg_ptr.dtype == torch.int32
+                                                      and seg_ptr.is_contiguous()):
+                raise ValueError(f'{what} needs seg_ptr as a contiguous int32 device tensor written before the call')
+            pred, gt, n, K, Tf = self._async_metric_inputs(handle, gt, what)
+            out, args = outputs(n, K, Tf, kw.get('seg_ptr'))
+            capi.call(entry, self.native().h, handle['slot'], pred, gt, n, K, Tf, float(scale), *args)
+            if handle.get('stream') is not None and hasattr(out, 'record_stream'):
+                out.record_stream(handle['stream'])
+        if key is not None:
+            handle[key] = out
+        return out
+
     def select_joint_async(self, handle, gt=None, seg_ptr='scenes', scale=1.0, collision_radius=None):
         """select_joint of an inference_async() call, enqueued on the pipeline stream the call runs on, behind its trajectory groups; nothing
         goes onto the caller's stream.  ``gt`` (default: the futures set with the batch) and ``seg_ptr`` (a device int32 tensor, or 'scenes':
         the call's own scene_ptr) must have been written before the inference_async() call.  Returns a ``metrics.JointSelection`` whose
         tensors are valid after ``wait(handle)``; the handle keeps it alive."""
         from . import metrics
-        if isinstance(seg_ptr, str):
-            if seg_ptr != 'scenes' or handle['inputs'][1] is None:
-                raise ValueError("seg_ptr='scenes' needs a call made on a scene batch (set_scene_batch / set_data)")
-            seg_ptr = handle['inputs'][1]
-        if handle.get('generic'):
-            js = self.select_joint(handle['pred'], gt=handle.get('gt_default') if gt is None else gt, seg_ptr=seg_ptr, scale=scale,
-                                   collision_radius=collision_radius)
-            handle['joint'] = js
-            return js
-        if not (isinstance(seg_ptr, torch.Tensor) and seg_ptr.is_cuda and seg_ptr.dtype == torch.int32 and seg_ptr.is_contiguous()):
-            raise ValueError('select_joint_async needs seg_ptr as a contiguous int32 device tensor written before the call')
-        pred, gt, n, K, Tf = self._async_metric_inputs(handle, gt, 'select_joint_async')
-        metrics.check_k(K)
-        r = metrics.check_radius(collision_radius)
-        metrics.check_seg_ptr(seg_ptr, n)
-        S = int(seg_ptr.numel()) - 1
-        js = metrics.JointSelection(S, self.device, r)
-        capi.call('sttode_async_joint_select', self.native().h, handle['slot'], pred, gt, n, K, Tf, float(scale), seg_ptr, S, *js.args())
-        if handle.get('stream') is not None:
-            js.record_stream(handle['stream'])
-        handle['joint'] = js
-        return js
+
+        def outputs(n, K, Tf, seg_ptr):
+            metrics.check_k(K)
+            r = metrics.check_radius(collision_radius)
+            if seg_ptr is None:
+                raise ValueError('select_joint_async needs seg_ptr as a contiguous int32 device tensor written before the call')
+            metrics.check_seg_ptr(seg_ptr, n)
+            S = int(seg_ptr.numel()) - 1
+            js = metrics.JointSelection(S, self.device, r)
+            return js, (seg_ptr, S, *js.args())
+        return self._follow_up(handle, 'sttode_async_joint_select', self.select_joint, outputs, gt, scale, 'joint',
+                               seg_ptr, collision_radius=collision_radius)
 
     def kde_nll_async(self, handle, gt=None, scale=1.0):
         """kde_nll of an inference_async() call on the pipeline stream the call runs on, behind its trajectory groups (as
         select_joint_async).  Returns a float64 device tensor [n], valid after ``wait(handle)``; the handle keeps it alive."""
         from . import metrics
-        if handle.get('generic'):
-            out = self.kde_nll(handle['pred'], gt=handle.get('gt_default') if gt is None else gt, scale=scale)
-            handle['kde_nll'] = out
-            return out
-        pred, gt, n, K, Tf = self._async_metric_inputs(handle, gt, 'kde_nll_async')
-        metrics.check_kde_k(K)
-        out = torch.empty(n, dtype=torch.float64, device=self.device)
-        capi.call('sttode_async_kde_nll', self.native().h, handle['slot'], pred, gt, n, K, Tf, float(scale), out)
-        if handle.get('stream') is not None:
-            out.record_stream(handle['stream'])
-        handle['kde_nll'] = out
-        return out
+
+        def outputs(n, K, Tf, seg_ptr):
+            metrics.check_kde_k(K)
+            out = torch.empty(n, dtype=torch.float64, device=self.device)
+            return out, (out,)
+        return self._follow_up(handle, 'sttode_async_kde_nll', self.kde_nll, outputs, gt, scale, 'kde_nll')
 
     @torch.no_grad()
     def sample_spread(self, pred_nk, gt=None, scale=1.0, div_scale=1.0):
@@ -1186,17 +1172,12 @@ class STTODENet(nn.Module):
         """sample_spread of an inference_async() call on the pipeline stream the call runs on, behind its trajectory groups (as
         kde_nll_async).  Returns a ``metrics.SampleSpread`` whose tensors are valid after ``wait(handle)``; the handle keeps it alive."""
         from . import metrics
-        if handle.get('generic'):
-            out = self.sample_spread(handle['pred'], gt=handle.get('gt_default') if gt is None else gt, scale=scale, div_scale=div_scale)
-            handle['spread'] = out
-            return out
-        pred, gt, n, K, Tf = self._async_metric_inputs(handle, gt, 'sample_spread_async')
-        out = metrics.SampleSpread(n, K, self.device, metrics.check_spread(K, div_scale), True)
-        capi.call('sttode_async_sample_spread', self.native().h, handle['slot'], pred, gt, n, K, Tf, float(scale), *out.args())
-        if handle.get('stream') is not None:
-            out.record_stream(handle['stream'])
-        handle['spread'] = out
-        return out
+
+        def outputs(n, K, Tf, seg_ptr):
+            out = metrics.SampleSpread(n, K, self.device, metrics.check_spread(K, div_scale), True)
+            return out, out.args()
+        return self._follow_up(handle, 'sttode_async_sample_spread', self.sample_spread, outputs, gt, scale, 'spread',
+                               div_scale=div_scale)
 
     @torch.no_grad()
     def horizon_metrics(self, pred_nk, gt=None, scale=1.0):
@@ -1212,17 +1193,16 @@ class STTODENet(nn.Module):
     def horizon_metrics_async(self, handle, gt=None, scale=1.0, out=None):
         """horizon_metrics of an inference_async() call, enqueued on the pipeline stream the call runs on (behind its trajectory groups; nothing
         goes onto the caller's stream).  Returns [n,Tf,2], valid after ``wait(handle)``."""
-        gt = handle.get('gt_default') if gt is None else gt
-        if not (isinstance(gt, torch.Tensor) and gt.is_cuda and gt.dtype == torch.float32 and gt.is_contiguous()):
-            raise ValueError('horizon_metrics_async needs a contiguous float32 device tensor gt [n, Tf, 2] that was written before the call')
-        pred = handle['pred']
-        n, K, Tf = pred.shape[:3]
-        if handle.get('generic'):
-            return self.horizon_metrics(pred, gt, scale)
-        if out is None:
-            out = torch.empty(n, Tf, 2, dtype=torch.float32, device=self.device)
-        capi.call('sttode_async_horizon_metrics', self.native().h, handle['slot'], pred, gt, n, K, Tf, float(scale), out)
-        return out
+        def outputs(n, K, Tf, seg_ptr):
+            o = torch.empty(n, Tf, 2, dtype=torch.float32, device=self.device) if out is None else out
+            return o, (o,)
+        return self._follow_up(handle, 'sttode_async_horizon_metrics', self.horizon_metrics, outputs, gt, scale)
+
+    def _async_shapes(self, slots=0):
+        """How many per-shape slot buffers inference_async() holds (it refuses beyond 16), counting those that calls on the first ``slots``
+        slots of the batch now set would add."""
+        n, S = self._past.shape[0], self._S if self._mode == 'scenes' else 0
+        return len(self._async_bufs) + sum((n, S, s) not in self._async_bufs for s in range(slots))
 
     def reset_async(self):
         if getattr(self, '_native', None) is not None:
