@@ -238,6 +238,29 @@ int sttode_kde_nll(const float* pred, const float* gt, int n, int K, int Tf, flo
  * Refused before any launch or write, naming the entry.  No atomics, every sum in a fixed order: the same bits on every run. */
 int sttode_sample_spread(const float* pred, const float* gt, int n, int K, int Tf, float scale, double div_scale, double* apd, double* fpd,
                          double* pade, double* dlow, double* es_ade, double* es_fde, float* ade_at_k, float* fde_at_k, void* stream);
+/* Multi-modal ground truth over a dataset: MMADE / MMFDE of DLow and its successors (the reference computes nothing like it).
+ * Do the K samples of agent i cover the futures that agents with a similar history actually had?
+ * pred [n,K,Tf,2], past [n,Tp,2], gt [n,Tf,2] float32; seg_ptr NULL (n_seg = 0: all agents are one segment) or a CSR [n_seg+1] over the
+ * agents, int32 on the device (every bound is clamped to [0, n]; an agent that no segment covers keeps only itself).
+ * Coordinates are x = (double)(x * scale), the product in float32 as sttode_kde_nll; everything after that is float64; eps is in scaled units.
+ *   anchor a_i = P_i[Tp-1];  history vector H_i = (P_i[t] - a_i) for t = Tp-1-h .. Tp-2, h = hist_frames: 2h numbers;
+ *   d_hist(i,j) = sqrt(sum (H_i - H_j)^2), summed in frame order, x then y;
+ *   S_i = { j in i's segment : d_hist(i,j) <= eps } + { i }.  A NaN in either history makes the comparison false: such an agent keeps only
+ *   itself and enters nobody else's set.  j in S_i <=> i in S_j.
+ *   translated future of a neighbour: g_j->i[t] = (Y_j[t] - a_j) + a_i, in exactly that order;
+ *   D_ade(i,k,j) = (1/Tf) sum_t |X_i,k,t - g_j->i[t]|, frames summed in frame order;  D_fde(i,k,j) = the last frame's term.
+ * Per agent [n]:  count = |S_i| (int32, >= 1);
+ *   mmade = (1/count) sum over j in S_i, ascending j, of min_k D_ade(i,k,j);  mmfde the same with D_fde (float64).  A sample with a NaN is
+ *   skipped in the minimum; if every sample is NaN the minimum is +inf, and it propagates.
+ * At eps = 0 with pairwise distinct histories count = 1 and mmade / mmfde are the float64 best-of-K ADE / FDE; with eps huge count is the size
+ * of i's segment.
+ * ws: a workspace of ws_doubles >= (2h + 2) n doubles (anchors and history vectors, component-major), overwritten.
+ * Limits: 1 <= n <= 2^20, 1 <= K <= 64, Tf >= 1, Tp >= 2, 1 <= h <= Tp - 1, eps >= 0 and finite, scale finite, n_seg >= 1 with seg_ptr.
+ * Refused before any launch or write, naming the entry.  No atomics, every sum in a fixed order: the same bits on every run, and an agent's
+ * values do not depend on the agents outside its segment. */
+int sttode_multimodal(const float* pred, const float* past, const float* gt, const int* seg_ptr_or_NULL, int n_seg, int n, int K, int Tp,
+                      int Tf, int hist_frames, float scale, double eps, double* ws, long ws_doubles, int* count, double* mmade, double* mmfde,
+                      void* stream);
 
 /* Stage-2 latent sampler (sampler.py:47-54): z = b (eps_mode 0) or A*eps + b with eps shared [nz] (1, share_eps) or per agent
  * [n,nz] (2); logvar = log(A^2 + 1e-8).  A, b, z, logvar [n*K, nz] (row = agent*K + k). */

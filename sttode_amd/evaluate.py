@@ -11,6 +11,8 @@
                   among themselves of DESIGN.md 4s: APD / FPD, the DLow kernel value, energy scores, best-of-k.
   eval_scenes_reduced  oversample and reduce: `rounds` calls per scene batch, k-means of the rounds * sample_k futures of every
                   agent to K representatives on the device, then the selection of eval_scenes_report on the representatives.
+  eval_scenes_multimodal  MMADE / MMFDE: the samples of the whole dataset gathered on the device, then one pass that scores every
+                  agent's samples against the futures of all agents with a similar history.
   embedding_delta  how tree-like the encoder's past features (or the observed tracks) of a dataset are: delta / diam of hyptorch/delta.py's
                    batched_delta_hyp over all agents.
 """
@@ -439,6 +441,82 @@ def eval_scenes_reduced(model, dataset, rounds, K=None, iters=10, from_frame=0, 
     if pipelined:
         model.reset_async()
     return acc.report(False)
+
+
+@dataclasses.dataclass
+class MultiModalReport:
+    """What eval_scenes_multimodal returns.  ``mmade`` / ``mmfde``: the means over all agents of the per-agent MMADE / MMFDE
+    (float64 sums in dataset order); ``n_agents``; ``mean_count``: the mean size of an agent's neighbour set, itself included;
+    ``frac_multi``: the share of agents with more than one neighbour (count > 1); ``mmade_multi`` / ``mmfde_multi``: the means over those
+    agents alone, NaN if there are none; ``eps``, ``hist_frames``, ``within`` as used; per agent in dataset order ``count`` [n] int32 and
+    ``mmade_agents`` / ``mmfde_agents`` [n] float64."""
+    mmade: float
+    mmfde: float
+    n_agents: int
+    mean_count: float
+    frac_multi: float
+    mmade_multi: float
+    mmfde_multi: float
+    eps: float
+    hist_frames: int
+    within: str
+    count: np.ndarray
+    mmade_agents: np.ndarray
+    mmfde_agents: np.ndarray
+
+
+def multimodal_segments(dataset, scene_ptr, within):
+    """The agent segments inside which eval_scenes_multimodal looks for neighbours, as a CSR over the agents of ``scene_ptr`` [S+1] (the
+    whole dataset's scenes in order), or None for one segment: ``within='dataset'`` -- None; ``'file'`` -- consecutive scenes with equal
+    ``dataset.seq_name`` form a segment (recordings with different homographies do not mix); ``'scene'`` -- ``scene_ptr`` itself."""
+    ptr = np.asarray(scene_ptr, dtype=np.int64)
+    if within == 'dataset':
+        return None
+    if within == 'scene':
+        return ptr.astype(np.int32)
+    if within != 'file':
+        raise ValueError(f"within must be 'dataset', 'file' or 'scene', got {within!r}")
+    names = getattr(dataset, 'seq_name', None)
+    if names is None or len(names) != len(ptr) - 1:
+        raise ValueError("within='file' needs dataset.seq_name with one name per scene")
+    first = [s for s in range(len(names)) if s == 0 or names[s] != names[s - 1]]
+    return ptr[first + [len(names)]].astype(np.int32)
+
+
+@torch.no_grad()
+def eval_scenes_multimodal(model, dataset, eps, hist_frames=None, within='dataset', traj_scale=1.0, scenes_per_call=512, z_fn=None,
+                           pipelined=True, sampler=None, mean=True, eps_fn=None):
+    """MMADE / MMFDE of a scene dataset (a ``MultiModalReport``): do the K samples of an agent cover the futures that agents
+    with a similar history actually had?  The calls and latents of eval_scenes (of eval_sampler with ``sampler``; ``mean`` / ``eps_fn`` as
+    there); every call's samples are copied into one device buffer [n, K, Tf, 2] for the whole dataset -- a pipelined call is waited for and
+    copied on the caller's stream before its slot is taken again -- and ONE ``metrics.multimodal`` pass runs over all agents, with the
+    dataset's own observed and future tracks.  ``eps`` (in units of ``traj_scale`` times the data's) and ``hist_frames`` (default
+    past_length - 1) define the neighbours, ``within`` where they are looked for (``multimodal_segments``)."""
+    from . import metrics
+    if within not in ('dataset', 'file', 'scene'):
+        raise ValueError(f"within must be 'dataset', 'file' or 'scene', got {within!r}")
+    whole = dataset.scene_batch(range(len(dataset)))
+    n, K, Tf = whole.n_agents, model.args.sample_k, model.args.future_length
+    e, h = metrics.check_multimodal(n, K, int(whole.past.shape[1]), Tf, eps, hist_frames, traj_scale)
+    seg = multimodal_segments(dataset, whole.scene_ptr, within)
+    buf = torch.empty(n, K, Tf, 2, dtype=torch.float32, device=model.device)
+    pos = 0
+
+    def put(pred):                                                        # [K, n_call, Tf, 2] of the next call in dataset order
+        nonlocal pos
+        buf[pos:pos + pred.shape[1]].copy_(pred.permute(1, 0, 2, 3))
+        pos += int(pred.shape[1])
+    launch, serial = _scene_calls(model, traj_scale, z_fn) if sampler is None else _sampler_calls(model, sampler, traj_scale, mean, eps_fn)
+    _scene_loop(model, dataset, scenes_per_call, pipelined, launch, lambda h_: put(model.wait(h_)), lambda sb: put(serial(sb)))
+    assert pos == n, (pos, n)
+    mm = metrics.multimodal(buf, whole.past, whole.future, e, hist_frames=h, scale=traj_scale, seg_ptr=seg)
+    count, a, f = mm.count.cpu().numpy(), mm.mmade.cpu().numpy(), mm.mmfde.cpu().numpy()
+    multi = count > 1
+    nan = float('nan')
+    return MultiModalReport(mmade=float(a.sum() / n), mmfde=float(f.sum() / n), n_agents=n, mean_count=float(count.sum(dtype=np.int64) / n),
+                            frac_multi=float(multi.sum() / n), mmade_multi=float(a[multi].sum() / multi.sum()) if multi.any() else nan,
+                            mmfde_multi=float(f[multi].sum() / multi.sum()) if multi.any() else nan, eps=e, hist_frames=h, within=within,
+                            count=count, mmade_agents=a, mmfde_agents=f)
 
 
 @torch.no_grad()

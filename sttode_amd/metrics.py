@@ -3,7 +3,8 @@ sttode_best_of_k_select).
 
 ``joint_select`` and ``kde_nll`` (csrc/metrics.hip) are the scene-level metrics the reference does not compute: joint min ADE / FDE
 and collision counts per segment, and the KDE NLL per agent.  ``sample_spread`` compares an agent's samples with each other:
-pairwise distances, the DLow kernel value, energy scores and best-of-k for every k.  ``reduce_samples`` (csrc/reduce.hip)
+pairwise distances, the DLow kernel value, energy scores and best-of-k for every k.  ``multimodal`` (csrc/multimodal.hip)
+scores them against the futures of all agents with a similar history, over a whole dataset: MMADE / MMFDE.  ``reduce_samples`` (csrc/reduce.hip)
 clusters M sampled futures per agent to K representatives.
 
 ``select`` is the kernel call: per agent the min-over-K ADE / FDE, the index of the best sample by ADE and by final displacement
@@ -245,6 +246,78 @@ def sample_spread(pred_nk, gt=None, scale=1.0, div_scale=1.0):
     out = SampleSpread(n, K, pred_nk.device, ds, gt is not None)
     with torch.cuda.device(pred_nk.device):
         capi.call('sttode_sample_spread', pred_nk, gt, n, K, Tf, float(scale), *out.args(), capi.stream_ptr())
+    return out
+
+
+# ----- multi-modal ground truth over a dataset (csrc/multimodal.hip: sttode_multimodal) -------------------------------------
+
+MM_MAX_AGENTS = 1 << 20
+
+
+class MultiModal:
+    """Outputs of one multi-modal pass (device tensors), per agent: ``count`` [n] int32 (the agents of its segment whose anchored history
+    lies within eps of its own, itself included), ``mmade`` / ``mmfde`` [n] float64 (the mean over those neighbours of the best sample's
+    ADE / FDE against the neighbour's future translated to the agent's anchor)."""
+    __slots__ = ('count', 'mmade', 'mmfde', 'eps', 'hist_frames')
+
+    def __init__(self, n, device, eps, hist_frames):
+        d = torch.empty(2 * n, dtype=torch.float64, device=device)
+        self.mmade, self.mmfde = d[:n], d[n:]
+        self.count = torch.empty(n, dtype=torch.int32, device=device)
+        self.eps, self.hist_frames = eps, hist_frames
+
+    def args(self):
+        """Output pointers in the order of sttode_multimodal."""
+        return (self.count, self.mmade, self.mmfde)
+
+    def record_stream(self, stream):
+        for t in (self.count, self.mmade):   # (views: the record covers the whole allocation)
+            t.record_stream(stream)
+
+
+def check_multimodal(n, K, Tp, Tf, eps, hist_frames, scale):
+    """(eps, hist_frames) as a float and an int (None: Tp - 1), after the checks of sttode_multimodal."""
+    if not 1 <= n <= MM_MAX_AGENTS:
+        raise ValueError(f'multi-modal ground truth needs 1 <= n <= 2^20 agents, got n = {n}')
+    if K < 1 or K > 64:
+        raise ValueError(f'multi-modal ground truth needs 1 <= K <= 64 samples (one lane per sample), got K = {K}')
+    if Tp < 2:
+        raise ValueError(f'multi-modal ground truth needs Tp >= 2 (an anchor and one history frame), got Tp = {Tp}')
+    h = Tp - 1 if hist_frames is None else int(hist_frames)
+    if not 1 <= h <= Tp - 1:
+        raise ValueError(f'hist_frames must be in [1, Tp - 1 = {Tp - 1}], got {hist_frames}')
+    e = float(eps)
+    if not (e >= 0.0 and e != float('inf')):
+        raise ValueError(f'eps must be non-negative and finite, got {eps}')
+    if not np.isfinite(float(scale)):
+        raise ValueError(f'scale must be finite, got {scale}')
+    return e, h
+
+
+@torch.no_grad()
+def multimodal(pred_nk, past, gt, eps, hist_frames=None, scale=1.0, seg_ptr=None):
+    """MMADE / MMFDE of pred_nk [n, K, Tf, 2] over the whole set of agents, in float64 on the current stream (include/sttode_hip.h
+    sttode_multimodal states every value): the neighbours of agent i are the agents of its segment -- ``seg_ptr`` [S+1], device or host; all
+    agents without it -- whose last ``hist_frames`` (default Tp - 1) frames of past [n, Tp, 2], relative to the last observed position, lie
+    within ``eps`` (scaled units, Euclidean over the 2 hist_frames numbers) of its own; their futures gt [n, Tf, 2], translated to i's last
+    position, are scored against i's K samples.  n <= 2^20, K <= 64.  The workspace is the function's own.  Returns a ``MultiModal``."""
+    pred_nk, gt, n, K, Tf = _inputs(pred_nk, gt, 'multi-modal ground truth')
+    dev = pred_nk.device
+    past = torch.as_tensor(past, dtype=torch.float32).to(dev).contiguous()
+    if past.dim() != 3 or past.shape[0] != n or past.shape[2] != 2:
+        raise ValueError(f'past must be [{n}, Tp, 2], got {tuple(past.shape)}')
+    Tp = int(past.shape[1])
+    e, h = check_multimodal(n, K, Tp, Tf, eps, hist_frames, scale)
+    sp, S = None, 0
+    if seg_ptr is not None:
+        check_seg_ptr(seg_ptr, n)
+        sp = seg_ptr_tensor(seg_ptr, dev)
+        S = int(sp.numel()) - 1
+    out = MultiModal(n, dev, e, h)
+    ws = torch.empty((2 * h + 2) * n, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        capi.call('sttode_multimodal', pred_nk, past, gt, sp, S, n, K, Tp, Tf, h, float(scale), e, ws, int(ws.numel()), *out.args(),
+                  capi.stream_ptr())
     return out
 
 
