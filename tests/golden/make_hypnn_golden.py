@@ -14,11 +14,12 @@ are drawn, rounded to float16 and stored as float16 (exact in float32).
   mab.<shape>   _mobius_addition_batch(x [B,d], y [C,d], c), both on the ball ([0.05, 0.9]); g [B,C,d]
   clip.<kind>   x min(1, r / (|x| + 1e-5)), r = 2.3: rows of norm [2.6, 5] (clipped), [0.1, 2] (unclipped), and [0.1, 5] with one zero row (mixed)
   mod.<name>    the reference's modules (hypnn_cases.MODULES) with drawn parameters; mod.mlr.<shape>: HyperbolicMLR with a_vals ~ 0.3 N(0,1) and
-                tangent p_vals with sqrt(c) |.| in [0.05, 0.9]
+                tangent p_vals with sqrt(c) |.| in [0.05, 0.9].  Every mod.* case also stores the module's forward value, <case>.out64 /
+                out32d, coded like the gradients
   init.<name>   state_dict names (.names), and values under torch.manual_seed(0), of every module of hypnn_cases.INIT_MODULES
   train.*       ToPoincare(c=1, clip_r=2.3) -> HypLinear(16, 8) -> HyperbolicMLR(8, 5) on 32 rows, cross-entropy, torch.optim.Adam(lr=1e-2), 5
                 steps: the initial state_dict (train.sd.<key>), x, labels, and the 5 losses of the float64 and of the float32 run
-The generator asserts that the reference's fp32 gradients are within the bound of its float64 ones for every case.
+The generator asserts that the reference's fp32 gradients and module forward values are within the bound of its float64 ones for every case.
 """
 import copy
 import os
@@ -34,7 +35,8 @@ from make_pmath_vjp_golden import ball_points, reference  # noqa: E402
 
 
 def store(out, case, fn, inputs, g, module=None):
-    """Run fn(*inputs) (fn: a function, or the module itself) in float64 and float32 and store inputs, parameters, g and every gradient."""
+    """Run fn(*inputs) (fn: a function, or the module itself) in float64 and float32 and store inputs, parameters, g, every gradient and,
+    for a module, its forward value (<case>.out64 / out32d)."""
     import torch
     for k, a in enumerate(inputs):
         out['%s.in.%d' % (case, k)] = a
@@ -47,12 +49,14 @@ def store(out, case, fn, inputs, g, module=None):
         ts = [torch.from_numpy(a).to(dt).requires_grad_() for a in inputs]
         res = (m if m is not None else fn)(*ts)
         res.backward(torch.from_numpy(g).to(dt).reshape(res.shape))
+        if m is not None:
+            out['%s.out%s' % (case, tag)] = res.detach().numpy().astype(np.float32)     # the module's forward value
         for k, t in enumerate(ts):
             out['%s.gin.%d%s' % (case, k, tag)] = t.grad.numpy().astype(np.float32)
         if m is not None:
             for n, p in m.named_parameters():
                 out['%s.gp.%s%s' % (case, n, tag)] = p.grad.numpy().astype(np.float32)
-    for k in [k for k in out if k.startswith(case + '.g') and k.endswith('32')]:
+    for k in [k for k in out if (k.startswith(case + '.g') or k == case + '.out32') and k.endswith('32')]:
         out[k + 'd'] = out.pop(k) - out[k[:-2] + '64']      # stored as the difference from the yardstick: few significant bits, it compresses
 
 
@@ -141,8 +145,8 @@ def main():
         if k.endswith('64') and k[:-2] + '32d' in out:
             assert np.isfinite(out[k]).all() and np.isfinite(out[k[:-2] + '32d']).all(), k
             e = err(out[k] + out[k[:-2] + '32d'], out[k])
-            assert e <= BOUND, ('the reference fp32 gradient is outside the bound', k, e)
-            fam = k.split('.')[0] + ('.' + k.split('.')[1] if k.startswith('mod.') else '')
+            assert e <= BOUND, ('the reference fp32 %s is outside the bound' % ('forward value' if k.endswith('.out64') else 'gradient'), k, e)
+            fam = k.split('.')[0] + ('.' + k.split('.')[1] if k.startswith('mod.') else '') + (' forward' if k.endswith('.out64') else '')
             worst[fam] = max(worst.get(fam, 0.0), e)
     path = os.path.join(HERE, 'hypnn.npz')
     np.savez_compressed(path, **out)

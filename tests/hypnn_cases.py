@@ -4,6 +4,7 @@
 Every gradient case <case> stores  <case>.in.<k> (inputs), <case>.p.<name> (module parameters), <case>.g (upstream gradient) and, for every
 input and parameter, <case>.gin.<k>64 / 32d and <case>.gp.<name>64 / 32d: the reference differentiated in float64 on the float32 inputs (the
 yardstick, stored rounded to float32) and the reference's own float32 run, stored as its difference from the yardstick.  g is float16.
+Every mod.* case also stores the reference module's forward value the same way: <case>.out64 / out32d.
 """
 import numpy as np
 
@@ -70,6 +71,11 @@ def case_arrays(z, case):
         ins.append(z['%s.in.%d' % (case, len(ins))])
     pre = case + '.p.'
     return ins, {k[len(pre):]: z[k] for k in z if k.startswith(pre)}, z[case + '.g'].astype(np.float32)
+
+
+def case_forward(z, case):
+    """(float64 yardstick, reference fp32) of the forward value of a stored mod.* case."""
+    return z[case + '.out64'], z[case + '.out64'] + z[case + '.out32d']
 
 
 def case_grads(z, case):

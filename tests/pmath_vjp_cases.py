@@ -1,5 +1,6 @@
 """The cases of tests/golden/pmath_vjp.npz and pmath_vjp_rows.npz (written by tests/golden/make_pmath_vjp_golden.py) as one list, shared by
-test_pmath_grad.py (CPU: the fixture checks itself) and test_pmath_grad_gpu.py (the kernels against the float64 yardstick)."""
+test_pmath_grad.py (CPU: the fixture checks itself), test_pmath_grad_gpu.py (the backward kernels against the float64 yardstick) and
+test_pmath_forward_gpu.py (the forward values at the same inputs against the oracle in float64)."""
 import numpy as np
 
 BOUND = 1e-4          # the bound of the project's golden comparisons, on max |got - ref| / (1 + |ref|)

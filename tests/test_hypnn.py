@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from hypnn_cases import BOUND, INIT_MODULES, MODULES, TRAIN_STEPS, case_arrays, case_grads, err, function_cases
+from hypnn_cases import BOUND, INIT_MODULES, MODULES, TRAIN_STEPS, case_arrays, case_forward, case_grads, err, function_cases
 
 
 def all_cases():
@@ -16,7 +16,7 @@ def all_cases():
 
 def test_fixture_holds_every_case_and_the_reference_fp32_is_within_the_bound(golden):
     z = golden('hypnn')
-    worst = 0.0
+    worst = worst_fwd = 0.0
     for case in all_cases():
         ins, _, g = case_arrays(z, case)
         grads = case_grads(z, case)
@@ -27,10 +27,18 @@ def test_fixture_holds_every_case_and_the_reference_fp32_is_within_the_bound(gol
             e = err(r32, ref)
             worst = max(worst, e)
             assert e <= BOUND, (case, key, e)
-    assert len(all_cases()) == 27
+        if case.startswith('mod.'):                                    # the module's forward value: the shape of g, fp32 run within the bound
+            ref, r32 = case_forward(z, case)
+            assert ref.dtype == np.float32 and ref.size == g.size and np.isfinite(ref).all() and np.isfinite(r32).all(), case
+            e = err(r32, ref)
+            worst_fwd = max(worst_fwd, e)
+            assert e <= BOUND, (case, 'out', e)
+        else:
+            assert case + '.out64' not in z, case
+    assert len(all_cases()) == 27 and sum(k.endswith('.out64') for k in z) == sum(k.endswith('.out32d') for k in z) == len(MODULES) == 14
     assert z['train.loss64'].shape == z['train.loss32'].shape == (TRAIN_STEPS,) and z['train.loss64'].dtype == np.float64
     assert err(z['train.loss32'], z['train.loss64']) <= BOUND
-    print('worst reference fp32 error over the fixture: %.2e' % worst)
+    print('worst reference fp32 error over the fixture: %.2e (gradients), %.2e (module forward values)' % (worst, worst_fwd))
 
 
 def test_modules_have_the_reference_state_dict_and_initial_values(golden):

@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 import torch
 
-from hypnn_cases import (BOUND, CLIP_R, MODULES, TRAIN_LR, TRAIN_STEPS, case_arrays, case_grads, err, function_cases, shape_tag,
-                         train_model)
+from hypnn_cases import (BOUND, CLIP_R, MODULES, TRAIN_LR, TRAIN_STEPS, case_arrays, case_forward, case_grads, err, function_cases,
+                         shape_tag, train_model)
 
 pytestmark = pytest.mark.gpu
 
@@ -103,7 +103,11 @@ def test_forward_values_of_the_two_paths_are_bitwise_equal(results):
 
 
 def test_forward_values_against_the_reference_formulas(results):
-    """The clip op's forward is new: held to its formula in float64.  (The pair kernel's forward values are test_pmath's.)"""
+    """The clip op's forward against its formula in float64, and the forward value of every module against the reference module's own
+    float64 run on the same float32 inputs and parameters (<case>.out64 of the fixture; its rounding to float32, 6e-8 relative, is inside the
+    1e-6 floor).  Two bounds per module family: the project's 1e-4, and eight times the error of the reference's own fp32 run (or 1e-6),
+    which a dropped tail element or a swapped index does not pass.  The forward values of the raw pair functions at these shapes, and of
+    every pmath function at the wave and block edges: test_pmath_forward_gpu.py."""
     z, res = results
     for kind in ('clipped', 'unclipped', 'mixed'):
         x = case_arrays(z, 'clip.' + kind)[0][0].astype(np.float64)
@@ -111,6 +115,20 @@ def test_forward_values_against_the_reference_formulas(results):
         e = err(res['clip.' + kind][1].cpu().numpy(), x * np.minimum(1.0, CLIP_R / n))
         print('clip.%s forward: error %.2e' % (kind, e))
         assert e <= 1e-6, (kind, e)       # one rounding of a float64 product to float32: 6e-8 relative
+    worst, ref32 = {}, {}
+    for case, (family, out, _, _) in res.items():
+        if not case.startswith('mod.'):
+            continue
+        ref, r32 = case_forward(z, case)
+        got = out.cpu().numpy()
+        assert got.shape == ref.shape and np.isfinite(got).all(), case
+        worst[family] = max(worst.get(family, 0.0), err(got, ref))
+        ref32[family] = max(ref32.get(family, 0.0), err(r32, ref))
+    for family in sorted(worst):
+        print('%-30s forward: worst error %.2e   (reference fp32: %.2e)' % (family, worst[family], ref32[family]))
+    assert len(worst) == 10 and sum(c.startswith('mod.') for c in res) == len(MODULES)
+    bad = [(f, worst[f], ref32[f]) for f in sorted(worst) if not (worst[f] <= BOUND and worst[f] <= max(8 * ref32[f], 1e-6))]
+    assert not bad, bad
 
 
 def test_hyperbolic_softmax_backward_is_bitwise_repeatable(golden):
