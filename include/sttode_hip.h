@@ -591,6 +591,39 @@ int sttode_pmath_clip_bwd(const float* x, const float* g, float* gx, int rows, i
 int sttode_oblique_dist(const float* p1, const float* p2, float* out, int nb, int n1, int n2, int d, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Riemannian optimisation (csrc/manifold.hip): the manifold interface of core/manifolds/base.py as row operations, and
+ * Riemannian Adam / SGD over every manifold parameter of a param group in one launch.  Added within ABI version 14.  Forward values only.
+ * ---------------------------------------------------------------------------------------------- */
+enum SttodeManifold { STT_MF_EUCLIDEAN = 0, STT_MF_OBLIQUE, STT_MF_POINCARE, STT_MF_COUNT };
+enum SttodeManifoldOp { STT_MOP_PROJ_TAN = 0, STT_MOP_EXPMAP, STT_MOP_PTRANSP, STT_MOP_INNER, STT_MOP_RETR, STT_MOP_RETR_TRANSP, STT_MOP_COUNT };
+enum SttodeRiemannianRule { STT_RULE_ADAM = 0, STT_RULE_SGD, STT_RULE_COUNT };
+/* One op on the rows of a, b, w [rows,d] (one wave per row, float64 row sums):
+ *   PROJ_TAN     (p, u)     out = egrad2rgrad(p, u): Oblique u - <p,u> p (its proj_tan), ball u (1 - c |p|^2)^2 / 4, Euclidean u
+ *   EXPMAP       (p, u)     out = expmap(u, p), no projection; Oblique keeps the reference's branch at |u| = 1e-4 (zero u: p / |p|)
+ *   PTRANSP      (x, y, u)  out = ptransp(x, y, u): Oblique proj_tan(u, y), ball gyr[y, -x] u lambda_x / lambda_y
+ *   INNER        (p, u, v)  out [rows] = inner_p(u, v); w == NULL: v = u
+ *   RETR         (x, u)     out = retr(x, u): Oblique expmap renormalised, ball project(expmap)
+ *   RETR_TRANSP  (x, u, v)  out = y = retr(x, u), out2 = ptransp(x, y, v)
+ * c: the ball's curvature magnitude (> 0, finite); ignored by the other manifolds.  Operands an op does not take may be NULL. */
+int sttode_manifold_rowop(int op, int manifold, const float* a, const float* b, const float* w, float* out, float* out2, int rows, int d,
+                          float c, void* stream);
+/* One optimiser step of every parameter of a DEVICE table.  A wave steps one WAVE SLOT: one row of d > 32 elements, two rows of d <= 32,
+ * four rows of d <= 16; a parameter takes ceil(rows / rows per slot) slots.  A table row is STTODE_RIEMANNIAN_ITEM_WORDS 8-byte words:
+ * parameter, state buffer 1 (Adam exp_avg [rows,d]; SGD momentum_buffer or NULL for momentum 0), state buffer 2 (Adam exp_avg_sq [rows];
+ * SGD unused), gradient, d, rows, first wave slot (ascending from 0; total_slots = the slots of all parameters), manifold code, c (a
+ * double), element count (rows d; a plain parameter of the SGD rule is cut into rows of d elements, the last may be short).  Per row, with g += weight_decay x
+ * and r = egrad2rgrad(x, g):
+ *   ADAM  m = beta1 m + (1 - beta1) r; v = beta2 v + (1 - beta2) inner_x(r, r); y = retr(x, -lr (m / (1 - beta1^t)) / (sqrt(v / (1 -
+ *         beta2^t)) + eps)); m = ptransp(x, y, m); x = y.  t >= 1: the step count.  t == 0 with tstate (DEVICE, one double): the count
+ *         is kept on the device, incremented by a one-thread launch in front of the step (a captured step replays correctly); a call with
+ *         t >= 1 and tstate writes t there.
+ *   SGD   buf = momentum buf + r (with a buffer); y = retr(x, -lr buf); buf = ptransp(x, y, buf); x = y.  beta1, beta2, eps, t unused.
+ * No atomics, no host synchronisation, no allocation; bitwise repeatable. */
+#define STTODE_RIEMANNIAN_ITEM_WORDS 10
+int sttode_riemannian_step(int rule, const void* table, int nrows_table, long total_slots, double lr, double beta1, double beta2,
+                           double eps, double weight_decay, double momentum, long t, void* tstate, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Gromov delta-hyperbolicity (hyptorch/delta.py:12-35).  Stand-alone analysis, not on the model's data flow.
  * ------------------------------------------------------------------------------------------------ */
 /* scipy.spatial.distance_matrix of T row samples (delta.py:29-31): X [rows,d] row-major; idx [T,n] int32 row indices into X (NULL: the rows

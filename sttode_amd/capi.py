@@ -101,6 +101,9 @@ SIGNATURES = {
     'sttode_pmath_hsoftmax_bwd': [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P],
     'sttode_pmath_clip': [_P, _P, _I, _I, _F, _P],
     'sttode_pmath_clip_bwd': [_P, _P, _P, _I, _I, _F, _P],
+    # manifold interface row ops and the Riemannian optimiser step (csrc/manifold.hip; added within ABI version 14)
+    'sttode_manifold_rowop': [_I, _I, _P, _P, _P, _P, _P, _I, _I, _F, _P],
+    'sttode_riemannian_step': [_I, _P, _I, _L, _D, _D, _D, _D, _D, _D, _L, _P, _P],
     # Gromov delta-hyperbolicity (csrc/delta.hip)
     'sttode_delta_dist': [_P, _I, _I, _P, _I, _I, _P, _L, _P, _P],
     'sttode_delta_workspace': [_I, _I, ctypes.POINTER(ctypes.c_long)],
@@ -188,6 +191,12 @@ class GradGroup(ctypes.Structure):
 
 GRAD_MAX_GROUPS = 16       # STTODE_GRAD_MAX_GROUPS
 GRAD_STATE_WORDS = 40      # STTODE_GRAD_STATE_WORDS: [0] total_norm [1] coef [2] apply [3] applied [4] skipped [8 + 2 g, 9 + 2 g] group scalars
+
+
+MANIFOLDS = dict(euclidean=0, oblique=1, poincare=2)                                         # enum SttodeManifold
+MANIFOLD_OPS = dict(proj_tan=0, expmap=1, ptransp=2, inner=3, retr=4, retr_transp=5)         # enum SttodeManifoldOp
+RIEMANNIAN_RULES = dict(adam=0, sgd=1)                                                       # enum SttodeRiemannianRule
+RIEMANNIAN_ITEM_WORDS = 10                                                                   # STTODE_RIEMANNIAN_ITEM_WORDS
 
 
 class SamplerPlan(ctypes.Structure):

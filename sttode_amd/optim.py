@@ -14,9 +14,13 @@ run on the device over the same table -- per-chunk sums of squares, one workgrou
 flag and the step counters to a small state block, and the update reading them -- with no host round trip: torch's clip walks the 88
 tensors again with foreach launches, which is the cost this file exists to remove.  A skipped step does not count towards the bias
 corrections (as a step a GradScaler skipped).  ``clip_grad_norm_`` below is the stand-alone drop-in for torch's function.
+
+``RiemannianAdam`` and ``RiemannianSGD`` (the end of this file; csrc/manifold.hip) step ``manifolds.ManifoldParameter``s on
+their manifolds -- the optimiser that the reference's core/manifolds interface is written for and the reference does not ship.
 """
 import ctypes
 import math
+import struct
 
 import torch
 
@@ -296,3 +300,273 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=Fals
         if L.sttode_grad_scale(table.data_ptr(), arr[0].n, arr[0].chunks, grads[0].data_ptr(), state.data_ptr(), st):
             raise capi.SttodeError('sttode_grad_scale failed: ' + L.sttode_last_error().decode())
     return norm
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# Riemannian Adam and SGD (csrc/manifold.hip): a ``manifolds.ManifoldParameter`` is stepped ON its manifold -- Riemannian
+# gradient, retraction, the momentum transported to the new point -- every manifold parameter of a param group in ONE launch over a device
+# table of the tensors (the manner of ``_chunk_rows`` above: one table row per parameter, one wave per row of the parameter, or per two or four short rows).
+# ---------------------------------------------------------------------------------------------------------------------------------------
+_PLAIN_ROW = 256         # a plain parameter under RiemannianSGD: cut into rows of this many elements (the rule is elementwise)
+
+
+def _manifold_code(p):
+    """(manifold code, c) of a parameter; plain parameters and ManifoldParameters on manifolds.Euclidean are Euclidean."""
+    from . import manifolds
+    man = getattr(p, 'manifold', None) if isinstance(p, manifolds.ManifoldParameter) else None
+    if man is None or isinstance(man, manifolds.Euclidean):
+        return None
+    if isinstance(man, manifolds.PoincareBall):
+        return capi.MANIFOLDS['poincare'], man.c
+    if isinstance(man, manifolds.Oblique):
+        return capi.MANIFOLDS['oblique'], 1.0
+    raise ValueError(f'{type(man).__module__}.{type(man).__qualname__} ({getattr(man, "name", man)!r}) is not a manifold the Riemannian '
+                     'optimisers step on: sttode_amd.manifolds.Oblique, PoincareBall or Euclidean')
+
+
+def _check_tensor(p, what):
+    for t, name in ((p, what), (p.grad, 'the gradient of ' + what)):
+        if t.is_sparse:
+            raise ValueError(f'{name} is sparse: the Riemannian step kernel takes dense tensors')
+        if not t.is_cuda:
+            raise ValueError(f'{name} is on {t.device}: the Riemannian step runs only on HIP tensors (no CPU fallback)')
+        if t.dtype != torch.float32:
+            raise ValueError(f'{name} is {t.dtype}: the Riemannian step kernel takes float32')
+        if not t.is_contiguous():
+            raise ValueError(f'{name} is not contiguous')
+    if p.grad.shape != p.shape or p.grad.device != p.device:
+        raise ValueError(f'the gradient of {what} does not match it in shape or device')
+
+
+class _RiemannianOptimizer(torch.optim.Optimizer):
+    """What the two rules share: the check of the manifolds, the device table of a group's tensors and the launch."""
+
+    _rule = None
+
+    def add_param_group(self, group):
+        if getattr(self, '_plans', None) is not None:
+            self._sync_steps()                                    # (the step counts go to the state before the plans that hold them go)
+        super().add_param_group(group)
+        for p in self.param_groups[-1]['params']:
+            _manifold_code(p)                                     # an unknown manifold is refused here, by name
+        self._plans = self._sig = self._plain = None
+
+    def load_state_dict(self, sd):
+        super().load_state_dict(sd)
+        self._plans = self._sig = self._plain = None
+        self._loaded()
+
+    def _loaded(self):
+        pass
+
+    def _sync_steps(self):
+        pass
+
+    def _signature(self):
+        return [tuple((p.data_ptr(), p.grad.data_ptr()) for p in group['params'] if p.grad is not None) for group in self.param_groups]
+
+    def _table(self, entries):
+        """entries: (parameter, state buffer 1 or None, state buffer 2 or None, manifold code, c, d) -> (device table, wave slots in all).
+        A wave steps one row of d > 32 elements, two rows of d <= 32, four rows of d <= 16 (csrc/manifold.hip riem_group)."""
+        words, slot0 = [], 0
+        for p, m, v, code, c, d in entries:
+            rows = (p.numel() + d - 1) // d
+            per_wave = 4 if d <= 16 else 2 if d <= 32 else 1
+            words.append((p.data_ptr(), m.data_ptr() if m is not None else 0, v.data_ptr() if v is not None else 0, p.grad.data_ptr(), d, rows,
+                          slot0, code, struct.unpack('<q', struct.pack('<d', c))[0], p.numel()))
+            slot0 += (rows + per_wave - 1) // per_wave
+        assert all(len(w) == capi.RIEMANNIAN_ITEM_WORDS for w in words)
+        return torch.tensor(words, dtype=torch.int64).to(entries[0][0].device), slot0
+
+    def _launch(self, dev, table, nrows, total, group, t, tstate):
+        b1, b2 = group.get('betas', (0.0, 0.0))
+        args = (capi.RIEMANNIAN_RULES[self._rule], table, nrows, total, float(group['lr']), float(b1), float(b2), float(group.get('eps', 0.0)),
+                float(group['weight_decay']), float(group.get('momentum', 0.0)), t, tstate)
+        if dev.index == torch.cuda.current_device():
+            capi.call('sttode_riemannian_step', *args, capi.stream_ptr())
+        else:
+            with torch.cuda.device(dev):
+                capi.call('sttode_riemannian_step', *args, capi.stream_ptr())
+
+
+class RiemannianAdam(_RiemannianOptimizer):
+    """Adam on manifolds.  Per row x of a ``ManifoldParameter`` (g: its gradient, t: the step count from 1):
+        g += weight_decay x;  r = egrad2rgrad(x, g);  m = beta1 m + (1 - beta1) r;  v = beta2 v + (1 - beta2) inner_x(r, r)
+        y = retr(x, -lr (m / (1 - beta1^t)) / (sqrt(v / (1 - beta2^t)) + eps));  m = ptransp(x, y, m);  x = y
+    with ONE second moment per row (``exp_avg_sq`` has shape ``x.shape[:-1] + (1,)``).  State keys: ``step``, ``exp_avg``, ``exp_avg_sq``.
+    Every manifold parameter of a group is stepped by one launch; plain parameters (and ManifoldParameters on ``manifolds.Euclidean``)
+    take ``sttode_amd.optim.Adam``'s own one-launch step and come out bitwise as that class gives them.  A manifold other than Oblique /
+    PoincareBall / Euclidean raises ValueError at construction; non-fp32, non-contiguous, sparse-gradient or CPU tensors raise ValueError
+    at the first step (no silent slow path).  No ``amsgrad``, ``max_grad_norm`` or ``skip_nonfinite``.
+
+    A step makes no host round trip.  Captured into a HIP graph (``torch.cuda.graph``), the manifold parameters' step count lives on the
+    device and a one-thread launch in front of the step advances it, so replays advance the bias corrections as eager steps do; after a
+    capture, the next eager step reads the count back (one synchronisation).  Plain parameters' count is a host argument of
+    ``optim.Adam``'s launch: capture a step only for groups of manifold parameters."""
+
+    _rule = 'adam'
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
+        if not 0.0 <= lr < math.inf:
+            raise ValueError(f'Invalid learning rate: {lr}')
+        if not 0.0 <= eps < math.inf:
+            raise ValueError(f'Invalid epsilon value: {eps}')
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f'Invalid betas: {betas}')
+        if not 0.0 <= weight_decay < math.inf:
+            raise ValueError(f'Invalid weight_decay value: {weight_decay}')
+        self._t, self._tstate, self._captured = {}, {}, False
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+
+    def _loaded(self):
+        self._t, self._tstate, self._captured = {}, {}, False
+
+    def _build(self):
+        plans, plain_groups = [], []
+        for gi, group in enumerate(self.param_groups):
+            entries, steps = [], set()
+            plain = [p for p in group['params'] if _manifold_code(p) is None]
+            if plain:
+                plain_groups.append((group, plain))
+            for p in group['params']:
+                if p.grad is None:
+                    continue
+                _check_tensor(p, 'a parameter')
+                mc = _manifold_code(p)
+                if mc is None or not p.numel():
+                    continue
+                if p.dim() == 0:
+                    raise ValueError('a ManifoldParameter needs a last dimension: its rows are the points of the manifold')
+                st = self.state[p]
+                if len(st) == 0:
+                    st['step'] = torch.tensor(0.0, dtype=torch.float32)
+                    st['exp_avg'] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                    st['exp_avg_sq'] = torch.zeros(p.shape[:-1] + (1,), dtype=torch.float32, device=p.device)
+                for k in ('exp_avg', 'exp_avg_sq'):
+                    if not (st[k].is_cuda and st[k].dtype == torch.float32 and st[k].is_contiguous()):
+                        raise ValueError(f'the state buffer {k} of a parameter is not a contiguous float32 HIP tensor')
+                steps.add(int(st['step']))
+                entries.append((p, st['exp_avg'], st['exp_avg_sq'], mc[0], mc[1], p.shape[-1]))
+            if not entries:
+                continue
+            if len(steps) != 1 or len({e[0].device for e in entries}) != 1:
+                raise ValueError('the manifold parameters of a param group must share one step count and one device')
+            self._t.setdefault(gi, steps.pop())
+            dev = entries[0][0].device
+            if gi not in self._tstate or self._tstate[gi].device != dev:
+                self._tstate[gi] = torch.full((1,), float(self._t[gi]), dtype=torch.float64, device=dev)
+            table, total = self._table(entries)
+            plans.append((gi, group, [e[0] for e in entries], table, len(entries), total, dev))
+        if self._plain is None and plain_groups:
+            # the plain parameters' step IS optim.Adam's: one instance over the same state dict, its groups following this class's groups
+            self._plain = Adam([dict(params=ps, lr=g['lr'], betas=g['betas'], eps=g['eps'], weight_decay=g['weight_decay']) for g, ps in plain_groups])
+            self._plain.state = self.state
+            self._plain_of = [g for g, _ in plain_groups]
+        return plans
+
+    def _sync_steps(self):
+        if self._captured:                                        # replays advanced the device counts behind the host's back
+            for gi, ts in self._tstate.items():
+                self._t[gi] = int(ts.item())
+        for gi, group, ps, *_ in (self._plans or ()):
+            t = float(self._t.get(gi, 0))
+            for p in ps:
+                self.state[p]['step'] = torch.tensor(t, dtype=torch.float32)
+        if self._plain is not None:
+            self._plain._sync_steps()
+
+    def state_dict(self):
+        self._sync_steps()
+        return super().state_dict()
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        sig = self._signature()
+        if self._plans is None or sig != self._sig:
+            self._sync_steps()
+            self._plans, self._sig = self._build(), sig
+        if self._plain is not None:
+            for pg, g in zip(self._plain.param_groups, self._plain_of):
+                pg['lr'], pg['betas'], pg['eps'], pg['weight_decay'] = g['lr'], g['betas'], g['eps'], g['weight_decay']
+            if any(p.grad is not None for pg in self._plain.param_groups for p in pg['params']):
+                self._plain.step()
+        capturing = bool(self._plans) and torch.cuda.is_current_stream_capturing()
+        if self._captured and not capturing:
+            for gi, ts in self._tstate.items():
+                self._t[gi] = int(ts.item())
+        for gi, group, ps, table, nrows, total, dev in self._plans:
+            if capturing:
+                self._captured, t = True, 0
+            else:
+                t = self._t[gi] = self._t[gi] + 1
+            self._launch(dev, table, nrows, total, group, t, self._tstate[gi])
+        return loss
+
+
+class RiemannianSGD(_RiemannianOptimizer):
+    """SGD with momentum on manifolds.  Per row x of a ``ManifoldParameter`` (g: its gradient):
+        g += weight_decay x;  r = egrad2rgrad(x, g);  buf = momentum buf + r (buf starts at zero; momentum 0: buf = r, not kept)
+        y = retr(x, -lr buf);  buf = ptransp(x, y, buf);  x = y
+    State key: ``momentum_buffer``.  Plain parameters go through the same launch with the Euclidean code, where the rule is elementwise and
+    is ``torch.optim.SGD``'s with ``dampening=0, nesterov=False``.  One launch per group, no host round trip, capturable into a HIP graph.
+    Manifolds and tensors are refused as by ``RiemannianAdam``."""
+
+    _rule = 'sgd'
+
+    def __init__(self, params, lr, momentum=0, weight_decay=0):
+        if not 0.0 <= lr < math.inf:
+            raise ValueError(f'Invalid learning rate: {lr}')
+        if not 0.0 <= momentum < math.inf:
+            raise ValueError(f'Invalid momentum value: {momentum}')
+        if not 0.0 <= weight_decay < math.inf:
+            raise ValueError(f'Invalid weight_decay value: {weight_decay}')
+        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay))
+
+    def _build(self):
+        plans = []
+        for gi, group in enumerate(self.param_groups):
+            entries = []
+            for p in group['params']:
+                if p.grad is None:
+                    continue
+                _check_tensor(p, 'a parameter')
+                mc = _manifold_code(p)
+                if mc is not None and p.dim() == 0:
+                    raise ValueError('a ManifoldParameter needs a last dimension: its rows are the points of the manifold')
+                buf = None
+                if group['momentum'] != 0:
+                    st = self.state[p]
+                    if 'momentum_buffer' not in st:
+                        st['momentum_buffer'] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                    buf = st['momentum_buffer']
+                    if not (buf.is_cuda and buf.dtype == torch.float32 and buf.is_contiguous()):
+                        raise ValueError('the momentum_buffer of a parameter is not a contiguous float32 HIP tensor')
+                if mc is None:
+                    entries.append((p, buf, None, capi.MANIFOLDS['euclidean'], 1.0, _PLAIN_ROW))
+                else:
+                    entries.append((p, buf, None, mc[0], mc[1], p.shape[-1]))
+            entries = [e for e in entries if e[0].numel()]
+            if not entries:
+                continue
+            if len({e[0].device for e in entries}) != 1:
+                raise ValueError('the parameters of a param group must be on one device')
+            table, total = self._table(entries)
+            plans.append((gi, group, [e[0] for e in entries], table, len(entries), total, entries[0][0].device))
+        return plans
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        sig = (self._signature(), [g['momentum'] != 0 for g in self.param_groups])
+        if self._plans is None or sig != self._sig:
+            self._plans, self._sig = self._build(), sig
+        for gi, group, ps, table, nrows, total, dev in self._plans:
+            self._launch(dev, table, nrows, total, group, 0, None)
+        return loss
