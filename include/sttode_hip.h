@@ -510,7 +510,8 @@ int sttode_ode_stage_bwd(const void* jobs, int count, void* stream);
  * agent (sample 0: decoded from the posterior draw, enters the prediction / recover terms; samples 1..K: the prior draws, best-of-K):
  * pred [n,K1,D], rec [n,K1,Dp], fut [n,D], past [n,Dp], qzp [n,2*zd] -> out[0..4] = (mse, recover, kl, diverse as the three entry
  * points above compute them, then their sum = total_loss), dpred [n,K1,D], drec [n,K1,Dp] (zero rows for samples 1..K), dqzp [n,2*zd].  Two launches.
- * scratch >= 3 n + max(S, 1) floats. */
+ * scratch_floats >= 3 n + S with a scene CSR, 4 n without one (3 n + max(S, n) floats cover both; refused otherwise): [3][n] per-agent
+ * partial sums, then one KL value per scene, or without a CSR one KL row sum per agent. */
 int sttode_loss_objective(const float* pred, const float* rec, const float* fut, const float* past, const float* qzp,
                           const int* scene_ptr, const int* agent_scene, int S, int n, int K1, int D, int Dp, int zd, float scale_mse,
                           float scale_rec, float kl_denom, float min_clip, float* out, float* dpred, float* drec, float* dqzp,
@@ -519,7 +520,7 @@ int sttode_loss_objective(const float* pred, const float* rec, const float* fut,
  * mse and recover terms, model/STTODE.py:553-560) and the best of samples 1..K (loss_diverse takes the min over K, :390-395: torch's min
  * passes its gradient to the selected sample alone) receive a gradient; the decoder treats columns independently, so the backward pass of
  * every other column is exactly zero.  -> dpred2 [n,2,D], drec2 [n,2,Dp] (row 1 zero), best [n] (1..K: which sample row 1 is), out / dqzp
- * as above.  The reference's autograd multiplies through the zero rows; a backward pass over 2 n instead of K1 n columns is the same
+ * and scratch (3 n + max(S, n) floats) as above.  The reference's autograd multiplies through the zero rows; a backward pass over 2 n instead of K1 n columns is the same
  * gradient (tests/test_gpu_parity.py::test_training_step_vs_reference_*). */
 int sttode_loss_objective_live(const float* pred, const float* rec, const float* fut, const float* past, const float* qzp,
                                const int* scene_ptr, const int* agent_scene, int S, int n, int K1, int D, int Dp, int zd, float scale_mse,

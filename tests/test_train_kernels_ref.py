@@ -1,4 +1,4 @@
-"""The float64 references of tests/train_ref.py (the yardsticks of tests/test_train_kernels_gpu.py) pinned against torch's own modules in
+"""The float64 references of tests/train_ref.py (the yardsticks of tests/test_train_kernels_gpu.py and test_train_loss_kernels_gpu.py) pinned against torch's own modules in
 float64 and against hand-worked element-wise cases.  No GPU needed."""
 import numpy as np
 import pytest
@@ -197,3 +197,162 @@ def test_f64_yardstick_rule():
         R.assert_f64_close(f64 + np.array([1.2e-5, 0.0, 0.0]), f64, f32)
     with pytest.raises(AssertionError):
         R.assert_f64_close(np.array([np.nan, 1e-3, 0.0]), f64, f32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# the loss, attention-backward and sampler references of tests/test_train_loss_kernels_gpu.py
+# ---------------------------------------------------------------------------------------------------------------------------------------
+def _objective_inputs(seed, n, K1, D, Dp, zd, kl_scale):
+    g = torch.Generator().manual_seed(seed)
+    r = lambda *s: torch.randn(*s, generator=g, dtype=D64)
+    return r(n, K1, D), r(n, K1, Dp), r(n, D), r(n, Dp), kl_scale * r(n, 2 * zd)
+
+
+def test_kl_rows_is_torch_kl_divergence():
+    """utils/dist.py:26-29 against torch.distributions: the only difference is the reference's 1e-8 on p.sigma (1e-8 relative)."""
+    from torch.distributions import Normal, kl_divergence
+    torch.manual_seed(7)
+    n, zd = 6, 16
+    qzp = 0.7 * torch.randn(n, 2 * zd, dtype=D64)
+    mu, lv = qzp[:, :zd], qzp[:, zd:]
+    want = kl_divergence(Normal(mu, torch.exp(0.5 * lv)), Normal(torch.zeros_like(mu), torch.ones_like(mu))).sum(1)
+    torch.testing.assert_close(R.kl_rows(qzp), want, rtol=1e-7, atol=1e-9)
+    # the stage-2 form with a general prior, summed per agent
+    K, nz = 3, 5
+    m, l, pm, pl = (0.8 * torch.randn(n * K, nz, dtype=D64) for _ in range(4))
+    want = kl_divergence(Normal(m, torch.exp(0.5 * l)), Normal(pm, torch.exp(0.5 * pl))).reshape(n, -1).sum(1)
+    motion = torch.randn(n, K, 4, dtype=D64)
+    got = R.sampler_loss(m, l, pm, pl, motion, 2.0, torch.ones(n, dtype=D64), torch.ones(n, dtype=D64))
+    torch.testing.assert_close(got['kld'], want, rtol=1e-7, atol=1e-9)
+    got0 = R.sampler_loss(m, l, None, None, motion, 2.0, torch.ones(n, dtype=D64), torch.ones(n, dtype=D64))
+    want0 = kl_divergence(Normal(m, torch.exp(0.5 * l)), Normal(torch.zeros_like(m), torch.ones_like(m))).reshape(n, -1).sum(1)
+    torch.testing.assert_close(got0['kld'], want0, rtol=1e-7, atol=1e-9)
+
+
+@pytest.mark.parametrize('csr', [None, (0, 2, 3, 7)])
+@pytest.mark.parametrize('kl_scale', [0.1, 1.2])
+def test_objective_values_and_gradients_against_closed_forms_and_a_finite_difference(csr, kl_scale):
+    """The autograd gradients of R.objective against the hand-derived ones (NumPy, no autograd): 2 scale (p - t) on sample 0, 2 w (p - t) on
+    the first-minimum sample, (mu, (sigma^2 - 1) / 2) / denom on the live KL rows and 0 on the clamped ones; and the directional derivative
+    of `total` against a central difference."""
+    n, K1, D, Dp, zd = 7, 5, 6, 4, 8
+    pred, rec, fut, past, qzp = _objective_inputs(21, n, K1, D, Dp, zd, kl_scale)
+    sm, sr, min_clip = 1 / 3.0, 1 / 2.0, 2.0
+    o = R.objective(pred, rec, fut, past, qzp, csr, K1, sm, sr, float(n), min_clip)
+    P, F_, Q = pred.numpy(), fut.numpy(), qzp.numpy()
+    ptr = np.array(csr if csr is not None else (0, n))
+    ags = R.scene_of(ptr, n)
+    cnt = np.diff(ptr)[ags].astype(np.float64)
+    d2 = ((F_[:, None] - P[:, 1:]) ** 2).sum(-1)
+    best = np.argmin(d2, 1)
+    assert np.array_equal(o['best'].numpy(), best + 1)
+    np.testing.assert_allclose(o['mse'].item(), ((P[:, 0] - F_) ** 2).sum() * sm, rtol=1e-13)
+    np.testing.assert_allclose(o['rec'].item(), ((rec.numpy()[:, 0] - past.numpy()) ** 2).sum() * sr, rtol=1e-13)
+    np.testing.assert_allclose(o['diverse'].item(), (d2.min(1) / cnt).sum(), rtol=1e-13)
+    mu, lv = Q[:, :zd], Q[:, zd:]
+    klr = (0.5 * (mu ** 2 + np.exp(lv)) - 0.5 - 0.5 * lv).sum(1)
+    kls = np.array([klr[a:b].sum() / (b - a) for a, b in zip(ptr[:-1], ptr[1:])])
+    assert ((kls < 0.9 * min_clip) | (kls > 1.1 * min_clip)).all() and (kls > min_clip).all() == (kl_scale > 0.5)
+    np.testing.assert_allclose(o['kl'].item(), np.maximum(kls, min_clip).sum(), rtol=1e-7, atol=1e-7)       # (the 1e-8 on p.sigma: 1e-8 per term)
+    np.testing.assert_allclose(R.scene_kl(qzp, csr, float(n)).numpy(), kls, rtol=1e-7, atol=1e-7)
+    np.testing.assert_allclose(o['total'].item(), o['mse'].item() + o['rec'].item() + o['kl'].item() + o['diverse'].item(), rtol=1e-14)
+    dpred = np.zeros_like(P)
+    dpred[:, 0] = 2 * sm * (P[:, 0] - F_)
+    dpred[np.arange(n), best + 1] = 2 * (P[np.arange(n), best + 1] - F_) / cnt[:, None]
+    np.testing.assert_allclose(o['dpred'].numpy(), dpred, rtol=1e-13, atol=1e-15)
+    drec = np.zeros_like(rec.numpy())
+    drec[:, 0] = 2 * sr * (rec.numpy()[:, 0] - past.numpy())
+    np.testing.assert_allclose(o['drec'].numpy(), drec, rtol=1e-13, atol=1e-15)
+    live = (kls > min_clip)[ags][:, None]
+    dq = np.concatenate([mu, 0.5 * (np.exp(lv) - 1)], 1) / cnt[:, None] * live
+    np.testing.assert_allclose(o['dqzp'].numpy(), dq, rtol=1e-7, atol=1e-7)
+    k = R.kl_term(qzp, csr, float(n), min_clip)
+    assert torch.equal(k['dqzp'], o['dqzp']) and k['kl'].item() == o['kl'].item()
+    # central difference of total along a random direction of all three inputs
+    g = torch.Generator().manual_seed(22)
+    dP, dR, dQ = (torch.randn(v.shape, generator=g, dtype=D64) for v in (pred, rec, qzp))
+    h = 1e-6
+    tot = lambda s: R.objective(pred + s * dP, rec + s * dR, fut, past, qzp + s * dQ, csr, K1, sm, sr, float(n), min_clip)['total'].item()
+    fd = (tot(h) - tot(-h)) / (2 * h)
+    an = ((o['dpred'] * dP).sum() + (o['drec'] * dR).sum() + (o['dqzp'] * dQ).sum()).item()
+    np.testing.assert_allclose(an, fd, rtol=1e-7)
+
+
+def test_objective_best_is_the_first_minimum_on_exact_ties():
+    n, K1, D = 4, 9, 6
+    pred, rec, fut, past, qzp = _objective_inputs(23, n, K1, D, 4, 8, 0.3)
+    pred[0, 6] = fut[0] + 1e-3
+    pred[0, 2] = pred[0, 6]                                          # the duplicate at the lower index
+    pred[1, 3] = fut[1] - 1e-3
+    pred[1, 8] = pred[1, 3]                                          # ... at the higher index
+    for dt in (D64, torch.float32):
+        o = R.objective(*(v.to(dt) for v in (pred, rec, fut, past, qzp)), None, K1, 1.0, 1.0, float(n), 2.0)
+        d2 = ((fut[:, None].to(dt) - pred[:, 1:].to(dt)) ** 2).sum(-1).numpy()
+        assert np.array_equal(o['best'].numpy(), np.argmin(d2, 1) + 1)
+        assert o['best'][0] == 2 and o['best'][1] == 3
+        assert (o['dpred'][0, 6] == 0).all() and (o['dpred'][0, 2] != 0).all() and (o['dpred'][1, 8] == 0).all()
+        assert o['dpred'].dtype == dt
+
+
+def test_sqerr_reference():
+    p, t = torch.tensor([1.0, 2.0, 4.0], dtype=D64), torch.tensor([0.0, 4.0, 4.0], dtype=D64)
+    o = R.sqerr(p, t, 0.5)
+    assert o['value'].item() == 2.5 and torch.equal(o['dpred'], torch.tensor([1.0, -2.0, 0.0], dtype=D64))
+
+
+def test_attention_reference_edges():
+    """L = 1: the softmax is over one key, so dq = dk = 0 and dv = dO.  A pair beyond the clamp (k_i = q_i: dot 1; k_i = -q_j: dot -1)
+    passes nothing to q and k: moving q_j along a tangent direction changes the output through its other pairs only."""
+    torch.manual_seed(8)
+    hd, DM = 8, 64
+    qkv, dO = torch.randn(3, 3 * DM, dtype=D64), torch.randn(3, DM, dtype=D64)
+    r = R.geodesic_self_attention(qkv, dO, 1, 3, hd)
+    assert torch.equal(r['dqkv'][:, :2 * DM], torch.zeros(3, 2 * DM, dtype=D64))
+    torch.testing.assert_close(r['dqkv'][:, 2 * DM:], dO, rtol=1e-14, atol=0)
+    # L = 2, one slot; every pair of head 0 beyond the clamp: k_0 = q_0, k_1 = q_1 (diagonal), and q_1 = -q_0 (off-diagonal dots -1)
+    qkv, dO = torch.randn(2, 3 * DM, dtype=D64), torch.randn(2, DM, dtype=D64)
+    qkv[1, :hd] = -qkv[0, :hd]
+    qkv[:, DM:DM + hd] = qkv[:, :hd]
+    r = R.geodesic_self_attention(qkv, dO, 2, 1, hd)
+    assert (r['dots'][0, 0].abs() > 1 - 1e-9).all()
+    assert torch.equal(r['dqkv'][:, :hd], torch.zeros(2, hd, dtype=D64)) and torch.equal(r['dqkv'][:, DM:DM + hd], torch.zeros(2, hd, dtype=D64))
+    assert (r['dqkv'][:, hd:DM] != 0).all() and (r['dqkv'][:, 2 * DM:2 * DM + hd] != 0).all()      # the other heads, and head 0's dv
+
+
+def test_sampler_references_on_worked_cases():
+    A = torch.tensor([[2.0, 0.0], [-1.0, 1e-4], [3.0, 1.0], [0.5, -2.0]], dtype=D64)         # n = 2, K = 2, nz = 2
+    b = torch.arange(8, dtype=D64).reshape(4, 2)
+    assert torch.equal(R.sampler_latent(A, b, None, 0, 2)['z'], b)
+    e1 = torch.tensor([10.0, 100.0], dtype=D64)
+    assert torch.equal(R.sampler_latent(A, b, e1, 1, 2)['z'], A * e1 + b)
+    e2 = torch.tensor([[10.0, 100.0], [1.0, 2.0]], dtype=D64)
+    z = R.sampler_latent(A, b, e2, 2, 2)
+    assert torch.equal(z['z'], torch.tensor([[20.0, 1.0], [-8.0, 3.01], [7.0, 7.0], [6.5, 3.0]], dtype=D64))
+    np.testing.assert_allclose(z['logvar'].numpy(), np.log(A.numpy() ** 2 + 1e-8), rtol=1e-15)
+    assert z['logvar'][0, 1].item() == np.log(1e-8)
+
+
+def test_sampler_diversity_is_the_double_loop_over_pairs_and_coincident_samples_pass_no_gradient():
+    torch.manual_seed(9)
+    n, K, D, nz, scale = 3, 5, 6, 4, 0.5
+    motion = 0.3 * torch.randn(n, K, D, dtype=D64)
+    motion[1, 3] = motion[1, 0]                                      # two samples identical bit for bit
+    mu, lv = torch.randn(n * K, nz, dtype=D64), torch.randn(n * K, nz, dtype=D64)
+    g_kld, g_div = torch.randn(n, dtype=D64), torch.randn(n, dtype=D64)
+    o = R.sampler_loss(mu, lv, None, None, motion, scale, g_kld, g_div)
+    m = motion.numpy()
+    div, dm = np.zeros(n), np.zeros_like(m)
+    npairs = K * (K - 1) // 2
+    for a in range(n):
+        for i in range(K):
+            for j in range(i + 1, K):
+                s = ((m[a, i] - m[a, j]) ** 2).sum()
+                e = np.exp(-s / scale)
+                div[a] += e / npairs
+                dm[a, i] += g_div[a].item() * e * (-2 / scale) * (m[a, i] - m[a, j]) / npairs
+                dm[a, j] -= g_div[a].item() * e * (-2 / scale) * (m[a, i] - m[a, j]) / npairs
+    np.testing.assert_allclose(o['div'].numpy(), div, rtol=1e-13)
+    np.testing.assert_allclose(o['dmotion'].numpy(), dm, rtol=1e-12, atol=1e-15)
+    assert np.isfinite(o['dmotion'].numpy()).all()
+    np.testing.assert_allclose(o['dmu'].numpy(), (g_kld.repeat_interleave(K)[:, None] * mu).numpy(), rtol=1e-7)
+    np.testing.assert_allclose(o['dlogvar'].numpy(), (g_kld.repeat_interleave(K)[:, None] * 0.5 * (lv.exp() - 1)).numpy(), rtol=1e-7, atol=1e-7)

@@ -1,4 +1,5 @@
-"""Plain restatements of the training-step kernels of csrc/train*.hip, for tests/test_train_kernels_*.py.
+"""Plain restatements of the training-step kernels of csrc/train*.hip and of the stage-2 sampler kernels of csrc/sampler.hip, for
+tests/test_train_kernels_*.py and tests/test_train_loss_kernels_gpu.py.
 
 Each reference runs in the dtype of its inputs: float64 is the rounding-free yardstick, float32 is torch's own fp32 evaluation of the same
 operation (how far a correct fp32 implementation may sit from float64).  Layouts are the kernels' (training.py block_fwd / block_bwd).
@@ -173,6 +174,123 @@ def ewise(op, p, count, i0, f0):
     else:
         raise ValueError(op)
     return out
+
+
+# ---- the objective of forward() (sttode_loss_objective and the three stand-alone loss entry points) ------------------------------------
+def kl_rows(qzp):
+    """Per row of qzp [n, 2 zd] = (mu | logvar): sum over zd of KL(N(mu, sigma) || N(0, 1)) in the two-distribution form of
+    utils/dist.py:26-29 with p.sigma = 1 (term = x / (p.sigma + 1e-8))."""
+    zd = qzp.shape[1] // 2
+    mu, lv = qzp[:, :zd], qzp[:, zd:]
+    ps = 1.0 + 1e-8
+    t1, t2 = mu / ps, torch.exp(0.5 * lv) / ps
+    return (0.5 * (t1 * t1 + t2 * t2) - 0.5 - torch.log(t2)).sum(1)
+
+
+def scene_of(scene_ptr, n):
+    """agent -> scene index of a CSR [S + 1] (the kernels' agent_scene)."""
+    ptr = np.asarray(scene_ptr, np.int64)
+    assert ptr[0] == 0 and ptr[-1] == n and (np.diff(ptr) > 0).all()
+    return np.repeat(np.arange(len(ptr) - 1), np.diff(ptr))
+
+
+def scene_kl(qzp, scene_ptr, kl_denom):
+    """The UNCLAMPED KL value of every scene (model/STTODE.py:378-382 before its clamp_min): the sum over all rows / kl_denom
+    without a CSR, else per scene the sum over its rows / its agents."""
+    klr = kl_rows(qzp)
+    if scene_ptr is None:
+        return (klr.sum() / kl_denom).reshape(1)
+    ptr = [int(v) for v in scene_ptr]
+    return torch.stack([klr[a:b].sum() / (b - a) for a, b in zip(ptr[:-1], ptr[1:])])
+
+
+def objective(pred, rec, fut, past, qzp, scene_ptr, K1, scale_mse, scale_rec, kl_denom, min_clip):
+    """The four terms of model/STTODE.py:372-395 for ONE decoder pass over K1 = 1 + K samples per agent, written out, and torch autograd of
+    their sum.  pred [n, K1, D], rec [n, K1, Dp], fut [n, D], past [n, Dp], qzp [n, 2 zd]; scene_ptr None (one scene: KL sum / kl_denom,
+    best-of-K mean over the n agents) or a CSR [S + 1] (KL: sum over scenes of clamp_min(scene sum / scene agents); best-of-K: sum over
+    scenes of the per-scene means).  -> dict mse, rec, kl, diverse, total (0-d), dpred, drec, dqzp, best [n] (1..K: first minimum) and
+    d2 [n, K] (the summed squared distances the minimum is taken over)."""
+    n = pred.shape[0]
+    assert pred.shape[1] == rec.shape[1] == K1
+    P, Rc, Q = (v.detach().clone().requires_grad_(True) for v in (pred, rec, qzp))
+    mse = (fut - P[:, 0]).pow(2).sum() * scale_mse
+    recover = (past - Rc[:, 0]).pow(2).sum() * scale_rec
+    kl = scene_kl(Q, scene_ptr, kl_denom).clamp_min(min_clip).sum()
+    d2 = (fut[:, None, :] - P[:, 1:]).pow(2).sum(-1)                 # [n, K]
+    mn, idx = d2.min(dim=1)                                          # (first minimum; its gradient goes to that sample alone)
+    if scene_ptr is None:
+        diverse = mn.mean()
+    else:
+        ptr = [int(v) for v in scene_ptr]
+        diverse = sum(mn[a:b].mean() for a, b in zip(ptr[:-1], ptr[1:]))
+    total = ((mse + recover) + kl) + diverse
+    total.backward()
+    return dict(mse=mse.detach(), rec=recover.detach(), kl=kl.detach(), diverse=diverse.detach(), total=total.detach(), dpred=P.grad,
+                drec=Rc.grad, dqzp=Q.grad, best=(idx + 1).to(torch.int32), d2=d2.detach())
+
+
+def kl_term(qzp, scene_ptr, kl_denom, min_clip):
+    """sttode_loss_kl alone: the KL value of ``objective`` and its gradient."""
+    Q = qzp.detach().clone().requires_grad_(True)
+    kl = scene_kl(Q, scene_ptr, kl_denom).clamp_min(min_clip).sum()
+    kl.backward()
+    return dict(kl=kl.detach(), dqzp=Q.grad)
+
+
+def sqerr(pred, target, scale):
+    """sttode_loss_sqerr: scale * sum (pred - target)^2 and its gradient."""
+    p = pred.detach().clone().requires_grad_(True)
+    v = (target - p).pow(2).sum() * scale
+    v.backward()
+    return dict(value=v.detach(), dpred=p.grad)
+
+
+# ---- geodesic self-attention backward (sttode_mhgsa_attn_bwd) ---------------------------------------------------------------------------
+ATTN_CLAMP = 1e-4
+
+
+def geodesic_self_attention(qkv, dO, L, Nb, hd):
+    """out_i = sum_j softmax_j(-acos(clamp(k^_i . q^_j, -1 + 1e-4, 1 - 1e-4))) v_j per (slot, head), scores untransposed
+    (hyptransformerlib.py:261-265); token (l, slot) is row l Nb + slot of qkv [L Nb, 3 * 8 hd] = (q | k | v).  -> dict out [L Nb, 8 hd],
+    dqkv (autograd of <dO, out>), dots [Nb, 8, L, L] (the unclamped k^_i . q^_j)."""
+    DM = 8 * hd
+    x = qkv.detach().clone().requires_grad_(True)
+    q, k, v = (x[:, i * DM:(i + 1) * DM].view(L, Nb, 8, hd) for i in range(3))
+    qn, kn = q / q.norm(dim=-1, keepdim=True), k / k.norm(dim=-1, keepdim=True)
+    dots = torch.einsum('inhd,jnhd->nhij', kn, qn)                   # [slot, head, key row i, query column j]
+    P = torch.softmax(-torch.acos(dots.clamp(-1 + ATTN_CLAMP, 1 - ATTN_CLAMP)), dim=-1)
+    out = torch.einsum('nhij,jnhd->inhd', P, v).reshape(L * Nb, DM)
+    out.backward(dO.to(out.dtype))
+    return dict(out=out.detach(), dqkv=x.grad, dots=dots.detach())
+
+
+# ---- stage-2 sampler (csrc/sampler.hip) -------------------------------------------------------------------------------------------------
+def sampler_latent(A, b, eps, mode, K):
+    """sampler.py:47-54: z = b (mode 0) or A eps + b with eps shared [nz] (1) or per agent [n, nz] (2); logvar = log(A^2 + 1e-8).
+    A, b [n K, nz], row = agent K + k."""
+    if mode == 0:
+        z = b.clone()
+    elif mode == 1:
+        z = A * eps[None, :] + b
+    else:
+        z = A * eps.repeat_interleave(K, dim=0) + b
+    return dict(z=z, logvar=torch.log(A * A + 1e-8))
+
+
+def sampler_loss(mu, logvar, pmu, plogvar, motion, scale, g_kld, g_div):
+    """samplerloss.py:4-20 per agent: kld[a] = sum over the agent's K nz latent entries of KL(N(mu, logvar) || N(pmu, plogvar))
+    (utils/dist.py:26-29; pmu / plogvar None: the standard normal), div[a] = mean over the K (K - 1) / 2 sample pairs of
+    exp(-F.pdist(motion[a]) ** 2 / scale); motion [n, K, D].  -> kld, div [n] and autograd of <g_kld, kld> + <g_div, div>: dmu, dlogvar,
+    dmotion."""
+    n, K = motion.shape[0], motion.shape[1]
+    m, lv, mo = (v.detach().clone().requires_grad_(True) for v in (mu, logvar, motion))
+    pm = 0.0 if pmu is None else pmu
+    ps = (1.0 if plogvar is None else torch.exp(0.5 * plogvar)) + 1e-8
+    t1, t2 = (m - pm) / ps, torch.exp(0.5 * lv) / ps
+    kld = (0.5 * (t1 * t1 + t2 * t2) - 0.5 - torch.log(t2)).reshape(n, -1).sum(1)
+    div = torch.stack([(-(F.pdist(mo[a], 2) ** 2) / scale).exp().mean() for a in range(n)])
+    ((kld * g_kld).sum() + (div * g_div).sum()).backward()
+    return dict(kld=kld.detach(), div=div.detach(), dmu=m.grad, dlogvar=lv.grad, dmotion=mo.grad)
 
 
 def ulps_f32(scale, n=4):
