@@ -526,6 +526,30 @@ int sttode_loss_objective_live(const float* pred, const float* rec, const float*
                                const int* scene_ptr, const int* agent_scene, int S, int n, int K1, int D, int Dp, int zd, float scale_mse,
                                float scale_rec, float kl_denom, float min_clip, float* out, float* dpred2, float* drec2, float* dqzp,
                                int* best, float* scratch, long scratch_floats, void* stream);
+/* The same objective with the SCENE-LEVEL (joint) best-of-K term in the diverse slot (beyond the reference): the min over the
+ * K = K1 - 1 prior samples is taken outside the sum over a segment's agents, so every agent of a segment selects the same sample.
+ * Segments are runs of consecutive agents: with scene_ptr [S+1] the scenes (seg_len must be 0); with scene_ptr NULL runs of seg_len agents
+ * (seg_len >= 1 divides n; seg_len == n: one scene; NBA: the agents of one game).  J_g(k) = sum_{a in g} sum_d (fut[a,d] - pred[a,k,d])^2,
+ * k*_g = the first k in 1..K minimising J_g (ties to the lowest k), out[3] = sum_g w_g J_g(k*_g) with w_g the weight sttode_loss_objective gives
+ * an agent of g (1 / agents of the scene with a CSR, 1 / n otherwise), out[4] = ((out[0] + out[1]) + out[2]) + out[3].
+ * -> dpred2 [n,2,D] (row 1 = 2 (pred[a,k*_g] - fut[a]) w_g), drec2 [n,2,Dp] (row 1 zero), best [n] = k*_g(a) (1..K), seg_best [G] = k*_g
+ * (optional, NULL: not written; G = S or n / seg_len); out[0..2], dqzp and row 0 of both gradients are sttode_loss_objective_live's bit for
+ * bit, and with one-agent segments so is everything else.  Per-agent sums in fp32, the sum over a segment's agents in double in a fixed
+ * order: results repeat bit for bit and a segment's best / gradients depend on its own agents only.  Two launches.
+ * Refused before any launch: a null pointer (best included), K1 outside 2..65, n, D, Dp or zd <= 0, scene_ptr without S > 0 and agent_scene,
+ * no scene_ptr and kl_denom <= 0, seg_len != 0 with scene_ptr, seg_len < 1 or not a divisor of n without, scratch_floats < 3 n + S with
+ * a CSR or < 4 n without one ([3][n] per-agent slots -- the third holds a segment's value in its first agent's slot and zeros -- then the KL
+ * values, as above). */
+int sttode_loss_objective_joint(const float* pred, const float* rec, const float* fut, const float* past, const float* qzp,
+                                const int* scene_ptr, const int* agent_scene, int S, int n, int K1, int D, int Dp, int zd, float scale_mse,
+                                float scale_rec, float kl_denom, float min_clip, float* out, float* dpred2, float* drec2, float* dqzp,
+                                int* best, int seg_len, int* seg_best, float* scratch, long scratch_floats, void* stream);
+/* The joint term alone (the counterpart of sttode_loss_diverse): pred [n,K,D] (the K prior samples), target [n,D], 1 <= K <= 64, segments
+ * as above (with scene_ptr, agent_scene [n] is required: the number of scenes is agent_scene[n-1] + 1).  out[0] = the term, bit for bit
+ * out[3] of sttode_loss_objective_joint on the same samples; dpred [n,K,D] optional (zero rows but the selected one), best [n] optional
+ * (1..K).  scratch >= n floats.  Two launches. */
+int sttode_loss_diverse_joint(const float* pred, const float* target, const int* scene_ptr, const int* agent_scene, int n, int K, int D,
+                              int seg_len, float* out, float* dpred, int* best, float* scratch, void* stream);
 /* ... and the rows of the forward pass's tape for those columns: items = HOST array of `count` <= 32 records {const float* src; float* dst;
  * long src_plane; long dst_plane; int row; int outer;} (40 bytes): src is `outer` planes (src_plane floats apart) of [n K1] rows of `row`
  * floats, dst `outer` planes (dst_plane apart) of [2 n] rows; dst row 2 a + j = src row a K1 + (j ? best[a] : 0).  One launch. */

@@ -135,40 +135,38 @@ struct ObjArgs {
     // drec2 = 0), and best [n] names the second one (1..K); dpred / drec are not written.
     int* best; float* dpred2; float* drec2;
 };
-__global__ __launch_bounds__(256) void objective_kernel(ObjArgs o) {
-    __shared__ float red[256];
-    if ((int)blockIdx.x >= o.n) {     // KL block (same arithmetic as kl_kernel): a batch of scenes (one block per scene) -- or the single-scene case
-                                      // when the agents' blocks did not take the term over (o.kl_rows == 0)
-        const int b = blockIdx.x - o.n;
-        const float ps = 1.0f + 1e-8f;
-        const long r0 = o.scene_ptr ? o.scene_ptr[b] : 0, r1 = o.scene_ptr ? o.scene_ptr[b + 1] : o.n;
-        const float denom = o.scene_ptr ? (float)(r1 - r0) : o.kl_denom;
-        const int zd = o.zd;
-        float acc = 0.f;
-        for (long i = r0 * zd + threadIdx.x; i < r1 * zd; i += 256) {
-            const long r = i / zd;
-            const int d = (int)(i % zd);
-            const float mu = o.qzp[r * 2 * zd + d], lv = o.qzp[r * 2 * zd + zd + d];
-            const float t1 = mu / ps, t2 = expf(0.5f * lv) / ps;
-            acc += 0.5f * (t1 * t1 + t2 * t2) - 0.5f - logf(t2);
-        }
-        const float sm = block_sum(acc, red) / denom;
-        const bool live = sm >= o.min_clip;
-        if (threadIdx.x == 0) o.part[3 * (long)o.n + b] = live ? sm : o.min_clip;
-        for (long i = r0 * zd + threadIdx.x; i < r1 * zd; i += 256) {
-            const long r = i / zd;
-            const int d = (int)(i % zd);
-            const float mu = o.qzp[r * 2 * zd + d], lv = o.qzp[r * 2 * zd + zd + d];
-            const float t2 = expf(0.5f * lv) / ps;
-            o.dqzp[r * 2 * zd + d] = live ? (mu / (ps * ps)) / denom : 0.f;
-            o.dqzp[r * 2 * zd + zd + d] = live ? (0.5f * t2 * t2 - 0.5f) / denom : 0.f;
-        }
-        return;
+// the pieces of objective_kernel, shared with the joint form below (inlined: one arithmetic, in one place)
+// KL block b (same arithmetic as kl_kernel): a batch of scenes (one block per scene)
+static __device__ __forceinline__ void obj_kl_block(const ObjArgs& o, int b, float* red) {
+    const float ps = 1.0f + 1e-8f;
+    const long r0 = o.scene_ptr ? o.scene_ptr[b] : 0, r1 = o.scene_ptr ? o.scene_ptr[b + 1] : o.n;
+    const float denom = o.scene_ptr ? (float)(r1 - r0) : o.kl_denom;
+    const int zd = o.zd;
+    float acc = 0.f;
+    for (long i = r0 * zd + threadIdx.x; i < r1 * zd; i += 256) {
+        const long r = i / zd;
+        const int d = (int)(i % zd);
+        const float mu = o.qzp[r * 2 * zd + d], lv = o.qzp[r * 2 * zd + zd + d];
+        const float t1 = mu / ps, t2 = expf(0.5f * lv) / ps;
+        acc += 0.5f * (t1 * t1 + t2 * t2) - 0.5f - logf(t2);
     }
-    const int a = blockIdx.x, t = threadIdx.x, K1 = o.K1, D = o.D, Dp = o.Dp;
+    const float sm = block_sum(acc, red) / denom;
+    const bool live = sm >= o.min_clip;
+    if (threadIdx.x == 0) o.part[3 * (long)o.n + b] = live ? sm : o.min_clip;
+    for (long i = r0 * zd + threadIdx.x; i < r1 * zd; i += 256) {
+        const long r = i / zd;
+        const int d = (int)(i % zd);
+        const float mu = o.qzp[r * 2 * zd + d], lv = o.qzp[r * 2 * zd + zd + d];
+        const float t2 = expf(0.5f * lv) / ps;
+        o.dqzp[r * 2 * zd + d] = live ? (mu / (ps * ps)) / denom : 0.f;
+        o.dqzp[r * 2 * zd + zd + d] = live ? (0.5f * t2 * t2 - 0.5f) / denom : 0.f;
+    }
+}
+// agent a, sample 0: squared errors (-> s0, s1 in every thread) + gradients; returns the agent's first gradient row of dpred
+static __device__ __forceinline__ float* obj_sample0(const ObjArgs& o, int a, float* red, float& s0, float& s1) {
+    const int t = threadIdx.x, K1 = o.K1, D = o.D, Dp = o.Dp;
     const float* pa = o.pred + (long)a * K1 * D;
     const float* ra = o.rec + (long)a * K1 * Dp;
-    // sample 0: squared errors + gradients
     float e0 = 0.f, e1 = 0.f;
     const bool live = o.best != nullptr;
     float* dp0 = live ? o.dpred2 + (long)a * 2 * D : o.dpred + (long)a * K1 * D;
@@ -176,7 +174,38 @@ __global__ __launch_bounds__(256) void objective_kernel(ObjArgs o) {
     for (int d = t; d < D; d += 256) { const float df = pa[d] - o.fut[(long)a * D + d]; e0 += df * df; dp0[d] = 2.0f * o.scale_mse * df; }
     for (int d = t; d < Dp; d += 256) { const float df = ra[d] - o.past[(long)a * Dp + d]; e1 += df * df; dr0[d] = 2.0f * o.scale_rec * df; }
     for (int i = Dp + t; i < (live ? 2 : K1) * Dp; i += 256) dr0[i] = 0.f;
-    const float s0 = block_sum(e0, red), s1 = block_sum(e1, red);
+    s0 = block_sum(e0, red);
+    s1 = block_sum(e1, red);
+    return dp0;
+}
+// agent a's row of the KL term (arithmetic of kl_kernel), gradient as if the clamp were inactive
+static __device__ __forceinline__ void obj_kl_row(const ObjArgs& o, int a, float* red) {
+    const int t = threadIdx.x;
+    const float ps = 1.0f + 1e-8f;
+    const int zd = o.zd;
+    float acc = 0.f;
+    for (int d = t; d < zd; d += 256) {
+        const float mu = o.qzp[(long)a * 2 * zd + d], lv = o.qzp[(long)a * 2 * zd + zd + d];
+        const float t1 = mu / ps, t2 = expf(0.5f * lv) / ps;
+        acc += 0.5f * (t1 * t1 + t2 * t2) - 0.5f - logf(t2);
+        o.dqzp[(long)a * 2 * zd + d] = (mu / (ps * ps)) / o.kl_denom;
+        o.dqzp[(long)a * 2 * zd + zd + d] = (0.5f * t2 * t2 - 0.5f) / o.kl_denom;
+    }
+    const float sk_ = block_sum(acc, red);
+    if (t == 0) o.part[3 * (long)o.n + a] = sk_;
+}
+__global__ __launch_bounds__(256) void objective_kernel(ObjArgs o) {
+    __shared__ float red[256];
+    if ((int)blockIdx.x >= o.n) {     // KL block: a batch of scenes (one block per scene) -- or the single-scene case when the agents' blocks
+                                      // did not take the term over (o.kl_rows == 0)
+        obj_kl_block(o, blockIdx.x - o.n, red);
+        return;
+    }
+    const int a = blockIdx.x, t = threadIdx.x, K1 = o.K1, D = o.D;
+    const float* pa = o.pred + (long)a * K1 * D;
+    const bool live = o.best != nullptr;
+    float s0, s1;
+    float* dp0 = obj_sample0(o, a, red, s0, s1);
     // samples 1..K: first minimum of the summed squared error (torch.min), weight 1 / (agents of the scene)
     float wgt = 1.0f / (float)o.n;
     if (o.scene_ptr) { const int sc = o.agent_scene[a]; wgt = 1.0f / (float)(o.scene_ptr[sc + 1] - o.scene_ptr[sc]); }
@@ -210,20 +239,7 @@ __global__ __launch_bounds__(256) void objective_kernel(ObjArgs o) {
         }
     }
     if (t == 0) { o.part[a] = s0; o.part[o.n + a] = s1; o.part[2 * (long)o.n + a] = sv[0] * wgt; }
-    if (o.kl_rows) {                  // this agent's row of the KL term (arithmetic of kl_kernel), gradient as if the clamp were inactive
-        const float ps = 1.0f + 1e-8f;
-        const int zd = o.zd;
-        float acc = 0.f;
-        for (int d = t; d < zd; d += 256) {
-            const float mu = o.qzp[(long)a * 2 * zd + d], lv = o.qzp[(long)a * 2 * zd + zd + d];
-            const float t1 = mu / ps, t2 = expf(0.5f * lv) / ps;
-            acc += 0.5f * (t1 * t1 + t2 * t2) - 0.5f - logf(t2);
-            o.dqzp[(long)a * 2 * zd + d] = (mu / (ps * ps)) / o.kl_denom;
-            o.dqzp[(long)a * 2 * zd + zd + d] = (0.5f * t2 * t2 - 0.5f) / o.kl_denom;
-        }
-        const float sk_ = block_sum(acc, red);
-        if (t == 0) o.part[3 * (long)o.n + a] = sk_;
-    }
+    if (o.kl_rows) obj_kl_row(o, a, red);
 }
 __global__ __launch_bounds__(256) void objective_sum_kernel(const float* part, int n, int nb, float scale_mse, float scale_rec, float* out,
                                                            int kl_rows, float kl_denom, float min_clip, float* dqzp, int zd) {
@@ -283,6 +299,147 @@ extern "C" int sttode_loss_objective_live(const float* pred, const float* rec, c
     STT_REQUIRE(best, "sttode_loss_objective_live: null pointer");
     return loss_objective_impl(pred, rec, fut, past, qzp, scene_ptr, agent_scene, S, n, K1, D, Dp, zd, scale_mse, scale_rec, kl_denom, min_clip, out,
                                dpred2, drec2, dqzp, best, scratch, scratch_floats, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The scene-level (joint) best-of-K term: the min over the K prior samples is taken OUTSIDE the sum over a segment's agents
+// (a scene of a CSR batch, all agents of one scene, one NBA game) -- every agent of a segment selects the same sample k*_g.
+//   J_g(k) = sum_{a in g} sq_a(k),   k*_g = first k minimising J_g,   term = sum_g w_g J_g(k*_g),   w_g = the marginal form's agent weight
+// One workgroup per segment, no block depends on another: lane <-> sample (K <= 64 = one wave), the four waves split the segment's agents
+// (wave w: agents r0 + w, r0 + w + 4, ...); sq_a(k) in fp32 in the marginal kernel's order, their sum over the wave's agents in double in
+// agent order, the four wave sums added in wave order, then the marginal kernel's first-minimum butterfly on the doubles.  A segment's
+// outputs depend on its own agents only -- not on the other segments, not on where it stands in the batch.
+// part[r0] = the segment's weighted value, part[r0 + 1 .. r1) = 0: the fixed-order sums over n slots (objective_sum_kernel, sum_kernel)
+// serve unchanged, and one-agent segments reproduce the marginal term bit for bit.
+// pred: agent a's K prior columns are rows a KS + k0 .. a KS + k0 + K - 1 of D floats.  Gradients: row1 != NULL -> [n][2][D], row 1 (the live
+// form); dense != NULL -> [n][K][D], zero rows but the selected one.  best / seg_best: 1..K.
+// ---------------------------------------------------------------------------------------------------
+static __device__ __forceinline__ void joint_segment(const float* pred, const float* fut, int KS, int k0, int K, int D, int r0, int r1,
+                                                     float wgt, float* part, float* row1, float* dense, int* best, int* seg_best) {
+    __shared__ double sj[4][64];
+    __shared__ int sk;
+    __shared__ float sval;
+    const int t = threadIdx.x, w = t >> 6, lane = t & 63;
+    double acc = 0.0;
+    if (lane < K)
+        for (int a = r0 + w; a < r1; a += 8) {      // two of the wave's agents per pass, their loads in flight together (one scene: the
+                                                    // segment's n agents wait on this one workgroup); each sum and the order of acc as one by one
+            const int a2 = a + 4 < r1 ? a + 4 : a;
+            const float* pa = pred + ((long)a * KS + k0 + lane) * D;
+            const float* pb = pred + ((long)a2 * KS + k0 + lane) * D;
+            const float* fa = fut + (long)a * D;
+            const float* fb = fut + (long)a2 * D;
+            float sq = 0.f, sq2 = 0.f;
+#pragma unroll 4
+            for (int d = 0; d < D; ++d) {
+                const float df = fa[d] - pa[d], df2 = fb[d] - pb[d];
+                sq += df * df;
+                sq2 += df2 * df2;
+            }
+            acc += (double)sq;
+            if (a2 != a) acc += (double)sq2;
+        }
+    sj[w][lane] = acc;
+    __syncthreads();
+    if (w == 0) {
+        double bs = lane < K ? ((sj[0][lane] + sj[1][lane]) + sj[2][lane]) + sj[3][lane] : __builtin_huge_val();
+        int bk = lane;
+#pragma unroll
+        for (int sh = 32; sh > 0; sh >>= 1) {
+            const double os = __shfl_xor(bs, sh, 64);
+            const int ok = __shfl_xor(bk, sh, 64);
+            if (os < bs || (os == bs && ok < bk)) { bs = os; bk = ok; }
+        }
+        if (lane == 0) { sk = bk; sval = (float)(bs * (double)wgt); }   // (lane 0 always ends on a lane < K, whatever the values: see DESIGN.md 4v)
+    }
+    __syncthreads();
+    const int bk = sk, cnt = r1 - r0;
+    if (row1)
+        for (long i = t; i < (long)cnt * D; i += 256) {
+            const long a = r0 + i / D;
+            const int d = (int)(i % D);
+            row1[(a * 2 + 1) * D + d] = 2.0f * (pred[(a * KS + k0 + bk) * D + d] - fut[a * D + d]) * wgt;
+        }
+    if (dense)
+        for (long i = t; i < (long)cnt * K * D; i += 256) {
+            const long a = r0 + i / ((long)K * D);
+            const int k = (int)(i / D % K), d = (int)(i % D);
+            dense[(long)r0 * K * D + i] = k == bk ? 2.0f * (pred[(a * KS + k0 + k) * D + d] - fut[a * D + d]) * wgt : 0.f;
+        }
+    for (int i = t; i < cnt; i += 256) {
+        if (best) best[r0 + i] = bk + 1;
+        part[r0 + i] = i == 0 ? sval : 0.f;
+    }
+    if (seg_best && t == 0) *seg_best = bk + 1;
+}
+// The objective with the joint term, live form: blocks [0, n) the agents' sample-0 work (and their KL rows), [n, n + nb) the KL blocks of a
+// batch of scenes -- both exactly objective_kernel's -- and [n + nb, n + nb + G) one workgroup per segment.
+__global__ __launch_bounds__(256) void objective_joint_kernel(ObjArgs o, int seg_len, int* seg_best) {
+    __shared__ float red[256];
+    const int b = blockIdx.x;
+    if (b >= o.n + o.nb) {
+        const int g = b - o.n - o.nb;
+        const int r0 = o.scene_ptr ? o.scene_ptr[g] : g * seg_len, r1 = o.scene_ptr ? o.scene_ptr[g + 1] : r0 + seg_len;
+        const float wgt = 1.0f / (float)(o.scene_ptr ? r1 - r0 : o.n);
+        joint_segment(o.pred, o.fut, o.K1, 1, o.K1 - 1, o.D, r0, r1, wgt, o.part + 2 * (long)o.n, o.dpred2, nullptr, o.best,
+                      seg_best ? seg_best + g : nullptr);
+        return;
+    }
+    if (b >= o.n) {
+        obj_kl_block(o, b - o.n, red);
+        return;
+    }
+    float s0, s1;
+    obj_sample0(o, b, red, s0, s1);
+    if (threadIdx.x == 0) { o.part[b] = s0; o.part[o.n + b] = s1; }
+    if (o.kl_rows) obj_kl_row(o, b, red);
+}
+// the term alone: one workgroup per possible segment (with a CSR the host does not know S: agent_scene[n - 1] + 1)
+__global__ __launch_bounds__(256) void diverse_joint_kernel(const float* pred, const float* target, const int* scene_ptr, const int* agent_scene,
+                                                            int n, int K, int D, int seg_len, float* part, float* dpred, int* best) {
+    const int g = blockIdx.x;
+    if (g >= (scene_ptr ? agent_scene[n - 1] + 1 : n / seg_len)) return;
+    const int r0 = scene_ptr ? scene_ptr[g] : g * seg_len, r1 = scene_ptr ? scene_ptr[g + 1] : r0 + seg_len;
+    const float wgt = 1.0f / (float)(scene_ptr ? r1 - r0 : n);
+    joint_segment(pred, target, K, 0, K, D, r0, r1, wgt, part, nullptr, dpred, best, nullptr);
+}
+extern "C" int sttode_loss_objective_joint(const float* pred, const float* rec, const float* fut, const float* past, const float* qzp,
+                                           const int* scene_ptr, const int* agent_scene, int S, int n, int K1, int D, int Dp, int zd,
+                                           float scale_mse, float scale_rec, float kl_denom, float min_clip, float* out, float* dpred2,
+                                           float* drec2, float* dqzp, int* best, int seg_len, int* seg_best, float* scratch,
+                                           long scratch_floats, void* stream) {
+    STT_REQUIRE(pred && rec && fut && past && qzp && out && dpred2 && drec2 && dqzp && best && scratch, "sttode_loss_objective_joint: null pointer");
+    STT_REQUIRE(n > 0 && K1 >= 2 && K1 <= 65 && D > 0 && Dp > 0 && zd > 0, "sttode_loss_objective_joint: bad sizes (2 <= K1 <= 65)");
+    STT_REQUIRE(scene_ptr ? (S > 0 && agent_scene) : kl_denom > 0.f,
+                "sttode_loss_objective_joint: scene_ptr needs S > 0 and agent_scene, otherwise kl_denom > 0");
+    STT_REQUIRE(scene_ptr ? seg_len == 0 : (seg_len >= 1 && n % seg_len == 0),
+                "sttode_loss_objective_joint: bad seg_len (0 with scene_ptr: the segments are the scenes; otherwise >= 1 and a divisor of n)");
+    STT_REQUIRE(3L * n + (scene_ptr ? S : n) <= scratch_floats, "sttode_loss_objective_joint: scratch too small (3 n + max(S, n) floats)");
+    const int nb = scene_ptr ? S : 0, kl_rows = scene_ptr ? 0 : n, G = scene_ptr ? S : n / seg_len;
+    ObjArgs o;
+    o.pred = pred; o.rec = rec; o.fut = fut; o.past = past; o.qzp = qzp; o.scene_ptr = scene_ptr; o.agent_scene = agent_scene;
+    o.dpred = nullptr; o.drec = nullptr; o.dqzp = dqzp; o.part = scratch;
+    o.best = best; o.dpred2 = dpred2; o.drec2 = drec2;
+    o.n = n; o.K1 = K1; o.D = D; o.Dp = Dp; o.zd = zd; o.nb = nb; o.kl_rows = kl_rows;
+    o.scale_mse = scale_mse; o.scale_rec = scale_rec; o.kl_denom = kl_denom; o.min_clip = min_clip;
+    hipLaunchKernelGGL(objective_joint_kernel, dim3(n + nb + G), dim3(256), 0, (hipStream_t)stream, o, seg_len, seg_best);
+    hipLaunchKernelGGL(objective_sum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, scratch, n, nb, scale_mse, scale_rec, out, kl_rows, kl_denom,
+                       min_clip, dqzp, zd);
+    STT_HIP(hipGetLastError());
+    return 0;
+}
+extern "C" int sttode_loss_diverse_joint(const float* pred, const float* target, const int* scene_ptr, const int* agent_scene, int n, int K,
+                                         int D, int seg_len, float* out, float* dpred, int* best, float* scratch, void* stream) {
+    STT_REQUIRE(pred && target && out && scratch && n > 0 && K > 0 && K <= 64 && D > 0,
+                "sttode_loss_diverse_joint: bad argument (1 <= K <= 64, scratch >= n floats)");
+    STT_REQUIRE(!scene_ptr || agent_scene, "sttode_loss_diverse_joint: scene_ptr needs agent_scene");
+    STT_REQUIRE(scene_ptr ? seg_len == 0 : (seg_len >= 1 && n % seg_len == 0),
+                "sttode_loss_diverse_joint: bad seg_len (0 with scene_ptr: the segments are the scenes; otherwise >= 1 and a divisor of n)");
+    hipLaunchKernelGGL(diverse_joint_kernel, dim3(scene_ptr ? n : n / seg_len), dim3(256), 0, (hipStream_t)stream, pred, target, scene_ptr,
+                       agent_scene, n, K, D, seg_len, scratch, dpred, best);
+    hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, scratch, n, out);
+    STT_HIP(hipGetLastError());
+    return 0;
 }
 
 extern "C" int sttode_loss_sqerr(const float* pred, const float* target, long count, float scale, float* out, float* dpred, void* stream) {

@@ -191,6 +191,10 @@ class STTODENet(nn.Module):
         # EXPLORATORY, opt-in: 'bf16x3' runs the two block-0 decoder MLPs of the fused launch as a three-way bf16 split on the bf16 matrix
         # cores (fp32-class accuracy, fp32 accumulate; csrc/chain32.hip B3M); 'f32' (default) = fp32 MFMA everywhere.  env STTODE_BF16X3=1
         self.mfma_mode = 'bf16x3' if os.environ.get('STTODE_BF16X3', '0') not in ('', '0') else 'f32'
+        # best-of-K term of forward(): 'marginal' = the reference's (min over K per agent, model/STTODE.py:390-395); 'joint' = the min over K
+        # outside the sum over a scene's / an NBA game's agents -- what joint=True evaluation measures
+        self.diverse_mode = getattr(args, 'diverse_mode', 'marginal')
+        self._diverse_joint()
         self._host_futures = {}  # slot -> pinned [n, K, Tf, 2] (futures_to_host_async)
         self.async_depth = 6     # calls in flight of the inference_async pipeline (workspace / prediction slots, <= 8; 2 x pipeline streams)
         # inference_async(z=None) in the lagged form: latents drawn by the call's own launch (csrc/role32.hpp); env STTODE_DEVICE_LATENTS=0: torch.randn
@@ -203,6 +207,18 @@ class STTODENet(nn.Module):
         self.to(self.device)
 
     # ------------------------------------------------------------------ plumbing
+    DIVERSE_MODES = ('marginal', 'joint')
+
+    def _diverse_joint(self):
+        """True in joint mode; any value but the two modes is refused here (forward() asks on every call: a plain attribute)."""
+        if self.diverse_mode not in self.DIVERSE_MODES:
+            raise ValueError(f"diverse_mode must be 'marginal' or 'joint', got {self.diverse_mode!r}")
+        return self.diverse_mode == 'joint'
+
+    def _joint_seg_len(self, n):
+        """seg_len of the joint loss entries where no scene CSR is passed: one NBA game's agents, otherwise the one scene's n."""
+        return int(self._N) if self._mode == 'nba' else int(n)
+
     @property
     def past_feature(self):
         """[n, 128] encoder output (model/STTODE.py:496); after inference() it is a view into the workspace, made on first read."""
@@ -696,7 +712,11 @@ class STTODENet(nn.Module):
         scratch = self._f(max(n, S, 1))
         capi.call('sttode_loss_kl', self.qz_param, sp, S, n, a.zdim, float(B * N), float(a.min_clip), losses[2:], None, scratch, st)
         self.decoder_future_1(self.pz_sampled)
-        capi.call('sttode_loss_diverse', self.diverse_pred_traj.contiguous(), fut, sp, ags, n, 20, 2 * Tf, losses[3:], None, scratch, st)   # :390-395
+        if self._diverse_joint():                             # the scene-level term: scenes of the CSR, one scene, or one NBA game each
+            capi.call('sttode_loss_diverse_joint', self.diverse_pred_traj.contiguous(), fut, sp, ags, n, 20, 2 * Tf,
+                      0 if seg else self._joint_seg_len(n), losses[3:], None, None, scratch, st)
+        else:
+            capi.call('sttode_loss_diverse', self.diverse_pred_traj.contiguous(), fut, sp, ags, n, 20, 2 * Tf, losses[3:], None, scratch, st)   # :390-395
         lv = losses.tolist()
         return losses.sum(), lv[0], lv[1], lv[2], lv[3]
 

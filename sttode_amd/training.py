@@ -972,7 +972,16 @@ class Engine:
         # gradient equals what S reference steps would accumulate (per-scene KL clamp and per-scene mean of the best-of-20 term)
         seg = net._mode == 'scenes' and net._S > 1
         sp, ags, S = (net._scene_ptr, ws['agent_scene'], net._S) if seg else (None, None, 0)
-        if live:
+        if net._diverse_joint():
+            # the scene-level best-of-K term: one prior sample per segment -- a scene of the CSR, the one scene, an NBA game --
+            # so the gradient still lives in sample 0 plus one prior column per agent and `best` feeds decoder_live as it is
+            if not live:
+                raise SttodeError("diverse_mode 'joint' is built on the live-column backward pass (its kernel writes the two live gradient "
+                                  "rows per agent); _LIVE_COLUMNS = False has no dense joint form")
+            capi.call('sttode_loss_objective_joint', d['pred'], d['rec'], fut, past, qzp, sp, ags, S, n, K1, 2 * Tf, 2 * Tp, zd, 1.0 / (B * Tf),
+                      1.0 / (B * Tp), float(B * N), float(a.min_clip), losses, dpred, drec, dqzp, best, 0 if seg else net._joint_seg_len(n), None,
+                      self.scratch, self.scratch.numel(), self.st)
+        elif live:
             capi.call('sttode_loss_objective_live', d['pred'], d['rec'], fut, past, qzp, sp, ags, S, n, K1, 2 * Tf, 2 * Tp, zd, 1.0 / (B * Tf),
                       1.0 / (B * Tp), float(B * N), float(a.min_clip), losses, dpred, drec, dqzp, best, self.scratch, self.scratch.numel(), self.st)
         else:
@@ -1302,6 +1311,8 @@ def training_forward(net, eps_q=None, eps_p=None, eps20=None, drop_past=None, dr
     prog = eng.ode_program()                                        # (raises for a non-default integrator at generic widths)
     if prog is not None:                                            # the stage program is part of what a graph holds (the default key is as before)
         key = key + (prog,)
+    if net._diverse_joint():                                        # a graph holds ONE objective launch: the two modes never share one (default key as before)
+        key = key + ('diverse_joint',)
     # a step is ~170 launches of 5-30 us each and the host needs ~15 us to enqueue one: replay wins as long as the launches are short
     # (one scene: launch-bound; an NBA batch of 32 x 11 agents: 3.5 ms eager for 2.5 ms of kernels)
     graphs = getattr(net, 'train_graphs', os.environ.get('STTODE_TRAIN_GRAPHS', '1') != '0') and net._future is not None and n <= _GRAPH_MAX_AGENTS

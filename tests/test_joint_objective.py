@@ -1,0 +1,191 @@
+"""CPU tests of the scene-level (joint) best-of-K objective: tests/joint_ref.py pinned in float64 against a NumPy double loop,
+np.argmin and a central difference; the three properties that relate the joint term to the marginal one; the two entry points in header,
+ctypes table and library; every refusal by name, without a launch; STTODENet.diverse_mode."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import joint_ref as JR
+import train_ref as R
+
+from helpers import make_args
+from test_capi_symbols import header_functions
+
+MIN_CLIP = 2.0
+
+
+def _inputs(seed, n, K1, D, Dp, zd):
+    rng = np.random.default_rng(seed)
+    f = lambda *s: torch.from_numpy(rng.standard_normal(s))
+    return f(n, K1, D), f(n, K1, Dp), f(n, D), f(n, Dp), 0.6 * f(n, 2 * zd)
+
+
+def _joint_np(pred, fut, segs, per_scene):
+    """The definition, as loops in NumPy doubles: J_g(k) agent by agent, np.argmin (first minimum), sum_g w_g J_g(k*_g)."""
+    n, K1, D = pred.shape
+    J = np.zeros((len(segs), K1 - 1))
+    for g, (a0, a1) in enumerate(segs):
+        for k in range(1, K1):
+            for a in range(a0, a1):
+                J[g, k - 1] += ((fut[a] - pred[a, k]) ** 2).sum()
+    kbest = np.argmin(J, axis=1)
+    w = np.array([1.0 / (a1 - a0) if per_scene else 1.0 / n for a0, a1 in segs])
+    return float((w * J[np.arange(len(segs)), kbest]).sum()), kbest + 1, J, w
+
+
+# (n, K1, D, scene_ptr, seg_len)
+REF_CASES = [(12, 21, 24, None, 12), (12, 21, 24, None, 3), (12, 5, 6, None, 1), (9, 21, 20, (0, 1, 5, 9), 0), (6, 2, 4, None, 2)]
+
+
+@pytest.mark.parametrize('n,K1,D,csr,seg_len', REF_CASES)
+def test_joint_ref_is_the_definition_in_numpy_doubles(n, K1, D, csr, seg_len):
+    pred, rec, fut, past, qzp = _inputs(7 + n + K1, n, K1, D, 10, 8)
+    r = JR.objective_joint(pred, rec, fut, past, qzp, csr, seg_len, K1, 2.0 / D, 0.2, float(n), MIN_CLIP)
+    segs = JR.segments_of(n, csr, seg_len)
+    val, kbest, J, w = _joint_np(pred.numpy(), fut.numpy(), segs, csr is not None)
+    np.testing.assert_allclose(r['J'].numpy(), J, rtol=1e-13)
+    assert np.array_equal(r['seg_best'].numpy(), kbest)
+    assert np.array_equal(r['best'].numpy(), np.concatenate([np.full(b - a, kbest[g]) for g, (a, b) in enumerate(segs)]))
+    np.testing.assert_allclose(float(r['diverse']), val, rtol=1e-13)
+    # the other three terms and their gradients are train_ref.objective's
+    m = R.objective(pred, rec, fut, past, qzp, csr, K1, 2.0 / D, 0.2, float(n), MIN_CLIP)
+    for k in ('mse', 'rec', 'kl', 'drec', 'dqzp'):
+        assert torch.equal(r[k], m[k]), k
+    assert torch.equal(r['dpred'][:, 0], m['dpred'][:, 0])
+    np.testing.assert_allclose(float(r['total']), float(m['mse'] + m['rec'] + m['kl']) + val, rtol=1e-13)
+    # the gradient: 2 (pred - fut) w_g on the selected column, zero on every other prior column ...
+    exp = np.zeros((n, K1, D))
+    for g, (a, b) in enumerate(segs):
+        exp[a:b, kbest[g]] = 2.0 * (pred.numpy()[a:b, kbest[g]] - fut.numpy()[a:b]) * w[g]
+    np.testing.assert_allclose(r['dpred'][:, 1:].numpy(), exp[:, 1:], rtol=1e-12, atol=1e-15)
+    # ... and a central difference of the term along a random direction (the minimum is not tied, so the term is smooth there)
+    rng = np.random.default_rng(3)
+    v = rng.standard_normal(pred.shape)
+    h = 1e-6
+    term = lambda P: _joint_np(P, fut.numpy(), segs, csr is not None)[0]
+    fd = (term(pred.numpy() + h * v) - term(pred.numpy() - h * v)) / (2 * h)
+    np.testing.assert_allclose(fd, float((r['dpred'][:, 1:].numpy() * v[:, 1:]).sum()), rtol=1e-6)
+
+
+@pytest.mark.parametrize('n,K1,D,csr,seg_len', REF_CASES)
+def test_joint_term_is_at_least_the_marginal_term(n, K1, D, csr, seg_len):
+    for seed in range(5):
+        pred, rec, fut, past, qzp = _inputs(100 + seed, n, K1, D, 10, 8)
+        j = JR.objective_joint(pred, rec, fut, past, qzp, csr, seg_len, K1, 2.0 / D, 0.2, float(n), MIN_CLIP)
+        m = R.objective(pred, rec, fut, past, qzp, csr, K1, 2.0 / D, 0.2, float(n), MIN_CLIP)
+        assert float(j['diverse']) >= float(m['diverse']) * (1 - 1e-14)
+        if seg_len == 1:
+            np.testing.assert_allclose(float(j['diverse']), float(m['diverse']), rtol=1e-14)
+            assert torch.equal(j['best'], m['best'])
+            np.testing.assert_allclose(j['dpred'].numpy(), m['dpred'].numpy(), rtol=1e-14, atol=0)
+
+
+def test_one_agent_segments_of_a_csr_are_the_marginal_term():
+    n, K1, D = 5, 21, 24
+    csr = tuple(range(n + 1))
+    pred, rec, fut, past, qzp = _inputs(11, n, K1, D, 10, 8)
+    j = JR.objective_joint(pred, rec, fut, past, qzp, csr, 0, K1, 2.0 / D, 0.2, float(n), MIN_CLIP)
+    m = R.objective(pred, rec, fut, past, qzp, csr, K1, 2.0 / D, 0.2, float(n), MIN_CLIP)
+    np.testing.assert_allclose(float(j['diverse']), float(m['diverse']), rtol=1e-14)
+    assert torch.equal(j['best'], m['best']) and torch.equal(j['dpred'], m['dpred'])
+
+
+def test_coinciding_and_differing_minima_constructed():
+    """Two agents, three samples.  Coinciding per-agent minima: the joint term is the marginal one.  Differing: agent 0 is best at sample 1,
+    agent 1 at sample 2, the pair at sample 3 -- the joint term is strictly larger and selects neither agent's own best."""
+    fut = torch.zeros(2, 2, dtype=torch.float64)
+    z = [0.0, 0.0]
+    rec, past, qzp = torch.zeros(2, 4, 2, dtype=torch.float64), torch.zeros(2, 2, dtype=torch.float64), torch.ones(2, 4, dtype=torch.float64)
+    # squared distances per (agent, sample): [[1, 16, 4], [16, 1, 4]] -> marginal (1 + 1) / 2, joint min(17, 17, 8) / 2 at sample 3
+    pred = torch.tensor([[z, [1.0, 0.0], [4.0, 0.0], [2.0, 0.0]], [z, [4.0, 0.0], [1.0, 0.0], [2.0, 0.0]]], dtype=torch.float64)
+    j = JR.objective_joint(pred, rec, fut, past, qzp, None, 2, 4, 1.0, 1.0, 2.0, MIN_CLIP)
+    m = R.objective(pred, rec, fut, past, qzp, None, 4, 1.0, 1.0, 2.0, MIN_CLIP)
+    assert m['best'].tolist() == [1, 2] and float(m['diverse']) == 1.0
+    assert j['best'].tolist() == [3, 3] and float(j['diverse']) == 4.0
+    assert (j['dpred'][:, 1:3] == 0).all() and torch.equal(j['dpred'][:, 3], 2 * pred[:, 3] / 2)
+    # coinciding: both agents best at sample 2
+    pred2 = torch.tensor([[z, [3.0, 0.0], [1.0, 0.0], [2.0, 0.0]], [z, [4.0, 0.0], [1.0, 1.0], [2.0, 0.0]]], dtype=torch.float64)
+    j = JR.objective_joint(pred2, rec, fut, past, qzp, None, 2, 4, 1.0, 1.0, 2.0, MIN_CLIP)
+    m = R.objective(pred2, rec, fut, past, qzp, None, 4, 1.0, 1.0, 2.0, MIN_CLIP)
+    assert m['best'].tolist() == [2, 2] == j['best'].tolist()
+    assert float(j['diverse']) == float(m['diverse']) == 1.5 and torch.equal(j['dpred'], m['dpred'])
+    # a tie between two segment sums goes to the lower sample (torch.min, np.argmin)
+    pred3 = torch.tensor([[z, [1.0, 0.0], [4.0, 0.0], [9.0, 0.0]], [z, [4.0, 0.0], [1.0, 0.0], [9.0, 0.0]]], dtype=torch.float64)
+    assert JR.objective_joint(pred3, rec, fut, past, qzp, None, 2, 4, 1.0, 1.0, 2.0, MIN_CLIP)['best'].tolist() == [1, 1]
+
+
+def test_entry_points_in_header_table_and_library():
+    from sttode_amd import capi
+    fns = header_functions()
+    for name, nargs in (('sttode_loss_objective_joint', 27), ('sttode_loss_diverse_joint', 13)):
+        assert name in fns and len(fns[name]) == nargs, name
+        assert name in capi.SIGNATURES and len(capi.SIGNATURES[name]) == nargs, name
+        assert hasattr(capi.lib(), name), name
+    live = fns['sttode_loss_objective_live']
+    joint = fns['sttode_loss_objective_joint']
+    assert joint[:22] == live[:22] and joint[22:24] == ['int seg_len', 'int* seg_best'] and joint[24:] == live[22:]
+    assert fns['sttode_loss_diverse_joint'][7] == 'int seg_len'
+    assert capi.ABI_VERSION == 14
+
+
+def _objective_joint_rc(L, **over):
+    """One refused sttode_loss_objective_joint call: valid arguments (never dereferenced), then ``over``."""
+    P = ctypes.c_void_p(16)
+    a = dict(pred=P, rec=P, fut=P, past=P, qzp=P, sp=None, ag=None, S=0, n=12, K1=21, D=24, Dp=16, zd=32, kl_denom=12.0, best=P, seg_len=12,
+             seg_best=None, scratch_floats=48)
+    a.update(over)
+    rc = L.sttode_loss_objective_joint(a['pred'], a['rec'], a['fut'], a['past'], a['qzp'], a['sp'], a['ag'], a['S'], a['n'], a['K1'], a['D'], a['Dp'],
+                                       a['zd'], ctypes.c_float(0.1), ctypes.c_float(0.1), ctypes.c_float(a['kl_denom']), ctypes.c_float(MIN_CLIP), P, P, P,
+                                       P, a['best'], a['seg_len'], a['seg_best'], P, ctypes.c_long(a['scratch_floats']), None)
+    return rc, L.sttode_last_error()
+
+
+def test_refusals_name_the_entry_point_without_a_launch():
+    from sttode_amd import capi
+    L = capi.lib()
+    P = ctypes.c_void_p(16)
+    name = b'sttode_loss_objective_joint'
+    for K1 in (1, 66):
+        rc, msg = _objective_joint_rc(L, K1=K1)
+        assert rc != 0 and name in msg and b'2 <= K1 <= 65' in msg, msg
+    for over in (dict(seg_len=5), dict(seg_len=0), dict(seg_len=-3), dict(seg_len=24), dict(sp=P, ag=P, S=3, seg_len=4)):
+        rc, msg = _objective_joint_rc(L, **over)
+        assert rc != 0 and name in msg and b'seg_len' in msg, (over, msg)
+    rc, msg = _objective_joint_rc(L, best=None)
+    assert rc != 0 and name in msg and b'null pointer' in msg, msg
+    rc, msg = _objective_joint_rc(L, scratch_floats=47)                  # 4 n - 1 without a CSR
+    assert rc != 0 and name in msg and b'scratch' in msg, msg
+    rc, msg = _objective_joint_rc(L, sp=P, ag=P, S=3, seg_len=0, scratch_floats=3 * 12 + 3 - 1)
+    assert rc != 0 and name in msg and b'scratch' in msg, msg
+    # the live form's own refusals: a CSR without agent_scene or S, no CSR and no KL denominator, a null input
+    for over in (dict(sp=P, ag=None, S=3, seg_len=0), dict(sp=P, ag=P, S=0, seg_len=0), dict(kl_denom=0.0), dict(fut=None), dict(n=0)):
+        rc, msg = _objective_joint_rc(L, **over)
+        assert rc != 0 and name in msg, (over, msg)
+    # the stand-alone term
+    name = b'sttode_loss_diverse_joint'
+    for K, seg_len, sp, ag, word in ((0, 12, None, None, b'K <= 64'), (65, 12, None, None, b'K <= 64'), (20, 5, None, None, b'seg_len'),
+                                     (20, 0, None, None, b'seg_len'), (20, 4, P, P, b'seg_len'), (20, 0, P, None, b'agent_scene')):
+        rc = L.sttode_loss_diverse_joint(P, P, sp, ag, 12, K, 24, seg_len, P, None, None, P, None)
+        assert rc != 0 and name in L.sttode_last_error() and word in L.sttode_last_error(), (K, seg_len, L.sttode_last_error())
+    rc = L.sttode_loss_diverse_joint(P, P, None, None, 12, 20, 24, 12, P, None, None, None, None)
+    assert rc != 0 and name in L.sttode_last_error()
+
+
+def test_diverse_mode_attribute():
+    from sttode_amd import STTODENet
+    m = STTODENet(make_args(), 'cpu')
+    assert m.diverse_mode == 'marginal' and not m._diverse_joint()
+    a = make_args()
+    a.diverse_mode = 'joint'
+    m = STTODENet(a, 'cpu')
+    assert m.diverse_mode == 'joint' and m._diverse_joint()
+    m.diverse_mode = 'marginal'
+    assert not m._diverse_joint()
+    m.diverse_mode = 'both'
+    with pytest.raises(ValueError, match='diverse_mode'):
+        m._diverse_joint()
+    a.diverse_mode = 'mixed'
+    with pytest.raises(ValueError, match='diverse_mode'):
+        STTODENet(a, 'cpu')
