@@ -24,7 +24,7 @@ extern "C" {
 #endif
 
 /* Version of this header: the library returns it from sttode_abi_version(); a binding compares before its first call (round 1-2: 1). */
-#define STTODE_ABI_VERSION 14
+#define STTODE_ABI_VERSION 15
 int sttode_abi_version(void);
 const char* sttode_last_error(void);
 
@@ -750,12 +750,10 @@ int sttode_set_chain(SttodeModel* m, int mode);
 /* Calls whose per-trajectory stage takes the fused chain: 1 (default) = the per-agent stage (encoder, block-0 GRU,
  * layer-1 pre-activation tables: PastEncoder.forward model/STTODE.py:214-236, DecomposeBlock.forward :62-75 of block 0) runs as the
  * leading workgroups of the chain launch, trajectory groups wait on one flag per 16-agent tile (attention groups > 1, the NBA branch:
- * the embedding and the attention stay launches in front, the roles start at the post-attention layer); 2 = as 1, and for scene batches
- * the roles also run set_data's normalisation of their tile (model/STTODE.py:397-461): the call is ONE launch; 0 = separate launches on
- * the pipeline's per-agent stream; 3 = as 1 with the roles interleaved 160 groups ahead of their consumers in the grid instead of all
- * in front (sttode_fused_block_of; measured neutral pipelined, slower serial); 4 = as 1 with a tile's stage split into FIVE role workgroups
- * -- encoder beside block-0 GRU, then one per layer-1 table: latency max(E, G) + one table instead of their sum; measured -1 % at 512
- * scenes, +3 % on the NBA-128 leg, not the default.  Results are bitwise the same in every mode. */
+ * the embedding and the attention stay launches in front, the roles start at the post-attention layer); 0 = separate launches on
+ * the pipeline's per-agent stream.  Results are bitwise the same in both modes.  Anything else is refused: modes 2-4 (the scene
+ * front-end inside the roles, roles interleaved with the groups, five role workgroups per tile) were A/B candidates that lost and are
+ * retired (DESIGN_HISTORY.md). */
 int sttode_set_fused(SttodeModel* m, int mode);
 /* EXPLORATORY, opt-in, never the default (own dtype label in bench.py): 1 = the per-trajectory chain (the three decoder MLPs and block 1's
  * conv + GRU: DecomposeBlock.forward model/STTODE.py:51-77, Decoder.forward :320-347) runs its matrix products as a three-way bf16
@@ -765,8 +763,7 @@ int sttode_set_fused(SttodeModel* m, int mode);
 int sttode_set_mfma_mode(SttodeModel* m, int mode);
 /* Fault injection for tests of the in-launch hand-off's give-up path: in fused launches the per-agent role of 16-agent tile `tile` computes
  * its tables but never publishes its flag (-1: off, the default).  The trajectory groups that read that tile then run into the bound of
- * their spin (~1 s), write NaN into their predictions and set the time-out word (workspace buffer STT_B_FLAGS, word [tiles]; with the split roles of
- * mode 4 the flag words are E [tiles] | time-out | G [tiles] | tables [3 tiles] and the withheld flags are the tile's three table flags) -- the
+ * their spin (~1 s), write NaN into their predictions and set the time-out word (workspace buffer STT_B_FLAGS, word [tiles]) -- the
  * launch ends, it never hangs; every other group is unaffected.  The model's host-visible word (sttode_timeout_word) is set as well. */
 int sttode_debug_drop_role_flag(SttodeModel* m, int tile);
 /* Host staging of one scene for the one-scene-per-call loop (test.py:171-188 -> set_data, model/STTODE.py:397-404): pre [N][2][Tp] and
@@ -793,10 +790,6 @@ int sttode_async_best_of_k(SttodeModel* m, int slot, const float* pred, const fl
  * `max_tiles` 16-trajectory tiles: -1 = default (128), 0 = never (six launches, as round 2).  Bitwise the
  * same predictions either way.  Replaces: model/STTODE.py:397-461 + :553-627 for one scene. */
 int sttode_set_scene_launch(SttodeModel* m, int max_tiles);
-/* Grid order of the fused launch (host-callable, no GPU): block -> group index (>= 0) or -1 - tile for the per-agent role of a 16-agent
- * tile; roles sit `lead` groups ahead of the first group that reads their tables, so every producer has a smaller block index than its
- * consumers (Decoder.forward's repeat_interleave layout, model/STTODE.py:322-328: trajectory = agent * K + k). */
-int sttode_fused_block_of(long block, long tiles, long groups, long K, long lead);
 /* integrator of the tensor-ODE encoder inside the native pipeline: method / steps as in sttode_post_attn_ode (default 0, 1 = reference).
  * Attention length 1 (scene batches): every stage inside the fused encoder kernel.  Attention groups > 1 (sttode_inference_nba): every
  * stage is a pass over the group -- in-projection of the state, sttode_mhgsa_attn, sttode_post_attn_rhs, axpy combinations -- enqueued

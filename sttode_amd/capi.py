@@ -11,7 +11,7 @@ _LIB = None
 LIB_PATH = os.environ.get('STTODE_HIP_LIB') or os.path.join(os.path.dirname(os.path.abspath(__file__)), 'lib', 'libsttode_hip.so')
 
 _P, _I, _L, _F, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double
-ABI_VERSION = 14  # == STTODE_ABI_VERSION of include/sttode_hip.h; lib() refuses a library built from another header
+ABI_VERSION = 15  # == STTODE_ABI_VERSION of include/sttode_hip.h; lib() refuses a library built from another header
 
 # name -> argtypes (mirrors include/sttode_hip.h; tests/test_capi_symbols.py checks header == table == .so)
 SIGNATURES = {
@@ -137,7 +137,6 @@ SIGNATURES = {
     'sttode_wait_value': [_P, _L, _D],
     'sttode_async_next_stream': [_P, _I, _P],
     'sttode_async_best_of_k': [_P, _I, _P, _P, _I, _I, _I, _F, _P, _P],
-    'sttode_fused_block_of': [_L, _L, _L, _L, _L],
     'sttode_set_ode': [_P, _I, _I],
     'sttode_timing_enable': [_P, _I],
     'sttode_timing_read': [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)],
@@ -262,10 +261,8 @@ class NativeModel:
         call('sttode_set_scene_launch', self.h, int(max_tiles))
 
     def set_fused(self, mode):
-        """1: per-agent roles inside the chain launch (default); 2: the roles also run the scene front-end (one launch per call);
-        3: as 1 with the roles interleaved 160 groups ahead of their consumers in the grid; 4: as 1 with five role workgroups per tile
-        (E | G | three tables) instead of one; 0: separate per-agent launches.
-        Results are bitwise the same in every mode."""
+        """1: per-agent roles inside the chain launch (default); 0: separate per-agent launches.
+        Results are bitwise the same in both modes."""
         if lib().sttode_set_fused(self.h, int(mode)) != 0:
             raise SttodeError('sttode_set_fused failed: ' + lib().sttode_last_error().decode())
 

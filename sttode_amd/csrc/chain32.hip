@@ -856,24 +856,12 @@ __device__ __forceinline__ int opaque(int v) { asm volatile("" : "+v"(v)); retur
 #define C32_STAMP(k) do { } while (0)
 #endif
 
-// Grid order of the fused launch.  Roles and groups are interleaved: the role of tile t is placed `lead` groups ahead of the first group
-// that reads its tables, g_first(t) = floor(t K / 8) (a tile = 16 agents = 16 K trajectories, a group = 128), so that in a running
-// pipeline a role has finished by the time its consumers are dispatched (nobody spins), and a single serial launch starts its
-// trajectory groups at once instead of behind ALL roles (the per-agent stage then costs its matrix work, not a prologue).  Sort key:
-// role t -> max(0, g_first(t) - lead), group g -> g, roles first on ties; every role a group needs has g_first <= g, hence a smaller
-// block index: workgroups are dispatched in index order PER XCD (each XCD takes block % 8), and a role never waits, so within ONE launch
-// every producer finishes whatever its consumers do (no deadlock; the bounded spin of wait_tiles is the backstop).  Several such launches
-// in flight on different queues have no such guarantee across XCDs: the pipelined path uses the lagged form (FUSE = 2), which has no hand-off.  Returns the group index, or -1 - tile for a role.  Scalar code: ~10 binary-search steps.
-__host__ __device__ __forceinline__ int fused_block_of(long b, long T, long G, long K, long lead) {
-    auto roles_upto = [&](long x) { const long c = (8 * (x + lead + 1) + K - 1) / K; return c < T ? c : T; };   // #roles with key <= x
-    long lo = -1, hi = G - 1;                       // largest g with position g + roles_upto(g) <= b
-    while (lo < hi) {
-        const long mid = (lo + hi + 1) >> 1;
-        if (mid + roles_upto(mid) <= b) lo = mid; else hi = mid - 1;
-    }
-    if (lo >= 0 && lo + roles_upto(lo) == b) return (int)lo;
-    return -1 - (int)(b - (lo + 1));
-}
+// Grid order of the fused launch: blocks [0, ntiles) are the roles, one per 16-agent tile, and the trajectory groups follow.  Every role a
+// group needs has a smaller block index: workgroups are dispatched in index order PER XCD (each XCD takes block % 8), and a role never
+// waits, so within ONE launch every producer finishes whatever its consumers do (no deadlock; the bounded spin of wait_tiles is the
+// backstop).  Several such launches in flight on different queues have no such guarantee across XCDs: the pipelined path uses the lagged
+// form (FUSE = 2), which has no hand-off.  (Roles interleaved with the groups, and five role workgroups per tile, were tried and lost:
+// DESIGN_HISTORY.md.)
 
 // XCD-aware group order.  Workgroups are dealt to the 8 XCDs round-robin in dispatch order, and each XCD has its own L2.  A 16-agent tile's
 // table rows (3 x 2 KiB per agent, written through to memory by its role) are read by the 2-3 trajectory groups of its 320 trajectories; in
@@ -917,16 +905,13 @@ __global__ __launch_bounds__(256, 2) void traj_chain_kernel(ChainArgs A) {
         C32_TRACE_END(1);
         return;
     }
-    if (FUSE == 1 && A.R.split && (int)blockIdx.x < 5 * A.R.ntiles) {   // (uniform) split per-agent roles, all in front of the groups
-        split_role(A.R, (A.ncols + A.K - 1) / A.K, A.Tp, A.ldx, A.xpad, blockIdx.x, smem);
-        C32_TRACE_END(1);
-        return;
-    }
-    int fb = FUSE == 0 ? (int)blockIdx.x : FUSE == 2 ? (int)blockIdx.x - A.R32.nwg : A.R.split ? (int)blockIdx.x - 5 * A.R.ntiles
-                                                : fused_block_of(blockIdx.x, A.R.ntiles, ngroups, A.K, A.R.lead);
+    // position among the group blocks; FUSE 1: < 0 for the roles in front, one workgroup per 16-agent tile.  (The role's tile is taken
+    // from fb, behind the group order: with blockIdx.x, or with the role branch in front of the order, hipcc gives the NY = 2 and NY = 3
+    // instantiations 32-36 B/lane more scratch -- profiles/fused_launch/resource_usage.txt)
+    int fb = FUSE == 0 ? (int)blockIdx.x : (int)blockIdx.x - (FUSE == 2 ? A.R32.nwg : A.R.ntiles);
     if (FUSE && A.xcd_map && fb >= 0) fb = xcd_group(fb, ngroups);   // (roles in front: fb was the group block's position in dispatch order)
     if (FUSE == 1 && fb < 0) {   // (uniform) a per-agent role
-        agent_role(A.R, (A.ncols + A.K - 1) / A.K, A.Tp, A.ldx, A.xpad, -1 - fb, smem);
+        agent_role(A.R, (A.ncols + A.K - 1) / A.K, A.Tp, A.ldx, A.xpad, A.R.ntiles + fb, smem);
         C32_TRACE_END(1);
         return;
     }
@@ -940,8 +925,7 @@ __global__ __launch_bounds__(256, 2) void traj_chain_kernel(ChainArgs A) {
         const int c_lo = g0 * 128, c_hi = (c_lo + 127 < A.ncols ? c_lo + 127 : A.ncols - 1);
         const int t_lo = (c_lo / A.K) >> 4, t_hi = (c_hi / A.K) >> 4;
         if (wave == 0) {
-            const bool ok = A.R.split ? wait_tiles(A.R.pflags, 3 * t_lo, 3 * t_hi + 2, A.R.flags + A.R.ntiles, lane, A.R.tmo_host)   // the three tables of every tile
-                                      : wait_tiles(A.R.flags, t_lo, t_hi, A.R.flags + A.R.ntiles, lane, A.R.tmo_host);
+            const bool ok = wait_tiles(A.R.flags, t_lo, t_hi, A.R.flags + A.R.ntiles, lane, A.R.tmo_host);
             if (!ok && lane == 0) sq[0] = -1;
         }
     }
@@ -1225,7 +1209,7 @@ template <int NY, int FUSE, bool B3M = false> static int chain_launch(ChainArgs 
     STT_SET_LDS_ONCE(kern, 96 * 1024);   // once per (instantiation, device): the switch is read once per process
     const int ngroups = (a.ncols + 127) / 128;
     int grid = ngroups;   // FUSE 0: one group per workgroup
-    if (FUSE == 1) grid = (a.R.split ? 5 : 1) * a.R.ntiles + ngroups;   // roles ahead of their consumers, one group per workgroup
+    if (FUSE == 1) grid = a.R.ntiles + ngroups;   // roles ahead of their consumers, one group per workgroup
     else if (FUSE == 2) {   // another call's throughput-form roles, then this call's groups: one workgroup each, or (persistent) workers
         int workers = ngroups;
         if (a.persistent && workers > 2 * chain_cus()) workers = 2 * chain_cus();   // workers: the chip's workgroup slots
@@ -1244,7 +1228,7 @@ template <int NY, int FUSE, bool B3M = false> static int chain_launch(ChainArgs 
     STT_REQUIRE(lds <= 96 * 1024, "sttode_traj_chain: dynamic LDS beyond the 96 KiB the kernel is registered for");
     STT_REQUIRE((long)a.ncols * 128 <= 0xffffffffL && (long)((a.ncols + a.K - 1) / a.K) * 2048 <= 0xffffffffL,
                 "sttode_traj_chain: z / per-agent table rows beyond the 32-bit byte offsets of the gathers");
-    if (FUSE == 1) STT_HIP(hipMemsetAsync(a.R.flags, 0, (((size_t)(a.R.split ? 5 : 1) * a.R.ntiles + 1) * 4 + 15) / 16 * 16, s));   // tile flags + time-out word
+    if (FUSE == 1) STT_HIP(hipMemsetAsync(a.R.flags, 0, (((size_t)a.R.ntiles + 1) * 4 + 15) / 16 * 16, s));   // tile flags + time-out word
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a);
     STT_HIP(hipGetLastError());
     return 0;
@@ -1331,11 +1315,6 @@ static int g_trace_tag = 0;
 extern "C" int sttode_chain_debug_buffer(void* p) { g_chain_dbg = (long long*)p; return 0; }  // >= grid * 4 * 16 int64, zeroed
 #endif
 
-// Host view of the fused launch's grid order (tests: every block is exactly one role or group; producers precede consumers).
-extern "C" int sttode_fused_block_of(long block, long tiles, long groups, long K, long lead) {
-    return fused_block_of(block, tiles, groups, K, lead);
-}
-
 extern "C" int sttode_chain_prog_len(int Tp, int Tf) {
     const int NY = (2 * Tf + 31) / 32;
     const int l3y = (8 * NY + 2) / 3;
@@ -1398,14 +1377,12 @@ int stt_traj_chain_b3(const float* A0x, const float* A0y, const float* A1y, cons
 
 // Internal (csrc/pipeline.hip): the fused launch -- per-agent roles + trajectory groups in ONE grid (see RoleArgs).  W = the model's
 // weight table (enum SttodeWeight), ws / off = the caller's workspace and its layout; the front-end (xpad, enc_in, cur, orig, last) has
-// run on `stream` before -- unless `past` / `scene_ptr` are given (scene batches): the roles then run it for their tiles themselves and the
-// call is ONE launch.  attn == nullptr: attention length 1 (scene batches), the roles run the embedding too; attn != nullptr (the NBA
+// run on `stream` before.  attn == nullptr: attention length 1 (scene batches), the roles run the embedding too; attn != nullptr (the NBA
 // branch: attention groups > 1): embed_qkv and mhgsa_attn have run on `stream` before, the roles start at the post-attention layer.
 // The reference's one Euler step only.
 bool stt_chain_fused_covers(int Tp) { return Tp >= 2 && 2 * Tp <= 32 && role_lds(Tp) <= 80 * 1024; }
 int stt_chain_fused(const float* const* W, float* ws, const long* off, int n, int K, int Tp, int Tf, int prog_len, const float* z, float* pred,
-                    float ode_time, const float* attn, int ld_attn, const float* past, const int* scene_ptr, int S, int wgs_per_cu, int b3,
-                    int lead, int drop_tile, unsigned* tmo_host, void* stream) {
+                    float ode_time, const float* attn, int ld_attn, int wgs_per_cu, int b3, int drop_tile, unsigned* tmo_host, void* stream) {
     STT_REQUIRE(W && ws && off && z && pred, "stt_chain_fused: null pointer");
     STT_REQUIRE(n > 0 && K > 0 && stt_chain_fused_covers(Tp) && Tf >= 1, "stt_chain_fused: shape outside the fused launch");
     STT_REQUIRE(!attn || (ld_attn >= 64 && ld_attn % 4 == 0), "stt_chain_fused: bad attention leading dimension");
@@ -1426,18 +1403,10 @@ int stt_chain_fused(const float* const* W, float* ws, const long* off, int n, in
     RoleArgs& r = a.R;
     role_args_fill(r, W, ws, off);
     r.attn = attn; r.ld_attn = ld_attn;
-    STT_REQUIRE(!past || (scene_ptr && S > 0 && !attn), "stt_chain_fused: the in-role front-end needs scene_ptr, S > 0 and attention length 1");
-    r.past = past; r.scene_ptr = scene_ptr; r.S = S;
+    r.past = nullptr; r.scene_ptr = nullptr; r.S = 0;   // (the scene front-end inside the role is the one-launch scene form's, scene_lat.hip)
     r.flags = (unsigned*)(ws + off[STT_B_FLAGS]); r.ntiles = (n + 15) / 16; r.ode_time = ode_time;
     r.tmo_host = tmo_host;
-    // grid order: `lead` groups of head start of a role over its first consumer; < 0 (default): all roles first.  Measured on one box
-    // (profiles/r03/ab_lead_frontend_depth.txt): pipelined 73.4-74.6 M trajectories/s for lead 64 / 160 / 400 / roles first alike, but a
-    // SERIAL launch is 5 % slower interleaved (0.65 vs 0.69 of peak): a role beside a trajectory group runs 2x longer than beside
-    // other roles, and holds its slot all the while
-    r.lead = lead < 0 ? (1 << 28) : lead;
-    a.xcd_map = lead < 0;   // XCD-aware group order whenever all roles sit in front of the groups (profiles/r03/ab_xcd_map.txt)
-    r.split = lead == -2;   // -2: roles first, each tile's role split into E | G | three table workgroups (opt-in, sttode_set_fused mode 4); -1 (default): one workgroup per tile
-    r.gflags = r.flags + r.ntiles + 1; r.pflags = r.gflags + r.ntiles;
+    a.xcd_map = 1;   // all roles sit in front of the groups: XCD-aware group order (profiles/r03/ab_xcd_map.txt)
     r.drop_tile = drop_tile;
     const int NY = (2 * Tf + 31) / 32;
     hipStream_t s = (hipStream_t)stream;

@@ -38,12 +38,10 @@ struct SttodeModel {
     hipEvent_t ev_fork, ev_join;
     int chain_mode;  // 1 fused chain kernel, 0 three-kernel form, -1 automatic
     int fused_mode;  // 1 per-agent roles inside the chain launch wherever the shape is covered, 0 separate per-agent launches
-    int role_lead;   // fused launch's grid order: groups of head start of a role over its first consumer, < 0 = all roles first (default)
     hipStream_t slot_stream[STT_MAX_SLOTS];   // the pipeline stream the slot's latest asynchronous call ran on (its follow-up work goes there)
     int scene_launch; // largest number of 16-trajectory tiles a serial scene call runs as ONE launch (scene_lat.hip); 0: never
     int drop_tile;   // fault injection (tests): the role of this 16-agent tile does not publish its flag in fused launches (-1: none)
     int b3;          // exploratory: block-0 MLPs of the fused launch as a three-way bf16 split (sttode_set_mfma_mode)
-    bool fe_in_role; // fused scene batches: the roles also run the scene front-end (sttode_set_fused mode 2; default: a launch in front)
     int ode_method, ode_steps;  // integrator of the encoder ODE (0, 1 = one Euler step = the reference)
     int prog_len;
     // cross-call software pipeline (sttode_inference_*_async): stage A (per agent) of call i+1 runs on sA beside stage B
@@ -123,7 +121,6 @@ extern "C" int sttode_model_create(SttodeModel** out, const void* const* weights
     m->ode_method = 0; m->ode_steps = 1;
     m->fused_mode = 1;
     m->b3 = 0;   // (STTODE_BF16X3=1 is honoured by the Python layer, which packs the bf16-split stream before switching the mode on)
-    m->role_lead = -1;   // -1: one role workgroup per tile, all in front (default); -2: split roles
     m->drop_tile = -1;
     for (int p = 0; p < STT_MAX_SLOTS; ++p) { m->slot_stream[p] = nullptr; m->lag[p].valid = false; }
     // 3 streams: the small legs gain 3-9 % over 2, 512 scenes tie (profiles/r04/streams_2_vs_3.txt); 4: -5..-12 % everywhere -- the fourth
@@ -134,9 +131,6 @@ extern "C" int sttode_model_create(SttodeModel** out, const void* const* weights
     for (int i = 0; i < 4; ++i) m->lag_qn[i] = 0;
     if (const char* e = getenv("STTODE_LAGGED")) m->lag_streams = atoi(e) >= 2 && atoi(e) <= 4 ? atoi(e) : 0;
     m->scene_launch = 128;
-    // default off: measured neutral to -0.6 % pipelined and -1.5 % serial at 512 scenes (the two front-end launches cost less than the
-    // ~10 us they add to every role), +1 % on the 256-scene SDD leg (profiles/r03/ab_lead_frontend_depth.txt)
-    m->fe_in_role = false;
     m->prog_len = sttode_chain_prog_len(Tp, Tf);
     // All internal streams run at normal priority.  Measured on MI355X: high priority for the per-agent streams makes the
     // cross-call pipeline slower (61.6 M traj/s with sA+side raised, 65.6 M with only side raised, 66.9 M with neither).
@@ -233,8 +227,9 @@ extern "C" int sttode_workspace_layout(const SttodeModel* m, int n, int S, long*
     put(STT_B_YBUF, mm * 16 * m->NOY);
     put(STT_B_STATE1, mm * 96);
     put(STT_B_QUEUE, 64);
-    // fused launches: five flags per 16-agent tile (E, G, three tables) + the time-out word, zeroed per call; behind them the one-launch scene
-    // form's: three per agent tile + time-out word + one per 16-trajectory tile + exit counter + initialised word (stt_scene_flags_offset)
+    // fused launches: one flag per 16-agent tile + the time-out word, zeroed per call (the first tiles + 1 words; the rest of the 5 tiles + 4
+    // words in front of the scene form's region is unused); behind them the one-launch scene form's: three per agent tile + time-out word +
+    // one per 16-trajectory tile + exit counter + initialised word (stt_scene_flags_offset)
     // (+ the one-launch scene form's exit counter and "initialised" word: sttode_workspace_init)
     put(STT_B_FLAGS, (size_t)8 * ((n + 15) / 16) + 8 + (mm + 15) / 16);
     put(STT_B_ODE, (size_t)6 * n * 64);   // multi-stage integrator with attention groups > 1 (always laid out: sttode_set_ode may come later)
@@ -251,10 +246,8 @@ extern "C" int sttode_set_chain(SttodeModel* m, int mode) {
 
 extern "C" int sttode_set_fused(SttodeModel* m, int mode) {
     STT_REQUIRE(m, "sttode_set_fused: null model");
-    STT_REQUIRE(mode >= 0 && mode <= 4, "sttode_set_fused: mode must be 0 .. 4");
-    m->fused_mode = mode ? 1 : 0;
-    m->fe_in_role = mode == 2;
-    m->role_lead = mode == 3 ? 160 : mode == 4 ? -2 : -1;
+    STT_REQUIRE(mode == 0 || mode == 1, "sttode_set_fused: mode must be 0 or 1 (modes 2-4 were retired)");
+    m->fused_mode = mode;
     return 0;
 }
 
@@ -573,8 +566,7 @@ static bool use_scene_launch(const SttodeModel* m, int n, const int* scene_ptr) 
     return scene_ptr != nullptr && !chain && m->scene_launch > 0 && (ncols_all + 15) / 16 <= m->scene_launch && m->ode_method == 0 &&
            m->ode_steps == 1 && stt_scene_lat_covers(m->Tp, m->TPX, m->NOY);
 }
-static int stage_fused(SttodeModel* m, float* ws, const long* off, int n, int groups, int attn_len, int attn_slots, const float* z, float* pred,
-                       const float* past, const int* scene_ptr, int S, hipStream_t s) {
+static int stage_fused(SttodeModel* m, float* ws, const long* off, int n, int groups, int attn_len, int attn_slots, const float* z, float* pred, hipStream_t s) {
     const float* const* W = m->w;
     const float* attn = nullptr;
     if (attn_len > 1) {
@@ -586,8 +578,7 @@ static int stage_fused(SttodeModel* m, float* ws, const long* off, int n, int gr
         RUN(STT_STAGE_ATTN, s, attention(qkv, ws + off[STT_B_ATTN], groups, attn_len, attn_slots, s));
         attn = ws + off[STT_B_ATTN];
     }
-    RUN(STT_STAGE_FUSED, s, stt_chain_fused(W, ws, off, n, m->K, m->Tp, m->Tf, m->prog_len, z, pred, 12.0f, attn, 64, past, scene_ptr, S, 2, m->b3, m->role_lead, m->drop_tile,
-                                            m->tmo_host, s));
+    RUN(STT_STAGE_FUSED, s, stt_chain_fused(W, ws, off, n, m->K, m->Tp, m->Tf, m->prog_len, z, pred, 12.0f, attn, 64, 2, m->b3, m->drop_tile, m->tmo_host, s));
     return 0;
 }
 
@@ -608,12 +599,9 @@ static int run_serial(SttodeModel* m, const float* past, const int* scene_ptr, i
                           m->drop_tile, m->tmo_host, s));
         return 0;
     }
-    // scene batches on the fused launch: the roles run the front-end of their own tiles (the call is ONE launch); otherwise it is a launch
-    const bool fe_in_role = use_fused(m, n) && scene_ptr != nullptr && m->fe_in_role;
-    if (!fe_in_role)
-        if (int rc = frontend(m, ws, off, past, scene_ptr, n, S, N, s)) return rc;
+    if (int rc = frontend(m, ws, off, past, scene_ptr, n, S, N, s)) return rc;
     if (use_fused(m, n))
-        return stage_fused(m, ws, off, n, G, scene_ptr ? 1 : B, scene_ptr ? 1 : N, z, pred, fe_in_role ? past : nullptr, scene_ptr, S, s);
+        return stage_fused(m, ws, off, n, G, scene_ptr ? 1 : B, scene_ptr ? 1 : N, z, pred, s);
     if (int rc = stage_agents(m, ws, off, n, G, scene_ptr ? 1 : B, scene_ptr ? 1 : N, s, true)) return rc;
     return stage_trajectories(m, ws, off, n, z, pred, s, false);
 }
@@ -749,10 +737,8 @@ static int run_async(SttodeModel* m, const float* past, const int* scene_ptr, in
         ++m->acalls;
         STT_HIP(hipStreamWaitEvent(sf, m->ev_call, 0));
         STT_HIP(hipStreamWaitEvent(sf, m->evB_done[slot], 0));   // the slot's previous user has drained
-        const bool fe_in_role = scene_ptr != nullptr && m->fe_in_role;
-        if (!fe_in_role)
-            if (int rc = frontend(m, ws, off, past, scene_ptr, n, S, N, sf)) return rc;
-        if (int rc = stage_fused(m, ws, off, n, G, scene_ptr ? 1 : B, scene_ptr ? 1 : N, z, pred, fe_in_role ? past : nullptr, scene_ptr, S, sf)) return rc;
+        if (int rc = frontend(m, ws, off, past, scene_ptr, n, S, N, sf)) return rc;
+        if (int rc = stage_fused(m, ws, off, n, G, scene_ptr ? 1 : B, scene_ptr ? 1 : N, z, pred, sf)) return rc;
         STT_HIP(hipEventRecord(m->evB_done[slot], sf));
         m->slot_stream[slot] = sf;
         return 0;

@@ -22,7 +22,7 @@ struct RoleArgs {
     const f32x4* convP; const float* convB; const f32x4* wihP; const f32x4* whhP; const float* gbias; float* state0;
     const f32x4* WAx; const float* b1x; const f32x4* WAy; const float* b1y; const f32x4* WA1; const float* b11;
     float* A0x; float* A0y; float* A1y;
-    // scene front-end inside the role (scene batches; nullptr: the front-end ran as a launch before): set_data's normalisation for the
+    // scene front-end inside the role (role_frontend; scene_lat.hip only, the fused chain launch runs the front-end as a launch before): set_data's normalisation for the
     // tile's 16 agents -- scene origin (mean of the scene's last observed positions, summed in agent order like scene_orig_kernel),
     // normalised track, velocities, flags -- written to the workspace rows the other phases and the trajectory groups read
     const float* past; const int* scene_ptr; int S; float* scene_orig; int* agent_scene;
@@ -32,12 +32,7 @@ struct RoleArgs {
     unsigned* flags;     // [ntiles] tile flags + [1] time-out word, zeroed by the launcher before every launch
     unsigned* tmo_host;  // the model's time-out word in pinned host memory (sttode_timeout_word), or nullptr: set (system scope) with the workspace's
     int ntiles; float ode_time;
-    int lead;            // grid order: the role of tile t sits `lead` groups ahead of the first group that needs it (fused_block_of)
     int drop_tile;       // fault injection (tests): the role of this tile never publishes its flag (-1: none) -- exercises the give-up path
-    // split roles (fused chain launch, default): a tile's per-agent stage as FIVE workgroups instead of one -- E (encoder -> pf) beside
-    // G (block-0 conv + GRU -> state0), then P_0 P_1 P_2 (one layer-1 table each) -- so its latency is max(E, G) + one table (~70 us)
-    // instead of their sum (~150 us): calls with fewer groups than workgroup slots are bound by exactly that latency.
-    int split; unsigned* gflags; unsigned* pflags;   // flags: E [T] | time-out | G [T] | P [3 T]
 };
 
 #ifndef ROLE_PRIO
@@ -86,10 +81,6 @@ __device__ __forceinline__ void agent_role(const RoleArgs& R, int nag, int Tp, i
     // slower than alone (283 vs 150 us, profiles/r03/trace_*), holding a workgroup slot all the while.  Raised priority lets its few
     // instructions issue first; the chain wave loses the same handful of pipe cycles either way.
     __builtin_amdgcn_s_setprio(ROLE_PRIO);
-    if (R.past) {   // (uniform) STTODENet.set_data for this tile
-        role_frontend(R, nag, Tp, ldx, tile, true, true);
-        __syncthreads();                                  // enc_in / last / xpad of this tile are visible to the workgroup
-    }
     if (R.attn == nullptr) {                      // (uniform) attention length 1: softmax over one key == 1, the attention output is v
         embed_lat_body(R.ew, R.enc_in, R.last, R.g, R.qkv, nag, Tp, tile, reinterpret_cast<f32x4*>(smem));
         __syncthreads();                          // g / qkv of this tile are visible to the workgroup; the LDS region changes hands
@@ -156,67 +147,6 @@ __device__ __forceinline__ void role_publish(unsigned* flag, bool really, unsign
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0 && really) __hip_atomic_store(flag, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Split roles of the fused chain launch (RoleArgs::split).  Block r < 2 T: tile r / 2, E (even) or G (odd); 2 T <= r < 5 T: table
-// (r - 2 T) % 3 of tile (r - 2 T) / 3.  Same bodies, same sums as agent_role: the tables carry the same bits.
-__device__ __forceinline__ void split_role(const RoleArgs& R, int nag, int Tp, int ldx, const float* __restrict__ xpad, int r, char* smem) {
-    __builtin_amdgcn_s_setprio(ROLE_PRIO);
-    const int T = R.ntiles;
-    if (r < 2 * T) {
-        const int tile = r >> 1;
-        if ((r & 1) == 0) {   // E: encoder
-            if (R.past) {
-                role_frontend(R, nag, Tp, ldx, tile, true, false);
-                __syncthreads();
-            }
-            if (R.attn == nullptr) {
-                embed_lat_body(R.ew, R.enc_in, R.last, R.g, R.qkv, nag, Tp, tile, reinterpret_cast<f32x4*>(smem));
-                __syncthreads();
-            }
-            C32_TRACE_PHASE(0);
-            post_attn_body<false, true>(R.pw, R.g, R.attn ? R.attn : R.qkv + 128, R.attn ? R.ld_attn : 192, R.pf, nag, R.ode_time, 0, 1, nullptr,
-                                        nullptr, tile, reinterpret_cast<f32x4(*)[4][64]>(smem));
-            C32_TRACE_PHASE(1);
-            role_publish(R.flags + tile, true);
-        } else {              // G: block-0 conv + GRU
-            if (R.past) {
-                role_frontend(R, nag, Tp, ldx, tile, false, true);
-                __syncthreads();
-            }
-            f32x4 (*sH)[6][64] = reinterpret_cast<f32x4(*)[6][64]>(smem);
-            f32x4* sW45 = reinterpret_cast<f32x4*>(smem) + 2 * 6 * 64;
-            if (ldx == 16) gru_lat4_body<1, false, true>(xpad, R.convP, R.convB, R.wihP, R.whhP, R.gbias, R.state0, nag, Tp, tile, sH, sW45);
-            else gru_lat4_body<2, false, true>(xpad, R.convP, R.convB, R.wihP, R.whhP, R.gbias, R.state0, nag, Tp, tile, sH, sW45);
-            C32_TRACE_PHASE(2);
-            role_publish(R.gflags + tile, true);
-        }
-        return;
-    }
-    const int tile = (r - 2 * T) / 3, k = (r - 2 * T) % 3;
-    const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int* ok = reinterpret_cast<int*>(smem);
-    if (threadIdx.x == 0) *ok = 1;
-    __syncthreads();
-    if (wv == 0) {
-        bool o = wait_tiles(R.flags, tile, tile, R.flags + T, lane);
-        if (k < 2) o = wait_tiles(R.gflags, tile, tile, R.flags + T, lane) && o;
-        if (!o && lane == 0) *ok = 0;
-    }
-    __syncthreads();
-    if (!*ok) return;         // (uniform) time-out: the flag stays down, the tile's groups give up in turn
-    const int col = tile * 16 + c;
-    const int colc = col < nag ? col : nag - 1;
-    f32x4 B[14];
-#pragma unroll
-    for (int Tt = 0; Tt < 8; ++Tt) B[Tt] = ld4(R.pf + (size_t)colc * 128 + 16 * Tt + 4 * q);
-#pragma unroll
-    for (int Tt = 0; Tt < 6; ++Tt) B[8 + Tt] = k < 2 ? ld4(R.state0 + (size_t)colc * 96 + 16 * Tt + 4 * q) : B[0];
-    if (k == 0) preact_rows<14, true>(R.WAx, R.b1x, R.A0x, B, col, col < nag, lane, q, wv);
-    else if (k == 1) preact_rows<14, true>(R.WAy, R.b1y, R.A0y, B, col, col < nag, lane, q, wv);
-    else preact_rows<8, true>(R.WA1, R.b11, R.A1y, B, col, col < nag, lane, q, wv);
-    role_publish(R.pflags + 3 * tile + k, tile != R.drop_tile);
 }
 
 // Host side: the weight fragments (model table W, STT_W_*) and workspace rows (ws + off[STT_B_*]) every launch that carries per-agent

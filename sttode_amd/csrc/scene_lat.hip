@@ -33,7 +33,7 @@ struct SceneLatArgs {
     MlpLatArgs x0, y0, y1;      // block-0 decoder_x / decoder_y, block-1 decoder_y (the LDS operands are set by the kernel)
     const f32x4* convP; const float* convB; const f32x4* wihP; const f32x4* whhP; const float* gbias;   // block-1 conv + GRU
     const float* xpad; int ldx;
-    unsigned *tmo, *gflags, *e2flags, *yflags;   // flag words: E [A] | time-out | G [A] | E2 [A] | Y [C] | exit counter | "initialised" word
+    unsigned *tmo, *gruflags, *e2flags, *yflags;   // flag words: E [A] | time-out | G [A] | E2 [A] | Y [C] | exit counter | "initialised" word
     unsigned *done, *magic;     // exit counter of the launch; SL_MAGIC once sttode_workspace_init has zeroed the flag words
     int n, K, Tp, Tf2, ntiles_c;
     long long* dbg;             // diagnostic build only (SL_DIAG_TRACE): [block][8] phase stamps (100 MHz)
@@ -108,7 +108,7 @@ __device__ __forceinline__ void scene_lat_body(const SceneLatArgs& A, char* smem
             };
             gru_bal_body<TPX, false, true, decltype(fe)>(A.xpad, R.convP, R.convB, R.wihP, R.whhP, R.gbias, R.state0, A.n, A.Tp, tile, sH, sX,
                                                          nullptr, fe);
-            role_publish(A.gflags + tile, true);
+            role_publish(A.gruflags + tile, true);
             SL_STAMP(2);
         }
         return;
@@ -145,7 +145,7 @@ __device__ __forceinline__ void scene_lat_body(const SceneLatArgs& A, char* smem
     }
     preact_prime<14, 8, 14, 6>(WA, w2, lane, wave);
     if (s_ok) preact_run<14, 0, 8, 8>(WA, w1, acc, B, lane, wave);
-    if (wave == 0 && inited && !wait_tiles(A.gflags, t_lo, t_hi, A.tmo, lane, R.tmo_host) && lane == 0) s_ok = 0;   // state0, xpad, cur, orig
+    if (wave == 0 && inited && !wait_tiles(A.gruflags, t_lo, t_hi, A.tmo, lane, R.tmo_host) && lane == 0) s_ok = 0;   // state0, xpad, cur, orig
     __syncthreads();
     if (s_ok) {
 #pragma unroll
@@ -257,11 +257,11 @@ int stt_scene_lat(const float* const* W, float* ws, const long* off, int n, int 
     const long ncols = (long)n * K;
     STT_REQUIRE(ncols <= 0x3fffffffL, "stt_scene_lat: too many trajectories");
     const int C_tiles = (int)((ncols + 15) / 16);
-    // the scene form's flag words sit BEHIND the fused launch's region of STT_B_FLAGS (5 tiles + 4 words): that form leaves its flags up
+    // the scene form's flag words sit BEHIND the fused launch's region of STT_B_FLAGS (stt_scene_flags_offset): that form leaves its flags up
     r.flags = (unsigned*)(ws + off[STT_B_FLAGS]) + stt_scene_flags_offset(n);
     r.tmo_host = tmo_host;
-    r.ntiles = A_tiles; r.ode_time = ode_time; r.lead = 0; r.drop_tile = drop_tile; r.split = 0; r.gflags = nullptr; r.pflags = nullptr;
-    a.tmo = r.flags + A_tiles; a.gflags = a.tmo + 1; a.e2flags = a.gflags + A_tiles; a.yflags = a.e2flags + A_tiles;
+    r.ntiles = A_tiles; r.ode_time = ode_time; r.drop_tile = drop_tile;
+    a.tmo = r.flags + A_tiles; a.gruflags = a.tmo + 1; a.e2flags = a.gruflags + A_tiles; a.yflags = a.e2flags + A_tiles;
     a.done = a.yflags + C_tiles; a.magic = a.done + 1;
     a.dbg = nullptr;
 #ifdef SL_DIAG_TRACE

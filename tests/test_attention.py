@@ -174,7 +174,7 @@ def bwd_args(**kw):
 def test_exports_exist_and_abi_version_is_unchanged():
     from sttode_amd import capi
     L = capi.lib()
-    assert capi.ABI_VERSION == 14 and L.sttode_abi_version() == 14
+    assert capi.ABI_VERSION == 15 and L.sttode_abi_version() == 15
     assert hasattr(L, 'sttode_attn_core') and hasattr(L, 'sttode_attn_core_bwd')
     assert len(capi.SIGNATURES['sttode_attn_core']) == len(fwd_args()) and len(capi.SIGNATURES['sttode_attn_core_bwd']) == len(bwd_args())
 

@@ -31,7 +31,7 @@ def test_entry_points_exported_and_declared():
     from test_capi_symbols import header_functions
     fns = header_functions()
     L = capi.lib()
-    assert capi.ABI_VERSION == 14 and L.sttode_abi_version() == 14
+    assert capi.ABI_VERSION == 15 and L.sttode_abi_version() == 15
     for name in ENTRY:
         assert name in fns and name in capi.SIGNATURES and hasattr(L, name), name
         assert len(fns[name]) == len(capi.SIGNATURES[name]), name

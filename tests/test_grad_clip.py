@@ -15,7 +15,7 @@ def _params(seed):
 
 def test_exports_and_abi_version():
     from sttode_amd import capi
-    assert capi.ABI_VERSION == 14
+    assert capi.ABI_VERSION == 15
     for name in ('sttode_grad_norm', 'sttode_adam_step_guarded', 'sttode_grad_scale'):
         assert name in capi.SIGNATURES
         assert hasattr(capi.lib(), name)

@@ -96,7 +96,7 @@ def test_modules_refuse_cpu_tensors():
 def test_new_exports_are_present_and_the_abi_version_is_unchanged():
     from sttode_amd import capi, pmath
     L = capi.lib()
-    assert capi.ABI_VERSION == 14 and L.sttode_abi_version() == 14
+    assert capi.ABI_VERSION == 15 and L.sttode_abi_version() == 15
     for name in ('sttode_pmath_hsoftmax_bwd', 'sttode_pmath_clip', 'sttode_pmath_clip_bwd'):
         assert name in capi.SIGNATURES and hasattr(L, name)
     assert callable(pmath.feature_clip)

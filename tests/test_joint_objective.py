@@ -127,7 +127,7 @@ def test_entry_points_in_header_table_and_library():
     joint = fns['sttode_loss_objective_joint']
     assert joint[:22] == live[:22] and joint[22:24] == ['int seg_len', 'int* seg_best'] and joint[24:] == live[22:]
     assert fns['sttode_loss_diverse_joint'][7] == 'int seg_len'
-    assert capi.ABI_VERSION == 14
+    assert capi.ABI_VERSION == 15
 
 
 def _objective_joint_rc(L, **over):

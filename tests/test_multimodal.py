@@ -167,12 +167,12 @@ def test_entry_point_in_header_table_and_library():
     f = fns['sttode_multimodal']
     assert f[3] == 'const int* seg_ptr_or_NULL' and f[10] == 'float scale' and f[11] == 'double eps' and f[13] == 'long ws_doubles'
     assert f[14] == 'int* count' and f[16] == 'double* mmfde' and f[17] == 'void* stream'
-    assert capi.ABI_VERSION == 14
+    assert capi.ABI_VERSION == 15
     if not os.path.exists(capi.LIB_PATH):
         import __graft_entry__ as g
         g.build()
     L = ctypes.CDLL(capi.LIB_PATH)
-    assert hasattr(L, 'sttode_multimodal') and L.sttode_abi_version() == 14
+    assert hasattr(L, 'sttode_multimodal') and L.sttode_abi_version() == 15
 
 
 def test_refusals_name_the_entry_point_without_a_device():

@@ -26,7 +26,7 @@ def test_library_header_and_table_agree_on_the_new_entry_points():
         for ct, decl in zip(capi.SIGNATURES[name], fns[name]):
             assert (ct is ctypes.c_int and decl.startswith('int ')) or (ct is ctypes.c_float and decl.startswith('float ')) or \
                 (ct is ctypes.c_void_p and '*' in decl), (name, decl)
-    assert L.sttode_abi_version() == capi.ABI_VERSION == 14
+    assert L.sttode_abi_version() == capi.ABI_VERSION == 15
 
 
 def test_new_entry_points_refuse_by_name_without_a_launch():

@@ -259,12 +259,12 @@ def test_yardstick_edge_rules():
     assert maximin_f64(np.zeros((5, 2, 2)), 3)[0].tolist() == [0, 0, 0]
 
 
-def test_entry_point_exported_declared_and_abi_stays_14():
+def test_entry_point_exported_declared_and_abi_version():
     from sttode_amd import capi, evaluate, metrics
     from test_capi_symbols import header_functions
     fns = header_functions()
     L = capi.lib()
-    assert capi.ABI_VERSION == 14 and L.sttode_abi_version() == 14
+    assert capi.ABI_VERSION == 15 and L.sttode_abi_version() == 15
     assert ENTRY in fns and ENTRY in capi.SIGNATURES and hasattr(L, ENTRY)
     assert len(fns[ENTRY]) == len(capi.SIGNATURES[ENTRY]) == 14
     assert callable(metrics.reduce_samples) and callable(evaluate.eval_scenes_reduced)

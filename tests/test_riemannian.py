@@ -137,7 +137,7 @@ def _header():
 def test_exports_exist_in_library_header_and_table_with_equal_arity():
     from sttode_amd import capi
     L, src = capi.lib(), _header()
-    assert capi.ABI_VERSION == 14 and L.sttode_abi_version() == 14 and re.search(r'#define STTODE_ABI_VERSION 14\b', src)
+    assert capi.ABI_VERSION == 15 and L.sttode_abi_version() == 15 and re.search(r'#define STTODE_ABI_VERSION 15\b', src)
     for name in ('sttode_manifold_rowop', 'sttode_riemannian_step'):
         m = re.search(r'\bint\s+%s\s*\(([^;]*?)\)\s*;' % name, src, flags=re.S)
         assert m, name + ' is not declared in include/sttode_hip.h'

@@ -115,14 +115,14 @@ def test_entry_points_in_header_table_and_library():
         assert name in capi.SIGNATURES and len(capi.SIGNATURES[name]) == nargs, name
     assert fns['sttode_sample_spread'][5] == 'float scale' and fns['sttode_sample_spread'][6] == 'double div_scale'
     assert fns['sttode_sample_spread'][7] == 'double* apd' and fns['sttode_sample_spread'][14] == 'float* fde_at_k'
-    assert capi.ABI_VERSION == 14
+    assert capi.ABI_VERSION == 15
     if not os.path.exists(capi.LIB_PATH):
         import __graft_entry__ as g
         g.build()
     L = ctypes.CDLL(capi.LIB_PATH)
     for name in ('sttode_sample_spread', 'sttode_async_sample_spread'):
         assert hasattr(L, name), name
-    assert L.sttode_abi_version() == 14
+    assert L.sttode_abi_version() == 15
 
 
 def test_refusals_name_the_entry_point_without_a_device():
