@@ -612,6 +612,30 @@ int sttode_pmath_hsoftmax_bwd(const float* X, const float* A, const float* P, co
  * pass g [rows,d] -> gx [rows,d]; r > 0. */
 int sttode_pmath_clip(const float* x, float* out, int rows, int d, float r, void* stream);
 int sttode_pmath_clip_bwd(const float* x, const float* g, float* gx, int rows, int d, float r, void* stream);
+/* The curvature on the device, and its gradient (csrc/pmath.hip, csrc/pmath_grad.hip; added within ABI version 15).
+ * c_dev points to ONE float on the device that the kernels read: no host read of a trainable curvature, and the calls can be captured.
+ * Forward: the argument lists of sttode_pmath_rowop (ops 0..11 only), sttode_pmath_matvec and sttode_pmath_pair with c_dev in place of c;
+ * for *c_dev == v the results are bitwise those of the float form at v.  A NULL c_dev is refused; the VALUE cannot be checked on the
+ * host: a curvature that is not positive gives NaN, not a refusal. */
+int sttode_pmath_rowop_c(int op, const float* x, const float* y, float* out, float* out2, int rows, int d, const float* c_dev, void* stream);
+int sttode_pmath_matvec_c(const float* m, const float* x, float* mx_ws, float* xnorm_ws, float* out, int rows, int d, int O,
+                          const float* c_dev, void* stream);
+int sttode_pmath_pair_c(int which, const float* x, const float* y, const float* A, float* out, int P, int R, int d, const float* c_dev,
+                        void* stream);
+/* Backward: the float forms' argument lists with c_dev in place of c, plus gc_ws -- one double per row of the op (rows; rows; P; B), each
+ * row's share of dL/dc -- and gc [1], the gradient of the curvature: WRITTEN (not accumulated) by one workgroup that adds gc_ws in a fixed
+ * order; no atomics, bitwise repeatable.  Tensor-gradient outputs may be NULL where nothing needs them: gx and gy of the row ops (gy must
+ * still be NULL for a one-operand op); gx, gm, gxn_ws of mobius_matvec (gmx_ws too when gx and gm are both NULL; mx_ws is always needed);
+ * gx, gy of dist_matrix; gX, and gA with gP, of _hyperbolic_softmax, whose coef_ws holds SEVEN planes here, 7 B C doubles.  Where they
+ * are given their values are bitwise those of the float form at c = *c_dev. */
+int sttode_pmath_rowop_bwd_c(int op, const float* x, const float* y, const float* g, float* gx, float* gy, int rows, int d, const float* c_dev,
+                             double* gc_ws, float* gc, void* stream);
+int sttode_pmath_matvec_bwd_c(const float* m, const float* x, const float* g, float* mx_ws, float* gmx_ws, float* gxn_ws, float* gx, float* gm,
+                              int rows, int d, int O, const float* c_dev, double* gc_ws, float* gc, void* stream);
+int sttode_pmath_dist_matrix_bwd_c(const float* x, const float* y, const float* g, float* gx, float* gy, int P, int R, int d,
+                                   const float* c_dev, double* gc_ws, float* gc, void* stream);
+int sttode_pmath_hsoftmax_bwd_c(const float* X, const float* A, const float* P, const float* g, double* coef_ws, float* gX, float* gA,
+                                float* gP, int B, int C, int d, const float* c_dev, double* gc_ws, float* gc, void* stream);
 /* Oblique.dist (core/manifolds/oblique.py:36-43): p1 [nb,n1,d], p2 [nb,n2,d] -> acos(clamp(p2 p1^T)) [nb,n2,n1]. */
 int sttode_oblique_dist(const float* p1, const float* p2, float* out, int nb, int n1, int n2, int d, void* stream);
 

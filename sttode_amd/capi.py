@@ -101,6 +101,14 @@ SIGNATURES = {
     'sttode_pmath_hsoftmax_bwd': [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P],
     'sttode_pmath_clip': [_P, _P, _I, _I, _F, _P],
     'sttode_pmath_clip_bwd': [_P, _P, _P, _I, _I, _F, _P],
+    # the curvature as one float on the device, and its gradient (csrc/pmath.hip, csrc/pmath_grad.hip; added within ABI version 15)
+    'sttode_pmath_rowop_c': [_I, _P, _P, _P, _P, _I, _I, _P, _P],
+    'sttode_pmath_matvec_c': [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P],
+    'sttode_pmath_pair_c': [_I, _P, _P, _P, _P, _I, _I, _I, _P, _P],
+    'sttode_pmath_rowop_bwd_c': [_I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P],
+    'sttode_pmath_matvec_bwd_c': [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
+    'sttode_pmath_dist_matrix_bwd_c': [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
+    'sttode_pmath_hsoftmax_bwd_c': [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
     # manifold interface row ops and the Riemannian optimiser step (csrc/manifold.hip; added within ABI version 14)
     'sttode_manifold_rowop': [_I, _I, _P, _P, _P, _P, _P, _I, _I, _F, _P],
     'sttode_riemannian_step': [_I, _P, _I, _L, _D, _D, _D, _D, _D, _D, _L, _P, _P],

@@ -36,10 +36,12 @@ __device__ __forceinline__ MobCoef mob_coef(float a2, float b2, float ab, float 
 }
 
 __global__ __launch_bounds__(256) void pmath_row_kernel(int op, const float* __restrict__ x, const float* __restrict__ y,
-                                                        float* __restrict__ out, float* __restrict__ out2, int rows, int d, float c) {
+                                                        float* __restrict__ out, float* __restrict__ out2, int rows, int d, float cv,
+                                                        const float* __restrict__ cp) {
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= rows) return;
+    const float c = cp ? *cp : cv;   // the curvature: a value of the launch, or one float on the device (the _c entry points)
     const float* xr = x + (size_t)r * d;
     const float* yr = y ? y + (size_t)r * d : nullptr;
     float x2 = 0.f, y2 = 0.f, xy = 0.f;
@@ -211,9 +213,10 @@ __global__ void rowdot_kernel(const float* __restrict__ x, const float* __restri
 
 // pairwise kernels: one thread per (p, q).  which: 0 dist_matrix [P,R]; 1 mobius_addition_batch [P,R,D]; 2 hyperbolic_softmax
 __global__ void pmath_pair_kernel(int which, const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ A,
-                                  float* __restrict__ out, int P, int R, int d, float c) {
+                                  float* __restrict__ out, int P, int R, int d, float cv, const float* __restrict__ cp) {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (long)P * R) return;
+    const float c = cp ? *cp : cv;   // as in pmath_row_kernel
     const int p = idx / R, q = idx % R;
     const float* xr = x + (size_t)p * d;
     const float* yr = y + (size_t)q * d;
@@ -277,7 +280,23 @@ extern "C" int sttode_pmath_rowop(int op, const float* x, const float* y, float*
     STT_REQUIRE((op != OP_MATVEC_FIN && op != OP_PMEAN_PREP) || out2, "sttode_pmath_rowop: this op needs the out2 buffer");
     STT_REQUIRE(c > 0.f || op == OP_OBL_PROJ, "sttode_pmath_rowop: curvature c must be positive");
     hipLaunchKernelGGL(pmath_row_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, op, x, needs_y ? y : nullptr, out, out2,
-                       rows, d, c);
+                       rows, d, c, (const float*)nullptr);
+    STT_HIP(hipGetLastError());
+    return 0;
+}
+
+// The forms with the curvature on the device: c_dev points to ONE float that the kernels read, so a trainable curvature
+// costs no host read and the call can be captured.  The same kernels, the same arithmetic: for *c_dev == v the results are bitwise those
+// of the float form at v.  The value cannot be checked here; the row ops 0..11 only (Oblique.proj has no curvature, 13/14 are internal).
+extern "C" int sttode_pmath_rowop_c(int op, const float* x, const float* y, float* out, float* out2, int rows, int d, const float* c_dev,
+                                    void* stream) {
+    STT_REQUIRE(c_dev, "sttode_pmath_rowop_c: c_dev is NULL (the curvature is read from the device)");
+    STT_REQUIRE(op >= 0 && op < OP_OBL_PROJ, "sttode_pmath_rowop_c: unknown op, or one without a device-curvature form");
+    STT_REQUIRE(x && out && rows > 0 && d > 0, "sttode_pmath_rowop_c: null pointer or empty shape");
+    const bool needs_y = op == OP_MOBIUS_ADD || op == OP_DIST || op == OP_LOGMAP || op == OP_EXPMAP;
+    STT_REQUIRE(!needs_y || y, "sttode_pmath_rowop_c: this op needs a second operand");
+    hipLaunchKernelGGL(pmath_row_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, op, x, needs_y ? y : nullptr, out, out2,
+                       rows, d, 0.f, c_dev);
     STT_HIP(hipGetLastError());
     return 0;
 }
@@ -296,16 +315,28 @@ extern "C" int sttode_pmath_riemannian_grad(const float* x, const float* g, floa
     return 0;
 }
 
-extern "C" int sttode_pmath_matvec(const float* m, const float* x, float* mx_ws, float* xnorm_ws, float* out, int rows, int d, int O,
-                                   float c, void* stream) {
-    STT_REQUIRE(m && x && mx_ws && xnorm_ws && out && rows > 0 && d > 0 && O > 0 && c > 0.f, "sttode_pmath_matvec: bad arguments");
+static int pmath_matvec_launch(const float* m, const float* x, float* mx_ws, float* xnorm_ws, float* out, int rows, int d, int O, float c,
+                               const float* c_dev, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     const long tot = (long)rows * O;
     hipLaunchKernelGGL(rowdot_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, x, m, mx_ws, xnorm_ws, rows, d, O);
     hipLaunchKernelGGL(pmath_row_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, (int)OP_MATVEC_FIN, (const float*)mx_ws,
-                       (const float*)nullptr, out, xnorm_ws, rows, O, c);
+                       (const float*)nullptr, out, xnorm_ws, rows, O, c, c_dev);
     STT_HIP(hipGetLastError());
     return 0;
+}
+
+extern "C" int sttode_pmath_matvec(const float* m, const float* x, float* mx_ws, float* xnorm_ws, float* out, int rows, int d, int O,
+                                   float c, void* stream) {
+    STT_REQUIRE(m && x && mx_ws && xnorm_ws && out && rows > 0 && d > 0 && O > 0 && c > 0.f, "sttode_pmath_matvec: bad arguments");
+    return pmath_matvec_launch(m, x, mx_ws, xnorm_ws, out, rows, d, O, c, nullptr, stream);
+}
+
+extern "C" int sttode_pmath_matvec_c(const float* m, const float* x, float* mx_ws, float* xnorm_ws, float* out, int rows, int d, int O,
+                                     const float* c_dev, void* stream) {
+    STT_REQUIRE(c_dev, "sttode_pmath_matvec_c: c_dev is NULL (the curvature is read from the device)");
+    STT_REQUIRE(m && x && mx_ws && xnorm_ws && out && rows > 0 && d > 0 && O > 0, "sttode_pmath_matvec_c: bad arguments");
+    return pmath_matvec_launch(m, x, mx_ws, xnorm_ws, out, rows, d, O, 0.f, c_dev, stream);
 }
 
 extern "C" int sttode_pmath_pair(int which, const float* x, const float* y, const float* A, float* out, int P, int R, int d, float c,
@@ -314,7 +345,19 @@ extern "C" int sttode_pmath_pair(int which, const float* x, const float* y, cons
     STT_REQUIRE(which != 2 || A, "sttode_pmath_pair: hyperbolic_softmax needs A");
     const long tot = (long)P * R;
     hipLaunchKernelGGL(pmath_pair_kernel, dim3((unsigned)((tot + 127) / 128)), dim3(128), 0, (hipStream_t)stream, which, x, y, A, out, P, R,
-                       d, c);
+                       d, c, (const float*)nullptr);
+    STT_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sttode_pmath_pair_c(int which, const float* x, const float* y, const float* A, float* out, int P, int R, int d,
+                                   const float* c_dev, void* stream) {
+    STT_REQUIRE(c_dev, "sttode_pmath_pair_c: c_dev is NULL (the curvature is read from the device)");
+    STT_REQUIRE(x && y && out && P > 0 && R > 0 && d > 0 && which >= 0 && which <= 2, "sttode_pmath_pair_c: bad arguments");
+    STT_REQUIRE(which != 2 || A, "sttode_pmath_pair_c: hyperbolic_softmax needs A");
+    const long tot = (long)P * R;
+    hipLaunchKernelGGL(pmath_pair_kernel, dim3((unsigned)((tot + 127) / 128)), dim3(128), 0, (hipStream_t)stream, which, x, y, A, out, P, R,
+                       d, 0.f, c_dev);
     STT_HIP(hipGetLastError());
     return 0;
 }
@@ -323,7 +366,7 @@ extern "C" int sttode_pmath_mean(const float* x, float* yl_ws, float* lam_ws, fl
     STT_REQUIRE(x && yl_ws && lam_ws && out && rows > 0 && d > 0 && c > 0.f, "sttode_pmath_mean: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(pmath_row_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, (int)OP_PMEAN_PREP, x, (const float*)nullptr, yl_ws, lam_ws,
-                       rows, d, c);
+                       rows, d, c, (const float*)nullptr);
     hipLaunchKernelGGL(pmean_fin_kernel, dim3(1), dim3(1024), 0, s, (const float*)yl_ws, (const float*)lam_ws, out, rows, d, c);
     STT_HIP(hipGetLastError());
     return 0;

@@ -7,6 +7,8 @@
 // (scalar results: g ds/dp_k in place of L_k, no alpha g / beta g term): ONE WAVE PER ROW, four rows per 256-thread block, as the forward
 // kernel.  Pass 1 forms the five dot products in one sweep (float64 accumulators, wavefront xor-shuffles), the per-row scalar stage runs
 // redundantly on all lanes, pass 2 writes gx and gy with coalesced stores.  No atomics, no LDS, no workspace; only x, y, g are read.
+// The _c entry points read the curvature from one float on the device and give it a gradient: the scalar stage is
+// evaluated a second time with c the one variable, each row's share of dL/dc goes to a float64 workspace and one workgroup adds them.
 //
 // The scalar stage is float64 forward-mode arithmetic (struct DN<N>: a value and N partials; D3: the three partials d/dp_k): 1 - c |x|^2, 1 - u^2 under artanh
 // and the Moebius denominator cancel near the ball boundary (pmath.hip's pair kernel and OP_PMEAN_PREP use float64 for the same reason).
@@ -95,29 +97,95 @@ __device__ __forceinline__ float wsumf(float v) {
     return v;
 }
 
+// The curvature in the scalar stage is a type CT: a plain double in the float-c entry points (no partial is carried for it, the
+// arithmetic is the one this file always had), or one more forward-mode variable DN<N> in the _c entry points, where
+// sqrt(c) is derived from it.  Every formula below is written once for both.
+__device__ __forceinline__ double csqrt(double c) { return sqrt(c); }
+template <int N> __device__ __forceinline__ DN<N> csqrt(const DN<N>& c) { return sqrt_(c); }
+
 // _mobius_add(a, b) = (ca a + cb b) / den from the row scalars of its operands (pmath.py:171-177)
-struct MobD { D3 ca, cb; };
-__device__ __forceinline__ MobD mob_d(const D3& a2, const D3& b2, const D3& ab, double c) {
-    const D3 den = 1.0 + 2.0 * c * ab + (c * c) * (a2 * b2) + cst<3>(EPS5);
-    return MobD{(1.0 + 2.0 * c * ab + c * b2) / den, (1.0 - c * a2) / den};
+template <int N> struct MobD { DN<N> ca, cb; };
+template <int N, class CT> __device__ __forceinline__ MobD<N> mob_d(const DN<N>& a2, const DN<N>& b2, const DN<N>& ab, const CT& c) {
+    const DN<N> den = 1.0 + 2.0 * c * ab + (c * c) * (a2 * b2) + cst<N>(EPS5);
+    return MobD<N>{(1.0 + 2.0 * c * ab + c * b2) / den, (1.0 - c * a2) / den};
 }
 // (-x) (+) y = A (-x) + B y and its norm (pmath.py:207, :335-336)
-struct SubD { D3 A, B, sn; };
-__device__ __forceinline__ SubD sub_d(const D3& p1, const D3& p2, const D3& p3, double c) {
-    const MobD m = mob_d(p1, p2, -1.0 * p3, c);
-    return SubD{m.ca, m.cb, norm_of(m.ca * m.ca * p1 - 2.0 * (m.ca * m.cb * p3) + m.cb * m.cb * p2)};
+template <int N> struct SubD { DN<N> A, B, sn; };
+template <int N, class CT> __device__ __forceinline__ SubD<N> sub_d(const DN<N>& p1, const DN<N>& p2, const DN<N>& p3, const CT& c) {
+    const MobD<N> m = mob_d(p1, p2, -1.0 * p3, c);
+    return SubD<N>{m.ca, m.cb, norm_of(m.ca * m.ca * p1 - 2.0 * (m.ca * m.cb * p3) + m.cb * m.cb * p2)};
 }
-// dist(x, y) (pmath.py:205-208) as a function of p = (|x|^2, |y|^2, <x,y>)
-__device__ __forceinline__ D3 dist_d(double x2, double y2, double xy, double c) {
-    const double sc = sqrt(c);
-    const SubD s = sub_d(var<3>(x2, 0), var<3>(y2, 1), var<3>(xy, 2), c);
+// dist(x, y) (pmath.py:205-208) as a function of p = (|x|^2, |y|^2, <x,y>) and c
+template <int N, class CT> __device__ __forceinline__ DN<N> dist_dn(const DN<N>& p1, const DN<N>& p2, const DN<N>& p3, const CT& c) {
+    const CT sc = csqrt(c);
+    const SubD<N> s = sub_d(p1, p2, p3, c);
     return (2.0 / sc) * artanh_d(sc * s.sn);
+}
+// ... its partials d/dp_k at a constant c (the tensor gradients), and its partial d/dc alone (the three scalars constants)
+__device__ __forceinline__ D3 dist_d(double x2, double y2, double xy, double c) {
+    return dist_dn(var<3>(x2, 0), var<3>(y2, 1), var<3>(xy, 2), c);
+}
+__device__ __forceinline__ double dist_dc(double x2, double y2, double xy, double c) {
+    return dist_dn(cst<1>(x2), cst<1>(y2), cst<1>(xy), var<1>(c, 0)).d[0];
 }
 
 // ---- row ops --------------------------------------------------------------------------------------------------------------------------
+// The scalar stage of the twelve row ops: alpha and beta (vector results) or al = s (scalar results) as functions of the row scalars p and
+// the curvature.  Written once, evaluated in two forms: <3, double> -- p the variables, c a constant: the tensor gradients, the arithmetic
+// this file always had -- and <1, DN<1>> -- c the variable, p constants: d/dc alone.  x2f, cf: the fp32 sum of squares and
+// curvature of the forward kernel's own test, which chooses project's branch.
+template <int N, class CT>
+__device__ __forceinline__ void row_stage(int op, const DN<N>& p1, const DN<N>& p2, const DN<N>& p3, const CT& c, float x2f, float cf, DN<N>& al,
+                                          DN<N>& be) {
+    using D = DN<N>;
+    const CT sc = csqrt(c);
+    al = cst<N>(0.); be = cst<N>(0.);
+    switch (op) {
+        case OPB_PROJECT: {  // pmath.py:98-103 (maxnorm = (1 - 1e-3) / sqrt_c: the clipped branch depends on c)
+            const float normf = fmaxf(sqrtf(x2f), 1e-5f), maxnormf = (1.0f - 1e-3f) / sqrtf(cf);
+            const D norm = clamp_min_(norm_of(p1), EPS5);
+            al = normf > maxnormf ? ((1.0 - 1e-3) / sc) / norm : cst<N>(1.0);
+        } break;
+        case OPB_LAMBDA_X: al = 2.0 / (1.0 - c * p1); break;   // pmath.py:128-129
+        case OPB_MOBIUS_ADD: { const MobD<N> m = mob_d(p1, p2, p3, c); al = m.ca; be = m.cb; } break;
+        case OPB_DIST: al = dist_dn(p1, p2, p3, c); break;
+        case OPB_LOGMAP: {   // pmath.py:334-339 : 2 / sqrt_c / lambda_x * artanh(sqrt_c |sub|) * sub / |sub|
+            const SubD<N> s = sub_d(p1, p2, p3, c);
+            const D k = (1.0 - c * p1) / sc * artanh_d(sc * s.sn) / s.sn;
+            al = -1.0 * (k * s.A); be = k * s.B;
+        } break;
+        case OPB_DIST0: al = (2.0 / sc) * artanh_d(sc * norm_of(p1)); break;   // pmath.py:231-234
+        case OPB_EXPMAP: {   // pmath.py:268-277, y = u
+            const D un = clamp_min_(norm_of(p2), EPS5);
+            const D lam = 2.0 / (1.0 - c * p1);
+            const D s = tanh_clamped_((sc / 2.0) * lam * un) / (sc * un);   // second_term = s u
+            const MobD<N> m = mob_d(p1, s * s * p2, s * p3, c);
+            al = m.ca; be = m.cb * s;
+        } break;
+        case OPB_EXPMAP0: {  // pmath.py:300-304
+            const D un = clamp_min_(norm_of(p1), EPS5);
+            al = tanh_clamped_(sc * un) / (sc * un);
+        } break;
+        case OPB_LOGMAP0: {  // pmath.py:365-368
+            const D yn = clamp_min_(norm_of(p1), EPS5);
+            al = 1.0 / yn / sc * artanh_d(sc * yn);
+        } break;
+        case OPB_P2K: al = 2.0 / (1.0 + c * p1); break;                  // pmath.py:440-442
+        case OPB_K2P: al = 1.0 / (1.0 + sqrt_(1.0 - c * p1)); break;     // pmath.py:445-447
+        case OPB_LORENZ: al = 1.0 / sqrt_(1.0 - c * p1); break;          // pmath.py:450-469
+    }
+}
+
+// CG = false: the float-c form.  CG = true (the _c entry point): the curvature is read from cp[0]; after the float form's own stage, a
+// second evaluation with c the one variable gives the row's share of dL/dc -- d alpha/dc <g,x> + d beta/dc <g,y>, or g ds/dc for a scalar
+// result -- written to gc_ws[r] as one float64.  gx / gy may then be NULL (c alone requires a gradient): the second pass is skipped.
+template <bool CG>
 __global__ __launch_bounds__(256) void pmath_row_bwd_kernel(int op, const float* __restrict__ x, const float* __restrict__ y,
                                                             const float* __restrict__ g, float* __restrict__ gx, float* __restrict__ gy,
-                                                            int rows, int d, float cf) {
+                                                            int rows, int d, float cv, const float* __restrict__ cp,
+                                                            double* __restrict__ gc_ws) {
+    float cf = cv;
+    if constexpr (CG) cf = *cp;
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= rows) return;
@@ -135,43 +203,15 @@ __global__ __launch_bounds__(256) void pmath_row_bwd_kernel(int op, const float*
         if (yr) { const double b = yr[i]; y2 += b * b; xy += a * b; gyd += gi * b; }
     }
     x2 = wsum(x2); y2 = wsum(y2); xy = wsum(xy); gxd = wsum(gxd); gyd = wsum(gyd); x2f = wsumf(x2f);
-    const double c = cf, sc = sqrt(c);
-    const D3 p1 = var<3>(x2, 0), p2 = var<3>(y2, 1), p3 = var<3>(xy, 2);
-    D3 al = cst<3>(0.), be = cst<3>(0.);   // vector results: alpha, beta; scalar results: al = s
-    switch (op) {
-        case OPB_PROJECT: {  // pmath.py:98-103
-            const float normf = fmaxf(sqrtf(x2f), 1e-5f), maxnormf = (1.0f - 1e-3f) / sqrtf(cf);
-            const D3 norm = clamp_min_(norm_of(p1), EPS5);
-            al = normf > maxnormf ? ((1.0 - 1e-3) / sc) / norm : cst<3>(1.0);
-        } break;
-        case OPB_LAMBDA_X: al = 2.0 / (1.0 - c * p1); break;   // pmath.py:128-129
-        case OPB_MOBIUS_ADD: { const MobD m = mob_d(p1, p2, p3, c); al = m.ca; be = m.cb; } break;
-        case OPB_DIST: al = dist_d(x2, y2, xy, c); break;
-        case OPB_LOGMAP: {   // pmath.py:334-339 : 2 / sqrt_c / lambda_x * artanh(sqrt_c |sub|) * sub / |sub|
-            const SubD s = sub_d(p1, p2, p3, c);
-            const D3 k = (1.0 - c * p1) / sc * artanh_d(sc * s.sn) / s.sn;
-            al = -1.0 * (k * s.A); be = k * s.B;
-        } break;
-        case OPB_DIST0: al = (2.0 / sc) * artanh_d(sc * norm_of(p1)); break;   // pmath.py:231-234
-        case OPB_EXPMAP: {   // pmath.py:268-277, y = u
-            const D3 un = clamp_min_(norm_of(p2), EPS5);
-            const D3 lam = 2.0 / (1.0 - c * p1);
-            const D3 s = tanh_clamped_((sc / 2.0) * lam * un) / (sc * un);   // second_term = s u
-            const MobD m = mob_d(p1, s * s * p2, s * p3, c);
-            al = m.ca; be = m.cb * s;
-        } break;
-        case OPB_EXPMAP0: {  // pmath.py:300-304
-            const D3 un = clamp_min_(norm_of(p1), EPS5);
-            al = tanh_clamped_(sc * un) / (sc * un);
-        } break;
-        case OPB_LOGMAP0: {  // pmath.py:365-368
-            const D3 yn = clamp_min_(norm_of(p1), EPS5);
-            al = 1.0 / yn / sc * artanh_d(sc * yn);
-        } break;
-        case OPB_P2K: al = 2.0 / (1.0 + c * p1); break;                  // pmath.py:440-442
-        case OPB_K2P: al = 1.0 / (1.0 + sqrt_(1.0 - c * p1)); break;     // pmath.py:445-447
-        case OPB_LORENZ: al = 1.0 / sqrt_(1.0 - c * p1); break;          // pmath.py:450-469
+    const double c = cf;
+    if constexpr (CG) {
+        DN<1> alc, bec;
+        row_stage(op, cst<1>(x2), cst<1>(y2), cst<1>(xy), var<1>(c, 0), x2f, cf, alc, bec);
+        if (lane == 0) gc_ws[r] = scalar ? (double)g[r] * alc.d[0] : alc.d[0] * gxd + bec.d[0] * gyd;
+        if (!gx && !gy) return;
     }
+    D3 al, be;   // vector results: alpha, beta; scalar results: al = s
+    row_stage(op, var<3>(x2, 0), var<3>(y2, 1), var<3>(xy, 2), c, x2f, cf, al, be);
     // gx = ag g + ax x + ay y ; gy = bg g + by y + bx x
     double ag, ax, ay, bg, by, bx;
     if (scalar) {
@@ -183,11 +223,11 @@ __global__ __launch_bounds__(256) void pmath_row_bwd_kernel(int op, const float*
         ag = al.v; ax = 2.0 * L1; ay = L3;
         bg = be.v; by = 2.0 * L2; bx = L3;
     }
-    float* gxr = gx + (size_t)r * d;
-    float* gyr = yr ? gy + (size_t)r * d : nullptr;
+    float* gxr = (!CG || gx) ? gx + (size_t)r * d : nullptr;
+    float* gyr = yr && (!CG || gy) ? gy + (size_t)r * d : nullptr;
     for (int i = lane; i < d; i += 64) {
         const double a = xr[i], b = yr ? (double)yr[i] : 0., gi = gr ? (double)gr[i] : 0.;
-        gxr[i] = (float)(ag * gi + ax * a + ay * b);
+        if (!CG || gxr) gxr[i] = (float)(ag * gi + ax * a + ay * b);
         if (gyr) gyr[i] = (float)(bg * gi + by * b + bx * a);
     }
 }
@@ -199,9 +239,28 @@ __global__ __launch_bounds__(256) void pmath_row_bwd_kernel(int op, const float*
 // _project's branch is chosen here by a float64 test on the recomputed mx; the forward kernel (pmath.hip OP_MATVEC_FIN) chose it with fp32
 // norms of ITS mx (a sequential fp32 dot product, where this one comes from the training GEMM), so its test cannot be repeated bit for
 // bit: a row whose |res| is within fp32 rounding of maxnorm may get the gradient of the other branch than its forward value came from.
+// The scalar stage, alpha(|mx|^2, |x|, c), once for both forms as row_stage is: <3, double> with q the variables (slots 0, 1), and
+// <1, DN<1>> with c the variable.  CG = true (the _c entry point): c is read from cp[0]; d alpha/dc <g,mx> -- through alpha's own sqrt_c
+// and through _project's maxnorm; mx does not depend on c -- goes to gc_ws[r]; gmx, gxn and gx may be NULL (nothing needs them).
+__device__ __forceinline__ double val_of(double a) { return a; }
+template <int N> __device__ __forceinline__ double val_of(const DN<N>& a) { return a.v; }
+template <int N, class CT> __device__ __forceinline__ DN<N> matvec_stage(const DN<N>& q1, const DN<N>& xnq, const CT& c) {
+    using D = DN<N>;
+    const CT sc = csqrt(c);
+    const D xn = clamp_min_(xnq, EPS5);
+    const D mxn = norm_of(q1);
+    const D ga = tanh_clamped_(mxn / xn * artanh_d(sc * xn)) / (mxn * sc);   // res = ga mx
+    const D norm = clamp_min_(norm_of(ga * ga * q1), EPS5);                 // _project, pmath.py:98-103
+    const CT maxnorm = (1.0 - 1e-3) / sc;
+    return norm.v > val_of(maxnorm) ? ga * (maxnorm / norm) : ga;
+}
+template <bool CG>
 __global__ __launch_bounds__(256) void pmath_matvec_bwd_kernel(const float* __restrict__ mx, const float* __restrict__ x, const float* __restrict__ g,
                                                                float* __restrict__ gmx, float* __restrict__ gxn, float* __restrict__ gx, int rows,
-                                                               int d, int O, float cf) {
+                                                               int d, int O, float cv, const float* __restrict__ cp,
+                                                               double* __restrict__ gc_ws) {
+    float cf = cv;
+    if constexpr (CG) cf = *cp;
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= rows) return;
@@ -212,20 +271,22 @@ __global__ __launch_bounds__(256) void pmath_matvec_bwd_kernel(const float* __re
     for (int i = lane; i < O; i += 64) { const double a = mr[i]; m2 += a * a; gm += (double)gr[i] * a; }
     for (int i = lane; i < d; i += 64) { const double a = xr[i]; x2 += a * a; }
     m2 = wsum(m2); gm = wsum(gm); x2 = wsum(x2);
-    const double c = cf, sc = sqrt(c), xnv = sqrt(x2);
+    const double c = cf, xnv = sqrt(x2);
+    if constexpr (CG) {
+        if (lane == 0) gc_ws[r] = m2 > 0. ? matvec_stage(cst<1>(m2), cst<1>(xnv), var<1>(c, 0)).d[0] * gm : 0.;
+        if (!gmx && !gx) return;
+    }
     double a0 = 0., c1 = 0., dn = 0.;   // mx == 0: zero gradient (the reference's 0/0 behind torch.where gives NaN)
     if (m2 > 0.) {
-        const D3 q1 = var<3>(m2, 0), xn = clamp_min_(var<3>(xnv, 1), EPS5);
-        const D3 mxn = norm_of(q1);
-        const D3 ga = tanh_clamped_(mxn / xn * artanh_d(sc * xn)) / (mxn * sc);   // res = ga mx
-        const D3 norm = clamp_min_(norm_of(ga * ga * q1), EPS5);                 // _project, pmath.py:98-103
-        const double maxnorm = (1.0 - 1e-3) / sc;
-        const D3 al = norm.v > maxnorm ? ga * (maxnorm / norm) : ga;
+        const D3 al = matvec_stage(var<3>(m2, 0), var<3>(xnv, 1), c);
         a0 = al.v; c1 = 2.0 * al.d[0] * gm; dn = al.d[1] * gm;
     }
-    float* go = gmx + (size_t)r * O;
-    for (int i = lane; i < O; i += 64) go[i] = (float)(a0 * (double)gr[i] + c1 * (double)mr[i]);
-    if (lane == 0) gxn[r] = (float)dn;
+    if (!CG || gmx) {
+        float* go = gmx + (size_t)r * O;
+        for (int i = lane; i < O; i += 64) go[i] = (float)(a0 * (double)gr[i] + c1 * (double)mr[i]);
+    }
+    if (lane == 0 && (!CG || gxn)) gxn[r] = (float)dn;
+    if (CG && !gx) return;
     const double kx = xnv > 0. ? dn / xnv : 0.;
     float* gxr = gx + (size_t)r * d;
     for (int i = lane; i < d; i += 64) gxr[i] = (float)(kx * (double)xr[i]);
@@ -235,9 +296,15 @@ __global__ __launch_bounds__(256) void pmath_matvec_bwd_kernel(const float* __re
 // its R partners -> gx; side 1: one wave per y row sums g[p, q] (2 y_q ds/dp2 + x_p ds/dp3) over its P partners -> gy.  Partners in index
 // order, every sum in a fixed order: bitwise repeatable, no atomics.  Scalars in float64 as in the forward pair kernel.  Each lane keeps
 // four elements of the row's sum; a row longer than 256 takes one sweep over the partners per 256 elements.
+// CPTR: the curvature is read from cp[0] (the _c entry point), the arithmetic of the tensor gradients unchanged.  CG (side 0 of the _c
+// entry point only): the row's sum over its partners, in index order, of g[p, q] ds/dc -- dist_dc, a second evaluation with c the one
+// variable -- goes to gc_ws[r] (taken in the first 256-element sweep); gout may then be NULL.
+template <bool CG, bool CPTR>
 __global__ __launch_bounds__(256) void pmath_dist_matrix_bwd_kernel(int side, const float* __restrict__ x, const float* __restrict__ y,
                                                                     const float* __restrict__ g, float* __restrict__ gout, int P, int R, int d,
-                                                                    float cf) {
+                                                                    float cv, const float* __restrict__ cp, double* __restrict__ gc_ws) {
+    float cf = cv;
+    if constexpr (CPTR) cf = *cp;
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int n_self = side ? R : P, n_part = side ? P : R;
@@ -249,18 +316,27 @@ __global__ __launch_bounds__(256) void pmath_dist_matrix_bwd_kernel(int side, co
     for (int i = lane; i < d; i += 64) { const double a = self[i]; s2 += a * a; }
     s2 = wsum(s2);
     for (int base = 0; base < d; base += 256) {
-        double acc[4] = {0., 0., 0., 0.}, ks = 0.;
+        double acc[4] = {0., 0., 0., 0.}, ks = 0., kc = 0.;
         for (int q = 0; q < n_part; ++q) {
             const float* pr = part + (size_t)q * d;
             double q2 = 0., sq = 0.;
             for (int i = lane; i < d; i += 64) { const double a = self[i], b = pr[i]; q2 += b * b; sq += a * b; }
             q2 = wsum(q2); sq = wsum(sq);
+            if constexpr (CG) {
+                if (base == 0)
+                    kc += (double)(side ? g[(size_t)q * R + r] : g[(size_t)r * R + q]) * (side ? dist_dc(q2, s2, sq, c) : dist_dc(s2, q2, sq, c));
+                if (!gout) continue;
+            }
             const D3 s = side ? dist_d(q2, s2, sq, c) : dist_d(s2, q2, sq, c);
             const double gv = side ? g[(size_t)q * R + r] : g[(size_t)r * R + q];
             ks += 2.0 * gv * s.d[side ? 1 : 0];
             const double kp = gv * s.d[2];
 #pragma unroll
             for (int j = 0; j < 4; ++j) { const int i = base + lane + 64 * j; if (i < d) acc[j] += kp * (double)pr[i]; }
+        }
+        if constexpr (CG) {
+            if (base == 0 && lane == 0) gc_ws[r] = kc;
+            if (!gout) return;
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) { const int i = base + lane + 64 * j; if (i < d) gout[(size_t)r * d + i] = (float)(ks * (double)self[i] + acc[j]); }
@@ -277,20 +353,29 @@ __global__ __launch_bounds__(256) void pmath_dist_matrix_bwd_kernel(int side, co
 // The coefficient kernel (one wave per pair) forms the six scalars in float64 -- as the forward pair kernel does, for the same cancellation in
 // cb and 1 - c |v|^2 -- and writes w [6,B,C] once per pair; the row-sum kernel (one wave per output row, partners in index order, each lane
 // four elements of the row, one sweep over the partners per 256 elements) adds the rows: no atomics, every sum in a fixed order.
-__device__ __forceinline__ D6 hsoftmax_d(double pi, double xi, double tau, double al, double be, double ga, double c) {
-    const double sc = sqrt(c);
-    const D6 p = var<6>(pi, 0), x = var<6>(xi, 1), t = var<6>(tau, 2), a = var<6>(al, 3), b = var<6>(be, 4), g = var<6>(ga, 5);
-    const D6 ca = 1.0 - 2.0 * c * t + c * x, cb = 1.0 - c * p;
-    const D6 den = 1.0 - 2.0 * c * t + (c * c) * (p * x) + cst<6>(EPS5);
-    const D6 va = (cb * g - ca * b) / den;
-    const D6 v2 = (ca * ca * p - 2.0 * (ca * cb * t) + cb * cb * x) / (den * den);
-    const D6 an = norm_of(a);
+template <int N, class CT>
+__device__ __forceinline__ DN<N> hsoftmax_dn(const DN<N>& p, const DN<N>& x, const DN<N>& t, const DN<N>& a, const DN<N>& b, const DN<N>& g,
+                                            const CT& c) {
+    const CT sc = csqrt(c);
+    const DN<N> ca = 1.0 - 2.0 * c * t + c * x, cb = 1.0 - c * p;
+    const DN<N> den = 1.0 - 2.0 * c * t + (c * c) * (p * x) + cst<N>(EPS5);
+    const DN<N> va = (cb * g - ca * b) / den;
+    const DN<N> v2 = (ca * ca * p - 2.0 * (ca * cb * t) + cb * cb * x) / (den * den);
+    const DN<N> an = norm_of(a);
     return (2.0 / sc) * an / cb * arsinh_d((2.0 * sc) * va / (an * (1.0 - c * v2)));
 }
+__device__ __forceinline__ D6 hsoftmax_d(double pi, double xi, double tau, double al, double be, double ga, double c) {
+    return hsoftmax_dn(var<6>(pi, 0), var<6>(xi, 1), var<6>(tau, 2), var<6>(al, 3), var<6>(be, 4), var<6>(ga, 5), c);
+}
 
+// CG = true (the _c entry point): c is read from cp[0]; after the float form's six partials, a second evaluation with c the one variable
+// gives the seventh plane of w, g[b, k] d logit / dc.
+template <bool CG>
 __global__ __launch_bounds__(256) void pmath_hsoftmax_coef_kernel(const float* __restrict__ X, const float* __restrict__ A, const float* __restrict__ P,
                                                                   const float* __restrict__ g, double* __restrict__ w, int B, int C, int d,
-                                                                  float cf) {
+                                                                  float cv, const float* __restrict__ cp) {
+    float cf = cv;
+    if constexpr (CG) cf = *cp;
     const int lane = threadIdx.x & 63;
     const long pair = (long)blockIdx.x * 4 + (threadIdx.x >> 6), BC = (long)B * C;
     if (pair >= BC) return;
@@ -308,14 +393,19 @@ __global__ __launch_bounds__(256) void pmath_hsoftmax_coef_kernel(const float* _
         const double gv = g[pair];
 #pragma unroll
         for (int k = 0; k < 6; ++k) w[(size_t)k * BC + pair] = gv * L.d[k];
+        if constexpr (CG)
+            w[(size_t)6 * BC + pair] = gv * hsoftmax_dn(cst<1>(pi), cst<1>(xi), cst<1>(tau), cst<1>(al), cst<1>(be), cst<1>(ga), var<1>((double)cf, 0)).d[0];
     }
 }
 
 // side 0: one wave per X row -> gX; side 1: one wave per class row -> gP and gA (both sum the same partners, the X rows)
+// CG = true (the _c entry point, side 0 only): the row's sum of the seventh plane over its classes, in index order, goes to gc_ws[r];
+// gX may be NULL.
+template <bool CG>
 __global__ __launch_bounds__(256) void pmath_hsoftmax_rowsum_kernel(int side, const float* __restrict__ X, const float* __restrict__ A,
                                                                     const float* __restrict__ P, const double* __restrict__ w,
                                                                     float* __restrict__ gX, float* __restrict__ gA, float* __restrict__ gP, int B,
-                                                                    int C, int d) {
+                                                                    int C, int d, double* __restrict__ gc_ws) {
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int n_self = side ? C : B, n_part = side ? B : C;
@@ -323,6 +413,12 @@ __global__ __launch_bounds__(256) void pmath_hsoftmax_rowsum_kernel(int side, co
     const size_t BC = (size_t)B * C;
     const float* trow = side ? X : P;   // the partner rows that w2 weights
     const float* grow = side ? X : A;   // ... and w5
+    if constexpr (CG) {
+        double kc = 0.;
+        for (int j = 0; j < n_part; ++j) kc += w[6 * BC + (size_t)r * C + j];
+        if (lane == 0) gc_ws[r] = kc;
+        if (!gX) return;
+    }
     for (int base = 0; base < d; base += 256) {
         double at[4] = {0., 0., 0., 0.}, ag[4] = {0., 0., 0., 0.}, s0 = 0., s3 = 0., s4 = 0.;
         for (int j = 0; j < n_part; ++j) {
@@ -381,6 +477,22 @@ __global__ __launch_bounds__(256) void pmath_clip_bwd_kernel(const float* __rest
     for (int i = lane; i < d; i += 64) gx[(size_t)r * d + i] = (float)(kg * (double)gr[i] + kx * (double)xr[i]);
 }
 
+// ---- dL/dc: the per-row float64 shares of gc_ws[rows] -> gc[0].  ONE workgroup of 256 threads: thread t sums rows t, t + 256, ... in
+// that order, then a fixed LDS tree (stride 128, 64, ..., 1) adds the 256 partial sums.  No atomics; the order depends on rows alone, so
+// the float that is stored -- written, not accumulated -- is bitwise repeatable.
+__global__ __launch_bounds__(256) void pmath_gc_finish_kernel(const double* __restrict__ gc_ws, float* __restrict__ gc, long rows) {
+    __shared__ double part[256];
+    double s = 0.;
+    for (long i = threadIdx.x; i < rows; i += 256) s += gc_ws[i];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) gc[0] = (float)part[0];
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------
@@ -394,8 +506,31 @@ extern "C" int sttode_pmath_rowop_bwd(int op, const float* x, const float* y, co
     STT_REQUIRE(!needs_y || (y && gy), "sttode_pmath_rowop_bwd: this op needs a second operand and its gradient buffer gy");
     STT_REQUIRE(needs_y || !gy, "sttode_pmath_rowop_bwd: gy given for an op with one operand");
     STT_REQUIRE(c > 0.f, "sttode_pmath_rowop_bwd: curvature c must be positive");
-    hipLaunchKernelGGL(pmath_row_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, op, x, needs_y ? y : nullptr, g, gx,
-                       needs_y ? gy : nullptr, rows, d, c);
+    hipLaunchKernelGGL(pmath_row_bwd_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, op, x, needs_y ? y : nullptr, g, gx,
+                       needs_y ? gy : nullptr, rows, d, c, (const float*)nullptr, (double*)nullptr);
+    STT_HIP(hipGetLastError());
+    return 0;
+}
+
+// The _c forms: the curvature is ONE float on the device, c_dev, and gets a gradient.  Each row kernel writes its rows'
+// float64 shares of dL/dc to gc_ws (one double per row of the op: rows, rows, P, B), pmath_gc_finish_kernel adds them in a fixed order
+// and WRITES the float gc[0].  The tensor gradients may be NULL when nothing needs them; where they are given, their values are bitwise
+// those of the float form at c = *c_dev.  *c_dev cannot be checked here: a curvature that is not positive gives NaN, not a refusal.
+extern "C" int sttode_pmath_rowop_bwd_c(int op, const float* x, const float* y, const float* g, float* gx, float* gy, int rows, int d,
+                                        const float* c_dev, double* gc_ws, float* gc, void* stream) {
+    STT_REQUIRE(c_dev, "sttode_pmath_rowop_bwd_c: c_dev is NULL (the curvature is read from the device)");
+    STT_REQUIRE(op != 12, "sttode_pmath_rowop_bwd_c: Oblique.proj has no backward pass here");
+    STT_REQUIRE(op != 13 && op != 14, "sttode_pmath_rowop_bwd_c: the internal halves of mobius_matvec / poincare_mean have no backward pass here");
+    STT_REQUIRE(op >= 0 && op < OPB_COUNT, "sttode_pmath_rowop_bwd_c: unknown op");
+    STT_REQUIRE(x && g && rows > 0 && d > 0, "sttode_pmath_rowop_bwd_c: null pointer or empty shape");
+    STT_REQUIRE(gc_ws && gc, "sttode_pmath_rowop_bwd_c: gc_ws [rows] doubles and gc [1] are required");
+    const bool needs_y = op == OPB_MOBIUS_ADD || op == OPB_DIST || op == OPB_LOGMAP || op == OPB_EXPMAP;
+    STT_REQUIRE(!needs_y || y, "sttode_pmath_rowop_bwd_c: this op needs a second operand y");
+    STT_REQUIRE(needs_y || !gy, "sttode_pmath_rowop_bwd_c: gy given for an op with one operand");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(pmath_row_bwd_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, s, op, x, needs_y ? y : nullptr, g, gx,
+                       needs_y ? gy : nullptr, rows, d, 0.f, c_dev, gc_ws);
+    hipLaunchKernelGGL(pmath_gc_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)gc_ws, gc, (long)rows);
     STT_HIP(hipGetLastError());
     return 0;
 }
@@ -413,12 +548,37 @@ extern "C" int sttode_pmath_matvec_bwd(const float* m, const float* x, const flo
     STT_REQUIRE(!stt_tgemm_group_open(), "sttode_pmath_matvec_bwd: not inside a sttode_tgemm_group bracket (its products depend on each other)");
     hipStream_t s = (hipStream_t)stream;
     if (int rc = sttode_tlinear(x, d, 1, m, d, 0, nullptr, nullptr, 0, mx_ws, O, rows, d, O, 0, 0, stream)) return rc;
-    hipLaunchKernelGGL(pmath_matvec_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, (const float*)mx_ws, x, g, gmx_ws, gxn_ws, gx, rows, d, O, c);
+    hipLaunchKernelGGL(pmath_matvec_bwd_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, s, (const float*)mx_ws, x, g, gmx_ws, gxn_ws, gx, rows, d,
+                       O, c, (const float*)nullptr, (double*)nullptr);
     STT_HIP(hipGetLastError());
     if (int rc = sttode_tlinear(gmx_ws, O, 1, m, d, 1, nullptr, nullptr, 0, gx, d, rows, O, d, 0, 1, stream)) return rc;
     STT_HIP(hipMemsetAsync(gm, 0, sizeof(float) * (size_t)O * d, s));
     if (int rc = sttode_twgrad(gmx_ws, O, x, d, 1, gm, d, nullptr, rows, O, d, mx_ws, (long)rows * O, stream)) return rc;
     return sttode_twgrad_flush();   // (inside a sttode_twgrad_defer bracket the split sums would otherwise be added later)
+}
+
+// mobius_matvec backward with the curvature on the device.  gx and gm may each be NULL (then its GEMM is not run); gmx_ws may be NULL when
+// both are, gxn_ws always.  mx_ws is always needed: x m^T is recomputed into it.
+extern "C" int sttode_pmath_matvec_bwd_c(const float* m, const float* x, const float* g, float* mx_ws, float* gmx_ws, float* gxn_ws, float* gx,
+                                         float* gm, int rows, int d, int O, const float* c_dev, double* gc_ws, float* gc, void* stream) {
+    STT_REQUIRE(c_dev, "sttode_pmath_matvec_bwd_c: c_dev is NULL (the curvature is read from the device)");
+    STT_REQUIRE(m && x && g && mx_ws, "sttode_pmath_matvec_bwd_c: null pointer");
+    STT_REQUIRE(gmx_ws || (!gx && !gm), "sttode_pmath_matvec_bwd_c: gx and gm need the workspace gmx_ws");
+    STT_REQUIRE(gc_ws && gc, "sttode_pmath_matvec_bwd_c: gc_ws [rows] doubles and gc [1] are required");
+    STT_REQUIRE(rows > 0 && d > 0 && O > 0, "sttode_pmath_matvec_bwd_c: rows, d, O must be positive");
+    STT_REQUIRE(!stt_tgemm_group_open(), "sttode_pmath_matvec_bwd_c: not inside a sttode_tgemm_group bracket (its products depend on each other)");
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = sttode_tlinear(x, d, 1, m, d, 0, nullptr, nullptr, 0, mx_ws, O, rows, d, O, 0, 0, stream)) return rc;
+    hipLaunchKernelGGL(pmath_matvec_bwd_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, s, (const float*)mx_ws, x, g, gmx_ws, gxn_ws, gx, rows, d,
+                       O, 0.f, c_dev, gc_ws);
+    hipLaunchKernelGGL(pmath_gc_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)gc_ws, gc, (long)rows);
+    STT_HIP(hipGetLastError());
+    if (gx)
+        if (int rc = sttode_tlinear(gmx_ws, O, 1, m, d, 1, nullptr, nullptr, 0, gx, d, rows, O, d, 0, 1, stream)) return rc;
+    if (!gm) return 0;
+    STT_HIP(hipMemsetAsync(gm, 0, sizeof(float) * (size_t)O * d, s));
+    if (int rc = sttode_twgrad(gmx_ws, O, x, d, 1, gm, d, nullptr, rows, O, d, mx_ws, (long)rows * O, stream)) return rc;
+    return sttode_twgrad_flush();
 }
 
 extern "C" int sttode_pmath_dist_matrix_bwd(const float* x, const float* y, const float* g, float* gx, float* gy, int P, int R, int d, float c,
@@ -427,8 +587,28 @@ extern "C" int sttode_pmath_dist_matrix_bwd(const float* x, const float* y, cons
     STT_REQUIRE(P > 0 && R > 0 && d > 0, "sttode_pmath_dist_matrix_bwd: P, R, d must be positive");
     STT_REQUIRE(c > 0.f, "sttode_pmath_dist_matrix_bwd: curvature c must be positive");
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(pmath_dist_matrix_bwd_kernel, dim3((P + 3) / 4), dim3(256), 0, s, 0, x, y, g, gx, P, R, d, c);
-    hipLaunchKernelGGL(pmath_dist_matrix_bwd_kernel, dim3((R + 3) / 4), dim3(256), 0, s, 1, x, y, g, gy, P, R, d, c);
+    hipLaunchKernelGGL((pmath_dist_matrix_bwd_kernel<false, false>), dim3((P + 3) / 4), dim3(256), 0, s, 0, x, y, g, gx, P, R, d, c,
+                       (const float*)nullptr, (double*)nullptr);
+    hipLaunchKernelGGL((pmath_dist_matrix_bwd_kernel<false, false>), dim3((R + 3) / 4), dim3(256), 0, s, 1, x, y, g, gy, P, R, d, c,
+                       (const float*)nullptr, (double*)nullptr);
+    STT_HIP(hipGetLastError());
+    return 0;
+}
+
+// dist_matrix backward with the curvature on the device: gc_ws holds P doubles (the side-0 pass, one wave per x row, sums its partners'
+// shares).  gx and gy may each be NULL; the side-1 pass runs only for gy.
+extern "C" int sttode_pmath_dist_matrix_bwd_c(const float* x, const float* y, const float* g, float* gx, float* gy, int P, int R, int d,
+                                              const float* c_dev, double* gc_ws, float* gc, void* stream) {
+    STT_REQUIRE(c_dev, "sttode_pmath_dist_matrix_bwd_c: c_dev is NULL (the curvature is read from the device)");
+    STT_REQUIRE(x && y && g, "sttode_pmath_dist_matrix_bwd_c: null pointer");
+    STT_REQUIRE(gc_ws && gc, "sttode_pmath_dist_matrix_bwd_c: gc_ws [P] doubles and gc [1] are required");
+    STT_REQUIRE(P > 0 && R > 0 && d > 0, "sttode_pmath_dist_matrix_bwd_c: P, R, d must be positive");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL((pmath_dist_matrix_bwd_kernel<true, true>), dim3((P + 3) / 4), dim3(256), 0, s, 0, x, y, g, gx, P, R, d, 0.f, c_dev, gc_ws);
+    if (gy)
+        hipLaunchKernelGGL((pmath_dist_matrix_bwd_kernel<false, true>), dim3((R + 3) / 4), dim3(256), 0, s, 1, x, y, g, gy, P, R, d, 0.f, c_dev,
+                           (double*)nullptr);
+    hipLaunchKernelGGL(pmath_gc_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)gc_ws, gc, (long)P);
     STT_HIP(hipGetLastError());
     return 0;
 }
@@ -443,9 +623,36 @@ extern "C" int sttode_pmath_hsoftmax_bwd(const float* X, const float* A, const f
     STT_REQUIRE(c > 0.f, "sttode_pmath_hsoftmax_bwd: curvature c must be positive");
     hipStream_t s = (hipStream_t)stream;
     const long BC = (long)B * C;
-    hipLaunchKernelGGL(pmath_hsoftmax_coef_kernel, dim3((unsigned)((BC + 3) / 4)), dim3(256), 0, s, X, A, P, g, coef_ws, B, C, d, c);
-    hipLaunchKernelGGL(pmath_hsoftmax_rowsum_kernel, dim3((B + 3) / 4), dim3(256), 0, s, 0, X, A, P, (const double*)coef_ws, gX, gA, gP, B, C, d);
-    hipLaunchKernelGGL(pmath_hsoftmax_rowsum_kernel, dim3((C + 3) / 4), dim3(256), 0, s, 1, X, A, P, (const double*)coef_ws, gX, gA, gP, B, C, d);
+    hipLaunchKernelGGL(pmath_hsoftmax_coef_kernel<false>, dim3((unsigned)((BC + 3) / 4)), dim3(256), 0, s, X, A, P, g, coef_ws, B, C, d, c,
+                       (const float*)nullptr);
+    hipLaunchKernelGGL(pmath_hsoftmax_rowsum_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, s, 0, X, A, P, (const double*)coef_ws, gX, gA, gP, B, C,
+                       d, (double*)nullptr);
+    hipLaunchKernelGGL(pmath_hsoftmax_rowsum_kernel<false>, dim3((C + 3) / 4), dim3(256), 0, s, 1, X, A, P, (const double*)coef_ws, gX, gA, gP, B, C,
+                       d, (double*)nullptr);
+    STT_HIP(hipGetLastError());
+    return 0;
+}
+
+// _hyperbolic_softmax backward with the curvature on the device: coef_ws holds SEVEN planes [7,B,C] (the seventh: g d logit / dc), gc_ws B
+// doubles (the X-row pass sums the seventh plane over the classes).  gX may be NULL; gA and gP may be NULL together (then the class-row
+// pass is not run).
+extern "C" int sttode_pmath_hsoftmax_bwd_c(const float* X, const float* A, const float* P, const float* g, double* coef_ws, float* gX, float* gA,
+                                           float* gP, int B, int C, int d, const float* c_dev, double* gc_ws, float* gc, void* stream) {
+    STT_REQUIRE(c_dev, "sttode_pmath_hsoftmax_bwd_c: c_dev is NULL (the curvature is read from the device)");
+    STT_REQUIRE(X && A && P && g && coef_ws, "sttode_pmath_hsoftmax_bwd_c: null pointer");
+    STT_REQUIRE(!gA == !gP, "sttode_pmath_hsoftmax_bwd_c: gA and gP are given together or not at all");
+    STT_REQUIRE(gc_ws && gc, "sttode_pmath_hsoftmax_bwd_c: gc_ws [B] doubles and gc [1] are required");
+    STT_REQUIRE(B > 0 && C > 0 && d > 0, "sttode_pmath_hsoftmax_bwd_c: B, C, d must be positive");
+    STT_REQUIRE((long)B * C <= 0x7fffffffL, "sttode_pmath_hsoftmax_bwd_c: more than 2^31 - 1 pairs");
+    hipStream_t s = (hipStream_t)stream;
+    const long BC = (long)B * C;
+    hipLaunchKernelGGL(pmath_hsoftmax_coef_kernel<true>, dim3((unsigned)((BC + 3) / 4)), dim3(256), 0, s, X, A, P, g, coef_ws, B, C, d, 0.f, c_dev);
+    hipLaunchKernelGGL(pmath_hsoftmax_rowsum_kernel<true>, dim3((B + 3) / 4), dim3(256), 0, s, 0, X, A, P, (const double*)coef_ws, gX, gA, gP, B, C,
+                       d, gc_ws);
+    if (gA)
+        hipLaunchKernelGGL(pmath_hsoftmax_rowsum_kernel<false>, dim3((C + 3) / 4), dim3(256), 0, s, 1, X, A, P, (const double*)coef_ws, gX, gA, gP, B,
+                           C, d, (double*)nullptr);
+    hipLaunchKernelGGL(pmath_gc_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)gc_ws, gc, (long)B);
     STT_HIP(hipGetLastError());
     return 0;
 }

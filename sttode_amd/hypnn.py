@@ -3,7 +3,13 @@ attribute and parameter names, repr strings and initial values, so a checkpoint 
 
 Every ``forward`` is a short chain of ``sttode_amd.pmath`` calls: it trains through their fused backward kernels and,
 like them, raises on CPU tensors.  The only torch arithmetic is parameter-sized (``HyperbolicMLR`` scales its normals by ``1 - c |p|^2``);
-nothing batch-sized goes through torch.  The curvature is a Python float without a gradient, so ``train_c=True`` is refused.
+nothing batch-sized goes through torch.
+
+The curvature ``c`` -- a constructor argument, and the per-call ``c=`` of the four layers that have one -- is a Python number or a 1-element
+float32 tensor on the device, passed through to pmath.  An ``nn.Parameter`` given as ``c`` is registered under the name
+``c`` and trained: ``ToPoincare(c=nn.Parameter(torch.tensor([0.7])))`` has the state dict of the reference's ``ToPoincare(0.7, train_c=True)``,
+and one Parameter handed to several layers is one shared, learned curvature.  The constructor flag ``train_c=True`` itself stays refused;
+its message names this spelling.
 """
 import math
 
@@ -42,7 +48,7 @@ class HyperbolicMLR(nn.Module):
             _init_like_linear(w)
 
     def forward(self, x, c=None):
-        c = float(_curvature(self, c))
+        c = _curvature(self, c)
         offsets = pmath.expmap0(self.p_vals, c=c)
         normals = self.a_vals * (1 - c * offsets.square().sum(-1, keepdim=True))
         return pmath._hyperbolic_softmax(x, normals, offsets, c)
@@ -106,13 +112,15 @@ class HyperbolicDistanceLayer(nn.Module):
 
 
 class _BasePointMap(nn.Module):
-    """What ToPoincare and FromPoincare share: a fixed curvature and, with ``train_x``, a trainable base point kept as the tangent
-    vector ``xp`` at the origin (zero at the start, so the map starts as the one at the origin)."""
+    """What ToPoincare and FromPoincare share: a curvature (a number, a tensor, or an ``nn.Parameter``, which is trained) and, with
+    ``train_x``, a trainable base point kept as the tangent vector ``xp`` at the origin (zero at the start, so the map starts as the one
+    at the origin).  ``xp`` is registered before ``c``, the reference's order."""
 
     def __init__(self, c, train_c, train_x, ball_dim):
         super().__init__()
         if train_c:
-            raise NotImplementedError('train_c=True is not supported: the curvature c is a Python float here and has no gradient')
+            raise NotImplementedError('train_c=True is not supported: hand the trainable curvature in as c=nn.Parameter(torch.tensor([c0], '
+                                      'device=...)) instead; it is registered under the name c, as the reference\'s train_c=True does')
         if train_x and ball_dim is None:
             raise ValueError('train_x=True needs ball_dim, the length of the trainable base point xp')
         self.register_parameter('xp', nn.Parameter(torch.zeros(ball_dim)) if train_x else None)
@@ -132,7 +140,8 @@ class ToPoincare(_BasePointMap):
         super().__init__(c, train_c, train_x, ball_dim)
         self.clip_r = clip_r
         self.riemannian = pmath.RiemannianGradient
-        self.riemannian.c = c
+        # the reference's float class attribute: the value c has NOW (a tensor's is read once, here; RiemannianGradient keeps a number)
+        self.riemannian.c = float(c.detach()) if isinstance(c, torch.Tensor) else c
         self._rescale_grad = bool(riemannian)
 
     def grad_fix(self, y):
@@ -153,7 +162,7 @@ class FromPoincare(_BasePointMap):
 
     def __init__(self, c, train_c=False, train_x=False, ball_dim=None):
         super().__init__(c, train_c, train_x, ball_dim)
-        self.train_c = False
+        self.train_c = isinstance(c, nn.Parameter)
 
     def forward(self, x):
         return pmath.logmap(self.base_point(), x, c=self.c) if self.train_x else pmath.logmap0(x, c=self.c)

@@ -261,6 +261,10 @@ class PoincareBall(Manifold):
 
     def __init__(self, c=1.0):
         super().__init__()
+        if isinstance(c, torch.Tensor):
+            raise ValueError('PoincareBall: c must be a positive finite Python float, not a tensor: the manifold ops and the Riemannian '
+                             'optimisers take the curvature as a launch argument and give it no gradient (a trainable curvature is '
+                             'pmath\'s and hypnn\'s: DESIGN.md 4w)')
         if isinstance(c, (bool, torch.Tensor)) or not isinstance(c, (int, float)) or not (0 < c < math.inf):
             raise ValueError(f'PoincareBall: c must be a positive finite Python float, got {c!r}')
         self.c = float(c)

@@ -7,9 +7,15 @@ Gradients: ``project, lambda_x, mobius_add, dist, dist0, expmap, expmap0, logmap
 ``mobius_matvec``, ``dist_matrix``, ``_mobius_addition_batch``, ``_hyperbolic_softmax`` and ``feature_clip`` are differentiable with respect
 to their tensor arguments (``artanh``, ``arsinh`` and ``RiemannianGradient`` always were): fused backward kernels (csrc/pmath_grad.hip,
 DESIGN.md 4q and 4r), first order only (``once_differentiable``).  A function takes that path only when grad mode is on and an input requires
-grad; otherwise it makes exactly the calls of the forward-only path, and the forward values of the two paths are bitwise equal.  ``c`` is a
-Python float and gets no gradient.  ``mobius_matvec`` deviates from the reference in one place: a row with ``x m^T == 0`` gets a zero
-gradient (the reference: NaN).  ``_hyperbolic_softmax`` needs non-zero rows of ``A`` (the reference gives NaN for a zero row).
+grad; otherwise it makes exactly the calls of the forward-only path, and the forward values of the two paths are bitwise equal.
+
+The curvature ``c`` is a Python number, which makes exactly the calls described above, or a 1-element float32 tensor on the inputs' device
+(DESIGN.md 4w): the kernels then read it from the device -- it is never brought to the host, so the calls can be captured into a graph --
+with results bitwise those of the float call at its value, and when it requires grad it gets a gradient of its own shape from the same
+backward kernels (the tensor gradients stay bitwise those of the float path).  Any other tensor ``c`` raises ``capi.SttodeError`` before
+any launch.  ``poincare_mean`` and ``RiemannianGradient.c`` keep a Python number.
+
+``mobius_matvec`` deviates from the reference in one place: a row with ``x m^T == 0`` gets a zero gradient (the reference: NaN).  ``_hyperbolic_softmax`` needs non-zero rows of ``A`` (the reference gives NaN for a zero row).
 ``poincare_mean`` and the Oblique ops stay FORWARD-ONLY: their results are cut off from the graph.
 ``feature_clip(x, r)`` is not a function of the reference's pmath.py: it is the clipping of hyptorch/nn.py's ``ToPoincare(clip_r=r)``.
 """
@@ -30,15 +36,36 @@ def _prep(x):
 
 
 def _wants_grad(*ts):
-    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
+    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in ts)
+
+
+def _curv(c, x):
+    """The curvature as the entry points take it: a Python number as a float (the float-c entry points), a tensor as it is (the _c entry
+    points, which read it on the device) after its dtype, size and device are checked -- by metadata alone, never by its value."""
+    if not isinstance(c, torch.Tensor):
+        return float(c)
+    if c.dtype != torch.float32 or c.numel() != 1 or c.device != x.device:
+        raise capi.SttodeError('a tensor curvature c must be a 1-element float32 tensor on the inputs\' device (%s): got %s, %d element(s), on %s'
+                               % (x.device, c.dtype, c.numel(), c.device))
+    return c
+
+
+def _on_device(c):
+    return isinstance(c, torch.Tensor)
+
+
+def _gc_buffers(c, rows):
+    """Workspace and result of dL/dc for an op of `rows` rows: one float64 per row, and the float that the finishing kernel writes."""
+    return torch.empty(rows, dtype=torch.float64, device=c.device), torch.empty(1, dtype=torch.float32, device=c.device)
 
 
 def _row(op, x, y=None, c=1.0, scalar=False, keepdim=False):
     x = _prep(x)
     if y is not None:
         y = _prep(y)
-    if op != 'oblique_proj' and _wants_grad(x, y):
-        return _RowOp.apply(x, y, op, float(c), scalar, keepdim)
+    c = _curv(c, x)
+    if op != 'oblique_proj' and _wants_grad(x, y, c):
+        return _RowOp.apply(x, y, op, c, scalar, keepdim)
     return _row_fwd(op, x, y, c, scalar, keepdim)
 
 
@@ -49,26 +76,29 @@ def _row_fwd(op, x, y, c, scalar, keepdim):
     d = x.shape[-1]
     rows = x.numel() // d
     out = torch.empty(rows if scalar else (rows, d), dtype=torch.float32, device=x.device)
-    capi.call('sttode_pmath_rowop', _OPS[op], x, y, out, None, rows, d, float(c), capi.stream_ptr())
+    capi.call('sttode_pmath_rowop_c' if _on_device(c) else 'sttode_pmath_rowop', _OPS[op], x, y, out, None, rows, d, c, capi.stream_ptr())
     if scalar:
         return out.view(*x.shape[:-1], 1) if keepdim else out.view(*x.shape[:-1])
     return out.view(x.shape)
 
 
 class _RowOp(torch.autograd.Function):
-    """A row op and its fused backward kernel (sttode_pmath_rowop_bwd).  Saves only its inputs; a broadcast operand's gradient is
-    summed back to the operand's shape."""
+    """A row op and its fused backward kernel (sttode_pmath_rowop_bwd; with a tensor c sttode_pmath_rowop_bwd_c, which also gives
+    dL/dc).  Saves only its inputs; a broadcast operand's gradient is summed back to the operand's shape."""
 
     @staticmethod
     def forward(ctx, x, y, op, c, scalar, keepdim):
-        ctx.save_for_backward(x, y)
-        ctx.op, ctx.c, ctx.scalar = op, c, scalar
+        ctx.save_for_backward(x, y, c if _on_device(c) else None)
+        ctx.op, ctx.c, ctx.scalar = op, c if not _on_device(c) else None, scalar
         return _row_fwd(op, x, y, c, scalar, keepdim)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        x, y = ctx.saved_tensors
+        x, y, c = ctx.saved_tensors
+        if c is not None:
+            return _row_bwd_c(ctx.op, x, y, c, g, ctx.scalar, ctx.needs_input_grad[0] or ctx.needs_input_grad[1], ctx.needs_input_grad[3]) \
+                + (None, None)
         xb, yb = x, y
         if y is not None:
             xb, yb = torch.broadcast_tensors(x, y)
@@ -81,6 +111,24 @@ class _RowOp(torch.autograd.Function):
         gy = torch.empty_like(yb) if y is not None else None
         capi.call('sttode_pmath_rowop_bwd', _OPS[ctx.op], xb, yb, g, gx, gy, rows, d, ctx.c, capi.stream_ptr())
         return gx.sum_to_size(x.shape), (gy.sum_to_size(y.shape) if y is not None else None), None, None, None, None
+
+
+def _row_bwd_c(op, x, y, c, g, scalar, want_tensors, want_c):
+    """The backward pass of a row op whose curvature is on the device: (gx, gy, None, gc)."""
+    xb, yb = x, y
+    if y is not None:
+        xb, yb = torch.broadcast_tensors(x, y)
+        xb, yb = xb.contiguous(), yb.contiguous()
+    d = xb.shape[-1]
+    rows = xb.numel() // d
+    g = _prep(g)
+    assert g.numel() == (rows if scalar else rows * d)
+    gx = torch.empty_like(xb) if want_tensors else None
+    gy = torch.empty_like(yb) if want_tensors and y is not None else None
+    ws, gc = _gc_buffers(c, rows)
+    capi.call('sttode_pmath_rowop_bwd_c', _OPS[op], xb, yb, g, gx, gy, rows, d, c, ws, gc, capi.stream_ptr())
+    return (gx.sum_to_size(x.shape) if gx is not None else None, gy.sum_to_size(y.shape) if gy is not None else None, None,
+            gc.view(c.shape) if want_c else None)
 
 
 def _scalar(which, x):
@@ -209,8 +257,9 @@ def lorenz_factor(x, *, c=1.0, dim=-1, keepdim=False):
 
 def mobius_matvec(m, x, *, c=1.0):
     m, x = _prep(m), _prep(x)
-    if _wants_grad(m, x):
-        return _MatVec.apply(m, x, float(c))
+    c = _curv(c, x)
+    if _wants_grad(m, x, c):
+        return _MatVec.apply(m, x, c)
     return _matvec_fwd(m, x, c)
 
 
@@ -220,27 +269,36 @@ def _matvec_fwd(m, x, c):
     mx = torch.empty(rows, O, dtype=torch.float32, device=x.device)
     xn = torch.empty(rows, dtype=torch.float32, device=x.device)
     out = torch.empty(rows, O, dtype=torch.float32, device=x.device)
-    capi.call('sttode_pmath_matvec', m, x, mx, xn, out, rows, d, O, float(c), capi.stream_ptr())
+    capi.call('sttode_pmath_matvec_c' if _on_device(c) else 'sttode_pmath_matvec', m, x, mx, xn, out, rows, d, O, c, capi.stream_ptr())
     return out.view(*x.shape[:-1], O)
 
 
 class _MatVec(torch.autograd.Function):
-    """mobius_matvec and its backward (sttode_pmath_matvec_bwd: a row kernel + the training GEMMs).  Saves only m and x."""
+    """mobius_matvec and its backward (sttode_pmath_matvec_bwd: a row kernel + the training GEMMs; with a tensor c
+    sttode_pmath_matvec_bwd_c).  Saves only its inputs."""
 
     @staticmethod
     def forward(ctx, m, x, c):
-        ctx.save_for_backward(m, x)
-        ctx.c = c
+        ctx.save_for_backward(m, x, c if _on_device(c) else None)
+        ctx.c = c if not _on_device(c) else None
         return _matvec_fwd(m, x, c)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        m, x = ctx.saved_tensors
+        m, x, c = ctx.saved_tensors
         O, d = m.shape
         rows = x.numel() // d
         g = _prep(g)
         f = dict(dtype=torch.float32, device=x.device)
+        if c is not None:
+            want_m, want_x, want_c = ctx.needs_input_grad
+            mx = torch.empty(rows, O, **f)
+            gmx = torch.empty(rows, O, **f) if want_m or want_x else None
+            gx, gm = torch.empty_like(x) if want_x else None, torch.empty_like(m) if want_m else None
+            ws, gc = _gc_buffers(c, rows)
+            capi.call('sttode_pmath_matvec_bwd_c', m, x, g, mx, gmx, None, gx, gm, rows, d, O, c, ws, gc, capi.stream_ptr())
+            return gm, gx, gc.view(c.shape) if want_c else None
         mx, gmx, gxn = torch.empty(rows, O, **f), torch.empty(rows, O, **f), torch.empty(rows, **f)   # gxn: an output the entry point requires; unused
         gx, gm = torch.empty_like(x), torch.empty_like(m)
         capi.call('sttode_pmath_matvec_bwd', m, x, g, mx, gmx, gxn, gx, gm, rows, d, O, ctx.c, capi.stream_ptr())
@@ -248,18 +306,24 @@ class _MatVec(torch.autograd.Function):
 
 
 class _DistMatrix(torch.autograd.Function):
-    """dist_matrix and its backward (sttode_pmath_dist_matrix_bwd).  Saves only x and y."""
+    """dist_matrix and its backward (sttode_pmath_dist_matrix_bwd; with a tensor c sttode_pmath_dist_matrix_bwd_c).  Saves only its inputs."""
 
     @staticmethod
     def forward(ctx, x, y, c):
-        ctx.save_for_backward(x, y)
-        ctx.c = c
+        ctx.save_for_backward(x, y, c if _on_device(c) else None)
+        ctx.c = c if not _on_device(c) else None
         return _pair(0, x, y, None, c, (x.shape[0], y.shape[0]))
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        x, y = ctx.saved_tensors
+        x, y, c = ctx.saved_tensors
+        if c is not None:
+            want_x, want_y, want_c = ctx.needs_input_grad
+            gx, gy = torch.empty_like(x) if want_x else None, torch.empty_like(y) if want_y else None
+            ws, gc = _gc_buffers(c, x.shape[0])
+            capi.call('sttode_pmath_dist_matrix_bwd_c', x, y, _prep(g), gx, gy, x.shape[0], y.shape[0], x.shape[1], c, ws, gc, capi.stream_ptr())
+            return gx, gy, gc.view(c.shape) if want_c else None
         gx, gy = torch.empty_like(x), torch.empty_like(y)
         capi.call('sttode_pmath_dist_matrix_bwd', x, y, _prep(g), gx, gy, x.shape[0], y.shape[0], x.shape[1], ctx.c, capi.stream_ptr())
         return gx, gy, None
@@ -268,33 +332,40 @@ class _DistMatrix(torch.autograd.Function):
 def _pair(which, x, y, A, c, shape):
     x, y = _prep(x), _prep(y)
     out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    capi.call('sttode_pmath_pair', which, x, y, _prep(A) if A is not None else None, out, x.shape[0], y.shape[0], x.shape[1], float(c),
-              capi.stream_ptr())
+    c = _curv(c, x)
+    capi.call('sttode_pmath_pair_c' if _on_device(c) else 'sttode_pmath_pair', which, x, y, _prep(A) if A is not None else None, out,
+              x.shape[0], y.shape[0], x.shape[1], c, capi.stream_ptr())
     return out
 
 
 def dist_matrix(x, y, c=1.0):
     x, y = _prep(x), _prep(y)
-    if _wants_grad(x, y):
-        return _DistMatrix.apply(x, y, float(c))
+    c = _curv(c, x)
+    if _wants_grad(x, y, c):
+        return _DistMatrix.apply(x, y, c)
     return _pair(0, x, y, None, c, (x.shape[0], y.shape[0]))
 
 
 class _MobiusAdditionBatch(torch.autograd.Function):
     """_mobius_addition_batch and its backward: the forward is the pair kernel's; the backward is mobius_add's row kernel
-    (sttode_pmath_rowop_bwd) on the broadcast operands, summed back to each operand's shape.  Saves only x and y."""
+    (sttode_pmath_rowop_bwd; with a tensor c sttode_pmath_rowop_bwd_c) on the broadcast operands, summed back to each operand's shape.
+    Saves only its inputs."""
 
     @staticmethod
     def forward(ctx, x, y, c):
-        ctx.save_for_backward(x, y)
-        ctx.c = c
+        ctx.save_for_backward(x, y, c if _on_device(c) else None)
+        ctx.c = c if not _on_device(c) else None
         return _pair(1, x, y, None, c, (x.shape[0], y.shape[0], x.shape[1]))
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        x, y = ctx.saved_tensors
+        x, y, c = ctx.saved_tensors
         shape = (x.shape[0], y.shape[0], x.shape[1])
+        if c is not None:
+            gx, gy, _, gc = _row_bwd_c('mobius_add', x.unsqueeze(1), y.unsqueeze(0), c, g, False,
+                                       ctx.needs_input_grad[0] or ctx.needs_input_grad[1], ctx.needs_input_grad[2])
+            return gx.view_as(x) if gx is not None else None, gy.view_as(y) if gy is not None else None, gc
         xb, yb = x.unsqueeze(1).expand(shape).contiguous(), y.unsqueeze(0).expand(shape).contiguous()
         gx, gy = torch.empty_like(xb), torch.empty_like(yb)
         capi.call('sttode_pmath_rowop_bwd', _OPS['mobius_add'], xb, yb, _prep(g), gx, gy, shape[0] * shape[1], shape[2], ctx.c, capi.stream_ptr())
@@ -303,25 +374,35 @@ class _MobiusAdditionBatch(torch.autograd.Function):
 
 def _mobius_addition_batch(x, y, c):
     x, y = _prep(x), _prep(y)
-    if _wants_grad(x, y):
-        return _MobiusAdditionBatch.apply(x, y, float(c))
-    return _pair(1, x, y, None, float(c), (x.shape[0], y.shape[0], x.shape[1]))
+    c = _curv(c, x)
+    if _wants_grad(x, y, c):
+        return _MobiusAdditionBatch.apply(x, y, c)
+    return _pair(1, x, y, None, c, (x.shape[0], y.shape[0], x.shape[1]))
 
 
 class _HyperbolicSoftmax(torch.autograd.Function):
-    """_hyperbolic_softmax and its backward (sttode_pmath_hsoftmax_bwd).  Saves only X, A and P."""
+    """_hyperbolic_softmax and its backward (sttode_pmath_hsoftmax_bwd; with a tensor c sttode_pmath_hsoftmax_bwd_c).  Saves only its
+    inputs."""
 
     @staticmethod
     def forward(ctx, X, A, P, c):
-        ctx.save_for_backward(X, A, P)
-        ctx.c = c
+        ctx.save_for_backward(X, A, P, c if _on_device(c) else None)
+        ctx.c = c if not _on_device(c) else None
         return _pair(2, P, X, A, c, (X.shape[0], P.shape[0]))
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        X, A, P = ctx.saved_tensors
+        X, A, P, c = ctx.saved_tensors
         B, C, d = X.shape[0], P.shape[0], X.shape[1]
+        if c is not None:
+            want_X, want_A, want_P, want_c = ctx.needs_input_grad
+            ws = torch.empty(7, B, C, dtype=torch.float64, device=X.device)
+            gX = torch.empty_like(X) if want_X else None
+            gA, gP = (torch.empty_like(A), torch.empty_like(P)) if want_A or want_P else (None, None)
+            gws, gc = _gc_buffers(c, B)
+            capi.call('sttode_pmath_hsoftmax_bwd_c', X, A, P, _prep(g), ws, gX, gA, gP, B, C, d, c, gws, gc, capi.stream_ptr())
+            return gX, gA if want_A else None, gP if want_P else None, gc.view(c.shape) if want_c else None
         ws = torch.empty(6, B, C, dtype=torch.float64, device=X.device)
         gX, gA, gP = torch.empty_like(X), torch.empty_like(A), torch.empty_like(P)
         capi.call('sttode_pmath_hsoftmax_bwd', X, A, P, _prep(g), ws, gX, gA, gP, B, C, d, ctx.c, capi.stream_ptr())
@@ -330,9 +411,10 @@ class _HyperbolicSoftmax(torch.autograd.Function):
 
 def _hyperbolic_softmax(X, A, P, c):
     X, A, P = _prep(X), _prep(A), _prep(P)
-    if _wants_grad(X, A, P):
-        return _HyperbolicSoftmax.apply(X, A, P, float(c))
-    return _pair(2, P, X, A, float(c), (X.shape[0], P.shape[0]))
+    c = _curv(c, X)
+    if _wants_grad(X, A, P, c):
+        return _HyperbolicSoftmax.apply(X, A, P, c)
+    return _pair(2, P, X, A, c, (X.shape[0], P.shape[0]))
 
 
 def _clip_fwd(x, r):
@@ -371,6 +453,8 @@ def feature_clip(x, r):
 
 def poincare_mean(x, dim=0, c=1.0):
     assert dim == 0 and x.dim() == 2
+    if isinstance(c, torch.Tensor):
+        raise capi.SttodeError('poincare_mean takes a Python number as c: it is forward-only, so a tensor curvature would get no gradient here')
     x = _prep(x)
     rows, d = x.shape
     yl = torch.empty_like(x)
