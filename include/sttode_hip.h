@@ -278,6 +278,37 @@ int sttode_sampler_loss_bwd(const float* mu, const float* logvar, const float* p
                             const float* g_kld, const float* g_div, int n, int K, int nz, int D, float scale, float* dmu,
                             float* dlogvar, float* dmotion, void* stream);
 
+/* Stage-2 objective with its ground-truth terms, one launch over all agents; an agent's K samples are staged once and
+ * serve every term.  Inputs of sttode_sampler_loss, plus gt [n,Tf,2] and mask [n,Tf] (float32; NULL = all ones); motion [n,K,Tf,2],
+ * D = 2 Tf.  Limits: n, nz > 0, K > 1, D even, K * D <= 4096, scale > 0; mu, logvar, motion, gt and every output are required.
+ * Per agent, float32 [n] (best: int32 [n]):
+ *   kld, div    sttode_sampler_loss's, bit for bit (its lane-to-pair assignment and its order of sums).
+ *   rec         min_k sum_t (m_t (x_k,t - y_t))^2 = min_k sum_t m_t^2 |x_k,t - y_t|^2: recon_loss (samplerloss.py:23-29) before its
+ *               mean over agents; the mask multiplies the difference, as there.
+ *   best        the k of that minimum, the smallest on exact ties (an agent masked entirely: K zeros, best 0).
+ *   es_ade      (1/K) sum_k D_ade(x_k, y) - ((K-1)/(2K)) pade,  D_ade(u, v) = (1/Tf) sum_t |m_t (u_t - v_t)|, pade the mean of D_ade over
+ *               the K(K-1)/2 sample pairs: sttode_sample_spread's energy score at scale 1 without a mask.
+ *   es_fde      the same with D_fde(u, v) = |m_Tf-1 (u_Tf-1 - v_Tf-1)| and fpd.
+ *   A masked frame (m_t = 0) contributes zero displacement to both halves; the denominators stay Tf.
+ * Precision: kld and div float32 as sttode_sampler_loss.  rec and the ground-truth half of the energy scores: float64 differences, norms
+ * and sums of the float32 inputs.  The pair half: sqrtf of the float32 dx, dy that the DLow sum forms, summed in float64.
+ * Refused before any launch or write, naming the entry.  No atomics, every sum in a fixed order: the same bits on every run. */
+int sttode_sampler_objective(const float* mu, const float* logvar, const float* pmu, const float* plogvar, const float* motion,
+                             const float* gt, const float* mask, int n, int K, int nz, int D, float scale, float* kld, float* div,
+                             float* rec, int* best, float* es_ade, float* es_fde, void* stream);
+
+/* Backward of sttode_sampler_objective: upstream g_kld, g_div, g_rec, g_es_ade, g_es_fde [n] (each may be NULL = zero) -> dmu, dlogvar
+ * [n*K,nz] and ONE summed dmotion [n,K,Tf,2]; every element is written (zeros where nothing flows).  The same limits and refusals.
+ *   dmu, dlogvar, and dmotion with g_rec = g_es_* = 0: sttode_sampler_loss_bwd's, bit for bit.
+ *   rec:     g_rec 2 m_t (m_t (x_best,t - y_t)) to the one sample `best`, recomputed by the forward's code.
+ *   energy:  ce_t (u(x_k,t - y_t) / K - sum_{j != k} u(x_k,t - x_j,t) / K^2),  u(v) = m_t (m_t v) / |m_t v|,
+ *            ce_t = g_es_ade / Tf + (t == Tf-1 ? g_es_fde : 0).
+ *   u(v) = 0 where |m_t v| = 0 (torch's subgradient of a 2-norm at 0; what sttode_sampler_loss_bwd does for pdist). */
+int sttode_sampler_objective_bwd(const float* mu, const float* logvar, const float* pmu, const float* plogvar, const float* motion,
+                                 const float* gt, const float* mask, const float* g_kld, const float* g_div, const float* g_rec,
+                                 const float* g_es_ade, const float* g_es_fde, int n, int K, int nz, int D, float scale, float* dmu,
+                                 float* dlogvar, float* dmotion, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Training step (csrc/train*.hip, one file per kernel family: index in train.hip): forward-with-tape + backward of STTODENet.forward() (model/STTODE.py:553-568; losses
  * :372-395; what train.py:81-87 drives through total_loss.backward()).  Generic kernels over row-major nn.Parameter storage;

@@ -50,6 +50,9 @@ SIGNATURES = {
     'sttode_sampler_loss': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P],
     'sttode_sampler_loss_bwd': [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P],
     'sttode_sampler_qnet': [_P, _P, _I, _P, _P],
+    # stage-2 objective with the reconstruction and energy-score terms (csrc/sampler_objective.hip)
+    'sttode_sampler_objective': [_P] * 7 + [_I, _I, _I, _I, _F] + [_P] * 7,
+    'sttode_sampler_objective_bwd': [_P] * 12 + [_I, _I, _I, _I, _F] + [_P] * 4,
     # training step (csrc/train*.hip)
     'sttode_tlinear': [_P, _L, _I, _P, _L, _I, _P, _P, _L, _P, _L, _I, _I, _I, _I, _I, _P],
     'sttode_tlinear_tab': [_P, _L, _P, _L, _P, _P, _L, _I, _P, _L, _I, _I, _I, _I, _P],

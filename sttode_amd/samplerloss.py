@@ -61,17 +61,116 @@ def diversity_loss(infer_dec_motion, agent_num, weight, scale, _div=None):
     return uw * weight, uw
 
 
-def compute_sampler_loss(args, fut_motion_orig, infer_dec_motion, batch_size, fut_mask, p_z_dist, q_z_dist_dlow, div_cfg):
-    """samplerloss.py:41-58: total = weighted clamped KL + weighted diversity (reconstruction term disabled upstream)."""
+class _Objective(torch.autograd.Function):
+    """(kld, div, rec, es_ade, es_fde)[a] = sttode_sampler_objective (one launch); backward = sttode_sampler_objective_bwd (one launch,
+    one summed dmotion).  An output nobody uses reaches the kernel as a NULL upstream gradient (= zero)."""
+
+    @staticmethod
+    def forward(ctx, mu, logvar, motion, pmu, plogvar, gt, mask, scale):
+        n, K = motion.shape[:2]
+        D = motion[0, 0].numel()
+        nz = mu.shape[-1]
+        kld, div, rec, es_ade, es_fde = (torch.empty(n, device=mu.device) for _ in range(5))
+        best = torch.empty(n, dtype=torch.int32, device=mu.device)
+        capi.call('sttode_sampler_objective', mu, logvar, pmu, plogvar, motion, gt, mask, n, K, nz, D, float(scale), kld, div, rec, best,
+                  es_ade, es_fde, capi.stream_ptr())
+        ctx.save_for_backward(mu, logvar, motion, gt, *(t for t in (pmu, plogvar, mask) if t is not None))
+        ctx.opt = (pmu is not None, mask is not None)
+        ctx.dims = (n, K, nz, D, float(scale))
+        ctx.set_materialize_grads(False)
+        return kld, div, rec, es_ade, es_fde
+
+    @staticmethod
+    def backward(ctx, *g):
+        mu, logvar, motion, gt, *rest = ctx.saved_tensors
+        pmu, plogvar = (rest.pop(0), rest.pop(0)) if ctx.opt[0] else (None, None)
+        mask = rest.pop(0) if ctx.opt[1] else None
+        n, K, nz, D, scale = ctx.dims
+        g = [None if t is None else t.contiguous().float() for t in g]
+        dmu, dlv, dmo = torch.empty_like(mu), torch.empty_like(logvar), torch.empty_like(motion)
+        capi.call('sttode_sampler_objective_bwd', mu, logvar, pmu, plogvar, motion, gt, mask, *g, n, K, nz, D, scale, dmu, dlv, dmo,
+                  capi.stream_ptr())
+        return dmu, dlv, dmo, None, None, None, None, None
+
+
+def _objective(q, p, motion, gt, fut_mask, scale):
+    """The five per-agent terms of sttode_sampler_objective for motion [n,K,Tf,2], gt [n,Tf,2], fut_mask None | [n,Tf] on any device;
+    differentiable wrt q.mu, q.logvar and motion."""
+    if motion.device.type != 'cuda' or gt.device.type != 'cuda' or q.mu.device.type != 'cuda':
+        raise capi.SttodeError('sampler objective runs only on a HIP device (no CPU fallback)')
+    f = lambda t: t.contiguous().float()
+    n, Tf = motion.shape[0], motion.shape[2] if motion.dim() == 4 else -1
+    if motion.dim() != 4 or motion.shape[3] != 2 or tuple(gt.shape) != (n, Tf, 2):
+        raise capi.SttodeError(f'sampler objective: motion [n,K,Tf,2] and gt [n,Tf,2] expected, got {tuple(motion.shape)} and {tuple(gt.shape)}')
+    mask = None
+    if fut_mask is not None:
+        mask = f(torch.as_tensor(fut_mask).to(motion.device)).detach()
+        if tuple(mask.shape) != (n, Tf):
+            raise capi.SttodeError(f'sampler objective: fut_mask [n,Tf] = {(n, Tf)} expected, got {tuple(mask.shape)}')
+    return _Objective.apply(f(q.mu), f(q.logvar), f(motion), None if p is None else f(p.mu).detach(),
+                            None if p is None else f(p.logvar).detach(), f(gt).detach(), mask, scale)
+
+
+def _motion_only(fut_motion_orig, infer_dec_motion, fut_mask):
+    """The objective's ground-truth terms for callers that have no latent distribution (recon_loss / energy_loss on their own)."""
+    from .dist import Normal
+    if infer_dec_motion.device.type != 'cuda':
+        raise capi.SttodeError('sampler objective runs only on a HIP device (no CPU fallback)')
+    n, K = infer_dec_motion.shape[:2]
+    zeros = torch.zeros(n * K, 1, device=infer_dec_motion.device)
+    return _objective(Normal(mu=zeros, logvar=zeros), None, infer_dec_motion, fut_motion_orig, fut_mask, 1.0)
+
+
+def recon_loss(fut_motion_orig, infer_dec_motion, fut_mask, weight, _rec=None):
+    """samplerloss.py:23-31: mean over agents of min_k sum_t |mask_t (x_k,t - y_t)|^2 -> (loss, loss_unweighted)."""
+    if _rec is None:
+        _rec = _motion_only(fut_motion_orig, infer_dec_motion, fut_mask)[2]
+    uw = _rec.mean()
+    return uw * weight, uw
+
+
+def energy_loss(fut_motion_orig, infer_dec_motion, fut_mask, weight, kind='ade', _es=None):
+    """Mean over agents of the energy score of the K samples against the ground truth, on the per-frame mean
+    displacement ('ade') or the last frame's ('fde') -> (loss, loss_unweighted)."""
+    if kind not in ('ade', 'fde'):
+        raise ValueError(f"energy_loss: kind 'ade' | 'fde', got {kind!r}")
+    if _es is None:
+        _es = _motion_only(fut_motion_orig, infer_dec_motion, fut_mask)[3 if kind == 'ade' else 4]
+    uw = _es.mean()
+    return uw * weight, uw
+
+
+def compute_sampler_loss(args, fut_motion_orig, infer_dec_motion, batch_size, fut_mask, p_z_dist, q_z_dist_dlow, div_cfg, *, recon=False,
+                         energy_weight=0.0, energy_kind='ade'):
+    """samplerloss.py:41-58: total = weighted clamped KL + weighted diversity (reconstruction term disabled upstream).
+    recon=True adds args.recon_weight * recon_loss (the call upstream comments out; loss_dict['recon']); energy_weight > 0 adds that weight
+    times the mean energy score (loss_dict['energy']).  With either on, the whole objective is one sttode_sampler_objective call and one
+    backward call; with both off, exactly the calls and the dict of the reference's two-term objective."""
     agent_num = fut_motion_orig.shape[0]
-    kld_a, div_a = _per_agent(q_z_dist_dlow, p_z_dist, infer_dec_motion, div_cfg['scale'])
+    if energy_kind not in ('ade', 'fde'):
+        raise ValueError(f"compute_sampler_loss: energy_kind 'ade' | 'fde', got {energy_kind!r}")
+    energy = energy_weight is not None and float(energy_weight) > 0.0
+    if not recon and not energy:
+        kld_a, div_a = _per_agent(q_z_dist_dlow, p_z_dist, infer_dec_motion, div_cfg['scale'])
+    else:
+        kld_a, div_a, rec_a, es_ade_a, es_fde_a = _objective(q_z_dist_dlow, p_z_dist, infer_dec_motion, fut_motion_orig, fut_mask,
+                                                             div_cfg['scale'])
     kld_loss, _ = compute_z_kld(q_z_dist_dlow, p_z_dist, agent_num, args.kld_min_clamp, args.kld_weight, _kld=kld_a)
     div_loss, _ = diversity_loss(infer_dec_motion, agent_num, div_cfg['weight'], div_cfg['scale'], _div=div_a)
     total_loss = kld_loss + div_loss
     loss_dict = {'kld': kld_loss, 'diverse': div_loss, 'recon': 0}
+    if recon:
+        loss_dict['recon'], _ = recon_loss(fut_motion_orig, infer_dec_motion, fut_mask, args.recon_weight, _rec=rec_a)
+        total_loss = total_loss + loss_dict['recon']
+    if energy:
+        loss_dict['energy'], _ = energy_loss(fut_motion_orig, infer_dec_motion, fut_mask, float(energy_weight), energy_kind,
+                                             _es=es_ade_a if energy_kind == 'ade' else es_fde_a)
+        total_loss = total_loss + loss_dict['energy']
     return total_loss, loss_dict, dict(loss_dict)
 
 
-def compute_sampler_loss_nba(args, fut_motion_orig, infer_dec_motion, batch_size, p_z_dist, q_z_dist_dlow, div_cfg):
+def compute_sampler_loss_nba(args, fut_motion_orig, infer_dec_motion, batch_size, p_z_dist, q_z_dist_dlow, div_cfg, *, recon=False,
+                             energy_weight=0.0, energy_kind='ade'):
     """samplerloss.py:60-73."""
-    return compute_sampler_loss(args, fut_motion_orig, infer_dec_motion, batch_size, None, p_z_dist, q_z_dist_dlow, div_cfg)
+    return compute_sampler_loss(args, fut_motion_orig, infer_dec_motion, batch_size, None, p_z_dist, q_z_dist_dlow, div_cfg, recon=recon,
+                                energy_weight=energy_weight, energy_kind=energy_kind)
