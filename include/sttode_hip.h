@@ -669,10 +669,35 @@ int sttode_pmath_hsoftmax_bwd_c(const float* X, const float* A, const float* P, 
                                 float* gP, int B, int C, int d, const float* c_dev, double* gc_ws, float* gc, void* stream);
 /* Oblique.dist (core/manifolds/oblique.py:36-43): p1 [nb,n1,d], p2 [nb,n2,d] -> acos(clamp(p2 p1^T)) [nb,n2,n1]. */
 int sttode_oblique_dist(const float* p1, const float* p2, float* out, int nb, int n1, int n2, int d, void* stream);
+/* Opt-in gradients through poincare_mean and the Oblique entry points (csrc/pmath.hip, csrc/pmath_grad.hip; added within
+ * ABI version 15).
+ * poincare_mean (pmath.py:472-479) at a general shape: x [outer,R,inner,d] -> out [outer,inner,d], the mean over R, with no permuted copy
+ * (pmath.py:475-479 with dim any but the last).  Workspaces yl_ws as x, lam_ws [outer,R,inner].  One block per group runs the sums of
+ * sttode_pmath_mean in its order: a group's result is bitwise that of sttode_pmath_mean on its rows.  The curvature is *c_dev when c_dev is
+ * given (one float on the device, unchecked), else c (> 0, finite).  klein [outer,inner,d] and lsum [outer,inner] (each may be NULL)
+ * receive the Klein mean before k2p and the sum of the Lorentz factors. */
+int sttode_pmath_mean_seg(const float* x, float* yl_ws, float* lam_ws, float* out, float* klein, float* lsum, int outer, int R, int inner,
+                          int d, float c, const float* c_dev, void* stream);
+/* poincare_mean backward: g [outer,inner,d] -> gx as x, WRITTEN.  Workspaces gS_ws [outer inner d] and gL_ws [outer inner] doubles: a group
+ * stage (one wave per group: the Klein sums recomputed in float64 from x, then k2p's vector-Jacobian product) and a row stage (one wave per
+ * row).  Two launches, no atomics, bitwise repeatable.  The _c form reads the curvature from c_dev and WRITES its gradient gc [1] in a third
+ * launch, from gc_ws: outer R inner + outer inner doubles (each row's share, then each group's); its gx may be NULL. */
+int sttode_pmath_mean_bwd(const float* x, const float* g, double* gS_ws, double* gL_ws, float* gx, int outer, int R, int inner, int d, float c,
+                          void* stream);
+int sttode_pmath_mean_bwd_c(const float* x, const float* g, double* gS_ws, double* gL_ws, float* gx, int outer, int R, int inner, int d,
+                            const float* c_dev, double* gc_ws, float* gc, void* stream);
+/* Oblique.proj backward (oblique.py:15-16): gp = (g - <g,y> y) / |p| with y = p / |p|, rows of [rows,d]; a zero row gives NaN as the
+ * forward does. */
+int sttode_oblique_proj_bwd(const float* p, const float* g, float* gp, int rows, int d, void* stream);
+/* Oblique.dist backward (oblique.py:36-43): g [nb,n2,n1] -> gp1 [nb,n1,d], gp2 [nb,n2,d] (either may be NULL, not both).  The clamp at
+ * +-(1 - 1e-4) has torch.clamp's gradient: zero where the un-clamped inner product is strictly outside.  One launch per output, row sums in
+ * a fixed order. */
+int sttode_oblique_dist_bwd(const float* p1, const float* p2, const float* g, float* gp1, float* gp2, int nb, int n1, int n2, int d,
+                            void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Riemannian optimisation (csrc/manifold.hip): the manifold interface of core/manifolds/base.py as row operations, and
- * Riemannian Adam / SGD over every manifold parameter of a param group in one launch.  Added within ABI version 14.  Forward values only.
+ * Riemannian Adam / SGD over every manifold parameter of a param group in one launch.  Added within ABI version 14.  sttode_manifold_rowop_bwd is the row ops' backward pass.
  * ---------------------------------------------------------------------------------------------- */
 enum SttodeManifold { STT_MF_EUCLIDEAN = 0, STT_MF_OBLIQUE, STT_MF_POINCARE, STT_MF_COUNT };
 enum SttodeManifoldOp { STT_MOP_PROJ_TAN = 0, STT_MOP_EXPMAP, STT_MOP_PTRANSP, STT_MOP_INNER, STT_MOP_RETR, STT_MOP_RETR_TRANSP, STT_MOP_COUNT };
@@ -687,6 +712,14 @@ enum SttodeRiemannianRule { STT_RULE_ADAM = 0, STT_RULE_SGD, STT_RULE_COUNT };
  * c: the ball's curvature magnitude (> 0, finite); ignored by the other manifolds.  Operands an op does not take may be NULL. */
 int sttode_manifold_rowop(int op, int manifold, const float* a, const float* b, const float* w, float* out, float* out2, int rows, int d,
                           float c, void* stream);
+/* The backward pass of the six row ops on every manifold (added within ABI version 15; core/manifolds/oblique.py:15-27,
+ * :60-74 and the ball's operations above, differentiated as the forward evaluates them).  g: the upstream gradient, [rows,d] ([rows] for
+ * INNER); g2: RETR_TRANSP's second upstream gradient (of out2), NULL for every other op; for RETR_TRANSP either of g, g2 may be NULL,
+ * meaning zero.  ga, gb, gw [rows,d]: the gradients of the operands, WRITTEN; each may be NULL (not all), gw is ignored by the ops that take
+ * no third operand.  Branches differentiate as taken: Oblique expmap below |u| = 1e-4 as proj(p + u); the ball's retraction through
+ * project's clip, chosen by the forward kernel's own fp32 test.  One launch, no workspace, no atomics, bitwise repeatable. */
+int sttode_manifold_rowop_bwd(int op, int manifold, const float* a, const float* b, const float* w, const float* g, const float* g2, float* ga,
+                              float* gb, float* gw, int rows, int d, float c, void* stream);
 /* One optimiser step of every parameter of a DEVICE table.  A wave steps one WAVE SLOT: one row of d > 32 elements, two rows of d <= 32,
  * four rows of d <= 16; a parameter takes ceil(rows / rows per slot) slots.  A table row is STTODE_RIEMANNIAN_ITEM_WORDS 8-byte words:
  * parameter, state buffer 1 (Adam exp_avg [rows,d]; SGD momentum_buffer or NULL for momentum 0), state buffer 2 (Adam exp_avg_sq [rows];

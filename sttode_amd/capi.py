@@ -115,6 +115,13 @@ SIGNATURES = {
     # manifold interface row ops and the Riemannian optimiser step (csrc/manifold.hip; added within ABI version 14)
     'sttode_manifold_rowop': [_I, _I, _P, _P, _P, _P, _P, _I, _I, _F, _P],
     'sttode_riemannian_step': [_I, _P, _I, _L, _D, _D, _D, _D, _D, _D, _L, _P, _P],
+    # opt-in gradients through poincare_mean, the Oblique entry points and the manifold row ops (added within ABI version 15)
+    'sttode_pmath_mean_seg': [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P],
+    'sttode_pmath_mean_bwd': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
+    'sttode_pmath_mean_bwd_c': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P],
+    'sttode_oblique_proj_bwd': [_P, _P, _P, _I, _I, _P],
+    'sttode_oblique_dist_bwd': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    'sttode_manifold_rowop_bwd': [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P],
     # Gromov delta-hyperbolicity (csrc/delta.hip)
     'sttode_delta_dist': [_P, _I, _I, _P, _I, _I, _P, _L, _P, _P],
     'sttode_delta_workspace': [_I, _I, ctypes.POINTER(ctypes.c_long)],

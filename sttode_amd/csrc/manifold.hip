@@ -83,6 +83,87 @@ __global__ __launch_bounds__(256) void manifold_row_kernel(int op, int man, cons
     }
 }
 
+// ---- row ops, backward ---------------------------------------------------------------------------------------------------
+// Every forward row is out = ca a + cb b + cw w (retr_transp: a second row out2 of the same form) with coefficients that are functions of
+// the five dot products p = (|a|^2, |b|^2, <a,b>, <a,w>, <b,w>).  With T_j = sum_k dc_k/dp_j <g, operand_k> (and the same over out2's
+// coefficients and g2) the vector-Jacobian product is
+//     ga = ca g + 2 T_0 a + T_2 b + T_3 w,   gb = cb g + 2 T_1 b + T_2 a + T_4 w,   gw = cw g + T_3 a + T_4 b
+// (inner: the scalar f(p) in place of the coefficients, T_j = g df/dp_j, no c g terms).  The coefficients and their partials come from
+// the forward's own mf_* functions evaluated on DN<5>: the gyration, the clamps and the branches are differentiated as the forward took
+// them, with no second formula to keep in step.  The ball's retraction takes project's branch by the forward kernel's fp32 test.
+// ONE WAVE PER ROW as the forward: pass 1, the five dot products and the operands' dot products with g and g2 in float64; the scalar
+// stage; pass 2, the three gradient rows with plain coalesced stores.  ONE launch, no atomics, no workspace; every sum in a fixed order.
+using D5 = DN<5>;
+struct MfCoef { D5 a, b, w; };   // a row as ca a + cb b + cw w
+
+__global__ __launch_bounds__(256) void manifold_row_bwd_kernel(int op, int man, const float* __restrict__ a, const float* __restrict__ b,
+                                                               const float* __restrict__ w, const float* __restrict__ g,
+                                                               const float* __restrict__ g2, float* __restrict__ ga, float* __restrict__ gb,
+                                                               float* __restrict__ gw, int rows, int d, double c) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const bool scalar = op == MOP_INNER;
+    const float* ar = a + (size_t)r * d;
+    const float* br = b + (size_t)r * d;
+    const float* wr = w ? w + (size_t)r * d : nullptr;
+    const float* gr = g && !scalar ? g + (size_t)r * d : nullptr;
+    const float* hr = g2 ? g2 + (size_t)r * d : nullptr;
+    double a2 = 0., b2 = 0., ab = 0., aw = 0., bw = 0., ga_ = 0., gb_ = 0., gw_ = 0., ha_ = 0., hb_ = 0., hw_ = 0.;
+    for (int i = lane; i < d; i += 64) {
+        const double x = ar[i], y = br[i], z = wr ? (double)wr[i] : 0., gi = gr ? (double)gr[i] : 0., hi = hr ? (double)hr[i] : 0.;
+        a2 += x * x; b2 += y * y; ab += x * y; aw += x * z; bw += y * z;
+        ga_ += gi * x; gb_ += gi * y; gw_ += gi * z; ha_ += hi * x; hb_ += hi * y; hw_ += hi * z;
+    }
+    a2 = mf_wsum(a2); b2 = mf_wsum(b2); ab = mf_wsum(ab); aw = mf_wsum(aw); bw = mf_wsum(bw);
+    ga_ = mf_wsum(ga_); gb_ = mf_wsum(gb_); gw_ = mf_wsum(gw_); ha_ = mf_wsum(ha_); hb_ = mf_wsum(hb_); hw_ = mf_wsum(hw_);
+    const D5 A2 = var<5>(a2, 0), B2 = var<5>(b2, 1), AB = var<5>(ab, 2), AW = var<5>(aw, 3), BW = var<5>(bw, 4), Z = cst<5>(0.);
+    MfCoef c1 = {Z, Z, Z}, c2 = {Z, Z, Z};
+    double T[5];
+    switch (op) {
+        case MOP_PROJ_TAN: { const MfLin2T<D5> e = mf_egrad2rgrad(man, c, A2, AB); c1.a = e.b; c1.b = e.a; } break;
+        case MOP_EXPMAP: { const MfLin2T<D5> e = mf_expmap(man, c, A2, B2, AB); c1.a = e.a; c1.b = e.b; } break;
+        case MOP_PTRANSP: { const MfLin3T<D5> p = mf_ptransp(man, c, A2, B2, AB, AW, BW); c1.a = p.x; c1.b = p.y; c1.w = p.w; } break;
+        case MOP_INNER: c1.a = mf_inner_scale(man, c, A2) * (wr ? BW : B2); break;   // the scalar f(p)
+        default: {   // MOP_RETR, MOP_RETR_TRANSP
+            const MfLin2T<D5> e = mf_expmap(man, c, A2, B2, AB);
+            float y2f = 0.f;
+            if (man == MF_POINCARE) {   // the forward kernel's own test, on the row it rounded
+                for (int i = lane; i < d; i += 64) { const float y = (float)(e.a.v * (double)ar[i] + e.b.v * (double)br[i]); y2f += y * y; }
+                y2f = mf_wsumf(y2f);
+            }
+            const D5 k = mf_retr_scale(man, c, e.a * e.a * A2 + 2.0 * e.a * e.b * AB + e.b * e.b * B2, y2f);
+            const D5 ya = k * e.a, yb = k * e.b;
+            c1.a = ya; c1.b = yb;
+            if (op == MOP_RETR_TRANSP) {
+                const D5 y2 = ya * ya * A2 + 2.0 * ya * yb * AB + yb * yb * B2, xy = ya * A2 + yb * AB, yw = ya * AW + yb * BW;
+                const MfLin3T<D5> p = mf_ptransp(man, c, A2, y2, xy, AW, yw);
+                c2.a = p.y * ya + p.x; c2.b = p.y * yb; c2.w = p.w;
+            }
+        } break;
+    }
+    double ka = 0., kb = 0., kw = 0., ha = 0., hb = 0., hw = 0.;   // the factors of g and g2 in ga, gb, gw
+    if (scalar) {
+        const double gs = g[r];
+#pragma unroll
+        for (int j = 0; j < 5; ++j) T[j] = gs * c1.a.d[j];
+    } else {
+#pragma unroll
+        for (int j = 0; j < 5; ++j)
+            T[j] = c1.a.d[j] * ga_ + c1.b.d[j] * gb_ + c1.w.d[j] * gw_ + c2.a.d[j] * ha_ + c2.b.d[j] * hb_ + c2.w.d[j] * hw_;
+        ka = c1.a.v; kb = c1.b.v; kw = c1.w.v; ha = c2.a.v; hb = c2.b.v; hw = c2.w.v;
+    }
+    float* gar = ga ? ga + (size_t)r * d : nullptr;
+    float* gbr = gb ? gb + (size_t)r * d : nullptr;
+    float* gwr = gw && wr ? gw + (size_t)r * d : nullptr;
+    for (int i = lane; i < d; i += 64) {
+        const double x = ar[i], y = br[i], z = wr ? (double)wr[i] : 0., gi = gr ? (double)gr[i] : 0., hi = hr ? (double)hr[i] : 0.;
+        if (gar) gar[i] = (float)(ka * gi + ha * hi + 2.0 * T[0] * x + T[2] * y + T[3] * z);
+        if (gbr) gbr[i] = (float)(kb * gi + hb * hi + 2.0 * T[1] * y + T[2] * x + T[4] * z);
+        if (gwr) gwr[i] = (float)(kw * gi + hw * hi + T[3] * x + T[4] * y);
+    }
+}
+
 // ---- the optimiser step -------------------------------------------------------------------------------------------------------------------
 // One row of the device table per parameter (10 x 8 bytes): the parameter, its two state buffers (Adam: exp_avg [rows, d], exp_avg_sq
 // [rows]; SGD: momentum_buffer or NULL, unused), its gradient, the row length d, the row count, the first wave slot (ascending from 0), the
@@ -217,6 +298,24 @@ extern "C" int sttode_manifold_rowop(int op, int manifold, const float* a, const
     const bool takes_w = op == MOP_PTRANSP || op == MOP_RETR_TRANSP || op == MOP_INNER;
     hipLaunchKernelGGL(manifold_row_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, op, manifold, a, b, takes_w ? w : nullptr, out,
                        out2, rows, d, (double)c);
+    STT_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sttode_manifold_rowop_bwd(int op, int manifold, const float* a, const float* b, const float* w, const float* g, const float* g2,
+                                         float* ga, float* gb, float* gw, int rows, int d, float c, void* stream) {
+    STT_REQUIRE(op >= 0 && op < MOP_COUNT, "sttode_manifold_rowop_bwd: unknown op");
+    STT_REQUIRE(manifold >= 0 && manifold < MF_COUNT, "sttode_manifold_rowop_bwd: unknown manifold");
+    STT_REQUIRE(a && b, "sttode_manifold_rowop_bwd: null pointer");
+    STT_REQUIRE(rows > 0 && d > 0, "sttode_manifold_rowop_bwd: empty shape");
+    STT_REQUIRE(w || (op != MOP_PTRANSP && op != MOP_RETR_TRANSP), "sttode_manifold_rowop_bwd: this op needs the third operand");
+    STT_REQUIRE(op == MOP_RETR_TRANSP ? (g || g2) : (g && !g2),
+                "sttode_manifold_rowop_bwd: the upstream gradient g is required (retr_transp: g or g2, NULL meaning zero), g2 is retr_transp's alone");
+    STT_REQUIRE(ga || gb || gw, "sttode_manifold_rowop_bwd: no gradient buffer given");
+    STT_REQUIRE(manifold != MF_POINCARE || (c > 0.f && finite_(c)), "sttode_manifold_rowop_bwd: curvature c must be positive and finite");
+    const bool takes_w = op == MOP_PTRANSP || op == MOP_RETR_TRANSP || op == MOP_INNER;
+    hipLaunchKernelGGL(manifold_row_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, op, manifold, a, b, takes_w ? w : nullptr, g,
+                       g2, ga, gb, takes_w ? gw : nullptr, rows, d, (double)c);
     STT_HIP(hipGetLastError());
     return 0;
 }

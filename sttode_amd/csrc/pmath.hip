@@ -7,6 +7,7 @@
 // the vector result (or lane 0 the scalar).  HBM-bound: 1 read of each operand + 1 write.  The reference's epsilons
 // and clamps are kept verbatim (cited per op).
 #include "api_util.hpp"
+#include <cmath>
 
 enum PmathOp {
     OP_PROJECT = 0, OP_LAMBDA_X, OP_MOBIUS_ADD, OP_DIST, OP_DIST0, OP_EXPMAP, OP_EXPMAP0, OP_LOGMAP, OP_LOGMAP0, OP_P2K, OP_K2P,
@@ -158,6 +159,47 @@ __global__ __launch_bounds__(1024) void pmean_fin_kernel(const float* __restrict
         out[i] = m;
         part += m * m;
     }
+    part = wsum(part);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = 0.f;
+        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += red[w];
+        tot = t;
+    }
+    __syncthreads();
+    const float den = 1.0f + sqrtf(1.0f - c * tot);
+    for (int i = threadIdx.x; i < d; i += blockDim.x) out[i] = out[i] / den;
+}
+
+// poincare_mean at a general shape: x is [outer, R, inner] rows of length d and the mean runs over R, with no permuted
+// copy.  ONE BLOCK PER GROUP (o, n), running pmean_fin_kernel's body -- the same thread count, the same sums in the same order -- at the
+// group's offset with the row stride inner d, so a group's result is bitwise that of the 2-D call on its rows.  The curvature as in
+// pmath_row_kernel.  klein / lsum (each may be NULL): the Klein mean before k2p [groups, d] and L = sum of the Lorentz factors [groups].
+__global__ __launch_bounds__(1024) void pmean_seg_fin_kernel(const float* __restrict__ yl, const float* __restrict__ lam,
+                                                             float* __restrict__ out, float* __restrict__ klein, float* __restrict__ lsum, int R,
+                                                             int inner, int d, float cv, const float* __restrict__ cp) {
+    __shared__ float red[16];
+    __shared__ float tot;
+    const float c = cp ? *cp : cv;
+    const size_t o = blockIdx.x / inner, n = blockIdx.x % inner;
+    const size_t row0 = o * R * inner + n;              // the group's first row; its rows are row0 + r inner
+    yl += row0 * d;
+    lam += row0;
+    out += (size_t)blockIdx.x * d;
+    const size_t rs = (size_t)inner * d;
+    float L = 0.f;
+    for (int r = 0; r < R; ++r) L += lam[(size_t)r * inner];
+    float part = 0.f;
+    for (int i = threadIdx.x; i < d; i += blockDim.x) {
+        float s = 0.f;
+        for (int r = 0; r < R; ++r) s += yl[(size_t)r * rs + i];
+        const float m = s / L;
+        out[i] = m;
+        if (klein) klein[(size_t)blockIdx.x * d + i] = m;
+        part += m * m;
+    }
+    if (lsum && threadIdx.x == 0) lsum[blockIdx.x] = L;
     part = wsum(part);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
     __syncthreads();
@@ -368,6 +410,24 @@ extern "C" int sttode_pmath_mean(const float* x, float* yl_ws, float* lam_ws, fl
     hipLaunchKernelGGL(pmath_row_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, (int)OP_PMEAN_PREP, x, (const float*)nullptr, yl_ws, lam_ws,
                        rows, d, c, (const float*)nullptr);
     hipLaunchKernelGGL(pmean_fin_kernel, dim3(1), dim3(1024), 0, s, (const float*)yl_ws, (const float*)lam_ws, out, rows, d, c);
+    STT_HIP(hipGetLastError());
+    return 0;
+}
+
+// poincare_mean over the middle dimension of x [outer, R, inner, d] -> out [outer, inner, d].  The curvature: *c_dev when c_dev is given
+// (never checked, as the other _c forms), else c.
+extern "C" int sttode_pmath_mean_seg(const float* x, float* yl_ws, float* lam_ws, float* out, float* klein, float* lsum, int outer, int R,
+                                     int inner, int d, float c, const float* c_dev, void* stream) {
+    STT_REQUIRE(x && yl_ws && lam_ws && out, "sttode_pmath_mean_seg: null pointer");
+    STT_REQUIRE(outer > 0 && R > 0 && inner > 0 && d > 0, "sttode_pmath_mean_seg: empty shape");
+    STT_REQUIRE((long)outer * R * inner <= 0x7fffffffL, "sttode_pmath_mean_seg: more than 2^31 - 1 rows");
+    STT_REQUIRE(c_dev || (c > 0.f && std::isfinite(c)), "sttode_pmath_mean_seg: curvature c must be positive and finite");
+    hipStream_t s = (hipStream_t)stream;
+    const int rows = outer * R * inner;
+    hipLaunchKernelGGL(pmath_row_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, (int)OP_PMEAN_PREP, x, (const float*)nullptr, yl_ws, lam_ws,
+                       rows, d, c, c_dev);
+    hipLaunchKernelGGL(pmean_seg_fin_kernel, dim3((unsigned)(outer * inner)), dim3(1024), 0, s, (const float*)yl_ws, (const float*)lam_ws, out,
+                       klein, lsum, R, inner, d, c, c_dev);
     STT_HIP(hipGetLastError());
     return 0;
 }

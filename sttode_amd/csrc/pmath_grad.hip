@@ -10,7 +10,7 @@
 // The _c entry points read the curvature from one float on the device and give it a gradient: the scalar stage is
 // evaluated a second time with c the one variable, each row's share of dL/dc goes to a float64 workspace and one workgroup adds them.
 //
-// The scalar stage is float64 forward-mode arithmetic (struct DN<N>: a value and N partials; D3: the three partials d/dp_k): 1 - c |x|^2, 1 - u^2 under artanh
+// The scalar stage is float64 forward-mode arithmetic (dual.hpp, struct DN<N>: a value and N partials; D3: the three partials d/dp_k): 1 - c |x|^2, 1 - u^2 under artanh
 // and the Moebius denominator cancel near the ball boundary (pmath.hip's pair kernel and OP_PMEAN_PREP use float64 for the same reason).
 // The stage is a few hundred float64 operations per row, tanh / log1p / sqrt among them, redundantly on 64 lanes (dist_matrix: once per
 // pair); it is EXPECTED to stay below the row's memory traffic, and has not been timed.
@@ -23,7 +23,9 @@
 // _hyperbolic_softmax's backward (per-pair coefficients, then row sums) and the feature clip of ToPoincare follow the same rules; their
 // forms are described where they stand below.
 #include "api_util.hpp"
+#include "dual.hpp"
 #include "train_group.hpp"
+#include <cmath>
 
 extern "C" int sttode_tlinear(const float* X, long ldx, int xdiv, const float* W, long ldw, int trans, const float* bias, const float* mask,
                               long ldm, float* Y, long ldy, int cols, int J, int I, int act, int accumulate, void* stream);
@@ -35,56 +37,6 @@ namespace {
 
 enum { OPB_PROJECT = 0, OPB_LAMBDA_X, OPB_MOBIUS_ADD, OPB_DIST, OPB_DIST0, OPB_EXPMAP, OPB_EXPMAP0, OPB_LOGMAP, OPB_LOGMAP0, OPB_P2K, OPB_K2P,
        OPB_LORENZ, OPB_COUNT };   // == the first twelve codes of pmath.hip's PmathOp (include/sttode_hip.h)
-
-constexpr double EPS5 = (double)1e-5f;   // the reference's 1e-5, as the forward kernels round it
-
-// value + partials with respect to N scalars (D3: the three row scalars; D6: the six pair scalars of _hyperbolic_softmax)
-template <int N> struct DN { double v, d[N]; };
-using D3 = DN<3>;
-using D6 = DN<6>;
-// the value v with partials d[k] = f(k)
-template <int N, class F> __device__ __forceinline__ DN<N> dn(double v, F f) {
-    DN<N> r; r.v = v;
-#pragma unroll
-    for (int k = 0; k < N; ++k) r.d[k] = f(k);
-    return r;
-}
-template <int N> __device__ __forceinline__ DN<N> cst(double v) { return dn<N>(v, [](int) { return 0.; }); }
-template <int N> __device__ __forceinline__ DN<N> var(double v, int i) { return dn<N>(v, [i](int k) { return k == i ? 1. : 0.; }); }
-template <int N> __device__ __forceinline__ DN<N> operator+(const DN<N>& a, const DN<N>& b) { return dn<N>(a.v + b.v, [&](int k) { return a.d[k] + b.d[k]; }); }
-template <int N> __device__ __forceinline__ DN<N> operator-(const DN<N>& a, const DN<N>& b) { return dn<N>(a.v - b.v, [&](int k) { return a.d[k] - b.d[k]; }); }
-template <int N> __device__ __forceinline__ DN<N> operator*(const DN<N>& a, const DN<N>& b) {
-    return dn<N>(a.v * b.v, [&](int k) { return a.d[k] * b.v + a.v * b.d[k]; });
-}
-template <int N> __device__ __forceinline__ DN<N> operator/(const DN<N>& a, const DN<N>& b) {
-    const double q = a.v / b.v, ib = 1.0 / b.v;
-    return dn<N>(q, [&](int k) { return (a.d[k] - q * b.d[k]) * ib; });
-}
-template <int N> __device__ __forceinline__ DN<N> operator+(double a, const DN<N>& b) { return dn<N>(a + b.v, [&](int k) { return b.d[k]; }); }
-template <int N> __device__ __forceinline__ DN<N> operator-(double a, const DN<N>& b) { return dn<N>(a - b.v, [&](int k) { return -b.d[k]; }); }
-template <int N> __device__ __forceinline__ DN<N> operator*(double a, const DN<N>& b) { return dn<N>(a * b.v, [&](int k) { return a * b.d[k]; }); }
-template <int N> __device__ __forceinline__ DN<N> operator/(double a, const DN<N>& b) { return cst<N>(a) / b; }
-template <int N> __device__ __forceinline__ DN<N> operator*(const DN<N>& a, double b) { return b * a; }
-template <int N> __device__ __forceinline__ DN<N> operator/(const DN<N>& a, double b) { return (1.0 / b) * a; }
-template <int N> __device__ __forceinline__ DN<N> chain(double v, double dv, const DN<N>& a) { return dn<N>(v, [&](int k) { return dv * a.d[k]; }); }
-// x.norm(): sqrt of a sum of squares, derivative 0 at a zero row
-template <int N> __device__ __forceinline__ DN<N> norm_of(const DN<N>& sq) { const double n = sqrt(sq.v); return chain(n, n > 0. ? 0.5 / n : 0., sq); }
-template <int N> __device__ __forceinline__ DN<N> sqrt_(const DN<N>& a) { const double n = sqrt(a.v); return chain(n, 0.5 / n, a); }
-template <int N> __device__ __forceinline__ DN<N> clamp_min_(const DN<N>& a, double lo) { return a.v >= lo ? a : cst<N>(lo); }
-template <int N> __device__ __forceinline__ DN<N> tanh_clamped_(const DN<N>& a) {   // pmath.py:11-12
-    const bool in = a.v >= -15.0 && a.v <= 15.0;
-    const double t = tanh(fmin(fmax(a.v, -15.0), 15.0));
-    return chain(t, in ? 1.0 - t * t : 0., a);
-}
-template <int N> __device__ __forceinline__ DN<N> artanh_d(const DN<N>& a) {        // pmath.py:16-27
-    const double xc = fmin(fmax(a.v, -1.0 + EPS5), 1.0 - EPS5);
-    return chain(0.5 * (log1p(xc) - log1p(-xc)), 1.0 / (1.0 - xc * xc), a);
-}
-// arsinh (pmath.py:51-60): log of the clamped x + sqrt(1 + x^2); the derivative Arsinh.backward gives, 1 / sqrt(1 + x^2), whatever the clamp
-template <int N> __device__ __forceinline__ DN<N> arsinh_d(const DN<N>& a) {
-    const double h = sqrt(1.0 + a.v * a.v);
-    return chain(log(fmax(a.v + h, EPS5)), 1.0 / h, a);
-}
 
 __device__ __forceinline__ double wsum(double v) {
 #pragma unroll
@@ -493,7 +445,199 @@ __global__ __launch_bounds__(256) void pmath_gc_finish_kernel(const double* __re
     if (threadIdx.x == 0) gc[0] = (float)part[0];
 }
 
+// ---- poincare_mean (pmath.py:472-479) over the middle dimension of x [outer, R, inner, d].  With q_r = 1 - c |x_r|^2,
+// S = sum_r 2 x_r / q_r, L = sum_r (1 + c |x_r|^2) / q_r, m = S / L (the Klein mean) and y = k2p(m) = al(p) m, p = |m|^2,
+// al = 1 / (1 + s), s = sqrt(1 - c p):
+//     g_m = al g + 2 al' <g,m> m,  al' = c / (2 s (1 + s)^2);   g_S = g_m / L;   g_L = -<g_m,m> / L;
+//     gx_r = (2 / q_r) g_S + (4 c / q_r^2) (<x_r,g_S> + g_L) x_r.
+// TWO launches.  The group stage, one wave per group (o, n): S and L are RECOMPUTED in float64 from x (the forward's fp32 sums are not
+// used), rows in index order, each lane four elements of S per 256-element sweep; S goes to gS_ws, the dot products |S|^2 and <g,S> close
+// the scalars, and the lane that wrote an element of S overwrites it with g_S; g_L goes to gL_ws.  The row stage, one wave per row: |x_r|^2
+// and <x_r,g_S> in one sweep, gx in the second.  dL/dc (CG): a row's share is (2 |x_r|^2 / q_r^2) (<x_r,g_S> + g_L) -- through
+// d(2 x / q)/dc and d lambda/dc -- to gc_ws[row]; a group's share through k2p is <g,m> p / (2 s (1 + s)^2), to gc_ws[rows + group].
+template <bool CPTR, bool CG>
+__global__ __launch_bounds__(256) void pmath_mean_group_bwd_kernel(const float* __restrict__ x, const float* __restrict__ g, double* __restrict__ gS,
+                                                                   double* __restrict__ gL, int groups, int R, int inner, int d, float cv,
+                                                                   const float* __restrict__ cp, double* __restrict__ gc_groups) {
+    float cf = cv;
+    if constexpr (CPTR) cf = *cp;
+    const int lane = threadIdx.x & 63;
+    const int grp = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (grp >= groups) return;
+    const double c = cf;
+    const size_t o = grp / inner, n = grp % inner, rs = (size_t)inner * d;
+    const float* x0 = x + (o * R * inner + n) * d;      // row r of the group: x0 + r rs
+    const float* gr = g + (size_t)grp * d;
+    double* Sr = gS + (size_t)grp * d;
+    double L = 0., SS = 0., GS = 0.;
+    for (int base = 0; base < d; base += 256) {
+        double acc[4] = {0., 0., 0., 0.};
+        for (int r = 0; r < R; ++r) {
+            const float* xr = x0 + (size_t)r * rs;
+            double x2 = 0.;
+            for (int i = lane; i < d; i += 64) { const double a = xr[i]; x2 += a * a; }
+            x2 = wsum(x2);
+            const double q = 1.0 - c * x2;
+            if (base == 0) L += (1.0 + c * x2) / q;
+            const double k = 2.0 / q;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { const int i = base + lane + 64 * j; if (i < d) acc[j] += k * (double)xr[i]; }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int i = base + lane + 64 * j;
+            if (i < d) { Sr[i] = acc[j]; SS += acc[j] * acc[j]; GS += (double)gr[i] * acc[j]; }
+        }
+    }
+    SS = wsum(SS); GS = wsum(GS);
+    const double p = SS / (L * L), gm = GS / L;                     // |m|^2, <g,m>
+    const double s = sqrt(1.0 - c * p), al = 1.0 / (1.0 + s), dal = c / (2.0 * s * (1.0 + s) * (1.0 + s));
+    const double kS = 2.0 * dal * gm / L;                            // g_m = al g + kS S
+    for (int i = lane; i < d; i += 64) Sr[i] = (al * (double)gr[i] + kS * Sr[i]) / L;
+    if (lane == 0) {
+        gL[grp] = -(al * gm + 2.0 * dal * gm * p) / L;
+        if constexpr (CG) gc_groups[grp] = gm * p / (2.0 * s * (1.0 + s) * (1.0 + s));
+    }
+}
+
+template <bool CPTR, bool CG>
+__global__ __launch_bounds__(256) void pmath_mean_row_bwd_kernel(const float* __restrict__ x, const double* __restrict__ gS,
+                                                                 const double* __restrict__ gL, float* __restrict__ gx, int rows, int R, int inner,
+                                                                 int d, float cv, const float* __restrict__ cp, double* __restrict__ gc_ws) {
+    float cf = cv;
+    if constexpr (CPTR) cf = *cp;
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const double c = cf;
+    const size_t grp = (size_t)(r / (R * inner)) * inner + r % inner;
+    const float* xr = x + (size_t)r * d;
+    const double* Sr = gS + grp * d;
+    double x2 = 0., xs = 0.;
+    for (int i = lane; i < d; i += 64) { const double a = xr[i]; x2 += a * a; xs += a * Sr[i]; }
+    x2 = wsum(x2); xs = wsum(xs);
+    const double q = 1.0 - c * x2, t = (xs + gL[grp]) / (q * q);
+    if constexpr (CG) {
+        if (lane == 0) gc_ws[r] = 2.0 * x2 * t;
+        if (!gx) return;
+    }
+    const double k1 = 2.0 / q, k2 = 4.0 * c * t;
+    for (int i = lane; i < d; i += 64) gx[(size_t)r * d + i] = (float)(k1 * Sr[i] + k2 * (double)xr[i]);
+}
+
+// ---- Oblique.proj (core/manifolds/oblique.py:15-16), y = p / |p|: gp = (g - <g,y> y) / |p|.  A zero row gives NaN, as the forward does.
+__global__ __launch_bounds__(256) void oblique_proj_bwd_kernel(const float* __restrict__ p, const float* __restrict__ g, float* __restrict__ gp,
+                                                               int rows, int d) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const float* pr = p + (size_t)r * d;
+    const float* gr = g + (size_t)r * d;
+    double p2 = 0., gpd = 0.;
+    for (int i = lane; i < d; i += 64) { const double a = pr[i]; p2 += a * a; gpd += (double)gr[i] * a; }
+    p2 = wsum(p2); gpd = wsum(gpd);
+    const double n = sqrt(p2), kg = 1.0 / n, kp = -gpd / (p2 * n);
+    for (int i = lane; i < d; i += 64) gp[(size_t)r * d + i] = (float)(kg * (double)gr[i] + kp * (double)pr[i]);
+}
+
+// ---- Oblique.dist (oblique.py:36-43): out[b, i, j] = acos(clamp(<p2_i, p1_j>, +-(1 - 1e-4))).  coef_ij = -g_ij / sqrt(1 - s_ij^2) where the
+// un-clamped inner product s_ij lies within the clamp (bounds included: torch.clamp's gradient), else 0; gp2_i = sum_j coef_ij p1_j (side
+// 0, one wave per p2 row), gp1_j = sum_i coef_ij p2_i (side 1, one wave per p1 row).  Partners in index order, the inner product in float64,
+// each lane four elements of the row per 256-element sweep, as pmath_dist_matrix_bwd_kernel; nb batches.
+__global__ __launch_bounds__(256) void oblique_dist_bwd_kernel(int side, const float* __restrict__ p1, const float* __restrict__ p2,
+                                                               const float* __restrict__ g, float* __restrict__ gout, int nb, int n1, int n2, int d) {
+    const int lane = threadIdx.x & 63;
+    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int n_self = side ? n1 : n2, n_part = side ? n2 : n1;
+    if (r >= (long)nb * n_self) return;
+    const long bt = r / n_self, k = r % n_self;
+    const float* self = (side ? p1 : p2) + (size_t)r * d;
+    const float* part = (side ? p2 : p1) + (size_t)bt * n_part * d;
+    const float* gb = g + (size_t)bt * n2 * n1;
+    const double hi = (double)(1.0f - 1e-4f), lo = (double)(-1.0f + 1e-4f);
+    for (int base = 0; base < d; base += 256) {
+        double acc[4] = {0., 0., 0., 0.};
+        for (int q = 0; q < n_part; ++q) {
+            const float* pr = part + (size_t)q * d;
+            double s = 0.;
+            for (int i = lane; i < d; i += 64) s += (double)self[i] * (double)pr[i];
+            s = wsum(s);
+            const double gv = side ? gb[(size_t)q * n1 + k] : gb[(size_t)k * n1 + q];
+            const double coef = (s >= lo && s <= hi) ? -gv / sqrt(1.0 - s * s) : 0.;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { const int i = base + lane + 64 * j; if (i < d) acc[j] += coef * (double)pr[i]; }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { const int i = base + lane + 64 * j; if (i < d) gout[(size_t)r * d + i] = (float)acc[j]; }
+    }
+}
+
 }  // namespace
+
+static int pmath_mean_bwd_launch(const float* x, const float* g, double* gS_ws, double* gL_ws, float* gx, int outer, int R, int inner, int d, float c,
+                                 const float* c_dev, double* gc_ws, float* gc, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const int groups = outer * inner, rows = groups * R;
+    if (gc_ws) {
+        hipLaunchKernelGGL((pmath_mean_group_bwd_kernel<true, true>), dim3((groups + 3) / 4), dim3(256), 0, s, x, g, gS_ws, gL_ws, groups, R, inner, d,
+                           0.f, c_dev, gc_ws + rows);
+        hipLaunchKernelGGL((pmath_mean_row_bwd_kernel<true, true>), dim3((rows + 3) / 4), dim3(256), 0, s, x, (const double*)gS_ws, (const double*)gL_ws,
+                           gx, rows, R, inner, d, 0.f, c_dev, gc_ws);
+        hipLaunchKernelGGL(pmath_gc_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)gc_ws, gc, (long)rows + groups);
+    } else {
+        hipLaunchKernelGGL((pmath_mean_group_bwd_kernel<false, false>), dim3((groups + 3) / 4), dim3(256), 0, s, x, g, gS_ws, gL_ws, groups, R, inner,
+                           d, c, (const float*)nullptr, (double*)nullptr);
+        hipLaunchKernelGGL((pmath_mean_row_bwd_kernel<false, false>), dim3((rows + 3) / 4), dim3(256), 0, s, x, (const double*)gS_ws,
+                           (const double*)gL_ws, gx, rows, R, inner, d, c, (const float*)nullptr, (double*)nullptr);
+    }
+    STT_HIP(hipGetLastError());
+    return 0;
+}
+
+// poincare_mean backward: x [outer,R,inner,d], g [outer,inner,d] -> gx as x.  Workspaces gS_ws [outer inner d] and gL_ws [outer inner]
+// doubles.  Two launches; bitwise repeatable, no atomics.
+extern "C" int sttode_pmath_mean_bwd(const float* x, const float* g, double* gS_ws, double* gL_ws, float* gx, int outer, int R, int inner, int d,
+                                     float c, void* stream) {
+    STT_REQUIRE(x && g && gS_ws && gL_ws && gx, "sttode_pmath_mean_bwd: null pointer");
+    STT_REQUIRE(outer > 0 && R > 0 && inner > 0 && d > 0, "sttode_pmath_mean_bwd: empty shape");
+    STT_REQUIRE((long)outer * R * inner <= 0x7fffffffL, "sttode_pmath_mean_bwd: more than 2^31 - 1 rows");
+    STT_REQUIRE(c > 0.f && std::isfinite(c), "sttode_pmath_mean_bwd: curvature c must be positive and finite");
+    return pmath_mean_bwd_launch(x, g, gS_ws, gL_ws, gx, outer, R, inner, d, c, nullptr, nullptr, nullptr, stream);
+}
+
+// ... with the curvature on the device: gc_ws holds outer R inner + outer inner doubles (the rows' shares, then the groups'), gc [1] is
+// WRITTEN by pmath_gc_finish_kernel (a third launch).  gx may be NULL (c alone requires a gradient).
+extern "C" int sttode_pmath_mean_bwd_c(const float* x, const float* g, double* gS_ws, double* gL_ws, float* gx, int outer, int R, int inner,
+                                       int d, const float* c_dev, double* gc_ws, float* gc, void* stream) {
+    STT_REQUIRE(c_dev, "sttode_pmath_mean_bwd_c: c_dev is NULL (the curvature is read from the device)");
+    STT_REQUIRE(x && g && gS_ws && gL_ws, "sttode_pmath_mean_bwd_c: null pointer");
+    STT_REQUIRE(gc_ws && gc, "sttode_pmath_mean_bwd_c: gc_ws [rows + groups] doubles and gc [1] are required");
+    STT_REQUIRE(outer > 0 && R > 0 && inner > 0 && d > 0, "sttode_pmath_mean_bwd_c: empty shape");
+    STT_REQUIRE((long)outer * R * inner <= 0x7fffffffL, "sttode_pmath_mean_bwd_c: more than 2^31 - 1 rows");
+    return pmath_mean_bwd_launch(x, g, gS_ws, gL_ws, gx, outer, R, inner, d, 0.f, c_dev, gc_ws, gc, stream);
+}
+
+extern "C" int sttode_oblique_proj_bwd(const float* p, const float* g, float* gp, int rows, int d, void* stream) {
+    STT_REQUIRE(p && g && gp, "sttode_oblique_proj_bwd: null pointer");
+    STT_REQUIRE(rows > 0 && d > 0, "sttode_oblique_proj_bwd: empty shape");
+    hipLaunchKernelGGL(oblique_proj_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, p, g, gp, rows, d);
+    STT_HIP(hipGetLastError());
+    return 0;
+}
+
+// Oblique.dist backward: p1 [nb,n1,d], p2 [nb,n2,d], g [nb,n2,n1] -> gp1, gp2 (each may be NULL; not both).  One launch per output.
+extern "C" int sttode_oblique_dist_bwd(const float* p1, const float* p2, const float* g, float* gp1, float* gp2, int nb, int n1, int n2, int d,
+                                       void* stream) {
+    STT_REQUIRE(p1 && p2 && g && (gp1 || gp2), "sttode_oblique_dist_bwd: null pointer");
+    STT_REQUIRE(nb > 0 && n1 > 0 && n2 > 0 && d > 0, "sttode_oblique_dist_bwd: empty shape");
+    hipStream_t s = (hipStream_t)stream;
+    if (gp2)
+        hipLaunchKernelGGL(oblique_dist_bwd_kernel, dim3((unsigned)(((long)nb * n2 + 3) / 4)), dim3(256), 0, s, 0, p1, p2, g, gp2, nb, n1, n2, d);
+    if (gp1)
+        hipLaunchKernelGGL(oblique_dist_bwd_kernel, dim3((unsigned)(((long)nb * n1 + 3) / 4)), dim3(256), 0, s, 1, p1, p2, g, gp1, nb, n1, n2, d);
+    STT_HIP(hipGetLastError());
+    return 0;
+}
 
 // ---------------------------------------------------------------------------------------------------
 extern "C" int sttode_pmath_rowop_bwd(int op, const float* x, const float* y, const float* g, float* gx, float* gy, int rows, int d, float c,

@@ -8,7 +8,15 @@ All operations act on the last dimension and take any leading shape, with broadc
 tensors only: anything else raises ``capi.SttodeError`` (no CPU fallback).  ``Euclidean`` is the exception, its methods are the
 reference's one-line identities and adds in plain torch.
 
-The operations are FORWARD-ONLY: they run under ``no_grad`` semantics, on detached operands, and their results never require grad.
+The operations are FORWARD-ONLY by default: they run under ``no_grad`` semantics, on detached operands, and their results never require
+grad.  ``differentiable(manifold)`` opts a manifold object in (the method signatures are the reference's, so it cannot be a
+keyword): it sets ``manifold.differentiable = True`` and returns the manifold, and from then on every operation of that object is
+differentiable in its tensor operands -- with grad mode on and an operand that requires grad the result carries a graph whose backward
+pass is one HIP launch (``sttode_manifold_rowop_bwd``; ``proj`` / ``expmap`` / ``logmap`` / ``dist`` of the ball and ``proj`` / ``dist``
+of Oblique go through ``pmath``'s own backward kernels), first order only.  Branches differentiate as taken: Oblique ``expmap`` below
+``|u| = 1e-4`` as ``proj(p + u)``, the ball's ``retr`` through ``project``'s clip.  Forward bits are the same either way; without the flag,
+under ``no_grad`` or with no operand that requires grad the calls are exactly the forward-only ones.  ``PoincareBall.c`` stays a Python
+float, and the Riemannian optimisers never build a graph.
 
 Where this deviates from the reference:
   * ``Oblique.inner`` and ``Oblique.logmap`` raise ``NotImplementedError``.  The reference's ``inner`` is a batched matmul that ignores
@@ -21,6 +29,7 @@ Where this deviates from the reference:
 import math
 
 import torch
+from torch.autograd.function import once_differentiable
 from torch.nn import Parameter
 
 from . import capi, pmath
@@ -49,6 +58,63 @@ def _operands(*ts):
     return [None if t is None else t.contiguous() for t in out]
 
 
+def _live(*ts):
+    """Does grad mode ask for a graph through these operands?"""
+    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in ts)
+
+
+def differentiable(manifold):
+    """Opt a manifold object in to gradients through its operations (the module docstring); returns the manifold."""
+    manifold.differentiable = True
+    return manifold
+
+
+class _RowOpGrad(torch.autograd.Function):
+    """A manifold row op and its backward kernel (sttode_manifold_rowop_bwd, one launch).  Saves only its operands; a broadcast operand's
+    gradient is summed back to the operand's shape."""
+
+    @staticmethod
+    def forward(ctx, a, b, w, op, manifold, c, scalar, keepdim):
+        ctx.save_for_backward(a, b, w)
+        ctx.op, ctx.manifold, ctx.c = op, manifold, c
+        out = _rowop(op, manifold, c, a, b, w, scalar, keepdim)
+        if op == 'retr_transp':
+            ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, g2=None):
+        a, b, w = ctx.saved_tensors
+        ab, bb, wb = _operands(a, b, w)
+        d = ab.shape[-1]
+        rows = ab.numel() // d
+        two = ctx.op == 'retr_transp'
+        if two and g is None and g2 is None:
+            return (None,) * 8
+        g, g2 = [None if t is None else t.to(torch.float32).contiguous() for t in (g, g2 if two else None)]
+        want = ctx.needs_input_grad
+        takes_w = wb is not None and ctx.op in ('ptransp', 'retr_transp', 'inner')
+        ga = torch.empty_like(ab) if want[0] else None
+        gb = torch.empty_like(bb) if want[1] else None
+        gw = torch.empty_like(wb) if takes_w and want[2] else None
+        if rows and (ga is not None or gb is not None or gw is not None):
+            with torch.cuda.device(ab.device):
+                capi.call('sttode_manifold_rowop_bwd', capi.MANIFOLD_OPS[ctx.op], capi.MANIFOLDS[ctx.manifold], ab, bb, wb if takes_w else None,
+                          g, g2, ga, gb, gw, rows, d, float(ctx.c), capi.stream_ptr())
+        return (None if ga is None else ga.sum_to_size(a.shape), None if gb is None else gb.sum_to_size(b.shape),
+                None if gw is None else gw.sum_to_size(w.shape), None, None, None, None, None)
+
+
+def _op(man, op, a, b, w=None, scalar=False, keepdim=False):
+    """A row op of manifold `man`: the forward-only call, or on a differentiable manifold with a live operand the autograd function."""
+    c = getattr(man, 'c', 1.0)
+    if man.differentiable and _live(a, b, w):
+        _operands(a, b, w)      # (the operand checks, before autograd sees them)
+        return _RowOpGrad.apply(a, b, w, op, man._code, c, scalar, keepdim)
+    return _rowop(op, man._code, c, a, b, w, scalar, keepdim)
+
+
 def _rowop(op, manifold, c, a, b, w=None, scalar=False, keepdim=False):
     with torch.no_grad():
         a, b, w = _operands(a, b, w)
@@ -72,8 +138,20 @@ def _detached(fn, *ts, **kw):
         return fn(*[t.detach() if isinstance(t, torch.Tensor) else t for t in ts], **kw)
 
 
+def _routed(man, fn, *ts, **kw):
+    """A pmath function as an operation of `man`: forward-only, or on a differentiable manifold with a live operand, itself."""
+    if man.differentiable and _live(*ts):
+        for t in ts:
+            if isinstance(t, torch.Tensor) and t.dtype != torch.float32:
+                raise capi.SttodeError(f'sttode_amd.manifolds takes float32 tensors, got {t.dtype}')
+        return fn(*ts, **kw)
+    return _detached(fn, *ts, **kw)
+
+
 class Manifold(object):
     """Abstract class to define operations on a manifold (core/manifolds/base.py: the same method list)."""
+
+    differentiable = False      # set by manifolds.differentiable(manifold): the operations of that object build a graph
 
     def __init__(self):
         super().__init__()
@@ -220,21 +298,21 @@ class Oblique(Manifold):
         self.name = 'Oblique'
 
     def proj(self, p):
-        return _detached(pmath.oblique_proj, p)
+        return _routed(self, pmath.oblique_proj, p, **({'differentiable': True} if self.differentiable else {}))
 
     def proj_tan(self, u, p):
-        return _rowop('proj_tan', self._code, 1.0, p, u)
+        return _op(self, 'proj_tan', p, u)
 
     def egrad2rgrad(self, p, dp):
-        return _rowop('proj_tan', self._code, 1.0, p, dp)
+        return _op(self, 'proj_tan', p, dp)
 
     def expmap(self, u, p):
-        return _rowop('expmap', self._code, 1.0, p, u)
+        return _op(self, 'expmap', p, u)
 
     def dist(self, p1, p2, keepdim=False):
         if keepdim:
             raise NotImplementedError('Oblique.dist returns the [..., n2, n1] matrix of the reference, which has no reduced dimension to keep')
-        return _detached(pmath.oblique_dist, p1, p2)
+        return _routed(self, pmath.oblique_dist, p1, p2, **({'differentiable': True} if self.differentiable else {}))
 
     def logmap(self, p1, p2):
         raise NotImplementedError("Oblique.logmap: the reference multiplies the [n, d] tangent projection by the [n, n] matrix its dist returns, "
@@ -245,13 +323,13 @@ class Oblique(Manifold):
                                   'of tangent vectors at p; the optimisers use the row-wise <u, v> on the device')
 
     def ptransp(self, x, y, u):
-        return _rowop('ptransp', self._code, 1.0, x, y, u)
+        return _op(self, 'ptransp', x, y, u)
 
     def retr(self, x, u):
-        return _rowop('retr', self._code, 1.0, x, u)
+        return _op(self, 'retr', x, u)
 
     def retr_transp(self, x, u, v):
-        return _rowop('retr_transp', self._code, 1.0, x, u, v)
+        return _op(self, 'retr_transp', x, u, v)
 
 
 class PoincareBall(Manifold):
@@ -271,37 +349,43 @@ class PoincareBall(Manifold):
         self.name = 'PoincareBall'
 
     def proj(self, p):
-        return _detached(pmath.project, p, c=self.c)
+        return _routed(self, pmath.project, p, c=self.c)
 
     def proj_tan(self, u, p):
-        return _operands(u)[0]
+        return self._identity(u)
 
     def proj_tan0(self, u):
+        return self._identity(u)
+
+    def _identity(self, u):
+        if self.differentiable and _live(u):
+            _operands(u)
+            return u.contiguous()
         return _operands(u)[0]
 
     def egrad2rgrad(self, p, dp):
-        return _rowop('proj_tan', self._code, self.c, p, dp)
+        return _op(self, 'proj_tan', p, dp)
 
     def expmap(self, u, p):
-        return _detached(pmath.expmap, p, u, c=self.c)
+        return _routed(self, pmath.expmap, p, u, c=self.c)
 
     def logmap(self, p1, p2):
-        return _detached(pmath.logmap, p2, p1, c=self.c)
+        return _routed(self, pmath.logmap, p2, p1, c=self.c)
 
     def dist(self, p1, p2, keepdim=False):
-        return _detached(pmath.dist, p1, p2, c=self.c, keepdim=keepdim)
+        return _routed(self, pmath.dist, p1, p2, c=self.c, keepdim=keepdim)
 
     def sqdist(self, p1, p2):
         return self.dist(p1, p2).pow(2)
 
     def inner(self, p, u, v=None, keepdim=False):
-        return _rowop('inner', self._code, self.c, p, u, v, scalar=True, keepdim=keepdim)
+        return _op(self, 'inner', p, u, v, scalar=True, keepdim=keepdim)
 
     def ptransp(self, x, y, u):
-        return _rowop('ptransp', self._code, self.c, x, y, u)
+        return _op(self, 'ptransp', x, y, u)
 
     def retr(self, x, u):
-        return _rowop('retr', self._code, self.c, x, u)
+        return _op(self, 'retr', x, u)
 
     def retr_transp(self, x, u, v):
-        return _rowop('retr_transp', self._code, self.c, x, u, v)
+        return _op(self, 'retr_transp', x, u, v)

@@ -13,10 +13,14 @@ The curvature ``c`` is a Python number, which makes exactly the calls described 
 (DESIGN.md 4w): the kernels then read it from the device -- it is never brought to the host, so the calls can be captured into a graph --
 with results bitwise those of the float call at its value, and when it requires grad it gets a gradient of its own shape from the same
 backward kernels (the tensor gradients stay bitwise those of the float path).  Any other tensor ``c`` raises ``capi.SttodeError`` before
-any launch.  ``poincare_mean`` and ``RiemannianGradient.c`` keep a Python number.
+any launch.  ``RiemannianGradient.c`` keeps a Python number; ``poincare_mean`` takes a tensor ``c`` only with ``differentiable=True``.
 
 ``mobius_matvec`` deviates from the reference in one place: a row with ``x m^T == 0`` gets a zero gradient (the reference: NaN).  ``_hyperbolic_softmax`` needs non-zero rows of ``A`` (the reference gives NaN for a zero row).
-``poincare_mean`` and the Oblique ops stay FORWARD-ONLY: their results are cut off from the graph.
+``poincare_mean``, ``oblique_proj`` and ``oblique_dist`` are FORWARD-ONLY by default: their results are cut off from the graph, and
+``poincare_mean`` refuses a tensor ``c``.  The keyword ``differentiable=True`` opts in, as ``ops.mhgsa(differentiable=)`` does:
+with grad mode on and an input that requires grad the result carries a graph whose backward pass is HIP (csrc/pmath_grad.hip: a group stage
+and a row stage for the mean, fixed-order row sums for ``oblique_dist``), first order only; the forward bits are those of the call without
+the keyword.  ``poincare_mean`` takes any rank >= 2 and any ``dim`` but the last, as the reference does, whatever the keyword.
 ``feature_clip(x, r)`` is not a function of the reference's pmath.py: it is the clipping of hyptorch/nn.py's ``ToPoincare(clip_r=r)``.
 """
 import numpy as np
@@ -451,17 +455,76 @@ def feature_clip(x, r):
     return _clip_fwd(x, float(r))
 
 
-def poincare_mean(x, dim=0, c=1.0):
-    assert dim == 0 and x.dim() == 2
-    if isinstance(c, torch.Tensor):
+def _mean_shape(x, dim):
+    """(outer, R, inner, d) of a mean over `dim` of x, and the result's shape: x as outer x R x inner rows of length d."""
+    nd = x.dim()
+    if nd < 2 or not -nd <= dim < nd:
+        raise capi.SttodeError('poincare_mean takes points [..., d] of rank >= 2 and a dim inside it: got shape %s, dim %d' % (tuple(x.shape), dim))
+    dim %= nd
+    if dim == nd - 1:
+        raise capi.SttodeError('poincare_mean: dim is the last (feature) dimension; the Lorentz factor is taken over the last dimension '
+                               '(hyptorch/pmath.py:474), so a mean over it is not a mean of points')
+    sh = tuple(x.shape)
+    return int(np.prod(sh[:dim], dtype=np.int64)), sh[dim], int(np.prod(sh[dim + 1:-1], dtype=np.int64)), sh[-1], sh[:dim] + sh[dim + 1:]
+
+
+def _mean_fwd(x, geom, c):
+    outer, R, inner, d, shape = geom
+    yl = torch.empty_like(x)
+    lam = torch.empty(outer * R * inner, dtype=torch.float32, device=x.device)
+    out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    if outer == 1 and inner == 1 and not _on_device(c):     # [rows, d] over dim 0 with a float c: the call this function always made
+        capi.call('sttode_pmath_mean', x, yl, lam, out, R, d, c, capi.stream_ptr())
+    else:
+        capi.call('sttode_pmath_mean_seg', x, yl, lam, out, None, None, outer, R, inner, d, 0.0 if _on_device(c) else c,
+                  c if _on_device(c) else None, capi.stream_ptr())
+    return out
+
+
+class _PoincareMean(torch.autograd.Function):
+    """poincare_mean and its backward (sttode_pmath_mean_bwd; with a tensor c sttode_pmath_mean_bwd_c, which also gives dL/dc).  Saves
+    only its inputs: the backward recomputes the Klein sums in float64."""
+
+    @staticmethod
+    def forward(ctx, x, geom, c):
+        ctx.save_for_backward(x, c if _on_device(c) else None)
+        ctx.geom, ctx.c = geom, c if not _on_device(c) else None
+        return _mean_fwd(x, geom, c)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, c = ctx.saved_tensors
+        outer, R, inner, d, _ = ctx.geom
+        groups = outer * inner
+        g = _prep(g)
+        assert g.numel() == groups * d
+        gS = torch.empty(groups * d, dtype=torch.float64, device=x.device)
+        gL = torch.empty(groups, dtype=torch.float64, device=x.device)
+        if c is not None:
+            want_x, _, want_c = ctx.needs_input_grad
+            gx = torch.empty_like(x) if want_x else None
+            ws, gc = _gc_buffers(c, groups * R + groups)
+            capi.call('sttode_pmath_mean_bwd_c', x, g, gS, gL, gx, outer, R, inner, d, c, ws, gc, capi.stream_ptr())
+            return gx, None, gc.view(c.shape) if want_c else None
+        gx = torch.empty_like(x)
+        capi.call('sttode_pmath_mean_bwd', x, g, gS, gL, gx, outer, R, inner, d, ctx.c, capi.stream_ptr())
+        return gx, None, None
+
+
+def poincare_mean(x, dim=0, c=1.0, *, differentiable=False):
+    """hyptorch/pmath.py:472-479: the Einstein midpoint over `dim` (any but the last) of points [..., d]; the result has x's shape without
+    `dim`.  differentiable=True: the result carries a graph (x, and a 1-element float32 tensor c), see the module docstring."""
+    if isinstance(c, torch.Tensor) and not differentiable:
         raise capi.SttodeError('poincare_mean takes a Python number as c: it is forward-only, so a tensor curvature would get no gradient here')
     x = _prep(x)
-    rows, d = x.shape
-    yl = torch.empty_like(x)
-    lam = torch.empty(rows, dtype=torch.float32, device=x.device)
-    out = torch.empty(d, dtype=torch.float32, device=x.device)
-    capi.call('sttode_pmath_mean', x, yl, lam, out, rows, d, float(c), capi.stream_ptr())
-    return out
+    geom = _mean_shape(x, dim)
+    if 0 in x.shape:
+        raise capi.SttodeError('poincare_mean: empty shape %s' % (tuple(x.shape),))
+    c = _curv(c, x)
+    if differentiable and _wants_grad(x, c):
+        return _PoincareMean.apply(x, geom, c)
+    return _mean_fwd(x.detach(), geom, c.detach() if _on_device(c) else c)
 
 
 def auto_select_c(d):
@@ -474,15 +537,61 @@ def auto_select_c(d):
 
 
 # Oblique manifold (core/manifolds/oblique.py)
-def oblique_proj(p):
+class _ObliqueProj(torch.autograd.Function):
+    """oblique_proj and its backward (sttode_oblique_proj_bwd).  Saves only p."""
+
+    @staticmethod
+    def forward(ctx, p):
+        ctx.save_for_backward(p)
+        return _row_fwd('oblique_proj', p, None, 1.0, False, False)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        (p,) = ctx.saved_tensors
+        d = p.shape[-1]
+        gp = torch.empty_like(p)
+        capi.call('sttode_oblique_proj_bwd', p, _prep(g), gp, p.numel() // d, d, capi.stream_ptr())
+        return gp
+
+
+def oblique_proj(p, *, differentiable=False):
+    if differentiable and _wants_grad(p):
+        return _ObliqueProj.apply(_prep(p))
     return _row('oblique_proj', p)
 
 
-def oblique_dist(p1, p2):
-    """Oblique.dist(p1, p2): [..., n1, d], [..., n2, d] -> [..., n2, n1]."""
-    p1, p2 = _prep(p1), _prep(p2)
+def _oblique_dist_fwd(p1, p2):
     n1, n2, d = p1.shape[-2], p2.shape[-2], p1.shape[-1]
     nb = p1.numel() // (n1 * d)
     out = torch.empty(*p1.shape[:-2], n2, n1, dtype=torch.float32, device=p1.device)
     capi.call('sttode_oblique_dist', p1, p2, out, nb, n1, n2, d, capi.stream_ptr())
     return out
+
+
+class _ObliqueDist(torch.autograd.Function):
+    """oblique_dist and its backward (sttode_oblique_dist_bwd).  Saves only its inputs."""
+
+    @staticmethod
+    def forward(ctx, p1, p2):
+        ctx.save_for_backward(p1, p2)
+        return _oblique_dist_fwd(p1, p2)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        p1, p2 = ctx.saved_tensors
+        n1, n2, d = p1.shape[-2], p2.shape[-2], p1.shape[-1]
+        want1, want2 = ctx.needs_input_grad
+        g1, g2 = torch.empty_like(p1) if want1 else None, torch.empty_like(p2) if want2 else None
+        capi.call('sttode_oblique_dist_bwd', p1, p2, _prep(g), g1, g2, p1.numel() // (n1 * d), n1, n2, d, capi.stream_ptr())
+        return g1, g2
+
+
+def oblique_dist(p1, p2, *, differentiable=False):
+    """Oblique.dist(p1, p2): [..., n1, d], [..., n2, d] -> [..., n2, n1].  differentiable=True: see the module docstring; the clamp at
+    +-(1 - 1e-4) has torch.clamp's gradient."""
+    p1, p2 = _prep(p1), _prep(p2)
+    if differentiable and _wants_grad(p1, p2):
+        return _ObliqueDist.apply(p1, p2)
+    return _oblique_dist_fwd(p1, p2)
