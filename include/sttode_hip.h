@@ -309,6 +309,47 @@ int sttode_sampler_objective_bwd(const float* mu, const float* logvar, const flo
                                  const float* g_es_ade, const float* g_es_fde, int n, int K, int nz, int D, float scale, float* dmu,
                                  float* dlogvar, float* dmotion, void* stream);
 
+/* Scene-level (joint) forms of the stage-2 objective's sample terms (csrc/sampler_joint.hip; added within ABI version 15).
+ * Inputs of sttode_sampler_objective, plus seg_ptr [S+1] (int32, device): CSR segment offsets in the convention of sttode_joint_select.
+ * Segment g is the agents seg_ptr[g] .. seg_ptr[g+1]-1 (n_g of them): a scene of a batch, the one scene of a step, one NBA game.
+ * x_{a,k} is agent a's sample k; sample k of all agents of g is one scene future.  np = K (K-1) / 2, D = 2 Tf.
+ *   kld [n]     per agent, sttode_sampler_loss's, bit for bit.
+ *   div [S]     joint DLow, unmasked over all D coordinates:  d2_g(i,j) = (1/n_g) sum_{a in g} |x_{a,i} - x_{a,j}|^2,
+ *               div_g = (1/np) sum_{i<j} exp(-d2_g(i,j) / scale).  The per-agent squared distance is the float32 sum that
+ *               sampler_loss_kernel forms; the sum over agents is float64, in agent order.
+ *   rec [S]     J_g(k) = sum_{a in g} sum_t (m_{a,t} (x_{a,k,t} - y_{a,t}))^2 in float64; rec_g = J_g(best_g).
+ *   best [S]    int32: the first k that minimises J_g(k); ties go to the lowest k by (ov < bv || (ov == bv && oi < bi)).  A NaN never wins
+ *               a comparison, best_g is always a valid column, and the NaN stays in its segment's values.
+ *   es [S]      joint energy score on the scene's RMS displacement
+ *               R_g(U,V) = sqrt( (1/(n_g Tf)) sum_{a in g} sum_t |m_{a,t} (u_{a,t} - v_{a,t})|^2 ):
+ *               es_g = (1/K) sum_k R_g(x_k, y) - (1/K^2) sum_{i<j} R_g(x_i, x_j)   (the 1/K^2 double sum of E R(X,y) - E R(X,X')/2).
+ *               With n_g = 1 and Tf = 1 this is sttode_sampler_objective's es_fde.
+ * An empty segment writes NaN values and index 0.  seg_ptr's contents are the caller's responsibility; every segment is clamped to [0, n].
+ * workspace: ws_bytes >= sttode_sampler_objective_joint_ws(n, K, S) bytes on the device, aligned to 8 bytes, overwritten; it carries
+ * nothing from one call to the next.  The entries allocate nothing and read nothing back (they can be captured into a graph).
+ * Limits: those of sttode_sampler_objective (n, nz > 0, K > 1, D even, K * D <= 4096, scale > 0), S >= 1; mu, logvar, motion, gt, seg_ptr,
+ * workspace and every output are required.  Refused before any launch or write, naming the entry.
+ * Precision: kld and the per-agent DLow sums float32; every sum over agents, the differences to the ground truth, R, J and the energy sums
+ * float64; outputs float32.  No atomics; every sum's order is a function of the segment's size alone: the same bits on every run, and a
+ * segment's outputs depend neither on the other segments nor on its place in the batch. */
+/* The workspace size in bytes for n agents, K samples, S segments; negative for arguments the entries refuse. */
+long long int sttode_sampler_objective_joint_ws(int n, int K, int S);
+int sttode_sampler_objective_joint(const float* mu, const float* logvar, const float* pmu, const float* plogvar, const float* motion,
+                                   const float* gt, const float* mask, const int* seg_ptr, int S, int n, int K, int nz, int D, float scale,
+                                   void* workspace, long ws_bytes, float* kld, float* div, float* rec, int* best, float* es, void* stream);
+
+/* Backward of sttode_sampler_objective_joint: upstream g_kld [n], g_div, g_rec, g_es [S] (each may be NULL = zero) -> dmu, dlogvar
+ * [n*K,nz] (sttode_sampler_loss_bwd's, bit for bit) and ONE summed dmotion [n,K,Tf,2]; every element is written.  The same limits and
+ * refusals; the segment's values are recomputed into the workspace by the forward's code.  For agent a of segment g, sample i, frame t:
+ *   div:  g_div[g] (1/np) sum_{j != i} exp(-d2_g(i,j) / scale) (-2 / (scale n_g)) (x_{a,i} - x_{a,j})
+ *   rec:  g_rec[g] 2 m (m (x_{a,i,t} - y_{a,t})) on i = best_g only, for every agent of g
+ *   es:   g_es[g] [ m (m (x_{a,i,t} - y_{a,t})) / (K n_g Tf R_g(x_i, y)) - sum_{j != i} m (m (x_{a,i,t} - x_{a,j,t})) / (K^2 n_g Tf R_g(x_i, x_j)) ]
+ * R = 0 contributes a zero gradient (the subgradient 0 of a norm at 0, as sttode_sampler_objective_bwd). */
+int sttode_sampler_objective_joint_bwd(const float* mu, const float* logvar, const float* pmu, const float* plogvar, const float* motion,
+                                       const float* gt, const float* mask, const int* seg_ptr, int S, const float* g_kld,
+                                       const float* g_div, const float* g_rec, const float* g_es, int n, int K, int nz, int D, float scale,
+                                       void* workspace, long ws_bytes, float* dmu, float* dlogvar, float* dmotion, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Training step (csrc/train*.hip, one file per kernel family: index in train.hip): forward-with-tape + backward of STTODENet.forward() (model/STTODE.py:553-568; losses
  * :372-395; what train.py:81-87 drives through total_loss.backward()).  Generic kernels over row-major nn.Parameter storage;

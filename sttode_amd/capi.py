@@ -53,6 +53,10 @@ SIGNATURES = {
     # stage-2 objective with the reconstruction and energy-score terms (csrc/sampler_objective.hip)
     'sttode_sampler_objective': [_P] * 7 + [_I, _I, _I, _I, _F] + [_P] * 7,
     'sttode_sampler_objective_bwd': [_P] * 12 + [_I, _I, _I, _I, _F] + [_P] * 4,
+    # scene-level (joint) DLow, reconstruction and energy terms (csrc/sampler_joint.hip; added within ABI version 15)
+    'sttode_sampler_objective_joint_ws': [_I, _I, _I],
+    'sttode_sampler_objective_joint': [_P] * 8 + [_I, _I, _I, _I, _I, _F, _P, _L] + [_P] * 6,
+    'sttode_sampler_objective_joint_bwd': [_P] * 8 + [_I] + [_P] * 4 + [_I, _I, _I, _I, _F, _P, _L] + [_P] * 4,
     # training step (csrc/train*.hip)
     'sttode_tlinear': [_P, _L, _I, _P, _L, _I, _P, _P, _L, _P, _L, _I, _I, _I, _I, _I, _P],
     'sttode_tlinear_tab': [_P, _L, _P, _L, _P, _P, _L, _I, _P, _L, _I, _I, _I, _I, _P],
@@ -178,6 +182,9 @@ SIGNATURES = {
     'sttode_async_enqueue': [_P, _I],
     'sttode_check': [_P, _P, _I, _I, _P],
 }
+
+# entries that do not return a status (everything else: int, 0 = success)
+RESTYPES = {'sttode_sampler_objective_joint_ws': ctypes.c_longlong}
 
 # enum SttodeWeight / SttodeBuffer / SttodeStage of include/sttode_hip.h (order is ABI)
 WEIGHT_ORDER = ([('past', k) for k in ('fc1P', 'fc1b', 'posP', 'peb', 'fc2P', 'fc2b', 'fc3P', 'fc3b', 'fc3last', 'inP', 'inb', 'outP',
@@ -357,7 +364,7 @@ def lib():
         for name, args in SIGNATURES.items():
             fn = getattr(L, name)
             fn.argtypes = args
-            fn.restype = ctypes.c_int
+            fn.restype = RESTYPES.get(name, ctypes.c_int)
         _LIB = L
     return _LIB
 
@@ -388,6 +395,15 @@ def call(name, *args, tag=None):
         rc = getattr(L, name)(*conv)
     if rc != 0:
         raise SttodeError(f'{name} failed (status {rc}): {L.sttode_last_error().decode()}')
+
+
+def sampler_joint_ws(n, K, S):
+    """Bytes of workspace sttode_sampler_objective_joint(_bwd) need for n agents, K samples and S segments."""
+    L = lib()
+    b = int(L.sttode_sampler_objective_joint_ws(int(n), int(K), int(S)))
+    if b < 0:
+        raise SttodeError(f'sttode_sampler_objective_joint_ws failed: {L.sttode_last_error().decode()}')
+    return b
 
 
 def stream_ptr():

@@ -50,12 +50,14 @@ def train_epoch(args, epoch, model, optimizer, scheduler, train_loader, log=prin
 
 
 def train_sampler_epoch(args, epoch, model, sampler, optimizer, scheduler, train_loader, div_cfg, log=print, max_iters=None, recon=False,
-                        energy_weight=0.0, energy_kind='ade'):
+                        energy_weight=0.0, energy_kind='ade', joint=False):
     """One epoch of stage 2, trainsampler.py:124-194: the prediction model stays frozen, ``optimizer`` steps the sampler's parameters
     (trainsampler.py:283) on compute_sampler_loss (samplerloss.py:41-73) through Sampler.forward's autograd path (csrc/train*.hip +
     csrc/sampler.hip).  NBA: loader yields seq_collate dicts; otherwise the per-scene tuples of TrajectoryDataset / SDD_Dataset wrapped by
     DataLoader(batch_size=1).  recon / energy_weight / energy_kind: the opt-in ground-truth terms of compute_sampler_loss,
-    handed through; a term that is on joins the printed line.  Returns the list of total losses."""
+    handed through; a term that is on joins the printed line.  joint=True: the scene-level forms of the diversity, reconstruction and energy
+    terms, the step's scene as one segment, an NBA batch as one segment per game of N agents.  Returns the list of total
+    losses."""
     from . import samplerloss
     terms = dict(recon=recon, energy_weight=energy_weight, energy_kind=energy_kind)
     total_iter_num = len(train_loader)
@@ -70,7 +72,8 @@ def train_sampler_epoch(args, epoch, model, sampler, optimizer, scheduler, train
             B, N = batch['past_traj'].shape[:2]
             fut = torch.as_tensor(batch['future_traj'], dtype=torch.float32).to(sampler.device).reshape(B * N, args.future_length, 2)
             total_loss, loss_dict, loss_dict_uw = samplerloss.compute_sampler_loss_nba(
-                args, fut, dec_motion.reshape(-1, sampler.nk, args.future_length, 2), 1, vae_dist, sampler_dist, div_cfg, **terms)
+                args, fut, dec_motion.reshape(-1, sampler.nk, args.future_length, 2), 1, vae_dist, sampler_dist, div_cfg, **terms,
+                **(dict(joint=True, seg_len=N) if joint else {}))
         else:
             batch = list(batch)
             batch.pop()                                            # seq_name
@@ -80,7 +83,8 @@ def train_sampler_epoch(args, epoch, model, sampler, optimizer, scheduler, train
             dec_motion, sampler_dist, vae_dist, _ = sampler.forward(model)
             fut = torch.as_tensor(pred_traj_gt, dtype=torch.float32).to(sampler.device).transpose(1, 2)   # [N 2 T] -> [N T 2]
             total_loss, loss_dict, loss_dict_uw = samplerloss.compute_sampler_loss(args, fut, dec_motion, 1, pred_loss_mask, vae_dist,
-                                                                                    sampler_dist, div_cfg, **terms)
+                                                                                    sampler_dist, div_cfg, **terms,
+                                                                                    **(dict(joint=True) if joint else {}))
         optimizer.zero_grad()
         total_loss.backward()
         optimizer.step()
