@@ -238,6 +238,36 @@ int sttode_kde_nll(const float* pred, const float* gt, int n, int K, int Tf, flo
  * Refused before any launch or write, naming the entry.  No atomics, every sum in a fixed order: the same bits on every run. */
 int sttode_sample_spread(const float* pred, const float* gt, int n, int K, int Tf, float scale, double div_scale, double* apd, double* fpd,
                          double* pade, double* dlow, double* es_ade, double* es_fde, float* ade_at_k, float* fde_at_k, void* stream);
+/* A weighted sample set against the ground truth (added within ABI version 15): K representatives per agent with raw weights
+ * (sttode_reduce_samples' counts, counts / M, or mode probabilities).  The reference computes none of this; kde_nll stands for
+ * Trajectron++'s compute_kde_nll over scipy.stats.gaussian_kde(dataset, weights=w), the rest for the probability-ranked minADE_k / minFDE_k,
+ * brier-minFDE and energy score of Argoverse / Waymo style tables.
+ * pred [n,K,Tf,2], weights [n,K], gt [n,Tf,2] float32; n >= 1, 1 <= K <= 64, Tf >= 1.  Coordinates are x = (double)(x * scale), the product
+ * in float32 as sttode_kde_nll; everything after that is float64 unless stated.
+ * Weights: W = sum_k w_k in sample order, p_k = w_k / W, s2 = sum_k p_k^2 in sample order, P = #{k : w_k > 0}.  A sample with w_k == 0 is not
+ * part of the set: its coordinates enter no sum, minimum or rank (they may be NaN).  A row with a negative or non-finite weight or W == 0
+ * makes every output of that agent NaN (decided on the device).  Multiplying a row's weights by a power of two changes no bit.
+ * ADE_k / FDE_k: bok_select_kernel's float32 values (bok_dist, frames in frame order).  D_k / L_k: the float64 mean-over-frames / last-frame
+ * distance to gt; d_ij / l_ij the same between samples i < j (F.pdist order), t_ij = sqrt(sum_t |x_i,t - x_j,t|^2).
+ * Per agent, float64 [n], required:
+ *   eade = sum p_k D_k, efde = sum p_k L_k;  es_ade = eade - sum_{i<j} p_i p_j d_ij, es_fde = efde - sum_{i<j} p_i p_j l_ij (energy scores;
+ *   p = 1/K: sttode_sample_spread's);  apd = 2 sum_{i<j} p_i p_j t_ij / (1 - s2), fpd the same with l_ij (the expected distance between two
+ *   different draws; NaN if 1 - s2 <= 0, i.e. P = 1; p = 1/K: sttode_sample_spread's);  neff = 1 / s2.
+ * Optional (may be NULL):
+ *   kde_nll [n]: per frame m = sum p_k x_k, C = sum p_k (x_k - m)(x_k - m)^T / (1 - s2), Sigma = f^2 C with f = neff^(-1/6),
+ *   logpdf = logsumexp_k(log p_k - (y - x_k)^T Sigma^-1 (y - x_k) / 2) - log det(2 pi Sigma) / 2 over the samples with p_k > 0, clipped below
+ *   at -20; nll = -mean over frames.  NaN if P < 3 (two points are collinear: det C is rounding noise), or C00 <= 0 or det C <= 0 at some
+ *   frame (sums in sample order; sttode_kde_nll's rule).  p = 1/K: sttode_kde_nll.
+ *   ade_top / fde_top [n,K] float32: samples ranked by weight, descending, ties to the lower index, zero weights last; column k-1 = the
+ *   minimum of ADE / FDE over the k highest-ranked samples (fminf: NaN skipped; a prefix that is all NaN gives +inf below 64 samples, as
+ *   sttode_sample_spread); columns beyond P repeat column P.  Equal weights: sttode_sample_spread's ade_at_k / fde_at_k bit for bit.
+ *   brier_ade / brier_fde [n]: (double)min_k ADE_k + (1 - p_k*)^2, k* the lowest-index positive-weight sample that attains the float32
+ *   minimum (NaN if none does); FDE alike.
+ * Refused before any launch or write, naming the entry.  One launch, no atomics, every sum in a fixed order: the same bits on every run, and
+ * an agent's values do not depend on the rest of the batch. */
+int sttode_weighted_set(const float* pred, const float* weights, const float* gt, int n, int K, int Tf, float scale, double* eade, double* efde,
+                        double* es_ade, double* es_fde, double* apd, double* fpd, double* kde_nll, double* brier_ade, double* brier_fde,
+                        double* neff, float* ade_top, float* fde_top, void* stream);
 /* Multi-modal ground truth over a dataset: MMADE / MMFDE of DLow and its successors (the reference computes nothing like it).
  * Do the K samples of agent i cover the futures that agents with a similar history actually had?
  * pred [n,K,Tf,2], past [n,Tp,2], gt [n,Tf,2] float32; seg_ptr NULL (n_seg = 0: all agents are one segment) or a CSR [n_seg+1] over the

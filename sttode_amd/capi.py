@@ -43,6 +43,8 @@ SIGNATURES = {
     'sttode_joint_select': [_P, _P, _I, _I, _I, _F, _P, _I, _F] + [_P] * 7,
     'sttode_kde_nll': [_P, _P, _I, _I, _I, _F, _P, _P],
     'sttode_sample_spread': [_P, _P, _I, _I, _I, _F, _D] + [_P] * 9,
+    # weighted sample sets (csrc/weighted.hip; added within ABI version 15)
+    'sttode_weighted_set': [_P, _P, _P, _I, _I, _I, _F] + [_P] * 13,
     # multi-modal ground truth (csrc/multimodal.hip)
     'sttode_multimodal': [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _D, _P, _L, _P, _P, _P, _P],
     # stage-2 sampler (csrc/sampler.hip)

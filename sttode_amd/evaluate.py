@@ -208,7 +208,15 @@ class EvalReport:
     mean pairwise trajectory / final-frame / per-frame distance), ``dlow`` (mean over agents of the DLow kernel value at ``div_scale``:
     diversity_loss's loss_unweighted), ``energy_ade`` / ``energy_fde`` (mean energy score), all float64 sums over agents in dataset order;
     ``spread_agents`` [n, 6] float64 (the six values per agent, in that order); ``ade_at_k`` / ``fde_at_k``: a dict k -> mean over agents of
-    the min ADE / FDE over the first k samples, for each k <= K of ``ks``."""
+    the min ADE / FDE over the first k samples, for each k <= K of ``ks``.
+
+    The samples as a weighted set, None unless ``weighted=True`` (eval_scenes_reduced: the centroids with the clusters'
+    shares as weights): ``w_kde_nll`` (KDE NLL under the weighted mixture), ``w_es_ade`` / ``w_es_fde`` (energy scores), ``w_apd`` / ``w_fpd``
+    (expected distance between two different draws), ``eade`` / ``efde`` (expected ADE / FDE), ``brier_ade`` / ``brier_fde``, ``mean_neff`` --
+    each the mean over the agents whose value is finite, as ``kde_nll`` -- ``w_kde_invalid`` (agents whose weighted KDE NLL is NaN),
+    ``weighted_agents`` [n, 10] float64 (per agent: eade, efde, es_ade, es_fde, apd, fpd, kde_nll, brier_ade, brier_fde, neff) and
+    ``ade_top_k`` / ``fde_top_k``: a dict k -> mean over agents of the min ADE / FDE over the k most probable samples, for k = 1 and each
+    k <= K of ``ks``."""
     ade: float
     fde: float
     n_agents: int
@@ -234,6 +242,20 @@ class EvalReport:
     kde_nll: float = None
     kde_nll_agents: np.ndarray = None
     kde_invalid: int = None
+    w_kde_nll: float = None
+    w_kde_invalid: int = None
+    w_es_ade: float = None
+    w_es_fde: float = None
+    w_apd: float = None
+    w_fpd: float = None
+    eade: float = None
+    efde: float = None
+    brier_ade: float = None
+    brier_fde: float = None
+    ade_top_k: dict = None
+    fde_top_k: dict = None
+    mean_neff: float = None
+    weighted_agents: np.ndarray = None
     apd: float = None
     fpd: float = None
     pade: float = None
@@ -254,7 +276,7 @@ class _ReportAcc:
     small per-scene / per-agent arrays, kept per call under the name of the EvalReport field they become."""
 
     def __init__(self, miss_threshold, joint=False, kde=False, collision_radius=None, K=None, spread=False, div_scale=None, ks=(1, 5, 10),
-                 dataset=None):
+                 dataset=None, weighted=False):
         from .metrics import check_radius, check_spread
         self.thr = float(miss_threshold)
         self.tot_a = self.tot_f = 0.0
@@ -268,6 +290,9 @@ class _ReportAcc:
                 div_scale = get_diversity_config(dataset)['scale'] if dataset is not None else 1.0
             self.div_scale = check_spread(K, div_scale)
             self.ks = [int(k) for k in ks if 1 <= int(k) <= K]
+        self.weighted = bool(weighted)
+        if self.weighted:
+            self.wks = sorted({1} | {int(k) for k in ks if 1 <= int(k) <= K})
 
     @property
     def scene_metrics(self):
@@ -285,6 +310,11 @@ class _ReportAcc:
         cols = torch.tensor([k - 1 for k in self.ks], dtype=torch.long, device=ss.apd.device)
         self._put(spread_agents=torch.stack([ss.apd, ss.fpd, ss.pade, ss.dlow, ss.es_ade, ss.es_fde], dim=1), ade_at_k=ss.ade_at_k[:, cols],
                   fde_at_k=ss.fde_at_k[:, cols])
+
+    def add_weighted(self, ws):
+        cols = torch.tensor([k - 1 for k in self.wks], dtype=torch.long, device=ws.eade.device)
+        self._put(weighted_agents=torch.stack([getattr(ws, f) for f in ws.F64], dim=1), ade_top_k=ws.ade_top[:, cols],
+                  fde_top_k=ws.fde_top[:, cols])
 
     def add_scene_metrics(self, js, kd, ss=None):
         if ss is not None:
@@ -331,6 +361,19 @@ class _ReportAcc:
             rep.apd, rep.fpd, rep.pade, rep.dlow, rep.energy_ade, rep.energy_fde = (float(x) for x in v.sum(axis=0) / v.shape[0])
             rep.ade_at_k = {k: float(ak[:, i].astype(np.float64).sum() / ak.shape[0]) for i, k in enumerate(self.ks)}
             rep.fde_at_k = {k: float(fk[:, i].astype(np.float64).sum() / fk.shape[0]) for i, k in enumerate(self.ks)}
+        if self.weighted:
+            v, ak, fk = (self._cat(f) for f in ('weighted_agents', 'ade_top_k', 'fde_top_k'))
+
+            def mean(x):                                                # over the agents whose value is finite, as kde_nll
+                x = x.astype(np.float64)
+                ok = np.isfinite(x)
+                return float(x[ok].mean()) if ok.any() else float('nan')
+            rep.weighted_agents = v
+            (rep.eade, rep.efde, rep.w_es_ade, rep.w_es_fde, rep.w_apd, rep.w_fpd, rep.w_kde_nll, rep.brier_ade, rep.brier_fde,
+             rep.mean_neff) = (mean(v[:, i]) for i in range(v.shape[1]))
+            rep.w_kde_invalid = int((~np.isfinite(v[:, 6])).sum())
+            rep.ade_top_k = {k: mean(ak[:, i]) for i, k in enumerate(self.wks)}
+            rep.fde_top_k = {k: mean(fk[:, i]) for i, k in enumerate(self.wks)}
         return rep
 
 
@@ -395,7 +438,7 @@ def eval_scenes_report(model, dataset, traj_scale=1.0, scenes_per_call=512, z_fn
 
 @torch.no_grad()
 def eval_scenes_reduced(model, dataset, rounds, K=None, iters=10, from_frame=0, init='first', traj_scale=1.0, scenes_per_call=512, z_fn=None,
-                        pipelined=True, miss_threshold=1.0, spread=False, div_scale=None, ks=(1, 5, 10)):
+                        pipelined=True, miss_threshold=1.0, spread=False, div_scale=None, ks=(1, 5, 10), weighted=False):
     """Oversample and reduce as an evaluation loop: per scene batch ``rounds`` inference calls -- M = rounds * sample_k futures
     per agent -- reduced to ``K`` (default sample_k) representatives per agent by ``metrics.reduce_samples`` (``iters``, ``from_frame``,
     ``init`` as there), and the best-of-K selection of eval_scenes_report on the representatives.  Returns an ``EvalReport``.
@@ -403,14 +446,17 @@ def eval_scenes_reduced(model, dataset, rounds, K=None, iters=10, from_frame=0, 
     in flight than ``async_depth`` allows; each is waited for and copied into the round buffer before its slot is taken again.  The reduction
     and the selection run on the caller's stream.  The two forms' samples differ by fp32 rounding (as inference_async and inference do), so
     with rounds > 1 a near-tied label may legitimately differ between them.  ``spread`` / ``div_scale`` / ``ks`` as eval_scenes_report, on the
-    representatives: what the reduction does to the diversity of the set."""
+    representatives: what the reduction does to the diversity of the set.  ``weighted`` adds the weighted-set pass (``weighted_set``) on the
+    representatives with the clusters' shares ``Reduction.weights`` as their probabilities: the ``w_*``, ``eade`` / ``efde``, ``brier_*``,
+    ``*_top_k`` (k = 1 and each k of ``ks``) and ``mean_neff`` fields; with it off the loop makes the calls it made before."""
     from . import metrics
     rounds = int(rounds)
     if rounds < 1:
         raise ValueError(f'eval_scenes_reduced needs rounds >= 1, got {rounds}')
     Ks = model.args.sample_k
     K = Ks if K is None else int(K)
-    acc = _ReportAcc(miss_threshold, K=K, spread=spread, div_scale=div_scale, ks=ks, dataset=getattr(model.args, 'dataset', None))
+    acc = _ReportAcc(miss_threshold, K=K, spread=spread, div_scale=div_scale, ks=ks, dataset=getattr(model.args, 'dataset', None),
+                     weighted=weighted)
     depth = max(2, min(8, int(model.async_depth)))
     for s0 in range(0, len(dataset), scenes_per_call):
         sb = dataset.scene_batch(range(s0, min(s0 + scenes_per_call, len(dataset))))
@@ -438,6 +484,8 @@ def eval_scenes_reduced(model, dataset, rounds, K=None, iters=10, from_frame=0, 
         acc.add(model.select_best_of_k(red.centroids, scale=traj_scale, miss_threshold=miss_threshold, seg_ptr=model._scene_ptr), sb.scene_ptr)
         if spread:
             acc.add_spread(model.sample_spread(red.centroids, scale=traj_scale, div_scale=acc.div_scale))
+        if weighted:
+            acc.add_weighted(model.weighted_set(red.centroids, red.weights, scale=traj_scale))
     if pipelined:
         model.reset_async()
     return acc.report(False)

@@ -5,7 +5,9 @@ sttode_best_of_k_select).
 and collision counts per segment, and the KDE NLL per agent.  ``sample_spread`` compares an agent's samples with each other:
 pairwise distances, the DLow kernel value, energy scores and best-of-k for every k.  ``multimodal`` (csrc/multimodal.hip)
 scores them against the futures of all agents with a similar history, over a whole dataset: MMADE / MMFDE.  ``reduce_samples`` (csrc/reduce.hip)
-clusters M sampled futures per agent to K representatives.
+clusters M sampled futures per agent to K representatives.  ``weighted_set`` (csrc/weighted.hip) scores K samples with
+probabilities -- those representatives and their cluster shares -- as a weighted set: expected errors, energy scores, the KDE NLL of the
+weighted mixture, probability-ranked best-of-k.
 
 ``select`` is the kernel call: per agent the min-over-K ADE / FDE, the index of the best sample by ADE and by final displacement
 (``get_best_idx``), the miss flag (``count_miss_samples``) and optionally the best trajectory; per CSR segment (a scene, an NBA batch) the
@@ -246,6 +248,67 @@ def sample_spread(pred_nk, gt=None, scale=1.0, div_scale=1.0):
     out = SampleSpread(n, K, pred_nk.device, ds, gt is not None)
     with torch.cuda.device(pred_nk.device):
         capi.call('sttode_sample_spread', pred_nk, gt, n, K, Tf, float(scale), *out.args(), capi.stream_ptr())
+    return out
+
+
+# ----- weighted sample sets (csrc/weighted.hip: sttode_weighted_set) --------------------------------------------------------
+
+class WeightedSet:
+    """Outputs of one weighted-set pass (device tensors), per agent.  float64 [n]: ``eade`` / ``efde`` (expected ADE / FDE under the
+    normalised weights), ``es_ade`` / ``es_fde`` (energy scores), ``apd`` / ``fpd`` (expected trajectory / final-frame distance between two
+    different draws; NaN with a single positive weight), ``kde_nll`` (the NLL under scipy's weighted gaussian_kde; NaN with fewer than three
+    positive weights or a singular covariance), ``brier_ade`` / ``brier_fde`` (min ADE / FDE + (1 - p of that sample)^2), ``neff`` (1 / sum
+    p^2).  float32 [n, K]: ``ade_top`` / ``fde_top`` (column k-1: min ADE / FDE over the k most probable samples).  A row whose weights
+    are negative, non-finite or all zero is NaN everywhere."""
+    F64 = ('eade', 'efde', 'es_ade', 'es_fde', 'apd', 'fpd', 'kde_nll', 'brier_ade', 'brier_fde', 'neff')
+    __slots__ = F64 + ('ade_top', 'fde_top', 'K')
+
+    def __init__(self, n, K, device):
+        d = torch.empty(len(self.F64) * n, dtype=torch.float64, device=device)
+        for i, name in enumerate(self.F64):
+            setattr(self, name, d[i * n:(i + 1) * n])
+        f = torch.empty(2 * n * K, dtype=torch.float32, device=device)
+        self.ade_top, self.fde_top = f[:n * K].view(n, K), f[n * K:].view(n, K)
+        self.K = K
+
+    def args(self):
+        """Output pointers in the order of sttode_weighted_set."""
+        return tuple(getattr(self, name) for name in self.F64) + (self.ade_top, self.fde_top)
+
+    def at(self, k):
+        """(min ADE, min FDE) [n] over the ``k`` most probable samples, 1 <= k <= K."""
+        k = int(k)
+        if not 1 <= k <= self.K:
+            raise ValueError(f'k must be in [1, {self.K}], got {k}')
+        return self.ade_top[:, k - 1], self.fde_top[:, k - 1]
+
+    def record_stream(self, stream):
+        for t in (self.eade, self.ade_top):   # (views: the record covers the whole allocation)
+            t.record_stream(stream)
+
+
+def check_weighted_k(K):
+    if K < 1 or K > 64:
+        raise ValueError(f'a weighted sample set needs 1 <= K <= 64 samples (one lane per sample), got K = {K}')
+
+
+@torch.no_grad()
+def weighted_set(pred_nk, weights, gt, scale=1.0):
+    """The K samples of pred_nk [n, K, Tf, 2] as a weighted set -- ``weights`` [n, K] float32, raw: ``Reduction.weights``,
+    ``Reduction.counts.float()`` or any mode probabilities, normalised per agent on the device -- scored against gt [n, Tf, 2], in float64
+    on the current stream (include/sttode_hip.h sttode_weighted_set states every value).  A sample with weight 0 is not part of the set.
+    1 <= K <= 64.  Returns a ``WeightedSet``."""
+    pred_nk, gt, n, K, Tf = _inputs(pred_nk, gt, 'a weighted sample set')
+    check_weighted_k(K)
+    if not (isinstance(weights, torch.Tensor) and weights.is_cuda):
+        raise capi.SttodeError('a weighted sample set runs on a HIP device only (no CPU fallback): pass the weights as a device tensor')
+    if weights.dtype != torch.float32:
+        raise ValueError(f'weights must be float32 (Reduction.weights, or Reduction.counts.float()), got {weights.dtype}')
+    if tuple(weights.shape) != (n, K) or weights.device != pred_nk.device:
+        raise ValueError(f'weights must be [{n}, {K}] on {pred_nk.device}, got {tuple(weights.shape)} on {weights.device}')
+    out = WeightedSet(n, K, pred_nk.device)
+    with torch.cuda.device(pred_nk.device):
+        capi.call('sttode_weighted_set', pred_nk, weights.contiguous(), gt, n, K, Tf, float(scale), *out.args(), capi.stream_ptr())
     return out
 
 

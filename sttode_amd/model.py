@@ -1200,6 +1200,16 @@ class STTODENet(nn.Module):
                                div_scale=div_scale)
 
     @torch.no_grad()
+    def weighted_set(self, pred_nk, weights, gt=None, scale=1.0):
+        """A weighted sample set against the ground truth per agent on device: pred_nk [n,K,Tf,2], weights [n,K] (raw:
+        ``Reduction.weights``, ``Reduction.counts.float()`` or mode probabilities), gt [n,Tf,2] (default: the futures set with the batch)
+        -> ``metrics.WeightedSet`` (expected errors, energy scores, KDE NLL under the weighted mixture, probability-ranked best-of-k,
+        Brier-penalised minima, effective sample size).  1 <= K <= 64.  The twin of ``sample_spread`` on the caller's stream."""
+        from . import metrics
+        gt = self._future if gt is None else _f32(gt, self.device)
+        return metrics.weighted_set(pred_nk, weights, gt, scale=scale)
+
+    @torch.no_grad()
     def horizon_metrics(self, pred_nk, gt=None, scale=1.0):
         """The NBA evaluation's per-horizon metric (test.py:530-551) on device: pred_nk [n,K,Tf,2], gt [n,Tf,2] -> [n,Tf,2] with
         [a, h-1] = (min_k mean_{t<h} |scale (pred - gt)|, min_k |scale (pred_h - gt_h)|)."""
