@@ -854,6 +854,40 @@ int sttode_reduce_samples(const float* pred, int n, int R, int K_in, int Tf, int
                           const float* init, float* centroids, int* labels, int* counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Oversample and reduce whole scenes: Lloyd k-means in which a sample is one future of a whole segment.  Added WITHIN ABI
+ * version 15: one new export, nothing else changed, so a binding built for 15 keeps working.
+ * ------------------------------------------------------------------------------------------------ */
+/* pred [R,n,K_in,Tf,2] fp32, round-major, exactly as for sttode_reduce_samples; M = R K_in.  seg_ptr [S+1] int32 on the device, the CSR of
+ * sttode_joint_select: segment s (a scene, an NBA game) holds the agents seg_ptr[s] .. seg_ptr[s+1]-1 (every bound is clamped to [0, n] and
+ * to its predecessor on the device; agents outside every segment keep whatever their centroids held).  Sample m of a segment is the scene
+ * future made of sample m of each of its A agents, a point of R^(A 2 Tf); all agents of a segment share one label per sample and one count
+ * per cluster.  With x[a,m] agent a's sample m and t0 = from_frame, per segment s:
+ *     c_0 = init
+ *     for i = 1 .. iters:
+ *         d_a(m,k)      = sum_{t >= t0} |x[a,m,t] - c_{i-1}[a,k,t]|^2                 (fp32)
+ *         D(m,k)        = sum over the segment's agents a, in order, of (double) d_a(m,k)
+ *         label_i[s,m]  = argmin_k D(m,k)                                             (the lowest k on exact ties)
+ *         c_i[a,k]      = mean of x[a,m] over {m : label_i[s,m] = k}, ALL frames      (c_{i-1}[a,k] if that set is empty, for every agent alike)
+ *     centroids [n,K,Tf,2] fp32 = c_iters, labels [S,M] int32 = label_iters, counts [S,K] int32: counts[s,k] = |{m : label_iters[s,m] = k}|
+ * Representative k of a segment is then one coherent scene future, and counts / M are the weights of the scene futures.
+ * init_mode 0 ('first'): scene futures 0 .. K-1, i.e. every agent's samples 0 .. K-1; 1 ('maximin'): scene future 0, then K-1 times the
+ * scene future whose distance D (same slice, float64 sum over the agents of the fp32 per-agent squared distances) to its nearest pick is
+ * largest, the lowest index on ties; 2: the caller's init [n,K,Tf,2].  init is non-NULL exactly in mode 2.
+ * Arithmetic: d_a(m,k) has the bits sttode_reduce_samples computes (an fma chain over the slice in coordinate order from 0, direct
+ * differences); the sum over agents is float64 in segment order; a cluster's members are added in sample order starting from the first
+ * member and the sum is divided by the count, in fp32; no floating-point atomics.  Hence a CSR of one-agent segments gives the bits of
+ * sttode_reduce_samples (centroids, labels, counts); two runs give the same bits; a segment's outputs are the same bits alone, with segments
+ * appended behind it or with agents put in front of it.  The loop ends early once an iteration changes no label.  An empty segment gets
+ * labels 0 and counts (M, 0, ..) and touches no centroid.  Non-finite inputs: outputs unspecified, labels still in [0, K), nothing read or
+ * written out of bounds.
+ * One workgroup per segment for the whole loop; the centroids live in the output array, labels and counts in LDS; no workspace.
+ * Limits, refused before anything is launched or written: n >= 1, S >= 1, 1 <= K <= 64, K <= M <= 4096, 1 <= Tf <= 200, 0 <= from_frame < Tf,
+ * 1 <= iters <= 1000, init_mode in {0, 1, 2}, no NULL among pred, seg_ptr, centroids, labels, counts.  Nothing is refused for the size of a
+ * segment: it may be all n agents. */
+int sttode_reduce_scenes(const float* pred, int n, int R, int K_in, int Tf, int K, int iters, int from_frame, int init_mode,
+                         const float* init, const int* seg_ptr, int S, float* centroids, int* labels, int* counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Native forward pipeline: one call enqueues STTODENet.inference (model/STTODE.py:574-623) end to end.
  * ------------------------------------------------------------------------------------------------ */
 typedef struct SttodeModel SttodeModel;

@@ -134,6 +134,8 @@ SIGNATURES = {
     'sttode_delta_hyp': [_P, _I, _I, _L, _I, _P, _L, _P, _P],
     # oversample and reduce (csrc/reduce.hip; added within ABI version 14)
     'sttode_reduce_samples': [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    # oversample and reduce whole scenes (csrc/reduce_scenes.hip; added within ABI version 15; no workspace)
+    'sttode_reduce_scenes': [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P],
     # attention core with a running maximum, two score modes, optional mask (csrc/attention.hip; added within ABI version 14)
     'sttode_attn_core': [_P, _P, _P, _P, _L, _P, _P, _P, _P, _I, _I, _I] + [_L] * 8 + [_F, _F, _I, _P],
     'sttode_attn_core_bwd': [_P, _P, _P, _P, _L, _P, _P, _P, _P, _I, _I, _I] + [_L] * 8 + [_F, _F, _I, _P],

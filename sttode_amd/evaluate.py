@@ -10,7 +10,9 @@
                   the scene-level metrics of DESIGN.md 4l: joint min ADE / FDE, collision rates, KDE NLL; and the spread of the samples
                   among themselves of DESIGN.md 4s: APD / FPD, the DLow kernel value, energy scores, best-of-k.
   eval_scenes_reduced  oversample and reduce: `rounds` calls per scene batch, k-means of the rounds * sample_k futures of every
-                  agent to K representatives on the device, then the selection of eval_scenes_report on the representatives.
+                  agent to K representatives on the device, then the selection of eval_scenes_report on the representatives; with
+                  level='scene'  k-means of every scene's futures as whole scene futures, and on request the joint,
+                  collision and KDE passes on the representatives of either level.
   eval_scenes_multimodal  MMADE / MMFDE: the samples of the whole dataset gathered on the device, then one pass that scores every
                   agent's samples against the futures of all agents with a similar history.
   embedding_delta  how tree-like the encoder's past features (or the observed tracks) of a dataset are: delta / diam of hyptorch/delta.py's
@@ -438,7 +440,8 @@ def eval_scenes_report(model, dataset, traj_scale=1.0, scenes_per_call=512, z_fn
 
 @torch.no_grad()
 def eval_scenes_reduced(model, dataset, rounds, K=None, iters=10, from_frame=0, init='first', traj_scale=1.0, scenes_per_call=512, z_fn=None,
-                        pipelined=True, miss_threshold=1.0, spread=False, div_scale=None, ks=(1, 5, 10), weighted=False):
+                        pipelined=True, miss_threshold=1.0, spread=False, div_scale=None, ks=(1, 5, 10), weighted=False, level='agent',
+                        joint=False, collision_radius=None, kde=False):
     """Oversample and reduce as an evaluation loop: per scene batch ``rounds`` inference calls -- M = rounds * sample_k futures
     per agent -- reduced to ``K`` (default sample_k) representatives per agent by ``metrics.reduce_samples`` (``iters``, ``from_frame``,
     ``init`` as there), and the best-of-K selection of eval_scenes_report on the representatives.  Returns an ``EvalReport``.
@@ -448,15 +451,22 @@ def eval_scenes_reduced(model, dataset, rounds, K=None, iters=10, from_frame=0, 
     with rounds > 1 a near-tied label may legitimately differ between them.  ``spread`` / ``div_scale`` / ``ks`` as eval_scenes_report, on the
     representatives: what the reduction does to the diversity of the set.  ``weighted`` adds the weighted-set pass (``weighted_set``) on the
     representatives with the clusters' shares ``Reduction.weights`` as their probabilities: the ``w_*``, ``eade`` / ``efde``, ``brier_*``,
-    ``*_top_k`` (k = 1 and each k of ``ks``) and ``mean_neff`` fields; with it off the loop makes the calls it made before."""
+    ``*_top_k`` (k = 1 and each k of ``ks``) and ``mean_neff`` fields; with it off the loop makes the calls it made before.
+    ``level='scene'`` reduces whole scenes by ``metrics.reduce_scenes`` over the batch's scene_ptr: representative k of a
+    scene's agents is one coherent scene future, and ``weighted`` takes ``SceneReduction.agent_weights``.  ``joint`` / ``collision_radius`` /
+    ``kde`` add ``select_joint`` / ``kde_nll`` on the representatives, at either level, into the scene-metric fields of the report: what
+    each kind of reduction does to the joint numbers (per-agent representatives share nothing but their cluster's number across agents;
+    scene representatives are scene futures).  With these four at their defaults the loop makes the calls it made before."""
     from . import metrics
     rounds = int(rounds)
     if rounds < 1:
         raise ValueError(f'eval_scenes_reduced needs rounds >= 1, got {rounds}')
+    if level not in ('agent', 'scene'):
+        raise ValueError(f"level must be 'agent' or 'scene', got {level!r}")
     Ks = model.args.sample_k
     K = Ks if K is None else int(K)
-    acc = _ReportAcc(miss_threshold, K=K, spread=spread, div_scale=div_scale, ks=ks, dataset=getattr(model.args, 'dataset', None),
-                     weighted=weighted)
+    acc = _ReportAcc(miss_threshold, joint=joint, kde=kde, collision_radius=collision_radius, K=K, spread=spread, div_scale=div_scale, ks=ks,
+                     dataset=getattr(model.args, 'dataset', None), weighted=weighted)
     depth = max(2, min(8, int(model.async_depth)))
     for s0 in range(0, len(dataset), scenes_per_call):
         sb = dataset.scene_batch(range(s0, min(s0 + scenes_per_call, len(dataset))))
@@ -480,12 +490,18 @@ def eval_scenes_reduced(model, dataset, rounds, K=None, iters=10, from_frame=0, 
         else:
             for r in range(rounds):
                 buf[r].copy_(model.inference(None, z=_latents(model, rows, z_fn)).permute(1, 0, 2, 3))
-        red = metrics.reduce_samples(buf, K, iters=iters, from_frame=from_frame, init=init)
+        if level == 'scene':
+            red = metrics.reduce_scenes(buf, model._scene_ptr, K, iters=iters, from_frame=from_frame, init=init)
+        else:
+            red = metrics.reduce_samples(buf, K, iters=iters, from_frame=from_frame, init=init)
         acc.add(model.select_best_of_k(red.centroids, scale=traj_scale, miss_threshold=miss_threshold, seg_ptr=model._scene_ptr), sb.scene_ptr)
         if spread:
             acc.add_spread(model.sample_spread(red.centroids, scale=traj_scale, div_scale=acc.div_scale))
+        if acc.scene_metrics or acc.kde:
+            acc.add_scene_metrics(model.select_joint(red.centroids, seg_ptr=model._scene_ptr, scale=traj_scale, collision_radius=acc.radius)
+                                  if acc.scene_metrics else None, model.kde_nll(red.centroids, scale=traj_scale) if acc.kde else None)
         if weighted:
-            acc.add_weighted(model.weighted_set(red.centroids, red.weights, scale=traj_scale))
+            acc.add_weighted(model.weighted_set(red.centroids, red.agent_weights if level == 'scene' else red.weights, scale=traj_scale))
     if pipelined:
         model.reset_async()
     return acc.report(False)

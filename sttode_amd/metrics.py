@@ -5,7 +5,8 @@ sttode_best_of_k_select).
 and collision counts per segment, and the KDE NLL per agent.  ``sample_spread`` compares an agent's samples with each other:
 pairwise distances, the DLow kernel value, energy scores and best-of-k for every k.  ``multimodal`` (csrc/multimodal.hip)
 scores them against the futures of all agents with a similar history, over a whole dataset: MMADE / MMFDE.  ``reduce_samples`` (csrc/reduce.hip)
-clusters M sampled futures per agent to K representatives.  ``weighted_set`` (csrc/weighted.hip) scores K samples with
+clusters M sampled futures per agent to K representatives, ``reduce_scenes`` (csrc/reduce_scenes.hip) a segment's M scene
+futures, all its agents under one label, so that representative k is a coherent scene future.  ``weighted_set`` (csrc/weighted.hip) scores K samples with
 probabilities -- those representatives and their cluster shares -- as a weighted set: expected errors, energy scores, the KDE NLL of the
 weighted mixture, probability-ranked best-of-k.
 
@@ -440,6 +441,93 @@ def reduce_samples(pred, K, iters=10, from_frame=0, init='first'):
     out = Reduction(n, R * K_in, K, Tf, dev)
     with torch.cuda.device(dev):
         capi.call('sttode_reduce_samples', pred, n, R, K_in, Tf, K, iters, from_frame % Tf, mode, init_t, out.centroids, out.labels,
+                  out.counts, capi.stream_ptr())
+    return out
+
+
+# ----- oversample and reduce whole scenes (csrc/reduce_scenes.hip: sttode_reduce_scenes) ----------------------------------
+
+class SceneReduction:
+    """Outputs of one scene-level reduction (device tensors): ``centroids`` [n, K, Tf, 2] float32 (representative k of a segment's agents is
+    one scene future), ``labels`` [S, M] int32 (the cluster of every scene future), ``counts`` [S, K] int32, ``weights`` [S, K] float32 =
+    counts / M, ``seg_ptr`` [S+1] int32 as used, and ``agent_weights`` [n, K] float32: every agent's segment row of ``weights`` (a gather on
+    the device; 0 for an agent outside every segment), what ``weighted_set`` takes."""
+    __slots__ = ('centroids', 'labels', 'counts', 'seg_ptr', 'M', '_weights', '_agent_weights')
+
+    def __init__(self, n, S, M, K, Tf, device, seg_ptr):
+        self.centroids = torch.empty(n, K, Tf, 2, dtype=torch.float32, device=device)
+        i = torch.empty(S * M + S * K, dtype=torch.int32, device=device)
+        self.labels, self.counts = i[:S * M].view(S, M), i[S * M:].view(S, K)
+        self.seg_ptr, self.M = seg_ptr, M
+        self._weights = self._agent_weights = None
+
+    @property
+    def weights(self):
+        if self._weights is None:
+            self._weights = self.counts.to(torch.float32) / float(self.M)
+        return self._weights
+
+    @property
+    def agent_weights(self):
+        if self._agent_weights is None:
+            n, S = self.centroids.shape[0], self.counts.shape[0]
+            sp = torch.cummax(self.seg_ptr.to(torch.int64).clamp(0, n), dim=0)[0]      # (as the kernel clamps a device CSR)
+            a = torch.arange(n, device=sp.device)
+            seg = torch.bucketize(a, sp[1:], right=True)                               # the segment whose [start, end) holds agent a
+            inside = ((a >= sp[0]) & (a < sp[-1])).unsqueeze(1)
+            self._agent_weights = torch.where(inside, self.weights[seg.clamp(max=S - 1)], torch.zeros((), device=sp.device))
+        return self._agent_weights
+
+
+@torch.no_grad()
+def reduce_scenes(pred, seg_ptr=None, K=None, iters=10, from_frame=0, init='first', *, seg_len=None):
+    """Lloyd k-means of every segment's M sampled SCENE futures to K representatives, on the current stream (include/sttode_hip.h
+    sttode_reduce_scenes states the iteration): sample m of a segment is sample m of all its agents together, so its agents share one label
+    per sample and representative k is a coherent scene future again -- what the joint metrics, the collision rate and ``weighted_set`` need.
+    ``pred``: [n, M, Tf, 2] or [R, n, K_in, Tf, 2] as for ``reduce_samples``.  ``seg_ptr``: CSR [S+1] (tensor, array or list; a host one must
+    run non-decreasing from 0 to n), or ``seg_len=N``: uniform segments of N agents (NBA games).  ``iters``, ``from_frame``, ``init`` as
+    ``reduce_samples`` ('maximin' picks whole scene futures).  K <= 64, K <= M <= 4096; a segment may be all n agents.  Returns a
+    ``SceneReduction``."""
+    if not (isinstance(pred, torch.Tensor) and pred.is_cuda):
+        raise capi.SttodeError('scene reduction runs on a HIP device only (no CPU fallback): pass device tensors')
+    if K is None:
+        raise ValueError('scene reduction needs K, the number of representatives')
+    if pred.dim() == 4:
+        pred = pred.unsqueeze(0)
+    if pred.dim() != 5 or pred.shape[4] != 2 or 0 in pred.shape:
+        raise ValueError(f'pred must be [n, M, Tf, 2] or [R, n, K_in, Tf, 2] with no empty dimension, got {tuple(pred.shape)}')
+    dev = pred.device
+    pred = pred.to(torch.float32).contiguous()
+    R, n, K_in, Tf = pred.shape[:4]
+    if (seg_ptr is None) == (seg_len is None):
+        raise ValueError('scene reduction needs seg_ptr [S+1] or seg_len=N (uniform segments), one of them')
+    if seg_len is not None:
+        N = int(seg_len)
+        if N < 1 or n % N:
+            raise ValueError(f'seg_len must be a positive divisor of n = {n}, got {seg_len}')
+        seg_ptr = torch.arange(0, n + 1, N, dtype=torch.int32, device=dev)
+    else:
+        check_seg_ptr(seg_ptr, n)
+    sp = seg_ptr_tensor(seg_ptr, dev)
+    S = int(sp.numel()) - 1
+    K, iters, from_frame = int(K), int(iters), int(from_frame)
+    if not -Tf <= from_frame < Tf:
+        raise ValueError(f'from_frame must be in [-{Tf}, {Tf}), got {from_frame}')
+    if isinstance(init, str):
+        if init not in REDUCE_INIT:
+            raise ValueError(f"init must be 'first', 'maximin' or a tensor [n, K, Tf, 2], got {init!r}")
+        mode, init_t = REDUCE_INIT[init], None
+    else:
+        mode, init_t = 2, torch.as_tensor(init, dtype=torch.float32).to(dev).contiguous()
+        if tuple(init_t.shape) != (n, K, Tf, 2):
+            raise ValueError(f'init must be [{n}, {K}, {Tf}, 2], got {tuple(init_t.shape)}')
+    if not 1 <= K <= 64 or not K <= R * K_in <= 4096:
+        raise ValueError(f'scene reduction needs 1 <= K <= 64 and K <= M <= 4096, got K = {K}, M = {R * K_in}')
+    if not 1 <= iters <= 1000:
+        raise ValueError(f'iters must be in [1, 1000], got {iters}')
+    out = SceneReduction(n, S, R * K_in, K, Tf, dev, sp)
+    with torch.cuda.device(dev):
+        capi.call('sttode_reduce_scenes', pred, n, R, K_in, Tf, K, iters, from_frame % Tf, mode, init_t, sp, S, out.centroids, out.labels,
                   out.counts, capi.stream_ptr())
     return out
 

@@ -810,17 +810,22 @@ class STTODENet(nn.Module):
         return bufs[key]
 
     @torch.no_grad()
-    def inference_reduced(self, rounds, K=None, iters=10, from_frame=0, init='first', z=None):
+    def inference_reduced(self, rounds, K=None, iters=10, from_frame=0, init='first', z=None, level='agent'):
         """Oversample and reduce: ``rounds`` inference() calls on the data that set_data / set_scene_batch / set_data_nba
         set -- M = rounds * sample_k futures per agent -- clustered to ``K`` (default sample_k) representatives per agent by
         ``metrics.reduce_samples`` (``iters``, ``from_frame``, ``init`` as there).  ``z``: None or [rounds, n * sample_k, zdim], one slice per
         call.  Sets ``diverse_pred`` to the centroids [n, K, Tf, 2] and ``reduction`` to the ``metrics.Reduction`` (labels, counts, weights);
-        returns the [K, n, Tf, 2] permuted view, like inference()."""
+        returns the [K, n, Tf, 2] permuted view, like inference().  ``level='scene'``: the M futures are clustered as SCENE
+        futures by ``metrics.reduce_scenes`` over the batch's segments -- the scene_ptr of set_scene_batch, games of N players after
+        set_data_nba, one segment after set_data -- so representative k is one coherent future of a whole scene, and ``reduction`` is the
+        ``metrics.SceneReduction`` (labels and counts per segment, ``agent_weights`` per agent)."""
         from . import metrics
         self._require_gpu()
         rounds = int(rounds)
         if rounds < 1:
             raise ValueError(f'inference_reduced needs rounds >= 1, got {rounds}')
+        if level not in ('agent', 'scene'):
+            raise ValueError(f"level must be 'agent' or 'scene', got {level!r}")
         if self._mode is None:
             raise capi.SttodeError('call set_data / set_data_nba / set_scene_batch before inference_reduced()')
         if z is not None and (getattr(z, 'ndim', 0) != 3 or z.shape[0] != rounds):
@@ -830,7 +835,11 @@ class STTODENet(nn.Module):
         for r in range(rounds):
             self.inference(None, z=None if z is None else z[r])
             buf[r].copy_(self.diverse_pred)
-        red = metrics.reduce_samples(buf, K, iters=iters, from_frame=from_frame, init=init)
+        if level == 'scene':
+            seg = dict(seg_len=self._N) if self._mode == 'nba' else dict(seg_ptr=self._scene_ptr)
+            red = metrics.reduce_scenes(buf, K=K, iters=iters, from_frame=from_frame, init=init, **seg)
+        else:
+            red = metrics.reduce_samples(buf, K, iters=iters, from_frame=from_frame, init=init)
         self.__dict__['reduction'] = red
         self.diverse_pred = red.centroids
         return red.centroids.permute(1, 0, 2, 3)
