@@ -886,6 +886,48 @@ int sttode_reduce_samples(const float* pred, int n, int R, int K_in, int Tf, int
  * segment: it may be all n agents. */
 int sttode_reduce_scenes(const float* pred, int n, int R, int K_in, int Tf, int K, int iters, int from_frame, int init_mode,
                          const float* init, const int* seg_ptr, int S, float* centroids, int* labels, int* counts, void* stream);
+/* Scores of a whole oversampled set (csrc/large_set.hip; added within ABI version 15): the M = R K_in futures per agent that
+ * sttode_reduce_samples / sttode_reduce_scenes cluster, scored themselves -- best-of-M and its prefixes, joint best-of-M, KDE NLL at the
+ * literature's sample count, and the pair statistics of the set -- where sttode_best_of_k_select, sttode_joint_select, sttode_kde_nll and
+ * sttode_sample_spread hold one sample per lane and keep refusing K > 64.
+ * pred is round-major [R,n,K_in,Tf,2] float32 (R stacked outputs of inference: sample m = r K_in + k; R = 1 is a plain [n,M,Tf,2]), gt
+ * [n,Tf,2] float32; coordinates are scaled as in the entry each one mirrors.
+ * Limits of all three, refused by name before anything is launched or written: n >= 1, R >= 1, K_in >= 1, 1 <= M <= 4096, 1 <= Tf <= 200, no
+ * NULL among the required pointers.  M <= 64 is taken: there the values tie to the entries above.
+ * Sum order, wherever a sum runs over samples or pairs: thread tid of 256 adds its own terms in ascending order (samples tid, tid + 256, ...),
+ * the 64 lanes of a wave are added by the xor tree 32, 16, .. 1, the four waves in wave order, the workgroups of an agent in workgroup order.
+ * No atomics: two runs give the same bits, and an agent's or a segment's values do not depend on the rest of the batch.
+ * sttode_large_select:
+ *   ADE(a,m) / FDE(a,m): the float32 values bok_select_kernel computes for a sample (bok_dist, frames added in frame order, / Tf).
+ *   ade / fde [n] = min over m; best_ade_idx / best_fde_idx [n] = the lowest m that attains it; miss [n] = fde > miss_threshold (strictly).
+ *   A value wins only by being smaller (<) than the best so far, which starts at +inf with index 0: a NaN never wins, and an agent with no
+ *   finite sample gets +inf and index 0 (not bok_select_kernel's NaN).  For finite inputs and M <= 64 the outputs are
+ *   sttode_best_of_k_select's bit for bit.
+ *   ks: nk <= 16 values ON THE HOST, strictly ascending in [1, M] (nk = 0: ks, ade_at, fde_at NULL): ade_at / fde_at [n,nk], column i = the
+ *   minimum over the first ks[i] samples in m order, by the same rule.
+ *   seg_ptr [S+1] (device CSR, bounds clamped to [0, n]; NULL: no joint outputs, the four seg_* NULL, S ignored): per segment and sample the
+ *   sum over the segment's agents of ADE(a,m), in double, in agent order, / agent count; seg_jade [S] = its minimum over m as float32,
+ *   seg_jade_idx [S] = the lowest m that attains it (compared as doubles); seg_jfde / seg_jfde_idx alike.  Any segment size.  An empty
+ *   segment gets NaN and -1, one without a finite sample +inf and 0; a one-agent segment gives the agent's ade / fde / indices bitwise.
+ *   The joint outputs need ws, ws_bytes >= sttode_large_select_ws(n, M) bytes on the device (the per-sample values, overwritten).
+ *   Optional (NULL): best_ade_idx, best_fde_idx, miss.
+ * sttode_large_kde_nll (M >= 3): sttode_kde_nll's definition over the M samples -- float64 on x = (double)(x * scale), per frame the
+ *   unbiased covariance, Scott's factor M^(-1/6), the closed-form inverse and determinant, a two-pass logsumexp, clipped below at -20, NaN
+ *   where C00 <= 0 or det C <= 0 at some frame; nll [n] float64 = -mean over frames.  The four sums over samples per frame in the order above.
+ * sttode_large_spread (M >= 2; div_scale > 0 and finite): sttode_sample_spread's apd / fpd / pade / dlow and, with gt (else es_ade = es_fde
+ *   = NULL), es_ade / es_fde over the M (M-1) / 2 pairs, float64 [n], same definitions and arithmetic.  The pairs are tiles of 64 x 64
+ *   samples (ib <= jb, row order) dealt to G = min(tiles, 64) workgroups per agent, tile g, g + G, ...; a thread adds its 4 x 4 pairs of a
+ *   tile in row order.  ws: ws_bytes >= sttode_large_spread_ws(n, M) bytes on the device (the workgroups' partial sums, overwritten).
+ * The two size queries return bytes, or -1 with the error set. */
+long long int sttode_large_select_ws(int n, int M);
+int sttode_large_select(const float* pred, const float* gt, int n, int R, int K_in, int Tf, float scale, float miss_threshold, const int* ks,
+                        int nk, const int* seg_ptr, int S, void* ws, long ws_bytes, float* ade, float* fde, int* best_ade_idx,
+                        int* best_fde_idx, unsigned char* miss, float* ade_at, float* fde_at, float* seg_jade, float* seg_jfde,
+                        int* seg_jade_idx, int* seg_jfde_idx, void* stream);
+int sttode_large_kde_nll(const float* pred, const float* gt, int n, int R, int K_in, int Tf, float scale, double* nll, void* stream);
+long long int sttode_large_spread_ws(int n, int M);
+int sttode_large_spread(const float* pred, const float* gt, int n, int R, int K_in, int Tf, float scale, double div_scale, void* ws,
+                        long ws_bytes, double* apd, double* fpd, double* pade, double* dlow, double* es_ade, double* es_fde, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Native forward pipeline: one call enqueues STTODENet.inference (model/STTODE.py:574-623) end to end.

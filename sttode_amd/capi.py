@@ -136,6 +136,12 @@ SIGNATURES = {
     'sttode_reduce_samples': [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     # oversample and reduce whole scenes (csrc/reduce_scenes.hip; added within ABI version 15; no workspace)
     'sttode_reduce_scenes': [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P],
+    # scores of a whole oversampled set, M <= 4096 (csrc/large_set.hip; added within ABI version 15)
+    'sttode_large_select_ws': [_I, _I],
+    'sttode_large_select': [_P, _P, _I, _I, _I, _I, _F, _F, _P, _I, _P, _I, _P, _L] + [_P] * 12,
+    'sttode_large_kde_nll': [_P, _P, _I, _I, _I, _I, _F, _P, _P],
+    'sttode_large_spread_ws': [_I, _I],
+    'sttode_large_spread': [_P, _P, _I, _I, _I, _I, _F, _D, _P, _L] + [_P] * 7,
     # attention core with a running maximum, two score modes, optional mask (csrc/attention.hip; added within ABI version 14)
     'sttode_attn_core': [_P, _P, _P, _P, _L, _P, _P, _P, _P, _I, _I, _I] + [_L] * 8 + [_F, _F, _I, _P],
     'sttode_attn_core_bwd': [_P, _P, _P, _P, _L, _P, _P, _P, _P, _I, _I, _I] + [_L] * 8 + [_F, _F, _I, _P],
@@ -188,7 +194,8 @@ SIGNATURES = {
 }
 
 # entries that do not return a status (everything else: int, 0 = success)
-RESTYPES = {'sttode_sampler_objective_joint_ws': ctypes.c_longlong}
+RESTYPES = {'sttode_sampler_objective_joint_ws': ctypes.c_longlong, 'sttode_large_select_ws': ctypes.c_longlong,
+            'sttode_large_spread_ws': ctypes.c_longlong}
 
 # enum SttodeWeight / SttodeBuffer / SttodeStage of include/sttode_hip.h (order is ABI)
 WEIGHT_ORDER = ([('past', k) for k in ('fc1P', 'fc1b', 'posP', 'peb', 'fc2P', 'fc2b', 'fc3P', 'fc3b', 'fc3last', 'inP', 'inb', 'outP',
@@ -407,6 +414,15 @@ def sampler_joint_ws(n, K, S):
     b = int(L.sttode_sampler_objective_joint_ws(int(n), int(K), int(S)))
     if b < 0:
         raise SttodeError(f'sttode_sampler_objective_joint_ws failed: {L.sttode_last_error().decode()}')
+    return b
+
+
+def large_set_ws(entry, n, M):
+    """Bytes of workspace ``entry`` ('sttode_large_select' with segments, 'sttode_large_spread') needs for n agents with M samples each."""
+    L = lib()
+    b = int(getattr(L, entry + '_ws')(int(n), int(M)))
+    if b < 0:
+        raise SttodeError(f'{entry}_ws failed: {L.sttode_last_error().decode()}')
     return b
 
 

@@ -13,6 +13,8 @@
                   agent to K representatives on the device, then the selection of eval_scenes_report on the representatives; with
                   level='scene'  k-means of every scene's futures as whole scene futures, and on request the joint,
                   collision and KDE passes on the representatives of either level.
+  eval_scenes_reduced_raw  the same loop that also scores the raw set the representatives are cut from: best-of-M with its
+                  prefixes, joint best-of-M, KDE NLL and the pair statistics over all M = rounds * sample_k <= 4096 samples per agent.
   eval_scenes_multimodal  MMADE / MMFDE: the samples of the whole dataset gathered on the device, then one pass that scores every
                   agent's samples against the futures of all agents with a similar history.
   embedding_delta  how tree-like the encoder's past features (or the observed tracks) of a dataset are: delta / diam of hyptorch/delta.py's
@@ -218,7 +220,15 @@ class EvalReport:
     each the mean over the agents whose value is finite, as ``kde_nll`` -- ``w_kde_invalid`` (agents whose weighted KDE NLL is NaN),
     ``weighted_agents`` [n, 10] float64 (per agent: eade, efde, es_ade, es_fde, apd, fpd, kde_nll, brier_ade, brier_fde, neff) and
     ``ade_top_k`` / ``fde_top_k``: a dict k -> mean over agents of the min ADE / FDE over the k most probable samples, for k = 1 and each
-    k <= K of ``ks``."""
+    k <= K of ``ks``.
+
+    The raw oversampled set, None unless eval_scenes_reduced_raw ran: the M = rounds * sample_k samples the representatives
+    were cut from, scored by ``score_samples``.  ``raw_m`` = M; ``raw_ade`` / ``raw_fde`` (mean over agents of best-of-M: the oracle bound of
+    any reduction), ``raw_miss_rate``; ``raw_ade_at_k`` / ``raw_fde_at_k``: a dict k -> mean over agents of the minimum over the first k
+    samples, for k = sample_k and each k <= M of ``ks``; with ``joint``: ``raw_joint_ade`` / ``raw_joint_fde`` (mean over scenes of joint
+    best-of-M); with ``kde``: ``raw_kde_nll`` (mean over the finite agents) and ``raw_kde_invalid``; with ``spread``: ``raw_apd`` /
+    ``raw_fpd`` / ``raw_pade`` / ``raw_dlow`` / ``raw_energy_ade`` / ``raw_energy_fde`` (means over agents, as the fields without the
+    prefix)."""
     ade: float
     fde: float
     n_agents: int
@@ -258,6 +268,22 @@ class EvalReport:
     fde_top_k: dict = None
     mean_neff: float = None
     weighted_agents: np.ndarray = None
+    raw_m: int = None
+    raw_ade: float = None
+    raw_fde: float = None
+    raw_miss_rate: float = None
+    raw_ade_at_k: dict = None
+    raw_fde_at_k: dict = None
+    raw_joint_ade: float = None
+    raw_joint_fde: float = None
+    raw_kde_nll: float = None
+    raw_kde_invalid: int = None
+    raw_apd: float = None
+    raw_fpd: float = None
+    raw_pade: float = None
+    raw_dlow: float = None
+    raw_energy_ade: float = None
+    raw_energy_fde: float = None
     apd: float = None
     fpd: float = None
     pade: float = None
@@ -327,6 +353,40 @@ class _ReportAcc:
                 self._put(scene_collision=torch.stack([js.seg_col, js.seg_gt_col], dim=1))
         if kd is not None:
             self._put(kde_nll_agents=kd)
+
+    def add_raw(self, sc):
+        """A batch's ``metrics.SampleScores`` of the raw set."""
+        ls = sc.select
+        self.raw_m, self.raw_ks = ls.M, ls.ks
+        self._put(raw_sel=torch.stack([ls.ade, ls.fde], dim=1), raw_miss=ls.miss, raw_ade_at=ls.ade_at, raw_fde_at=ls.fde_at)
+        if self.joint:
+            self._put(raw_joint=torch.stack([ls.seg_jade, ls.seg_jfde], dim=1))
+        if sc.kde_nll is not None:
+            self._put(raw_kde=sc.kde_nll)
+        if sc.spread is not None:
+            sp = sc.spread
+            self._put(raw_spread=torch.stack([sp.apd, sp.fpd, sp.pade, sp.dlow, sp.es_ade, sp.es_fde], dim=1))
+
+    def report_raw(self, rep):
+        v, miss = self._cat('raw_sel').astype(np.float64), self._cat('raw_miss')
+        ak, fk = self._cat('raw_ade_at').astype(np.float64), self._cat('raw_fde_at').astype(np.float64)
+        rep.raw_m = self.raw_m
+        rep.raw_ade, rep.raw_fde = (float(x) for x in v.sum(axis=0) / v.shape[0])
+        rep.raw_miss_rate = int(miss.sum()) / v.shape[0]
+        rep.raw_ade_at_k = {k: float(ak[:, i].sum() / ak.shape[0]) for i, k in enumerate(self.raw_ks)}
+        rep.raw_fde_at_k = {k: float(fk[:, i].sum() / fk.shape[0]) for i, k in enumerate(self.raw_ks)}
+        if 'raw_joint' in self.parts:
+            rep.raw_joint_ade, rep.raw_joint_fde = (float(x) for x in self._cat('raw_joint').astype(np.float64).mean(axis=0))
+        if 'raw_kde' in self.parts:
+            kd = self._cat('raw_kde')
+            ok = np.isfinite(kd)
+            rep.raw_kde_invalid = int((~ok).sum())
+            rep.raw_kde_nll = float(kd[ok].mean()) if ok.any() else float('nan')
+        if 'raw_spread' in self.parts:
+            sv = self._cat('raw_spread')
+            (rep.raw_apd, rep.raw_fpd, rep.raw_pade, rep.raw_dlow, rep.raw_energy_ade,
+             rep.raw_energy_fde) = (float(x) for x in sv.sum(axis=0) / sv.shape[0])
+        return rep
 
     def add(self, sel, seg_ptr):
         self.tot_a += float(sel.ade.double().sum())
@@ -456,7 +516,28 @@ def eval_scenes_reduced(model, dataset, rounds, K=None, iters=10, from_frame=0, 
     scene's agents is one coherent scene future, and ``weighted`` takes ``SceneReduction.agent_weights``.  ``joint`` / ``collision_radius`` /
     ``kde`` add ``select_joint`` / ``kde_nll`` on the representatives, at either level, into the scene-metric fields of the report: what
     each kind of reduction does to the joint numbers (per-agent representatives share nothing but their cluster's number across agents;
-    scene representatives are scene futures).  With these four at their defaults the loop makes the calls it made before."""
+    scene representatives are scene futures).  With these four at their defaults the loop makes the calls it made before.
+    ``eval_scenes_reduced_raw`` is this loop with the raw set scored as well."""
+    return _eval_scenes_reduced(model, dataset, rounds, K, iters, from_frame, init, traj_scale, scenes_per_call, z_fn, pipelined, miss_threshold,
+                                spread, div_scale, ks, weighted, level, joint, collision_radius, kde, False)
+
+
+@torch.no_grad()
+def eval_scenes_reduced_raw(model, dataset, rounds, K=None, iters=10, from_frame=0, init='first', traj_scale=1.0, scenes_per_call=512,
+                            z_fn=None, pipelined=True, miss_threshold=1.0, spread=False, div_scale=None, ks=(1, 5, 10), weighted=False,
+                            level='agent', joint=False, collision_radius=None, kde=False):
+    """eval_scenes_reduced -- the same arguments, calls and report fields, bit for bit -- that also scores the raw set the representatives are
+    cut from: per batch, before the reduction, ``model.score_samples`` on the round buffer of M = rounds * sample_k <= 4096
+    samples per agent, with ``ks=(sample_k, *ks)`` (sorted, those <= M), ``kde`` and ``spread`` as this loop's own keywords, joint best-of-M
+    over the scenes with ``joint``, and the loop's ``traj_scale``, ``miss_threshold`` and ``div_scale``.  Fills the ``raw_*`` fields of the
+    ``EvalReport``: what the reduction costs against the oracle bound (``raw_ade`` against ``ade``), and what it does to the diversity
+    (``raw_apd`` against ``apd``)."""
+    return _eval_scenes_reduced(model, dataset, rounds, K, iters, from_frame, init, traj_scale, scenes_per_call, z_fn, pipelined, miss_threshold,
+                                spread, div_scale, ks, weighted, level, joint, collision_radius, kde, True)
+
+
+def _eval_scenes_reduced(model, dataset, rounds, K, iters, from_frame, init, traj_scale, scenes_per_call, z_fn, pipelined, miss_threshold, spread,
+                         div_scale, ks, weighted, level, joint, collision_radius, kde, raw):
     from . import metrics
     rounds = int(rounds)
     if rounds < 1:
@@ -468,6 +549,11 @@ def eval_scenes_reduced(model, dataset, rounds, K=None, iters=10, from_frame=0, 
     acc = _ReportAcc(miss_threshold, joint=joint, kde=kde, collision_radius=collision_radius, K=K, spread=spread, div_scale=div_scale, ks=ks,
                      dataset=getattr(model.args, 'dataset', None), weighted=weighted)
     depth = max(2, min(8, int(model.async_depth)))
+    if raw:
+        if rounds * Ks > metrics.LARGE_MAX_M:
+            raise ValueError(f'the raw set needs M = rounds * sample_k <= {metrics.LARGE_MAX_M}, got {rounds * Ks}')
+        raw_ks = sorted({int(k) for k in (Ks, *ks) if 1 <= int(k) <= rounds * Ks})
+        raw_div = acc.div_scale if spread else 1.0
     for s0 in range(0, len(dataset), scenes_per_call):
         sb = dataset.scene_batch(range(s0, min(s0 + scenes_per_call, len(dataset))))
         model.set_scene_batch(sb.past, sb.future, sb.scene_ptr)
@@ -490,6 +576,9 @@ def eval_scenes_reduced(model, dataset, rounds, K=None, iters=10, from_frame=0, 
         else:
             for r in range(rounds):
                 buf[r].copy_(model.inference(None, z=_latents(model, rows, z_fn)).permute(1, 0, 2, 3))
+        if raw:
+            acc.add_raw(model.score_samples(buf, scale=traj_scale, miss_threshold=miss_threshold, ks=raw_ks,
+                                            seg_ptr=model._scene_ptr if joint else False, kde=kde, spread=spread, div_scale=raw_div))
         if level == 'scene':
             red = metrics.reduce_scenes(buf, model._scene_ptr, K, iters=iters, from_frame=from_frame, init=init)
         else:
@@ -504,7 +593,7 @@ def eval_scenes_reduced(model, dataset, rounds, K=None, iters=10, from_frame=0, 
             acc.add_weighted(model.weighted_set(red.centroids, red.agent_weights if level == 'scene' else red.weights, scale=traj_scale))
     if pipelined:
         model.reset_async()
-    return acc.report(False)
+    return acc.report_raw(acc.report(False)) if raw else acc.report(False)
 
 
 @dataclasses.dataclass

@@ -8,7 +8,9 @@ scores them against the futures of all agents with a similar history, over a who
 clusters M sampled futures per agent to K representatives, ``reduce_scenes`` (csrc/reduce_scenes.hip) a segment's M scene
 futures, all its agents under one label, so that representative k is a coherent scene future.  ``weighted_set`` (csrc/weighted.hip) scores K samples with
 probabilities -- those representatives and their cluster shares -- as a weighted set: expected errors, energy scores, the KDE NLL of the
-weighted mixture, probability-ranked best-of-k.
+weighted mixture, probability-ranked best-of-k.  ``large_select`` / ``large_kde_nll`` / ``large_spread`` (csrc/large_set.hip)
+score the M <= 4096 samples themselves, before any reduction: best-of-M with prefix minima, joint best-of-M, KDE NLL, pair statistics
+(DESIGN.md 4ac).
 
 ``select`` is the kernel call: per agent the min-over-K ADE / FDE, the index of the best sample by ADE and by final displacement
 (``get_best_idx``), the miss flag (``count_miss_samples``) and optionally the best trajectory; per CSR segment (a scene, an NBA batch) the
@@ -18,6 +20,8 @@ mean ADE / FDE and the miss count.  ``STTODENet.select_best_of_k`` / ``select_be
 and gt [n, Tf, 2], or stacked [n, K, Tf, 2] -- and return its types, so a script can swap ``from utils.metrics import ...`` for
 ``from sttode_amd.metrics import ...``.  They need a HIP device (there is no CPU fallback).
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -529,6 +533,159 @@ def reduce_scenes(pred, seg_ptr=None, K=None, iters=10, from_frame=0, init='firs
     with torch.cuda.device(dev):
         capi.call('sttode_reduce_scenes', pred, n, R, K_in, Tf, K, iters, from_frame % Tf, mode, init_t, sp, S, out.centroids, out.labels,
                   out.counts, capi.stream_ptr())
+    return out
+
+
+# ----- scores of a whole oversampled set (csrc/large_set.hip: sttode_large_select / _kde_nll / _spread) -------------------
+
+LARGE_MAX_M, LARGE_MAX_TF, LARGE_MAX_KS = 4096, 200, 16
+
+
+class LargeSelection:
+    """Outputs of one ``large_select`` pass (device tensors).  Per agent: ``ade``, ``fde`` [n] float32 (min over the M samples),
+    ``best_ade_idx``, ``best_fde_idx`` [n] int32 (the lowest m that attains it; +inf and 0 for an agent without a finite sample), ``miss``
+    [n] bool; ``ade_at`` / ``fde_at`` [n, len(ks)] float32 (column i: the minimum over the first ``ks[i]`` samples; None without ``ks``).
+    Per segment (``seg_ptr`` given, else None): ``seg_jade`` / ``seg_jfde`` [S] float32 and ``seg_jade_idx`` / ``seg_jfde_idx`` [S] int32
+    (an empty segment: NaN and -1).  ``M``, ``ks``."""
+    __slots__ = ('ade', 'fde', 'best_ade_idx', 'best_fde_idx', 'miss', 'ade_at', 'fde_at', 'seg_jade', 'seg_jfde', 'seg_jade_idx',
+                 'seg_jfde_idx', 'M', 'ks')
+
+    def __init__(self, n, M, ks, S, device):
+        nk = len(ks)
+        f = torch.empty(2 * n + 2 * n * nk + 2 * S, dtype=torch.float32, device=device)
+        i = torch.empty(2 * n + 2 * S, dtype=torch.int32, device=device)
+        self.ade, self.fde = f[:n], f[n:2 * n]
+        self.ade_at = f[2 * n:2 * n + n * nk].view(n, nk) if nk else None
+        self.fde_at = f[2 * n + n * nk:2 * n + 2 * n * nk].view(n, nk) if nk else None
+        o = 2 * n + 2 * n * nk
+        self.seg_jade = f[o:o + S] if S else None
+        self.seg_jfde = f[o + S:] if S else None
+        self.best_ade_idx, self.best_fde_idx = i[:n], i[n:2 * n]
+        self.seg_jade_idx = i[2 * n:2 * n + S] if S else None
+        self.seg_jfde_idx = i[2 * n + S:] if S else None
+        self.miss = torch.empty(n, dtype=torch.bool, device=device)
+        self.M, self.ks = M, tuple(ks)
+
+    def args(self):
+        """Output pointers in the order of sttode_large_select."""
+        return (self.ade, self.fde, self.best_ade_idx, self.best_fde_idx, self.miss, self.ade_at, self.fde_at, self.seg_jade, self.seg_jfde,
+                self.seg_jade_idx, self.seg_jfde_idx)
+
+    def at(self, k):
+        """(min ADE, min FDE) [n] over the first ``k`` samples, ``k`` one of ``ks``."""
+        if int(k) not in self.ks:
+            raise ValueError(f'k must be one of ks = {self.ks}, got {k}')
+        c = self.ks.index(int(k))
+        return self.ade_at[:, c], self.fde_at[:, c]
+
+    def record_stream(self, stream):
+        for t in (self.ade, self.best_ade_idx, self.miss):   # (views: the record covers the whole allocation)
+            t.record_stream(stream)
+
+
+class LargeSpread:
+    """Outputs of one ``large_spread`` pass (device tensors), per agent, float64 [n]: ``apd``, ``fpd``, ``pade``, ``dlow`` as
+    ``SampleSpread``'s, over the M (M-1) / 2 pairs; with a ground truth, else None: ``es_ade`` / ``es_fde``.  ``M``, ``div_scale``."""
+    __slots__ = ('apd', 'fpd', 'pade', 'dlow', 'es_ade', 'es_fde', 'M', 'div_scale')
+
+    def __init__(self, n, M, device, div_scale, has_gt):
+        d = torch.empty((6 if has_gt else 4) * n, dtype=torch.float64, device=device)
+        self.apd, self.fpd, self.pade, self.dlow = d[:n], d[n:2 * n], d[2 * n:3 * n], d[3 * n:4 * n]
+        self.es_ade = d[4 * n:5 * n] if has_gt else None
+        self.es_fde = d[5 * n:] if has_gt else None
+        self.M, self.div_scale = M, div_scale
+
+    def args(self):
+        """Output pointers in the order of sttode_large_spread."""
+        return (self.apd, self.fpd, self.pade, self.dlow, self.es_ade, self.es_fde)
+
+    def record_stream(self, stream):
+        self.apd.record_stream(stream)   # (views: the record covers the whole allocation)
+
+
+class SampleScores:
+    """What ``STTODENet.score_samples`` returns: ``select`` (a ``LargeSelection``), ``kde_nll`` (float64 [n], or None) and ``spread`` (a
+    ``LargeSpread``, or None)."""
+    __slots__ = ('select', 'kde_nll', 'spread')
+
+    def __init__(self, select, kde_nll=None, spread=None):
+        self.select, self.kde_nll, self.spread = select, kde_nll, spread
+
+
+def _large_inputs(pred, gt, what, need_gt=True, m_min=1):
+    """(pred [R, n, K_in, Tf, 2] -- the caller's memory when it is contiguous float32 --, gt, R, n, K_in, Tf) after the entries' checks."""
+    if not (isinstance(pred, torch.Tensor) and pred.is_cuda):
+        raise capi.SttodeError(f'{what} runs on a HIP device only (no CPU fallback): pass device tensors')
+    if pred.dim() == 4:
+        pred = pred.unsqueeze(0)
+    if pred.dim() != 5 or pred.shape[4] != 2 or 0 in pred.shape:
+        raise ValueError(f'pred must be [n, M, Tf, 2] or [R, n, K_in, Tf, 2] with no empty dimension, got {tuple(pred.shape)}')
+    if pred.dtype != torch.float32:
+        raise ValueError(f'pred must be float32, got {pred.dtype}')
+    R, n, K_in, Tf = pred.shape[:4]
+    if not m_min <= R * K_in <= LARGE_MAX_M:
+        raise ValueError(f'{what} needs {m_min} <= M <= {LARGE_MAX_M} samples, got M = {R * K_in}')
+    if Tf > LARGE_MAX_TF:
+        raise ValueError(f'{what} needs Tf <= {LARGE_MAX_TF}, got Tf = {Tf}')
+    pred = pred.contiguous()
+    if gt is None and not need_gt:
+        return pred, None, R, n, K_in, Tf
+    gt = torch.as_tensor(gt, dtype=torch.float32).to(pred.device).contiguous()
+    if tuple(gt.shape) != (n, Tf, 2):
+        raise ValueError(f'gt must be [{n}, {Tf}, 2], got {tuple(gt.shape)}')
+    return pred, gt, R, n, K_in, Tf
+
+
+@torch.no_grad()
+def large_select(pred, gt, scale=1.0, miss_threshold=1.0, ks=(), seg_ptr=None):
+    """Best-of-M over a whole oversampled set, on the current stream (include/sttode_hip.h sttode_large_select states every value).
+    ``pred``: [n, M, Tf, 2], or [R, n, K_in, Tf, 2] -- the round buffer of ``inference_reduced``, M = R K_in, sample m = r K_in + k -- float32,
+    read in place; gt [n, Tf, 2].  1 <= M <= 4096.  ``ks``: up to 16 prefix sizes, strictly ascending in [1, M]: the minima over the first k
+    samples (best-of-20 beside best-of-M from one pass).  ``seg_ptr`` [S+1] (device or host): joint best-of-M per segment.  Returns a
+    ``LargeSelection``."""
+    pred, gt, R, n, K_in, Tf = _large_inputs(pred, gt, 'large-set selection')
+    M = R * K_in
+    ks = [int(k) for k in ks]
+    if len(ks) > LARGE_MAX_KS or any(not 1 <= k <= M for k in ks) or any(b <= a for a, b in zip(ks, ks[1:])):
+        raise ValueError(f'ks must be at most {LARGE_MAX_KS} values, strictly ascending in [1, M = {M}], got {ks}')
+    sp, S, ws = None, 0, None
+    if seg_ptr is not None:
+        check_seg_ptr(seg_ptr, n)
+        sp = seg_ptr_tensor(seg_ptr, pred.device)
+        S = int(sp.numel()) - 1
+        ws = torch.empty(capi.large_set_ws('sttode_large_select', n, M), dtype=torch.uint8, device=pred.device)
+    out = LargeSelection(n, M, ks, S, pred.device)
+    kh = (ctypes.c_int * len(ks))(*ks) if ks else None
+    with torch.cuda.device(pred.device):
+        capi.call('sttode_large_select', pred, gt, n, R, K_in, Tf, float(scale), float(miss_threshold),
+                  ctypes.cast(kh, ctypes.c_void_p) if ks else None, len(ks), sp, S, ws, int(ws.numel()) if ws is not None else 0, *out.args(),
+                  capi.stream_ptr())
+    return out
+
+
+@torch.no_grad()
+def large_kde_nll(pred, gt, scale=1.0):
+    """``kde_nll`` over a whole oversampled set (3 <= M <= 4096; Trajectron++ reports it at 2000 samples), float64 on the current stream.
+    ``pred`` as ``large_select``.  Returns a float64 tensor [n], NaN where the covariance is singular at some frame."""
+    pred, gt, R, n, K_in, Tf = _large_inputs(pred, gt, 'large-set KDE NLL', m_min=3)
+    out = torch.empty(n, dtype=torch.float64, device=pred.device)
+    with torch.cuda.device(pred.device):
+        capi.call('sttode_large_kde_nll', pred, gt, n, R, K_in, Tf, float(scale), out, capi.stream_ptr())
+    return out
+
+
+@torch.no_grad()
+def large_spread(pred, gt=None, scale=1.0, div_scale=1.0):
+    """``sample_spread``'s pair statistics over a whole oversampled set (2 <= M <= 4096: up to 8.4 million pairs per agent), float64 on the
+    current stream.  ``pred`` as ``large_select``.  The best-of-k columns are ``large_select``'s (``ks``).  Returns a ``LargeSpread``."""
+    pred, gt, R, n, K_in, Tf = _large_inputs(pred, gt, 'large-set spread', need_gt=False, m_min=2)
+    ds = float(div_scale)
+    if not (ds > 0.0 and ds != float('inf')):
+        raise ValueError(f'div_scale must be positive and finite, got {div_scale}')
+    out = LargeSpread(n, R * K_in, pred.device, ds, gt is not None)
+    ws = torch.empty(capi.large_set_ws('sttode_large_spread', n, R * K_in), dtype=torch.uint8, device=pred.device)
+    with torch.cuda.device(pred.device):
+        capi.call('sttode_large_spread', pred, gt, n, R, K_in, Tf, float(scale), ds, ws, int(ws.numel()), *out.args(), capi.stream_ptr())
     return out
 
 

@@ -841,8 +841,34 @@ class STTODENet(nn.Module):
         else:
             red = metrics.reduce_samples(buf, K, iters=iters, from_frame=from_frame, init=init)
         self.__dict__['reduction'] = red
+        self.__dict__['reduced_samples'] = buf
         self.diverse_pred = red.centroids
         return red.centroids.permute(1, 0, 2, 3)
+
+    def inference_reduced_samples(self, rounds, K=None, iters=10, from_frame=0, init='first', z=None, level='agent'):
+        """inference_reduced that also hands out what it reduced: returns ``(reduction, samples)``, ``samples`` the
+        [rounds, n, sample_k, Tf, 2] round buffer -- what ``score_samples`` and ``metrics.large_*`` take.  The round buffer is reused per
+        shape: ``samples`` (also kept as ``reduced_samples``) is valid until the next inference_reduced call with that shape."""
+        self.inference_reduced(rounds, K=K, iters=iters, from_frame=from_frame, init=init, z=z, level=level)
+        return self.reduction, self.reduced_samples
+
+    @torch.no_grad()
+    def score_samples(self, pred, gt=None, scale=1.0, miss_threshold=1.0, ks=(), seg_ptr=None, kde=False, spread=False, div_scale=1.0):
+        """Scores of a whole oversampled set on device: ``pred`` [n, M, Tf, 2] or the round buffer [R, n, K_in, Tf, 2],
+        M <= 4096, against gt [n, Tf, 2] (default: the futures set with the batch).  Always ``metrics.large_select`` -- best-of-M, the
+        prefix minima of ``ks``, and joint best-of-M over ``seg_ptr`` (default: the scene_ptr of set_scene_batch, when one is set; False: none) --
+        ``kde``: ``metrics.large_kde_nll``; ``spread``: ``metrics.large_spread`` at ``div_scale``.  Returns a ``metrics.SampleScores``;
+        what was not asked for is None."""
+        from . import metrics
+        gt = self._future if gt is None else _f32(gt, self.device)
+        if seg_ptr is None and self._mode == 'scenes':
+            seg_ptr = self._scene_ptr
+        elif seg_ptr is False:
+            seg_ptr = None
+        return metrics.SampleScores(
+            metrics.large_select(pred, gt, scale=scale, miss_threshold=miss_threshold, ks=ks, seg_ptr=seg_ptr),
+            metrics.large_kde_nll(pred, gt, scale=scale) if kde else None,
+            metrics.large_spread(pred, gt, scale=scale, div_scale=div_scale) if spread else None)
 
     @torch.no_grad()
     def inference_nba_sharded(self, data_local, z=None, gather=None):
