@@ -5,6 +5,7 @@
 #include <cstdio>
 
 void stt_set_error(const char* msg);
+int stt_refuse(const char* who, const char* why);   // sets the error "<who>: <why>" and returns 1 (frontend.hip)
 int stt_gru_cols_form(const float* xin, const float* convP, const float* convB, const float* wihP, const float* whhP, const float* gbias,
                       float* state, int ncols, int Tp, int TPX, int lat_max_tiles, void* stream);   // decoder.hip
 int stt_agents_fused(const float* const* W, const float* enc_in, const int* last, float* g, float* qkv, float* pf, const float* xpad,

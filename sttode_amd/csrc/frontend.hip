@@ -10,6 +10,12 @@
 
 static thread_local std::string g_err;
 void stt_set_error(const char* msg) { g_err = msg ? msg : ""; }
+int stt_refuse(const char* who, const char* why) {
+    char b[256];
+    snprintf(b, sizeof(b), "%s: %s", who, why);
+    stt_set_error(b);
+    return 1;
+}
 extern "C" const char* sttode_last_error() { return g_err.c_str(); }
 // bumped whenever an exported signature or an ABI enum (SttodeWeight / SttodeBuffer / SttodeStage) changes; capi.py checks it at load
 extern "C" int sttode_abi_version() { return STTODE_ABI_VERSION; }

@@ -11,7 +11,7 @@
 //   large_spread_kernel    the M (M-1) / 2 pairs as tiles of 64 x 64 samples, a thread a 4 x 4 patch of one; a tile's samples go through LDS in
 //                          blocks of frames; the tiles of an agent are dealt to up to 64 workgroups, whose partial sums go to the caller's
 //                          workspace.  large_spread_finish adds them in workgroup order and forms the energy scores.
-// Sum order, everywhere a sum runs over samples or pairs: a thread adds its own terms in ascending order (sample tid, tid + 256, ...; tiles
+// Sum order, everywhere a sum runs over samples or pairs (wave_then_block_sum of set_body.hpp): a thread adds its own terms in ascending order (sample tid, tid + 256, ...; tiles
 // g, g + G, ..., patch rows then columns), the 64 lanes of a wave are added by the xor tree 32, 16, ... 1, the four waves in wave order, the
 // workgroups of an agent in workgroup order.  No atomics: two runs give the same bits, and an agent's or segment's values depend on nothing
 // else in the batch (the number of workgroups per agent is a function of M alone).
@@ -19,17 +19,15 @@
 #include <cmath>
 
 #include "api_util.hpp"
-#include "frontend_body.hpp"
+#include "set_body.hpp"
 #include "../../include/sttode_hip.h"
 
 namespace {
 
-constexpr int LS_MAX_M = 4096, LS_MAX_TF = 200, LS_MAX_KS = 16;
+constexpr int LS_MAX_KS = 16;   // (MAX_M, MAX_TF: set_body.hpp, the sets sttode_reduce_samples takes)
 constexpr int LS_SD = 4096;        // floats of the distance staging tile of large_select_kernel: min(256, 4096 / Tf) >= 20 samples per pass
-constexpr int LK_PER = LS_MAX_M / 256;   // samples per thread of large_kde_kernel
+constexpr int LK_PER = MAX_M / 256;   // samples per thread of large_kde_kernel
 constexpr int SP_B = 64;           // samples per side of a pair tile
-constexpr int SP_FT = 32;          // frames per LDS block of the spread pass
-constexpr int SP_STRIDE = SP_FT + 1;   // row stride in float2: odd, so that lanes on different samples at one frame fall on different banks
 constexpr int SP_MAX_G = 64;       // workgroups per agent at most
 
 struct LargeKs {
@@ -37,32 +35,17 @@ struct LargeKs {
     int k[LS_MAX_KS];
 };
 
-// float2 index of sample m, frame 0 of agent a in the round-major buffer
-__device__ __forceinline__ size_t sample_base(int a, int m, int n, int K_in, int Tf) {
-    const int r = m / K_in, k = m - r * K_in;
-    return (((size_t)r * n + a) * K_in + k) * Tf;
-}
-
-// (v, i) <- the smaller of (v, i) and (ov, oi): by value, the lower index on equal values.  Neither value is ever NaN.
-template <typename T>
-__device__ __forceinline__ void take_min(T& v, int& i, T ov, int oi) {
-    if (ov < v || (ov == v && oi < i)) {
-        v = ov;
-        i = oi;
-    }
-}
-
 // Minimum and lowest index of two value lists at once over the workgroup: wave xor tree, then the four waves in wave order (thread 0 holds
 // the result).  red: 4 x 2 values and indices of LDS.
 template <typename T>
 __device__ __forceinline__ void block_argmin2(T& va, int& ia, T& vf, int& jf, T (*rv)[2], int (*ri)[2]) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
+    for (int o = 32; o > 0; o >>= 1) {   // (wave_take_lower's tree for both lists at once: the two chains of shuffles overlap)
         const T oa = __shfl_xor(va, o, 64), of = __shfl_xor(vf, o, 64);
         const int oia = __shfl_xor(ia, o, 64), oif = __shfl_xor(jf, o, 64);
-        take_min(va, ia, oa, oia);
-        take_min(vf, jf, of, oif);
+        take_lower(va, ia, oa, oia);
+        take_lower(vf, jf, of, oif);
     }
     __syncthreads();   // (the last use of rv / ri is over)
     if (lane == 0) {
@@ -75,8 +58,8 @@ __device__ __forceinline__ void block_argmin2(T& va, int& ia, T& vf, int& jf, T 
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int q = 1; q < 4; ++q) {
-            take_min(va, ia, rv[q][0], ri[q][0]);
-            take_min(vf, jf, rv[q][1], ri[q][1]);
+            take_lower(va, ia, rv[q][0], ri[q][0]);
+            take_lower(vf, jf, rv[q][1], ri[q][1]);
         }
     }
 }
@@ -91,8 +74,8 @@ __global__ __launch_bounds__(256) void large_select_kernel(const float* __restri
                                                            int* __restrict__ ifd, unsigned char* __restrict__ miss, float* __restrict__ ade_at,
                                                            float* __restrict__ fde_at) {
     __shared__ float sd[LS_SD];
-    __shared__ float2 sg[LS_MAX_TF];
-    __shared__ float va[LS_MAX_M], vf[LS_MAX_M];
+    __shared__ float2 sg[MAX_TF];
+    __shared__ float va[MAX_M], vf[MAX_M];
     __shared__ float rv[4][2];
     __shared__ int ri[4][2];
     const int tid = threadIdx.x, a = blockIdx.x;
@@ -105,7 +88,7 @@ __global__ __launch_bounds__(256) void large_select_kernel(const float* __restri
         __syncthreads();   // (sg is written; the last pass's reads of sd are over)
         for (int e = tid; e < sc * Tf; e += 256) {
             const int s = e / Tf, t = e - s * Tf;
-            const float2 v = p[sample_base(a, m0 + s, n, K_in, Tf) + t], r = sg[t];
+            const float2 v = p[round_major_row(a, m0 + s, n, K_in, Tf) + t], r = sg[t];
             sd[e] = bok_dist(v.x, v.y, r.x, r.y, scale);
         }
         __syncthreads();
@@ -170,7 +153,8 @@ __global__ __launch_bounds__(256) void large_joint_kernel(const float* __restric
     __shared__ double rv[4][2];
     __shared__ int ri[4][2];
     const int tid = threadIdx.x, s = blockIdx.x;
-    const int a0 = min(max(seg_ptr[s], 0), n), a1 = min(max(seg_ptr[s + 1], a0), n);
+    int a0, a1;
+    clamped_segment(seg_ptr, s, n, a0, a1);
     if (a1 == a0) {
         if (tid == 0) {
             seg_jade[s] = seg_jfde[s] = NAN;
@@ -209,23 +193,6 @@ __global__ __launch_bounds__(256) void large_joint_kernel(const float* __restric
     }
 }
 
-// Sum of NV doubles per thread over the workgroup, in the file's order; every thread gets the result.  red: [4][NV] of LDS.
-template <int NV>
-__device__ __forceinline__ void block_sum(double (&v)[NV], double (*red)[NV]) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < NV; ++q)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v[q] += __shfl_xor(v[q], o, 64);
-    __syncthreads();   // (the last use of red is over)
-    if (lane == 0)
-#pragma unroll
-        for (int q = 0; q < NV; ++q) red[w][q] = v[q];
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < NV; ++q) v[q] = ((red[0][q] + red[1][q]) + red[2][q]) + red[3][q];
-}
-
 // KDE NLL of agent a = blockIdx.x over its M samples (sttode_kde_nll's definition), frame after frame.  Thread tid holds the
 // frame's samples m = tid + 256 j, j < LK_PER, raw, in registers; x = (double)(v * scale) with the product in fp32.  Four sums / one maximum
 // over the samples per frame, each in the file's order: mean; unbiased covariance; the largest exponent; the sum of exp.  Every thread
@@ -238,9 +205,9 @@ __global__ __launch_bounds__(256) void large_kde_kernel(const float* __restrict_
     const float2* g = reinterpret_cast<const float2*>(gt) + (size_t)a * Tf;
     size_t base[LK_PER];
 #pragma unroll
-    for (int j = 0; j < LK_PER; ++j) base[j] = tid + 256 * j < M ? sample_base(a, tid + 256 * j, n, K_in, Tf) : 0;
+    for (int j = 0; j < LK_PER; ++j) base[j] = tid + 256 * j < M ? round_major_row(a, tid + 256 * j, n, K_in, Tf) : 0;
     const double f = pow((double)M, -1.0 / 6.0), f2 = f * f;
-    const double logM = log((double)M), two_pi = 6.283185307179586;
+    const double logM = log((double)M);
     double acc = 0.0;
     bool bad = false;
     for (int t = 0; t < Tf; ++t) {
@@ -254,7 +221,7 @@ __global__ __launch_bounds__(256) void large_kde_kernel(const float* __restrict_
                 s[0] += (double)(x[j].x * scale);
                 s[1] += (double)(x[j].y * scale);
             }
-        block_sum<3>(s, red);
+        wave_then_block_sum<3>(s, red);
         const double mx = s[0] / M, my = s[1] / M;
         double c[3] = {0.0, 0.0, 0.0};
 #pragma unroll
@@ -265,27 +232,25 @@ __global__ __launch_bounds__(256) void large_kde_kernel(const float* __restrict_
                 c[1] += dx * dy;
                 c[2] += dy * dy;
             }
-        block_sum<3>(c, red);
+        wave_then_block_sum<3>(c, red);
         const double c00 = c[0] / (M - 1), c01 = c[1] / (M - 1), c11 = c[2] / (M - 1);
-        const double det = c00 * c11 - c01 * c01;
-        if (!(c00 > 0.0) || !(det > 0.0)) {
+        double det, inv;
+        if (!kde_cov(c00, c01, c11, f2, det, inv)) {
             bad = true;
             continue;
         }
         const float2 r = g[t];
         const double gx = (double)(r.x * scale), gy = (double)(r.y * scale);
-        const double inv = 1.0 / (f2 * det);   // Sigma^-1 = [[c11, -c01], [-c01, c00]] / (f^2 det C)
         double e[LK_PER];
         double mxe = -INFINITY;
 #pragma unroll
         for (int j = 0; j < LK_PER; ++j)
             if (tid + 256 * j < M) {
                 const double dx = gx - (double)(x[j].x * scale), dy = gy - (double)(x[j].y * scale);
-                e[j] = -0.5 * ((c11 * dx * dx - 2.0 * c01 * dx * dy + c00 * dy * dy) * inv);
+                e[j] = -0.5 * kde_quad(c00, c01, c11, inv, dx, dy);
                 mxe = fmax(mxe, e[j]);
             }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mxe = fmax(mxe, __shfl_xor(mxe, o, 64));
+        mxe = wave_max(mxe);
         __syncthreads();
         if ((tid & 63) == 0) red[tid >> 6][0] = mxe;
         __syncthreads();
@@ -294,11 +259,8 @@ __global__ __launch_bounds__(256) void large_kde_kernel(const float* __restrict_
 #pragma unroll
         for (int j = 0; j < LK_PER; ++j)
             if (tid + 256 * j < M) se[0] += exp(e[j] - mxe);
-        block_sum<3>(se, red);
-        const double tf2 = two_pi * f2;   // det(2 pi Sigma) = (2 pi f^2)^2 det C
-        double lp = log(se[0]) + mxe - logM - 0.5 * log(tf2 * tf2 * det);
-        lp = lp < -20.0 ? -20.0 : lp;
-        acc += lp;
+        wave_then_block_sum<3>(se, red);
+        acc += kde_clip(log(se[0]) + mxe - logM - kde_log_norm(f2, det));
     }
     if (tid == 0) nll[a] = bad ? (double)NAN : -acc / Tf;
 }
@@ -313,13 +275,13 @@ __host__ __device__ inline int spread_groups(int M) { return spread_tiles(M) < S
 
 // Workgroup blockIdx.x = a G + g: the tiles g, g + G, ... of agent a.  In a tile thread tid holds the 4 x 4 pairs (i, j) = (64 ib + ti + 16 u,
 // 64 jb + tj + 16 v), ti = tid / 16, tj = tid % 16: per pair the running sum of squared distances and of distances, frames in frame order;
-// the two blocks of samples go through LDS SP_FT frames at a time (raw float2; x = (double)(v * scale), everything after that float64, as
+// the two blocks of samples go through LDS SET_FT frames at a time (raw float2; x = (double)(v * scale), everything after that float64, as
 // sample_spread_kernel).  The last frame's distance goes straight into the thread's final-distance sum.  After the last frame the valid
 // pairs (i < j < M) are finished in (u, v) order into the thread's four sums; after the last tile those are added over the workgroup and
 // stored as part[(a G + g) 4 + q], q = trajectory distance, final distance, mean frame distance, DLow kernel value.
 __global__ __launch_bounds__(256) void large_spread_kernel(const float* __restrict__ pred, int n, int K_in, int M, int Tf, float scale,
                                                            double div_scale, double* __restrict__ part) {
-    __shared__ float2 xi[SP_B * SP_STRIDE], xj[SP_B * SP_STRIDE];
+    __shared__ float2 xi[SP_B * SET_STRIDE], xj[SP_B * SET_STRIDE];
     __shared__ double red[4][4];
     const int tid = threadIdx.x, ti = tid >> 4, tj = tid & 15;
     const int G = spread_groups(M), T = spread_tiles(M), NB = (M + SP_B - 1) / SP_B;
@@ -327,12 +289,9 @@ __global__ __launch_bounds__(256) void large_spread_kernel(const float* __restri
     const float2* p = reinterpret_cast<const float2*>(pred);
     double tot[4] = {0.0, 0.0, 0.0, 0.0};
     for (int tile = g; tile < T; tile += G) {
-        int q = tile, ib = 0;
-        while (q >= NB - ib) {
-            q -= NB - ib;
-            ++ib;
-        }
-        const int jb = ib + q;
+        int ib, jb;   // the tiles in row order with ib <= jb: the pairs (ib, jb + 1) of NB + 1 items
+        pdist_pair(tile, NB + 1, ib, jb);
+        --jb;
         double s2[4][4], s1[4][4];
         bool ok[4][4];
 #pragma unroll
@@ -343,21 +302,21 @@ __global__ __launch_bounds__(256) void large_spread_kernel(const float* __restri
                 const int i = SP_B * ib + ti + 16 * u, j = SP_B * jb + tj + 16 * v;
                 ok[u][v] = i < j && j < M;
             }
-        for (int t0 = 0; t0 < Tf; t0 += SP_FT) {
-            const int ft = min(SP_FT, Tf - t0);
+        for (int t0 = 0; t0 < Tf; t0 += SET_FT) {
+            const int ft = min(SET_FT, Tf - t0);
             __syncthreads();   // (the last block's reads are over)
             for (int e = tid; e < SP_B * ft; e += 256) {
                 const int s = e / ft, tl = e - s * ft;
                 const int mi = SP_B * ib + s, mj = SP_B * jb + s;
-                xi[s * SP_STRIDE + tl] = mi < M ? p[sample_base(a, mi, n, K_in, Tf) + t0 + tl] : make_float2(0.f, 0.f);
-                xj[s * SP_STRIDE + tl] = mj < M ? p[sample_base(a, mj, n, K_in, Tf) + t0 + tl] : make_float2(0.f, 0.f);
+                xi[s * SET_STRIDE + tl] = mi < M ? p[round_major_row(a, mi, n, K_in, Tf) + t0 + tl] : make_float2(0.f, 0.f);
+                xj[s * SET_STRIDE + tl] = mj < M ? p[round_major_row(a, mj, n, K_in, Tf) + t0 + tl] : make_float2(0.f, 0.f);
             }
             __syncthreads();
             for (int tl = 0; tl < ft; ++tl) {
                 double ax[4], ay[4], bx[4], by[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
-                    const float2 vi = xi[(ti + 16 * u) * SP_STRIDE + tl], vj = xj[(tj + 16 * u) * SP_STRIDE + tl];
+                    const float2 vi = xi[(ti + 16 * u) * SET_STRIDE + tl], vj = xj[(tj + 16 * u) * SET_STRIDE + tl];
                     ax[u] = (double)(vi.x * scale);
                     ay[u] = (double)(vi.y * scale);
                     bx[u] = (double)(vj.x * scale);
@@ -387,7 +346,7 @@ __global__ __launch_bounds__(256) void large_spread_kernel(const float* __restri
                     tot[3] += exp(-s2[u][v] / div_scale);
                 }
     }
-    block_sum<4>(tot, red);
+    wave_then_block_sum<4>(tot, red);
     if (tid == 0) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) part[(size_t)blockIdx.x * 4 + q] = tot[q];
@@ -408,7 +367,7 @@ __global__ __launch_bounds__(256) void large_spread_finish(const float* __restri
         const float2* p = reinterpret_cast<const float2*>(pred);
         const float2* g = reinterpret_cast<const float2*>(gt) + (size_t)a * Tf;
         for (int m = tid; m < M; m += 256) {
-            const float2* x = p + sample_base(a, m, n, K_in, Tf);
+            const float2* x = p + round_major_row(a, m, n, K_in, Tf);
             double sum = 0.0, d = 0.0;
             for (int t = 0; t < Tf; ++t) {
                 const float2 v = x[t], y = g[t];
@@ -419,7 +378,7 @@ __global__ __launch_bounds__(256) void large_spread_finish(const float* __restri
             gs[0] += sum / Tf;
             gs[1] += d;
         }
-        block_sum<2>(gs, red);
+        wave_then_block_sum<2>(gs, red);
     }
     if (tid != 0) return;
     double v[4] = {0.0, 0.0, 0.0, 0.0};
@@ -438,23 +397,16 @@ __global__ __launch_bounds__(256) void large_spread_finish(const float* __restri
 // The checks the three entries share: nullptr, or why not.  M_min: the smallest M the entry takes.
 const char* large_shape_check(int n, int R, int K_in, int Tf, int M_min) {
     if (n < 1) return "n must be positive";
-    if (R < 1 || K_in < 1 || R > LS_MAX_M || K_in > LS_MAX_M || R * K_in > LS_MAX_M) return "needs 1 <= M = R K_in <= 4096 (R, K_in >= 1)";
+    if (R < 1 || K_in < 1 || R > MAX_M || K_in > MAX_M || R * K_in > MAX_M) return "needs 1 <= M = R K_in <= 4096 (R, K_in >= 1)";
     if (R * K_in < M_min) return M_min == 3 ? "needs M = R K_in >= 3 (two points are collinear: no covariance)" : "needs M = R K_in >= 2 (a pair)";
-    if (Tf < 1 || Tf > LS_MAX_TF) return "Tf must be in [1, 200]";
+    if (Tf < 1 || Tf > MAX_TF) return "Tf must be in [1, 200]";
     return nullptr;
-}
-
-int large_refuse(const char* who, const char* why) {
-    char b[256];
-    snprintf(b, sizeof(b), "%s: %s", who, why);
-    stt_set_error(b);
-    return 1;
 }
 
 }  // namespace
 
 extern "C" long long int sttode_large_select_ws(int n, int M) {
-    if (n < 1 || M < 1 || M > LS_MAX_M) {
+    if (n < 1 || M < 1 || M > MAX_M) {
         stt_set_error("sttode_large_select_ws: needs n >= 1 and 1 <= M <= 4096");
         return -1;
     }
@@ -466,25 +418,25 @@ extern "C" int sttode_large_select(const float* pred, const float* gt, int n, in
                                    int* best_ade_idx, int* best_fde_idx, unsigned char* miss, float* ade_at, float* fde_at, float* seg_jade,
                                    float* seg_jfde, int* seg_jade_idx, int* seg_jfde_idx, void* stream) {
     const char* who = "sttode_large_select";
-    if (!(pred && gt && ade && fde)) return large_refuse(who, "null pointer (pred, gt, ade and fde are required)");
-    if (const char* why = large_shape_check(n, R, K_in, Tf, 1)) return large_refuse(who, why);
+    if (!(pred && gt && ade && fde)) return stt_refuse(who, "null pointer (pred, gt, ade and fde are required)");
+    if (const char* why = large_shape_check(n, R, K_in, Tf, 1)) return stt_refuse(who, why);
     const int M = R * K_in;
     LargeKs kk = {};
-    if (nk < 0 || nk > LS_MAX_KS) return large_refuse(who, "nk must be in [0, 16]");
-    if (nk > 0 && !(ks && ade_at && fde_at)) return large_refuse(who, "null pointer (nk > 0 needs ks, ade_at and fde_at)");
-    if (nk == 0 && (ade_at || fde_at)) return large_refuse(who, "ade_at and fde_at need ks (pass them as NULL with nk = 0)");
+    if (nk < 0 || nk > LS_MAX_KS) return stt_refuse(who, "nk must be in [0, 16]");
+    if (nk > 0 && !(ks && ade_at && fde_at)) return stt_refuse(who, "null pointer (nk > 0 needs ks, ade_at and fde_at)");
+    if (nk == 0 && (ade_at || fde_at)) return stt_refuse(who, "ade_at and fde_at need ks (pass them as NULL with nk = 0)");
     for (int i = 0; i < nk; ++i) {
-        if (ks[i] < 1 || ks[i] > M || (i > 0 && ks[i] <= ks[i - 1])) return large_refuse(who, "ks must be strictly ascending in [1, M]");
+        if (ks[i] < 1 || ks[i] > M || (i > 0 && ks[i] <= ks[i - 1])) return stt_refuse(who, "ks must be strictly ascending in [1, M]");
         kk.k[i] = ks[i];
     }
     kk.nk = nk;
     const bool segs = seg_ptr || seg_jade || seg_jfde || seg_jade_idx || seg_jfde_idx;
     if (segs) {
         if (!(seg_ptr && seg_jade && seg_jfde && seg_jade_idx && seg_jfde_idx))
-            return large_refuse(who, "null pointer (the joint outputs need seg_ptr, seg_jade, seg_jfde, seg_jade_idx and seg_jfde_idx together)");
-        if (S < 1) return large_refuse(who, "S must be positive with seg_ptr");
+            return stt_refuse(who, "null pointer (the joint outputs need seg_ptr, seg_jade, seg_jfde, seg_jade_idx and seg_jfde_idx together)");
+        if (S < 1) return stt_refuse(who, "S must be positive with seg_ptr");
         if (!ws || ws_bytes < sttode_large_select_ws(n, M))
-            return large_refuse(who, "the joint outputs need a workspace of sttode_large_select_ws(n, M) bytes");
+            return stt_refuse(who, "the joint outputs need a workspace of sttode_large_select_ws(n, M) bytes");
     }
     hipStream_t st = (hipStream_t)stream;
     float* wsv = segs ? (float*)ws : nullptr;
@@ -500,15 +452,15 @@ extern "C" int sttode_large_select(const float* pred, const float* gt, int n, in
 extern "C" int sttode_large_kde_nll(const float* pred, const float* gt, int n, int R, int K_in, int Tf, float scale, double* nll,
                                     void* stream) {
     const char* who = "sttode_large_kde_nll";
-    if (!(pred && gt && nll)) return large_refuse(who, "null pointer (pred, gt and nll are required)");
-    if (const char* why = large_shape_check(n, R, K_in, Tf, 3)) return large_refuse(who, why);
+    if (!(pred && gt && nll)) return stt_refuse(who, "null pointer (pred, gt and nll are required)");
+    if (const char* why = large_shape_check(n, R, K_in, Tf, 3)) return stt_refuse(who, why);
     hipLaunchKernelGGL(large_kde_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, pred, gt, n, K_in, R * K_in, Tf, scale, nll);
     STT_HIP(hipGetLastError());
     return 0;
 }
 
 extern "C" long long int sttode_large_spread_ws(int n, int M) {
-    if (n < 1 || M < 2 || M > LS_MAX_M || (long long)n * spread_groups(M) > INT_MAX) {
+    if (n < 1 || M < 2 || M > MAX_M || (long long)n * spread_groups(M) > INT_MAX) {
         stt_set_error("sttode_large_spread_ws: needs n >= 1, 2 <= M <= 4096 and n * min(tiles, 64) workgroups below 2^31");
         return -1;
     }
@@ -519,13 +471,13 @@ extern "C" int sttode_large_spread(const float* pred, const float* gt, int n, in
                                    long ws_bytes, double* apd, double* fpd, double* pade, double* dlow, double* es_ade, double* es_fde,
                                    void* stream) {
     const char* who = "sttode_large_spread";
-    if (!(pred && apd && fpd && pade && dlow)) return large_refuse(who, "null pointer (pred, apd, fpd, pade and dlow are required)");
-    if (!gt && (es_ade || es_fde)) return large_refuse(who, "es_ade and es_fde need gt (pass them as NULL without it)");
-    if (const char* why = large_shape_check(n, R, K_in, Tf, 2)) return large_refuse(who, why);
-    if (!(div_scale > 0.0) || std::isinf(div_scale)) return large_refuse(who, "div_scale must be positive and finite");
+    if (!(pred && apd && fpd && pade && dlow)) return stt_refuse(who, "null pointer (pred, apd, fpd, pade and dlow are required)");
+    if (!gt && (es_ade || es_fde)) return stt_refuse(who, "es_ade and es_fde need gt (pass them as NULL without it)");
+    if (const char* why = large_shape_check(n, R, K_in, Tf, 2)) return stt_refuse(who, why);
+    if (!(div_scale > 0.0) || std::isinf(div_scale)) return stt_refuse(who, "div_scale must be positive and finite");
     const int M = R * K_in, G = spread_groups(M);
-    if ((long long)n * G > INT_MAX) return large_refuse(who, "n is too large (n * min(tiles, 64) workgroups must stay below 2^31)");
-    if (!ws || ws_bytes < sttode_large_spread_ws(n, M)) return large_refuse(who, "needs a workspace of sttode_large_spread_ws(n, M) bytes");
+    if ((long long)n * G > INT_MAX) return stt_refuse(who, "n is too large (n * min(tiles, 64) workgroups must stay below 2^31)");
+    if (!ws || ws_bytes < sttode_large_spread_ws(n, M)) return stt_refuse(who, "needs a workspace of sttode_large_spread_ws(n, M) bytes");
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(large_spread_kernel, dim3(n * G), dim3(256), 0, st, pred, n, K_in, M, Tf, scale, div_scale, (double*)ws);
     hipLaunchKernelGGL(large_spread_finish, dim3(n), dim3(256), 0, st, pred, gt, n, K_in, M, Tf, scale, (const double*)ws, apd, fpd, pade, dlow,

@@ -11,7 +11,7 @@
 #include <cmath>
 
 #include "api_util.hpp"
-#include "frontend_body.hpp"
+#include "set_body.hpp"
 #include "../../include/sttode_hip.h"
 
 namespace {
@@ -32,7 +32,8 @@ __global__ __launch_bounds__(256) void joint_select_kernel(const float* __restri
     __shared__ double part[2][4][64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int s = blockIdx.x;
-    const int a0 = min(max(seg_ptr[s], 0), n), a1 = min(max(seg_ptr[s + 1], a0), n);
+    int a0, a1;
+    clamped_segment(seg_ptr, s, n, a0, a1);
     const int tot = K * Tf;
     double pa = 0.0, pf = 0.0;
     for (int a = a0 + w; a < a1; a += 4) {
@@ -75,12 +76,7 @@ __global__ __launch_bounds__(256) void joint_select_kernel(const float* __restri
         va = (((part[0][0][lane] + part[0][1][lane]) + part[0][2][lane]) + part[0][3][lane]) / c;
         vf = (((part[1][0][lane] + part[1][1][lane]) + part[1][2][lane]) + part[1][3][lane]) / c;
     }
-    double ma = va, mf = vf;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        ma = fmin(ma, __shfl_xor(ma, o, 64));
-        mf = fmin(mf, __shfl_xor(mf, o, 64));
-    }
+    const double ma = wave_min(va), mf = wave_min(vf);
     const unsigned long long ba = __ballot(lane < K && va == ma), bf = __ballot(lane < K && vf == mf);
     if (lane == 0) {
         seg_jade[s] = ba ? (float)ma : NAN;
@@ -104,7 +100,8 @@ __global__ __launch_bounds__(256) void joint_collision_kernel(const float* __res
     __shared__ int cnt[4][2];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int s = blockIdx.x;
-    const int a0 = min(max(seg_ptr[s], 0), n), a1 = min(max(seg_ptr[s + 1], a0), n);
+    int a0, a1;
+    clamped_segment(seg_ptr, s, n, a0, a1);
     const int na = a1 - a0, nblk = (na + 63) / 64;
     int col = 0, gcol = 0;
     for (int u = w; u < (K + 1) * nblk; u += 4) {
@@ -175,7 +172,7 @@ __global__ __launch_bounds__(256) void kde_nll_kernel(const float* __restrict__ 
     const float2* g = reinterpret_cast<const float2*>(gt + (size_t)a * Tf * 2);
     const int ftm = min(64, 1024 / K);
     const double f = pow((double)K, -1.0 / 6.0), f2 = f * f;
-    const double logK = log((double)K), two_pi = 6.283185307179586;
+    const double logK = log((double)K);
     double acc = 0.0;
     bool bad = false;
     for (int t0 = 0; t0 < Tf; t0 += ftm) {
@@ -206,50 +203,41 @@ __global__ __launch_bounds__(256) void kde_nll_kernel(const float* __restrict__ 
             c00 /= (K - 1);
             c01 /= (K - 1);
             c11 /= (K - 1);
-            const double det = c00 * c11 - c01 * c01;
-            if (!(c00 > 0.0) || !(det > 0.0)) {
+            double det, inv;
+            if (!kde_cov(c00, c01, c11, f2, det, inv)) {
                 bad = true;
             } else {
                 const float2 r = g[t0 + lane];
                 const double gx = (double)(r.x * scale), gy = (double)(r.y * scale);
-                const double inv = 1.0 / (f2 * det);   // Sigma^-1 = [[c11, -c01], [-c01, c00]] / (f^2 det C)
                 double m = -INFINITY;
                 for (int k = 0; k < K; ++k) {
                     const float2 v = sx[w][k * ft + lane];
                     const double dx = gx - (double)(v.x * scale), dy = gy - (double)(v.y * scale);
-                    m = fmax(m, -0.5 * ((c11 * dx * dx - 2.0 * c01 * dx * dy + c00 * dy * dy) * inv));
+                    m = fmax(m, -0.5 * kde_quad(c00, c01, c11, inv, dx, dy));
                 }
                 double sum = 0.0;
                 for (int k = 0; k < K; ++k) {
                     const float2 v = sx[w][k * ft + lane];
                     const double dx = gx - (double)(v.x * scale), dy = gy - (double)(v.y * scale);
-                    sum += exp(-0.5 * ((c11 * dx * dx - 2.0 * c01 * dx * dy + c00 * dy * dy) * inv) - m);
+                    sum += exp(-0.5 * kde_quad(c00, c01, c11, inv, dx, dy) - m);
                 }
-                const double tf2 = two_pi * f2;   // det(2 pi Sigma) = (2 pi f^2)^2 det C
-                lp = log(sum) + m - logK - 0.5 * log(tf2 * tf2 * det);
-                lp = lp < -20.0 ? -20.0 : lp;
+                lp = kde_clip(log(sum) + m - logK - kde_log_norm(f2, det));
             }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) lp += __shfl_xor(lp, o, 64);
-        acc += lp;
+        acc += wave_sum(lp);
         __builtin_amdgcn_wave_barrier();   // (the next tile overwrites sx[w])
     }
     const bool any_bad = __ballot(bad) != 0;
     if (lane == 0) nll[a] = any_bad ? (double)NAN : -acc / Tf;
 }
 
-constexpr int SS_FT = 32;             // frames per LDS tile of the spread pass
-constexpr int SS_STRIDE = SS_FT + 1;  // row stride in float2: odd, so that lanes on different samples at one frame fall on different banks
-constexpr int SS_K1 = 23;             // the largest K with one pair per thread at most: 23 * 22 / 2 = 253 <= 256
-
 // Spread of agent a's K samples among themselves (include/sttode_hip.h sttode_sample_spread), one workgroup per agent.
-// Coordinates are (double)(x * scale) with the product in fp32, everything after that float64.  The samples go through LDS in tiles of SS_FT
-// frames (raw float2, rows of SS_STRIDE).  Pair p (F.pdist order: (0,1), (0,2), ... (K-2,K-1)) belongs to thread p mod 256; a thread keeps, per
+// Coordinates are (double)(x * scale) with the product in fp32, everything after that float64.  The samples go through LDS in tiles of SET_FT
+// frames (raw float2, rows of SET_STRIDE).  Pair p (F.pdist order: (0,1), (0,2), ... (K-2,K-1)) belongs to thread p mod 256; a thread keeps, per
 // pair, the running sum of squared distances, the running sum of distances and the last frame's distance, frames in frame order.  After the
 // last tile it finishes its pairs in pair order (sqrt, exp) into four partial sums; those go through LDS, wave 0 adds the four of lane l,
 // l + 64, l + 128, l + 192 in that order and the 64 lanes by a fixed xor tree.  No atomics.
-// R = pairs per thread, KM = the largest K.  <8, 64> takes any K (2016 pairs <= 8 * 256); <1, SS_K1> is the same code for K <= 23, where the
+// R = pairs per thread, KM = the largest K.  <8, 64> takes any K (2016 pairs <= 8 * 256); <1, SET_K1> is the same code for K <= 23, where the
 // registers of seven more pairs and the LDS of 41 more samples would halve the workgroups a CU holds: the kernel waits on latency.
 // With gt: wave 3 (the one with the fewest pairs), lane = sample, sums the float64 distances to the ground truth for the energy scores and, in
 // fp32 with bok_dist in frame order, bok_select_kernel's ADE(a, k) / FDE(a, k); an inclusive prefix minimum over the lanes (fminf: NaN
@@ -260,8 +248,8 @@ __global__ __launch_bounds__(256) void sample_spread_kernel(const float* __restr
                                                             double* __restrict__ pade, double* __restrict__ dlow, double* __restrict__ es_ade,
                                                             double* __restrict__ es_fde, float* __restrict__ ade_at_k,
                                                             float* __restrict__ fde_at_k) {
-    __shared__ float2 sx[KM * SS_STRIDE];
-    __shared__ float2 sg[SS_FT];
+    __shared__ float2 sx[KM * SET_STRIDE];
+    __shared__ float2 sg[SET_FT];
     __shared__ double red[4][256];
     __shared__ double gsum[2];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -274,50 +262,21 @@ __global__ __launch_bounds__(256) void sample_spread_kernel(const float* __restr
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         int q = tid + 256 * r, i = 0;
-        if (q < P)
-            while (q >= K - 1 - i) {
-                q -= K - 1 - i;
-                ++i;
-            }
+        if (q < P) i = pdist_row(q, K);
         ij[r] = i | (i + 1 + q) << 8;
         s2[r] = s1[r] = dl[r] = 0.0;
     }
     const bool gw = g != nullptr && w == 3;
     double ga = 0.0, gl = 0.0;                            // wave 3, lane k: sum over frames of |x_k - y| and the last frame's, float64
     float fa = 0.f, fl = 0.f;                             // the same with bok_dist in fp32
-    for (int t0 = 0; t0 < Tf; t0 += SS_FT) {
-        const int ft = min(SS_FT, Tf - t0);
-        for (int i = tid; i < K * ft; i += 256) {
-            const int k = i / ft, tl = i - k * ft;
-            sx[k * SS_STRIDE + tl] = p[k * Tf + t0 + tl];
-        }
-        if (g && tid < ft) sg[tid] = g[t0 + tid];
+    for (int t0 = 0; t0 < Tf; t0 += SET_FT) {
+        const int ft = min(SET_FT, Tf - t0);
+        stage_tile<int>(sx, sg, p, g, K, Tf, t0, ft, tid);
         __syncthreads();
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-            if (tid + 256 * r < P) {
-                const float2* xi = sx + (ij[r] & 255) * SS_STRIDE;
-                const float2* xj = sx + (ij[r] >> 8) * SS_STRIDE;
-                for (int tl = 0; tl < ft; ++tl) {
-                    const float2 u = xi[tl], v = xj[tl];
-                    const double dx = (double)(u.x * scale) - (double)(v.x * scale), dy = (double)(u.y * scale) - (double)(v.y * scale);
-                    const double d2 = dx * dx + dy * dy;
-                    dl[r] = sqrt(d2);
-                    s2[r] += d2;
-                    s1[r] += dl[r];
-                }
-            }
-        }
-        if (gw && lane < K) {
-            for (int tl = 0; tl < ft; ++tl) {
-                const float2 v = sx[lane * SS_STRIDE + tl], y = sg[tl];
-                const double dx = (double)(v.x * scale) - (double)(y.x * scale), dy = (double)(v.y * scale) - (double)(y.y * scale);
-                gl = sqrt(dx * dx + dy * dy);
-                ga += gl;
-                fl = bok_dist(v.x, v.y, y.x, y.y, scale);
-                fa += fl;
-            }
-        }
+        for (int r = 0; r < R; ++r)
+            if (tid + 256 * r < P) pair_tile_accumulate(sx, ij[r], ft, scale, s2[r], s1[r], dl[r]);
+        if (gw && lane < K) gt_tile_accumulate(sx, sg, lane, ft, scale, ga, gl, fa, fl);
         __syncthreads();   // (the next tile overwrites sx and sg)
     }
     double t_apd = 0.0, t_fpd = 0.0, t_pade = 0.0, t_dlow = 0.0;
@@ -335,30 +294,13 @@ __global__ __launch_bounds__(256) void sample_spread_kernel(const float* __restr
     red[2][tid] = t_pade;
     red[3][tid] = t_dlow;
     if (gw) {
-        double da = lane < K ? ga / Tf : 0.0, df = lane < K ? gl : 0.0;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            da += __shfl_xor(da, o, 64);
-            df += __shfl_xor(df, o, 64);
-        }
+        const double da = wave_sum(lane < K ? ga / Tf : 0.0), df = wave_sum(lane < K ? gl : 0.0);
         if (lane == 0) {
             gsum[0] = da;
             gsum[1] = df;
         }
         if (ade_at_k || fde_at_k) {
-            float va = lane < K ? fa / (float)Tf : INFINITY, vf = lane < K ? fl : INFINITY;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const float ua = __shfl_up(va, o, 64), uf = __shfl_up(vf, o, 64);
-                if (lane >= o) {
-                    va = fminf(va, ua);
-                    vf = fminf(vf, uf);
-                }
-            }
-            if (lane < 63) {                              // (the selection of k < 64 samples takes its minimum with the idle lanes' +inf)
-                va = fminf(va, INFINITY);
-                vf = fminf(vf, INFINITY);
-            }
+            const float va = prefix_fmin64(lane < K ? fa / (float)Tf : INFINITY, lane), vf = prefix_fmin64(lane < K ? fl : INFINITY, lane);
             if (lane < K) {
                 if (ade_at_k) ade_at_k[(size_t)a * K + lane] = va;
                 if (fde_at_k) fde_at_k[(size_t)a * K + lane] = vf;
@@ -369,11 +311,7 @@ __global__ __launch_bounds__(256) void sample_spread_kernel(const float* __restr
     if (w != 0) return;
     double v[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        v[q] = ((red[q][lane] + red[q][lane + 64]) + red[q][lane + 128]) + red[q][lane + 192];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v[q] += __shfl_xor(v[q], o, 64);
-    }
+    for (int q = 0; q < 4; ++q) v[q] = quad_then_wave_sum(red[q], lane);
     if (lane == 0) {
         const double np = (double)P, c = (double)(K - 1) / (2.0 * K);
         apd[a] = v[0] / np;
@@ -391,7 +329,6 @@ __global__ __launch_bounds__(256) void sample_spread_kernel(const float* __restr
 int stt_joint_check(const char* who, const float* pred, const float* gt, int n, int K, int Tf, const int* seg_ptr, int S, float radius,
                     const float* seg_jade, const float* seg_jfde, const int* seg_jade_idx, const int* seg_jfde_idx, const int* seg_col,
                     const int* seg_gt_col) {
-    char b[256];
     const char* why = nullptr;
     if (!(pred && gt && seg_ptr && seg_jade && seg_jfde && seg_jade_idx && seg_jfde_idx))
         why = "null pointer (pred, gt, seg_ptr and the four joint outputs are required)";
@@ -401,14 +338,10 @@ int stt_joint_check(const char* who, const float* pred, const float* gt, int n, 
         why = "n, K, Tf and S must be positive";
     else if (K > 64)
         why = "K > 64 is not supported (one lane per sample)";
-    if (!why) return 0;
-    snprintf(b, sizeof(b), "%s: %s", who, why);
-    stt_set_error(b);
-    return 1;
+    return why ? stt_refuse(who, why) : 0;
 }
 
 int stt_kde_check(const char* who, const float* pred, const float* gt, int n, int K, int Tf, const double* nll) {
-    char b[256];
     const char* why = nullptr;
     if (!(pred && gt && nll))
         why = "null pointer (pred, gt and nll are required)";
@@ -416,16 +349,12 @@ int stt_kde_check(const char* who, const float* pred, const float* gt, int n, in
         why = "n and Tf must be positive";
     else if (K < 2 || K > 64)
         why = "needs 2 <= K <= 64 (K < 2: no covariance; K > 64: one LDS tile per frame block)";
-    if (!why) return 0;
-    snprintf(b, sizeof(b), "%s: %s", who, why);
-    stt_set_error(b);
-    return 1;
+    return why ? stt_refuse(who, why) : 0;
 }
 
 int stt_spread_check(const char* who, const float* pred, const float* gt, int n, int K, int Tf, double div_scale, const double* apd,
                      const double* fpd, const double* pade, const double* dlow, const double* es_ade, const double* es_fde,
                      const float* ade_at_k, const float* fde_at_k) {
-    char b[256];
     const char* why = nullptr;
     if (!(pred && apd && fpd && pade && dlow))
         why = "null pointer (pred, apd, fpd, pade and dlow are required)";
@@ -437,10 +366,7 @@ int stt_spread_check(const char* who, const float* pred, const float* gt, int n,
         why = "needs 2 <= K <= 64 (K < 2: no pair; K > 64: one lane per sample)";
     else if (!(div_scale > 0.0) || std::isinf(div_scale))
         why = "div_scale must be positive and finite";
-    if (!why) return 0;
-    snprintf(b, sizeof(b), "%s: %s", who, why);
-    stt_set_error(b);
-    return 1;
+    return why ? stt_refuse(who, why) : 0;
 }
 
 extern "C" int sttode_joint_select(const float* pred, const float* gt, int n, int K, int Tf, float scale, const int* seg_ptr, int S, float radius,
@@ -471,8 +397,8 @@ extern "C" int sttode_sample_spread(const float* pred, const float* gt, int n, i
                                     void* stream) {
     if (stt_spread_check("sttode_sample_spread", pred, gt, n, K, Tf, div_scale, apd, fpd, pade, dlow, es_ade, es_fde, ade_at_k, fde_at_k))
         return 1;
-    if (K <= SS_K1)
-        hipLaunchKernelGGL((sample_spread_kernel<1, SS_K1>), dim3(n), dim3(256), 0, (hipStream_t)stream, pred, gt, K, Tf, scale, div_scale, apd,
+    if (K <= SET_K1)
+        hipLaunchKernelGGL((sample_spread_kernel<1, SET_K1>), dim3(n), dim3(256), 0, (hipStream_t)stream, pred, gt, K, Tf, scale, div_scale, apd,
                            fpd, pade, dlow, es_ade, es_fde, ade_at_k, fde_at_k);
     else
         hipLaunchKernelGGL((sample_spread_kernel<8, 64>), dim3(n), dim3(256), 0, (hipStream_t)stream, pred, gt, K, Tf, scale, div_scale, apd, fpd,

@@ -11,6 +11,7 @@
 #include <cmath>
 
 #include "api_util.hpp"
+#include "set_body.hpp"
 #include "../../include/sttode_hip.h"
 
 namespace {
@@ -62,8 +63,7 @@ __global__ __launch_bounds__(256) void mm_main_kernel(const float* __restrict__ 
             else
                 s1 = mid;
         }
-        a0 = min(max(seg_ptr[s0], 0), n);
-        a1 = min(max(seg_ptr[s0 + 1], a0), n);
+        clamped_segment(seg_ptr, s0, n, a0, a1);
         if (i < a0 || i >= a1) {
             a0 = i;
             a1 = i + 1;
@@ -139,13 +139,8 @@ __global__ __launch_bounds__(256) void mm_main_kernel(const float* __restrict__ 
             double va = sum / (double)Tf, vf = dl;
             if (lane >= K || va != va) va = INFINITY;
             if (lane >= K || vf != vf) vf = INFINITY;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                va = fmin(va, __shfl_xor(va, o, 64));
-                vf = fmin(vf, __shfl_xor(vf, o, 64));
-            }
-            sa += va;
-            sf += vf;
+            sa += wave_min(va);
+            sf += wave_min(vf);
             ++cnt;
         }
     }
@@ -161,7 +156,6 @@ __global__ __launch_bounds__(256) void mm_main_kernel(const float* __restrict__ 
 extern "C" int sttode_multimodal(const float* pred, const float* past, const float* gt, const int* seg_ptr, int n_seg, int n, int K, int Tp,
                                  int Tf, int hist_frames, float scale, double eps, double* ws, long ws_doubles, int* count, double* mmade,
                                  double* mmfde, void* stream) {
-    char b[256];
     const char* why = nullptr;
     if (!(pred && past && gt && ws && count && mmade && mmfde))
         why = "null pointer (pred, past, gt, ws, count, mmade and mmfde are required)";
@@ -183,11 +177,7 @@ extern "C" int sttode_multimodal(const float* pred, const float* past, const flo
         why = "workspace too small: needs (2 hist_frames + 2) n doubles";
     else if (seg_ptr ? n_seg < 1 : n_seg != 0)
         why = "seg_ptr must be a CSR [n_seg + 1] with n_seg >= 1 (or NULL with n_seg = 0)";
-    if (why) {
-        snprintf(b, sizeof(b), "sttode_multimodal: %s", why);
-        stt_set_error(b);
-        return 1;
-    }
+    if (why) return stt_refuse("sttode_multimodal", why);
     hipLaunchKernelGGL(mm_prepass_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, past, n, Tp, hist_frames, scale, ws);
     STT_HIP(hipGetLastError());
     // lo < eps^2 < thr with room for every rounding of eps * eps, of the bounds and of a square root.  Where eps^2 overflows, every finite

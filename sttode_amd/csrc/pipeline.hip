@@ -715,12 +715,7 @@ static int run_async(SttodeModel* m, const float* past, const int* scene_ptr, in
     if (o.sampler) {
         STT_REQUIRE(!o.device_latents, "sttode_inference_*_async: a sampler plan and device_latents both ask to fill z: pass one of them");
         STT_REQUIRE(use_lagged(m, n), "sttode_inference_*_async: a sampler plan needs the lagged form (sttode_async_is_lagged)");
-        if (const char* why = stt_sampler_plan_check(o.sampler, m->K)) {
-            char b[256];
-            snprintf(b, sizeof(b), "sttode_inference_*_async: %s", why);
-            stt_set_error(b);
-            return 1;
-        }
+        if (const char* why = stt_sampler_plan_check(o.sampler, m->K)) return stt_refuse("sttode_inference_*_async", why);
     }
     arm_timing(m);
     long off[STT_B_COUNT], tot;
@@ -804,17 +799,11 @@ extern "C" int sttode_inference_nba_async(SttodeModel* m, const float* past, int
 // sequence: the slot's outstanding groups first (lagged form: nobody has enqueued them yet), then `launch`, the synchronous entry on the
 // slot's stream, then the slot's completion event re-recorded behind it: sttode_wait(slot) and the slot's next user wait for the pass too.
 // Passes that check their arguments themselves (stt_*_check) do so in front of this: a refused pass enqueues nothing.
-static int follow_up_refused(const char* who, const char* why) {
-    char b[128];
-    snprintf(b, sizeof(b), "%s: %s", who, why);
-    stt_set_error(b);
-    return 1;
-}
 template <class F>
 static int slot_follow_up(SttodeModel* m, int slot, const char* who, F&& launch) {
-    if (!(m && slot >= 0 && slot < STT_MAX_SLOTS)) return follow_up_refused(who, "bad model / slot");
+    if (!(m && slot >= 0 && slot < STT_MAX_SLOTS)) return stt_refuse(who, "bad model / slot");
     std::lock_guard<std::mutex> lk(m->mu);
-    if (!m->slot_stream[slot]) return follow_up_refused(who, "no asynchronous call has used this slot");
+    if (!m->slot_stream[slot]) return stt_refuse(who, "no asynchronous call has used this slot");
     if (int rc = lag_flush(m, slot)) return rc;
     if (int rc = launch(m->slot_stream[slot])) return rc;
     STT_HIP(hipEventRecord(m->evB_done[slot], m->slot_stream[slot]));

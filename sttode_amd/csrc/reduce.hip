@@ -9,19 +9,16 @@
 //   assign    lane -> SB samples (m = tid + 256 s) x 4 centroids per pass: the centroids are kept as ct[f][KP] (k contiguous, KP = K rounded
 //             up to 4), so one 16-byte broadcast read serves four distances.  d(m, k) = sum over f >= 2 from_frame, in order, of
 //             fma(x - c, x - c, d): direct differences, never the expanded form.  Strict < over ascending k: the lowest k wins exact ties.
-//   update    a stable counting sort of the samples by label (per 64-sample chunk one ballot per k gives each sample its rank among the
+//   update    a stable counting sort of the samples by label (sort_by_label of set_body.hpp: per 64-sample chunk one ballot per k gives each sample its rank among the
 //             chunk's members of its cluster; a prefix over chunks and clusters gives the offsets), then one lane per (k, f) adds its
 //             cluster's members IN SAMPLE ORDER and divides by the count; an empty cluster keeps its centroid.
 //   stop      an iteration that changes no label would reproduce the same centroids: the loop ends there.
 // No floating-point atomics, no cross-workgroup traffic: an agent's result depends on its own samples only.
 #include "api_util.hpp"
+#include "set_body.hpp"
 #include "../../include/sttode_hip.h"
 
 namespace {
-
-constexpr int NT = 256;                       // lanes per workgroup
-constexpr int MAX_K = 64, MAX_M = 4096, MAX_TF = 200, MAX_ITERS = 1000;
-constexpr int LDS_LIMIT = 159 * 1024;         // dynamic LDS of one workgroup: gfx950's 160 KiB less 1 KiB for the static words of the barrier-or
 
 struct Shape {
     int n, R, K_in, Tf, K, M, F, f0, KP, MP, chunks;
@@ -31,8 +28,6 @@ struct Shape {
 struct Layout {
     int ct, xs, cnt, off, red, lab, scratch, ccnt, total;
 };
-
-__host__ __device__ inline int up16(int b) { return (b + 15) & ~15; }
 
 __host__ __device__ inline Layout layout_of(const Shape& s, bool staged) {
     Layout l;
@@ -55,21 +50,9 @@ struct Samples {
     const float* xs;
     const float* pred;
     int MP, n, K_in, F, a;
-    __device__ __forceinline__ size_t row(int m) const {
-        if (STAGED) return (size_t)m;
-        const int r = m / K_in, k = m - r * K_in;
-        return (((size_t)r * n + a) * K_in + k) * (size_t)F;
-    }
+    __device__ __forceinline__ size_t row(int m) const { return STAGED ? (size_t)m : round_major_row(a, m, n, K_in, F); }
     __device__ __forceinline__ float at(size_t row, int f) const { return STAGED ? xs[(size_t)f * MP + row] : pred[row + f]; }
 };
-
-// (value, index) argmax with the lowest index on ties; a NaN value never replaces a finite one and the index stays one that was offered.
-__device__ __forceinline__ void arg_better(float& v, int& i, float v2, int i2) {
-    if (v2 > v || (v2 == v && i2 < i)) {
-        v = v2;
-        i = i2;
-    }
-}
 
 template <bool STAGED, int SB>
 __global__ __launch_bounds__(NT) void reduce_kernel(const float* __restrict__ pred, Shape s, int iters, int init_mode,
@@ -142,9 +125,9 @@ __global__ __launch_bounds__(NT) void reduce_kernel(const float* __restrict__ pr
                 }
                 if (j > 0) d = d < mind[m] ? d : mind[m];
                 mind[m] = d;
-                arg_better(bv, bi, d, m);
+                take_higher(bv, bi, d, m);
             }
-            for (int o = 32; o > 0; o >>= 1) arg_better(bv, bi, __shfl_xor(bv, o), __shfl_xor(bi, o));
+            wave_take_higher(bv, bi);
             __syncthreads();                                            // (the previous round's redv / redi have been read)
             if (lane == 0) {
                 redv[wave] = bv;
@@ -153,7 +136,7 @@ __global__ __launch_bounds__(NT) void reduce_kernel(const float* __restrict__ pr
             __syncthreads();
             bv = redv[0];
             bi = redi[0];
-            for (int w = 1; w < NT / 64; ++w) arg_better(bv, bi, redv[w], redi[w]);
+            for (int w = 1; w < NT / 64; ++w) take_higher(bv, bi, redv[w], redi[w]);
             chosen = bi;
         }
     }
@@ -212,42 +195,8 @@ __global__ __launch_bounds__(NT) void reduce_kernel(const float* __restrict__ pr
         }
         if (!__syncthreads_or(changed)) break;
 
-        // rank of every sample among its 64-sample chunk's members of the same cluster, and the chunk's member counts
-        for (int c = wave; c < s.chunks; c += NT / 64) {
-            const int m = 64 * c + lane;
-            const int l = m < M ? lab[m] : 255;
-            int rank = 0;
-            for (int k = 0; k < K; ++k) {
-                const unsigned long long mask = __ballot(l == k);
-                if (l == k) rank = __popcll(mask & ((1ull << lane) - 1ull));
-                if (lane == 0) ccnt[c * KP + k] = (unsigned short)__popcll(mask);
-            }
-            if (m < M) rnk[m] = (unsigned short)rank;
-        }
-        __syncthreads();
-        if (wave == 0) {                                                // chunk counts -> exclusive prefix over chunks; cluster sizes and offsets
-            int run = 0;
-            if (lane < K)
-                for (int c = 0; c < s.chunks; ++c) {
-                    const int t = ccnt[c * KP + lane];
-                    ccnt[c * KP + lane] = (unsigned short)run;
-                    run += t;
-                }
-            int scan = run;
-            for (int o = 1; o < 64; o <<= 1) {
-                const int up = __shfl_up(scan, o);
-                if (lane >= o) scan += up;
-            }
-            if (lane < K) {
-                cnt[lane] = run;
-                off[lane] = scan - run;
-            }
-        }
-        __syncthreads();
-        for (int m = tid; m < M; m += NT) {
-            const int l = lab[m];
-            perm[off[l] + ccnt[(m >> 6) * KP + l] + rnk[m]] = (unsigned short)m;
-        }
+        sort_by_label(lab, M, K, KP, s.chunks, rnk, ccnt, cnt, off);
+        for (int m = tid; m < M; m += NT) perm[sorted_slot(m, lab, KP, rnk, ccnt, off)] = (unsigned short)m;
         __syncthreads();
         for (int p = tid; p < K * F; p += NT) {
             const int k = p / F, f = p - k * F;

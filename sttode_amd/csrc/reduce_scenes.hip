@@ -12,21 +12,19 @@
 //             16-byte broadcast read serves four distances.  Per agent d_a(m, k) = sum over f >= 2 from_frame, in order, of
 //             fma(x - c, x - c, d) in fp32 -- the bits of reduce_kernel (reduce.hip) -- and D(m, k) += (double)d_a(m, k) in segment order in
 //             SB x KC float64 registers.  Strict < over ascending k: the lowest k wins exact ties.
-//   update    ONE stable counting sort of the samples by label per iteration (reduce_kernel's: per 64-sample chunk one ballot per k, a prefix
+//   update    ONE stable counting sort of the samples by label per iteration (sort_by_label of set_body.hpp, as reduce_kernel: per 64-sample chunk one ballot per k, a prefix
 //             over chunks and clusters), which leaves the members' row offsets in cluster order; then one lane per (agent, k, f), f fastest,
 //             adds its cluster's members IN SAMPLE ORDER and divides by the count; an empty cluster's centroid is not touched.
 //   stop      an iteration that changes no label would reproduce the same centroids: the loop ends there.
 // No floating-point atomics, no workspace: a segment's result depends on its own agents' samples only.
 #include "api_util.hpp"
+#include "set_body.hpp"
 #include "../../include/sttode_hip.h"
 
 namespace {
 
-constexpr int NT = 256;                       // lanes per workgroup
-constexpr int MAX_K = 64, MAX_M = 4096, MAX_TF = 200, MAX_ITERS = 1000;
 constexpr int FC = 24;                        // floats of a sample's row held in registers at a time
 constexpr int MAX_AB = 16, CTQ_BYTES = 32 * 1024;   // agents staged per barrier pair: as many groups [F][KC] as fit in CTQ_BYTES, at most MAX_AB
-constexpr int LDS_LIMIT = 159 * 1024;         // dynamic LDS of one workgroup: gfx950's 160 KiB less 1 KiB for the static words of the barrier-or
 
 struct Shape {
     int n, R, K_in, Tf, K, M, F, f0, KP, AB, chunks, S;
@@ -36,8 +34,6 @@ struct Shape {
 struct Layout {
     int ctq, cnt, off, red, lab, wide, rnk, ccnt, total;
 };
-
-__host__ __device__ inline int up16(int b) { return (b + 15) & ~15; }
 
 __host__ __device__ inline Layout layout_of(const Shape& s, int KC) {
     Layout l;
@@ -52,14 +48,6 @@ __host__ __device__ inline Layout layout_of(const Shape& s, int KC) {
     l.ccnt = p;  p += up16(s.chunks * s.KP * 2);            // per (64-sample chunk, cluster): member count, then exclusive prefix over chunks
     l.total = p;
     return l;
-}
-
-// (value, index) argmax with the lowest index on ties; a NaN value never replaces a finite one and the index stays one that was offered.
-__device__ __forceinline__ void arg_better(double& v, int& i, double v2, int i2) {
-    if (v2 > v || (v2 == v && i2 < i)) {
-        v = v2;
-        i = i2;
-    }
 }
 
 // p[0 .. cnt) into x (cnt even, <= FC; the rest of x is zero and never used) in 16- and 8-byte loads issued together.  A row starts at an even
@@ -101,9 +89,8 @@ __global__ __launch_bounds__(NT) void reduce_scenes_kernel(const float* __restri
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int sg = blockIdx.x;
     const int M = s.M, K = s.K, F = s.F, KP = s.KP, f0 = s.f0, KF = s.K * s.F;
-    int a0 = seg_ptr[sg], a1 = seg_ptr[sg + 1];                         // clamped: a CSR on the device is never read back by the host
-    a0 = a0 < 0 ? 0 : (a0 > s.n ? s.n : a0);
-    a1 = a1 < a0 ? a0 : (a1 > s.n ? s.n : a1);
+    int a0, a1;                                                         // clamped: a CSR on the device is never read back by the host
+    clamped_segment(seg_ptr, sg, s.n, a0, a1);
     const int A = a1 - a0;
     int* lab_out = labels + (size_t)sg * M;
     int* cnt_out = counts + (size_t)sg * K;
@@ -114,10 +101,7 @@ __global__ __launch_bounds__(NT) void reduce_scenes_kernel(const float* __restri
     }
     // sample m of agent a starts at row0(m) + a astr in pred ([R,n,K_in,Tf,2]: sample m = r K_in + k)
     const size_t astr = (size_t)s.K_in * F;
-    auto row0 = [&](int m) -> size_t {
-        const int r = m / s.K_in, k = m - r * s.K_in;
-        return ((size_t)r * s.n * s.K_in + k) * (size_t)F;
-    };
+    auto row0 = [&](int m) -> size_t { return round_major_row(0, m, s.n, s.K_in, F); };
     float* cseg = centroids + (size_t)a0 * KF;                          // the segment's centroids [A][K][F]
     const float* xseg = pred + (size_t)a0 * astr;                       // the segment's samples: agent i of it at xseg + i astr
 
@@ -167,9 +151,9 @@ __global__ __launch_bounds__(NT) void reduce_scenes_kernel(const float* __restri
                 }
                 if (j > 0) D = D < mind[m] ? D : mind[m];
                 mind[m] = D;
-                arg_better(bv, bi, D, m);
+                take_higher(bv, bi, D, m);
             }
-            for (int o = 32; o > 0; o >>= 1) arg_better(bv, bi, __shfl_xor(bv, o), __shfl_xor(bi, o));
+            wave_take_higher(bv, bi);
             __syncthreads();                                            // (the previous round's redv / redi have been read)
             if (lane == 0) {
                 redv[wave] = bv;
@@ -178,7 +162,7 @@ __global__ __launch_bounds__(NT) void reduce_scenes_kernel(const float* __restri
             __syncthreads();
             bv = redv[0];
             bi = redi[0];
-            for (int w = 1; w < NT / 64; ++w) arg_better(bv, bi, redv[w], redi[w]);
+            for (int w = 1; w < NT / 64; ++w) take_higher(bv, bi, redv[w], redi[w]);
             chosen = bi;
         }
     }
@@ -271,42 +255,8 @@ __global__ __launch_bounds__(NT) void reduce_scenes_kernel(const float* __restri
         }
         if (!__syncthreads_or(changed)) break;
 
-        // rank of every sample among its 64-sample chunk's members of the same cluster, and the chunk's member counts
-        for (int c = wave; c < s.chunks; c += NT / 64) {
-            const int m = 64 * c + lane;
-            const int l = m < M ? lab[m] : 255;
-            int rank = 0;
-            for (int k = 0; k < K; ++k) {
-                const unsigned long long mask = __ballot(l == k);
-                if (l == k) rank = __popcll(mask & ((1ull << lane) - 1ull));
-                if (lane == 0) ccnt[c * KP + k] = (unsigned short)__popcll(mask);
-            }
-            if (m < M) rnk[m] = (unsigned short)rank;
-        }
-        __syncthreads();
-        if (wave == 0) {                                                // chunk counts -> exclusive prefix over chunks; cluster sizes and offsets
-            int run = 0;
-            if (lane < K)
-                for (int c = 0; c < s.chunks; ++c) {
-                    const int t = ccnt[c * KP + lane];
-                    ccnt[c * KP + lane] = (unsigned short)run;
-                    run += t;
-                }
-            int scan = run;
-            for (int o = 1; o < 64; o <<= 1) {
-                const int up = __shfl_up(scan, o);
-                if (lane >= o) scan += up;
-            }
-            if (lane < K) {
-                cnt[lane] = run;
-                off[lane] = scan - run;
-            }
-        }
-        __syncthreads();
-        for (int m = tid; m < M; m += NT) {
-            const int l = lab[m];
-            prow[off[l] + ccnt[(m >> 6) * KP + l] + rnk[m]] = row0(m);
-        }
+        sort_by_label(lab, M, K, KP, s.chunks, rnk, ccnt, cnt, off);
+        for (int m = tid; m < M; m += NT) prow[sorted_slot(m, lab, KP, rnk, ccnt, off)] = row0(m);
         __syncthreads();
         for (size_t e = tid; e < (size_t)A * KF; e += NT) {
             const int i = (int)(e / KF), rem = (int)(e - (size_t)i * KF), k = rem / F, f = rem - k * F;

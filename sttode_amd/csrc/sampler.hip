@@ -5,6 +5,7 @@
 // The Q-net itself (linear 128->64, tanh MLP, q_A / q_b / q_c) runs on sttode_linear_cols (decoder.hip).
 // All of this is O(n*K*nz) elementwise / O(n*K^2*Tf) pairwise work: HBM/VALU bound, one wave per agent for the losses.
 #include "api_util.hpp"
+#include "sampler_body.hpp"
 
 __global__ void sampler_latent_kernel(const float* __restrict__ A, const float* __restrict__ b, const float* __restrict__ eps,
                                       int eps_mode, float* __restrict__ z, float* __restrict__ logvar, long total, int nz, int K) {
@@ -22,12 +23,6 @@ __global__ void sampler_latent_kernel(const float* __restrict__ A, const float* 
     logvar[i] = logf(a * a + 1e-8f);
 }
 
-static __device__ inline float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // one wave per agent; motion [n][K][D] staged in LDS (K*D <= 4096 floats)
 __global__ __launch_bounds__(64) void sampler_loss_kernel(const float* __restrict__ mu, const float* __restrict__ logvar,
                                                           const float* __restrict__ pmu, const float* __restrict__ plogvar,
@@ -35,26 +30,15 @@ __global__ __launch_bounds__(64) void sampler_loss_kernel(const float* __restric
                                                           float scale, float* __restrict__ kld, float* __restrict__ div) {
     __shared__ float sM[4096];
     const int a = blockIdx.x, lane = threadIdx.x;
-    // KL(q || p), utils/dist.py:26-29
-    float kl = 0.f;
-    const size_t base = (size_t)a * K * nz;
-    for (int i = lane; i < K * nz; i += 64) {
-        const float m = mu[base + i], sg = expf(0.5f * logvar[base + i]);
-        const float pm = pmu ? pmu[base + i] : 0.f;
-        const float ps = (plogvar ? expf(0.5f * plogvar[base + i]) : 1.f) + 1e-8f;
-        const float t1 = (m - pm) / ps, t2 = sg / ps;
-        kl += 0.5f * (t1 * t1 + t2 * t2) - 0.5f - logf(t2);
-    }
-    kl = wave_sum(kl);
+    const float kl = sampler_kld(mu, logvar, pmu, plogvar, a, K, nz, lane);
     for (int i = lane; i < K * D; i += 64) sM[i] = motion[(size_t)a * K * D + i];
     __syncthreads();
     // pairs (i < j) in F.pdist order; the order does not matter for the mean
     const int np = K * (K - 1) / 2;
     float acc = 0.f;
     for (int p = lane; p < np; p += 64) {
-        int i = 0, r = p;
-        while (r >= K - 1 - i) { r -= K - 1 - i; ++i; }
-        const int j = i + 1 + r;
+        int i, j;
+        pdist_pair(p, K, i, j);
         float s = 0.f;
         for (int d = 0; d < D; ++d) {
             const float t = sM[i * D + d] - sM[j * D + d];

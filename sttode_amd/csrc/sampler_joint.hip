@@ -2,8 +2,8 @@
 // the DLow kernel on the segment's mean squared distance, the reconstruction term with ONE best sample per segment, and the energy score
 // on the scene's RMS displacement; kld stays per agent.  A segment (a scene, an NBA game) may hold hundreds of agents, so nothing stages
 // a segment: the work goes in phases through a caller-provided workspace, each phase a launch of its own on the caller's stream.
-//   sj_agent_kernel    (A) one wave per agent, sampler_objective_kernel's staging and pair-to-lane assignment.  kld[a] (sampler_loss_kernel's
-//                      statements: the same bits), and into the workspace the agent's np unmasked pair sums (float32, the DLow s), its np
+//   sj_agent_kernel    (A) one wave per agent, sampler_objective_kernel's staging and pair-to-lane assignment.  kld[a] (sampler_body.hpp's
+//                      sampler_kld, as sampler_loss_kernel: the same bits), and into the workspace the agent's np unmasked pair sums (float32, the DLow s), its np
 //                      masked pair sums and its K per-sample sums against the ground truth (float64).
 //   sj_segment_kernel  (B) one workgroup of 256 threads per segment.  Pairs and samples strided over the threads; each summed over the
 //                      segment's agents in agent order in float64; a fixed-order LDS tree adds the threads; wave 0 runs the (value, index)
@@ -19,6 +19,7 @@
 #include <cmath>
 
 #include "api_util.hpp"
+#include "sampler_body.hpp"
 
 constexpr int SJ_LDS = 4096;   // floats of motion one agent may stage (K D), as sampler_loss_kernel
 constexpr int SJ_WG = 256;     // threads of a segment's (B) and of an agent's backward (C) workgroup
@@ -50,12 +51,6 @@ static inline SjWs sj_ws_layout(void* ws, long n, long K, long S) {
     return w;
 }
 
-static __device__ inline float sj_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // (A) one wave per agent
 __global__ __launch_bounds__(64) void sj_agent_kernel(const float* __restrict__ mu, const float* __restrict__ logvar,
                                                       const float* __restrict__ pmu, const float* __restrict__ plogvar,
@@ -66,29 +61,16 @@ __global__ __launch_bounds__(64) void sj_agent_kernel(const float* __restrict__ 
     float *sM = sj_lds, *sY = sM + K * D, *sW = sY + D;
     const int a = blockIdx.x, lane = threadIdx.x;
     const int Tf = D / 2;
-    if (kld) {   // KL(q || p): sampler_loss_kernel's loop (the backward's pass has no kld to write)
-        float kl = 0.f;
-        const size_t base = (size_t)a * K * nz;
-        for (int i = lane; i < K * nz; i += 64) {
-            const float m = mu[base + i], sg = expf(0.5f * logvar[base + i]);
-            const float pm_ = pmu ? pmu[base + i] : 0.f;
-            const float ps_ = (plogvar ? expf(0.5f * plogvar[base + i]) : 1.f) + 1e-8f;
-            const float t1 = (m - pm_) / ps_, t2 = sg / ps_;
-            kl += 0.5f * (t1 * t1 + t2 * t2) - 0.5f - logf(t2);
-        }
-        kl = sj_wave_sum(kl);
+    if (kld) {   // (the backward's pass has no kld to write)
+        const float kl = sampler_kld(mu, logvar, pmu, plogvar, a, K, nz, lane);
         if (lane == 0) kld[a] = kl;
     }
-    for (int i = lane; i < K * D; i += 64) sM[i] = motion[(size_t)a * K * D + i];
-    for (int i = lane; i < D; i += 64) sY[i] = gt[(size_t)a * D + i];
-    for (int i = lane; i < Tf; i += 64) sW[i] = mask ? mask[(size_t)a * Tf + i] : 1.f;
-    __syncthreads();
+    sampler_stage(motion, gt, mask, a, K, D, lane, 64, sM, sY, sW);
     // pairs (i < j) in F.pdist order, pair p on lane p mod 64; s takes x then y of every frame in frame order, as sampler_loss_kernel
     const int np = K * (K - 1) / 2;
     for (int p = lane; p < np; p += 64) {
-        int i = 0, r = p;
-        while (r >= K - 1 - i) { r -= K - 1 - i; ++i; }
-        const int j = i + 1 + r;
+        int i, j;
+        pdist_pair(p, K, i, j);
         float s = 0.f;
         double sm = 0.0;
         for (int t = 0; t < Tf; ++t) {
@@ -104,35 +86,11 @@ __global__ __launch_bounds__(64) void sj_agent_kernel(const float* __restrict__ 
         ps[(size_t)a * np + p] = s;
         pm[(size_t)a * np + p] = sm;
     }
-    // sample k on lane k mod 64: sum_t (m_t (x_k,t - y_t))^2, frames in frame order
+    // sample k on lane k mod 64: sum_t (m_t (x_k,t - y_t))^2 (the displacement sums are not wanted here)
     for (int k = lane; k < K; k += 64) {
-        double r2 = 0.0;
-        for (int t = 0; t < Tf; ++t) {
-            const double m = (double)sW[t];
-            const double ex = m * ((double)sM[k * D + 2 * t] - (double)sY[2 * t]);
-            const double ey = m * ((double)sM[k * D + 2 * t + 1] - (double)sY[2 * t + 1]);
-            r2 += ex * ex + ey * ey;
-        }
-        gs[(size_t)a * K + k] = r2;
+        double ga = 0.0, last = 0.0;
+        gs[(size_t)a * K + k] = sampler_gt_sample(sM, sY, sW, k, D, ga, last);
     }
-}
-
-// segment g of the CSR, clamped to [0, n] (as sttode_joint_select: no address depends on seg_ptr's contents being sane)
-static __device__ inline void sj_segment(const int* __restrict__ seg_ptr, int g, int n, int& a0, int& a1) {
-    a0 = min(max(seg_ptr[g], 0), n);
-    a1 = min(max(seg_ptr[g + 1], a0), n);
-}
-
-// the 256 threads' values added in a fixed order (a tree over the thread index); every thread returns the sum
-static __device__ inline double sj_block_sum(double v, double* red, int tid) {
-    __syncthreads();   // (red may still be read from the sum before)
-    red[tid] = v;
-    __syncthreads();
-    for (int o = SJ_WG / 2; o > 0; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
-    return red[0];
 }
 
 // (B) one workgroup per segment.  div / rec / best / es may be NULL (the backward's pass): then only the tables are written.
@@ -147,7 +105,7 @@ __global__ __launch_bounds__(SJ_WG) void sj_segment_kernel(const int* __restrict
     const int g = blockIdx.x, tid = threadIdx.x;
     const int np = K * (K - 1) / 2, Tf = D / 2;
     int a0, a1;
-    sj_segment(seg_ptr, g, n, a0, a1);
+    clamped_segment(seg_ptr, g, n, a0, a1);
     const int ng = a1 - a0;
     if (ng <= 0) {   // an empty segment: NaN values, index 0 (no agent reads its tables)
         if (tid == 0) {
@@ -188,30 +146,15 @@ __global__ __launch_bounds__(SJ_WG) void sj_segment_kernel(const int* __restrict
             bi = k;
         }
     }
-    dsum = sj_block_sum(dsum, red, tid);
-    rpsum = sj_block_sum(rpsum, red, tid);
-    rgsum = sj_block_sum(rgsum, red, tid);
+    dsum = index_tree_block_sum(dsum, red, tid);
+    rpsum = index_tree_block_sum(rpsum, red, tid);
+    rgsum = index_tree_block_sum(rgsum, red, tid);
     sbv[tid] = bv;
     sbi[tid] = bi;
     __syncthreads();
     if (tid < 64) {   // wave 0: the four waves' candidates of this lane, then the butterfly
-        for (int q = 1; q < SJ_WG / 64; ++q) {
-            const double ov = sbv[tid + 64 * q];
-            const int oi = sbi[tid + 64 * q];
-            if (ov < bv || (ov == bv && oi < bi)) {
-                bv = ov;
-                bi = oi;
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const double ov = __shfl_xor(bv, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            if (ov < bv || (ov == bv && oi < bi)) {
-                bv = ov;
-                bi = oi;
-            }
-        }
+        for (int q = 1; q < SJ_WG / 64; ++q) take_lower(bv, bi, sbv[tid + 64 * q], sbi[tid + 64 * q]);
+        wave_take_lower(bv, bi);
         if (bi >= K) {   // no sample compared below +inf (NaN inputs)
             bi = 0;
             bv = NAN;
@@ -261,7 +204,7 @@ __global__ __launch_bounds__(SJ_WG) void sj_bwd_kernel(const float* __restrict__
     }
     const int g = lo;
     int a0, a1;
-    sj_segment(seg_ptr, g, n, a0, a1);
+    clamped_segment(seg_ptr, g, n, a0, a1);
     if (a < a0 || a >= a1) {
         for (int e = tid; e < K * D; e += SJ_WG) dmotion[(size_t)a * K * D + e] = 0.f;
         return;
@@ -276,10 +219,7 @@ __global__ __launch_bounds__(SJ_WG) void sj_bwd_kernel(const float* __restrict__
         const double r = trg[(size_t)g * K + i];
         sIg[i] = r > 0.0 ? 1.0 / r : 0.0;
     }
-    for (int i = tid; i < K * D; i += SJ_WG) sM[i] = motion[(size_t)a * K * D + i];
-    for (int i = tid; i < D; i += SJ_WG) sY[i] = gt[(size_t)a * D + i];
-    for (int i = tid; i < Tf; i += SJ_WG) sW[i] = mask ? mask[(size_t)a * Tf + i] : 1.f;
-    __syncthreads();
+    sampler_stage(motion, gt, mask, a, K, D, tid, SJ_WG, sM, sY, sW);
     const int bi = tbest[g];
     const double gd = g_div ? (double)g_div[g] : 0.0, gr = g_rec ? (double)g_rec[g] : 0.0, ge = g_es ? (double)g_es[g] : 0.0;
     const double cd = gd * (-2.0 / ((double)scale * (double)ng)) / (double)np;
@@ -310,7 +250,6 @@ __global__ __launch_bounds__(SJ_WG) void sj_bwd_kernel(const float* __restrict__
 
 static int sj_check(const char* who, const void* mu, const void* logvar, const void* motion, const void* gt, const void* seg_ptr,
                     const void* workspace, bool outs, int S, int n, int K, int nz, int D, float scale, long ws_bytes) {
-    char b[200];
     const char* why = nullptr;
     if (!(mu && logvar && motion && gt && seg_ptr && workspace && outs))
         why = "null pointer (mu, logvar, motion, gt, seg_ptr, workspace and every output are required)";
@@ -322,10 +261,7 @@ static int sj_check(const char* who, const void* mu, const void* logvar, const v
     else if (!(scale > 0.f)) why = "scale must be positive";
     else if (((size_t)workspace & 7) != 0) why = "workspace must be aligned to 8 bytes";
     else if (ws_bytes < sj_ws_bytes(n, K, S)) why = "ws_bytes is less than sttode_sampler_objective_joint_ws(n, K, S)";
-    if (!why) return 0;
-    snprintf(b, sizeof(b), "%s: %s", who, why);
-    stt_set_error(b);
-    return 1;
+    return why ? stt_refuse(who, why) : 0;
 }
 
 extern "C" long long int sttode_sampler_objective_joint_ws(int n, int K, int S) {

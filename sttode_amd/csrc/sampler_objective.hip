@@ -1,7 +1,7 @@
 // Stage-2 objective with its ground-truth terms (include/sttode_hip.h sttode_sampler_objective): next to sampler.hip's
 // kld / div, the reconstruction term of samplerloss.py:23-29 (min over K of the masked squared error) and the energy scores of 4s, in one
 // launch over all agents, and their backward in a second one.
-//   sampler_objective_kernel      one wave per agent.  kld and div are sampler_loss_kernel's statements, lane for lane and in its
+//   sampler_objective_kernel      one wave per agent.  kld is sampler_body.hpp's sampler_kld and div has sampler_loss_kernel's statements, lane for lane and in its
 //                                 order (the same bits); the loop over the pairs that forms dx, dy for sum d^2 also takes the per-frame
 //                                 norm |x_i,t - x_j,t| for pade / fpd.  Lane k then walks sample k against the ground truth.
 //   sampler_objective_bwd_kernel  sampler_loss_bwd_kernel's (sample i, coordinate d) threads; inside its loop over j the frame's unit
@@ -15,66 +15,29 @@
 #include <cmath>
 
 #include "api_util.hpp"
+#include "sampler_body.hpp"
 
 constexpr int SO_LDS = 4096;   // floats of motion one agent may stage (K D), as sampler_loss_kernel
 static inline unsigned so_lds_bytes(int K, int D) { return 4u * (unsigned)(K * D + D + D / 2); }   // K >= 2: at most 4 (4096 + 2048 + 1024)
-
-static __device__ inline float so_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-static __device__ inline double so_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// motion of agent a -> sM [K][D], ground truth -> sY [D], mask -> sW [Tf] (ones without a mask)
-static __device__ inline void so_stage(const float* __restrict__ motion, const float* __restrict__ gt, const float* __restrict__ mask,
-                                       int a, int K, int D, int lane, float* sM, float* sY, float* sW) {
-    for (int i = lane; i < K * D; i += 64) sM[i] = motion[(size_t)a * K * D + i];
-    for (int i = lane; i < D; i += 64) sY[i] = gt[(size_t)a * D + i];
-    for (int i = lane; i < D / 2; i += 64) sW[i] = mask ? mask[(size_t)a * (D / 2) + i] : 1.f;
-    __syncthreads();
-}
 
 // Ground-truth half.  Sample k belongs to lane k mod 64; per sample, frames in frame order, float64:
 //   rec_k = sum_t (m_t (x_k,t - y_t))^2, and the displacements |m_t (x_k,t - y_t)| summed over the frames (ga) and at the last one (gl).
 // -> the smallest rec_k and the smallest index that has it (every lane holds both); ga, gl summed over the lane's samples.
 static __device__ inline void so_gt_half(const float* sM, const float* sY, const float* sW, int K, int D, int lane, double& rec, int& best,
                                          double& ga, double& gl) {
-    const int Tf = D / 2;
     double bv = INFINITY;
     int bi = INT_MAX;
     ga = gl = 0.0;
     for (int k = lane; k < K; k += 64) {
-        double r2 = 0.0, last = 0.0;
-        for (int t = 0; t < Tf; ++t) {
-            const double m = (double)sW[t];
-            const double ex = m * ((double)sM[k * D + 2 * t] - (double)sY[2 * t]);
-            const double ey = m * ((double)sM[k * D + 2 * t + 1] - (double)sY[2 * t + 1]);
-            const double d2 = ex * ex + ey * ey;
-            r2 += d2;
-            last = sqrt(d2);
-            ga += last;
-        }
+        double last = 0.0;
+        const double r2 = sampler_gt_sample(sM, sY, sW, k, D, ga, last);
         gl += last;
         if (r2 < bv) {
             bv = r2;
             bi = k;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (ov < bv || (ov == bv && oi < bi)) {
-            bv = ov;
-            bi = oi;
-        }
-    }
+    wave_take_lower(bv, bi);
     if (bi >= K) {   // no sample compared below +inf (NaN inputs)
         bi = 0;
         bv = NAN;
@@ -94,26 +57,15 @@ __global__ __launch_bounds__(64) void sampler_objective_kernel(const float* __re
     float *sM = so_lds, *sY = sM + K * D, *sW = sY + D;
     const int a = blockIdx.x, lane = threadIdx.x;
     const int Tf = D / 2;
-    // KL(q || p): sampler_loss_kernel's loop
-    float kl = 0.f;
-    const size_t base = (size_t)a * K * nz;
-    for (int i = lane; i < K * nz; i += 64) {
-        const float m = mu[base + i], sg = expf(0.5f * logvar[base + i]);
-        const float pm = pmu ? pmu[base + i] : 0.f;
-        const float ps = (plogvar ? expf(0.5f * plogvar[base + i]) : 1.f) + 1e-8f;
-        const float t1 = (m - pm) / ps, t2 = sg / ps;
-        kl += 0.5f * (t1 * t1 + t2 * t2) - 0.5f - logf(t2);
-    }
-    kl = so_wave_sum(kl);
-    so_stage(motion, gt, mask, a, K, D, lane, sM, sY, sW);
+    const float kl = sampler_kld(mu, logvar, pmu, plogvar, a, K, nz, lane);
+    sampler_stage(motion, gt, mask, a, K, D, lane, 64, sM, sY, sW);
     // pairs (i < j) in F.pdist order, pair p on lane p mod 64 as in sampler_loss_kernel; s takes x then y of every frame, in frame order
     const int np = K * (K - 1) / 2;
     float acc = 0.f;
     double pa = 0.0, pf = 0.0;   // over the lane's pairs: the per-frame norms summed over the frames, and the last frame's
     for (int p = lane; p < np; p += 64) {
-        int i = 0, r = p;
-        while (r >= K - 1 - i) { r -= K - 1 - i; ++i; }
-        const int j = i + 1 + r;
+        int i, j;
+        pdist_pair(p, K, i, j);
         float s = 0.f, last = 0.f;
         for (int t = 0; t < Tf; ++t) {
             // (fmaf spelled out: sampler_loss_kernel's `s += t * t` compiles to one fused multiply-add per coordinate, and the bits must agree)
@@ -129,14 +81,14 @@ __global__ __launch_bounds__(64) void sampler_objective_kernel(const float* __re
         const float dist = sqrtf(s);
         acc += expf(-(dist * dist) / scale);
     }
-    acc = so_wave_sum(acc);
-    pa = so_wave_sum(pa);
-    pf = so_wave_sum(pf);
+    acc = wave_sum(acc);
+    pa = wave_sum(pa);
+    pf = wave_sum(pf);
     double rv, ga, gl;
     int bi;
     so_gt_half(sM, sY, sW, K, D, lane, rv, bi, ga, gl);
-    ga = so_wave_sum(ga);
-    gl = so_wave_sum(gl);
+    ga = wave_sum(ga);
+    gl = wave_sum(gl);
     if (lane == 0) {
         kld[a] = kl;
         div[a] = acc / (float)np;
@@ -171,7 +123,7 @@ __global__ __launch_bounds__(64) void sampler_objective_bwd_kernel(const float* 
         dmu[base + i] = gk * t1 / ps;
         dlogvar[base + i] = gk * 0.5f * (t2 * t2 - 1.0f);
     }
-    so_stage(motion, gt, mask, a, K, D, lane, sM, sY, sW);
+    sampler_stage(motion, gt, mask, a, K, D, lane, 64, sM, sY, sW);
     double rv, ga, gl;
     int bi;
     so_gt_half(sM, sY, sW, K, D, lane, rv, bi, ga, gl);   // the forward's choice of the best sample, by the forward's code
@@ -212,7 +164,6 @@ __global__ __launch_bounds__(64) void sampler_objective_bwd_kernel(const float* 
 
 static int so_check(const char* who, const void* mu, const void* logvar, const void* motion, const void* gt, bool outs, int n, int K, int nz,
                     int D, float scale) {
-    char b[160];
     const char* why = nullptr;
     if (!(mu && logvar && motion && gt && outs)) why = "null pointer (mu, logvar, motion, gt and every output are required)";
     else if (!(n > 0 && nz > 0 && D > 0)) why = "n, nz, D must be positive";
@@ -220,10 +171,7 @@ static int so_check(const char* who, const void* mu, const void* logvar, const v
     else if (D % 2 != 0) why = "D must be even (D = 2 Tf)";
     else if ((long)K * D > SO_LDS) why = "K * D must be <= 4096";
     else if (!(scale > 0.f)) why = "scale must be positive";
-    if (!why) return 0;
-    snprintf(b, sizeof(b), "%s: %s", who, why);
-    stt_set_error(b);
-    return 1;
+    return why ? stt_refuse(who, why) : 0;
 }
 
 extern "C" int sttode_sampler_objective(const float* mu, const float* logvar, const float* pmu, const float* plogvar, const float* motion,

@@ -2,21 +2,17 @@
 // with raw weights w_k (cluster counts or probabilities, sttode_reduce_samples' `counts` / M), p_k = w_k / sum w.  Expected ADE / FDE, the
 // energy scores and the expected pairwise distances under p, the KDE NLL of scipy.stats.gaussian_kde(weights=), the probability-ranked
 // best-of-k rows, the Brier-penalised minimum and the effective sample size, in one launch.  The reference computes none of them.
-//   weighted_set_kernel  one workgroup of 256 threads per agent, the layout of sample_spread_kernel (metrics.hip): raw float2 samples through
-//                        LDS in tiles of WS_FT frames with an odd row stride; the pairs in F.pdist order on threads p mod 256; wave 2 with
+//   weighted_set_kernel  one workgroup of 256 threads per agent, the layout of sample_spread_kernel (the tile pieces of set_body.hpp): raw float2 samples through
+//                        LDS in tiles of SET_FT frames with an odd row stride; the pairs in F.pdist order on threads p mod 256; wave 2 with
 //                        lane = sample for the distances to the ground truth and the rank; wave 3 with lane = frame for the KDE frames.
 // No atomics: every sum has a fixed order, so two runs give the same bits and an agent's values do not depend on the rest of the batch.
 #include <cmath>
 
 #include "api_util.hpp"
-#include "frontend_body.hpp"
+#include "set_body.hpp"
 #include "../../include/sttode_hip.h"
 
 namespace {
-
-constexpr int WS_FT = 32;             // frames per LDS tile
-constexpr int WS_STRIDE = WS_FT + 1;  // row stride in float2: odd, so that lanes on different samples at one frame fall on different banks
-constexpr int WS_K1 = 23;             // the largest K with one pair per thread at most: 23 * 22 / 2 = 253 <= 256
 
 // Lane q's value of v in every lane; q must be the same in all lanes.
 __device__ __forceinline__ double lane_value(double v, int q) {
@@ -42,8 +38,8 @@ __device__ __forceinline__ double lane_value(double v, int q) {
 // two passes (max, then the sum of exp), minus log det(2 pi Sigma) / 2, clipped below at -20; the tile's frames by the xor tree, tiles in
 // order; nll = -sum / Tf.  C00 <= 0 or det C <= 0 at some frame: NaN (kde_nll_kernel's rule).  The positive-weight samples (k, p_k, log p_k)
 // are compacted by wave 0 and kept by wave 3 in registers, entry q in lane q, read by v_readlane inside the loops over q.
-// R = pairs per thread, KM = the largest K, as sample_spread_kernel: <8, 64> takes any K, <1, WS_K1> is the same code for K <= 23.
-// The workgroup waits on its KDE wave, so the time of a launch is set by how many workgroups a CU holds: <1, WS_K1> is built for 6 waves
+// R = pairs per thread, KM = the largest K, as sample_spread_kernel: <8, 64> takes any K, <1, SET_K1> is the same code for K <= 23.
+// The workgroup waits on its KDE wave, so the time of a launch is set by how many workgroups a CU holds: <1, SET_K1> is built for 6 waves
 // per SIMD (80 VGPRs, 68 bytes of scratch per lane; measured against 4 waves without scratch and 8 with 136 bytes: DESIGN.md 7).
 template <int R, int KM>
 __global__ __launch_bounds__(256, R == 1 ? 6 : 2) void weighted_set_kernel(const float* __restrict__ pred, const float* __restrict__ weights,
@@ -52,8 +48,8 @@ __global__ __launch_bounds__(256, R == 1 ? 6 : 2) void weighted_set_kernel(const
                                                            double* __restrict__ apd, double* __restrict__ fpd, double* __restrict__ kde,
                                                            double* __restrict__ brier_ade, double* __restrict__ brier_fde,
                                                            double* __restrict__ neff, float* __restrict__ ade_top, float* __restrict__ fde_top) {
-    __shared__ float2 sx[KM * WS_STRIDE];
-    __shared__ float2 sg[WS_FT];
+    __shared__ float2 sx[KM * SET_STRIDE];
+    __shared__ float2 sg[SET_FT];
     __shared__ double red[3][256];
     __shared__ double sp[64];                    // p_k (0 beyond K)
     __shared__ double cp[64], clp[64];           // the samples with w_k > 0, compacted in sample order: p_k and log p_k
@@ -98,11 +94,7 @@ __global__ __launch_bounds__(256, R == 1 ? 6 : 2) void weighted_set_kernel(const
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         int q = tid + 256 * r, i = 0;
-        if (q < P)
-            while (q >= K - 1 - i) {
-                q -= K - 1 - i;
-                ++i;
-            }
+        if (q < P) i = pdist_row(q, K);
         ij[r] = i | (i + 1 + q) << 8;
         s2[r] = s1[r] = dl[r] = 0.0;
     }
@@ -123,41 +115,16 @@ __global__ __launch_bounds__(256, R == 1 ? 6 : 2) void weighted_set_kernel(const
     bool sing = false;
     // wave 3 keeps the compacted samples in registers, entry q in lane q: a loop over q reads them by v_readlane (q is uniform), so that no
     // LDS address of its loops waits on an LDS read
-    const int rix = cix[lane] * WS_STRIDE;
+    const int rix = cix[lane] * SET_STRIDE;
     const double rp = cp[lane], rlp = clp[lane];
-    for (int t0 = 0; t0 < Tf; t0 += WS_FT) {
-        const int ft = min(WS_FT, Tf - t0);
-        for (int i = tid; i < K * ft; i += 256) {
-            const int k = i / ft, tl = i - k * ft;
-            sx[k * WS_STRIDE + tl] = p[(size_t)k * Tf + t0 + tl];
-        }
-        if (tid < ft) sg[tid] = g[t0 + tid];
+    for (int t0 = 0; t0 < Tf; t0 += SET_FT) {
+        const int ft = min(SET_FT, Tf - t0);
+        stage_tile<size_t>(sx, sg, p, g, K, Tf, t0, ft, tid);
         __syncthreads();
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-            if (live >> r & 1) {
-                const float2* xi = sx + (ij[r] & 255) * WS_STRIDE;
-                const float2* xj = sx + (ij[r] >> 8) * WS_STRIDE;
-                for (int tl = 0; tl < ft; ++tl) {
-                    const float2 u = xi[tl], v = xj[tl];
-                    const double dx = (double)(u.x * scale) - (double)(v.x * scale), dy = (double)(u.y * scale) - (double)(v.y * scale);
-                    const double d2 = dx * dx + dy * dy;
-                    dl[r] = sqrt(d2);
-                    s2[r] += d2;
-                    s1[r] += dl[r];
-                }
-            }
-        }
-        if (gw) {
-            for (int tl = 0; tl < ft; ++tl) {
-                const float2 v = sx[lane * WS_STRIDE + tl], y = sg[tl];
-                const double dx = (double)(v.x * scale) - (double)(y.x * scale), dy = (double)(v.y * scale) - (double)(y.y * scale);
-                gl = sqrt(dx * dx + dy * dy);
-                ga += gl;
-                fl = bok_dist(v.x, v.y, y.x, y.y, scale);
-                fa += fl;
-            }
-        }
+        for (int r = 0; r < R; ++r)
+            if (live >> r & 1) pair_tile_accumulate(sx, ij[r], ft, scale, s2[r], s1[r], dl[r]);
+        if (gw) gt_tile_accumulate(sx, sg, lane, ft, scale, ga, gl, fa, fl);
         if (kw) {
             // every lane runs every loop (the lane reads need all lanes active); a lane beyond the tile redoes its last frame and drops the
             // value, as a lane whose frame is singular does
@@ -181,31 +148,25 @@ __global__ __launch_bounds__(256, R == 1 ? 6 : 2) void weighted_set_kernel(const
             c00 /= om;
             c01 /= om;
             c11 /= om;
-            const double det = c00 * c11 - c01 * c01;
-            const bool pd = c00 > 0.0 && det > 0.0;
             const float2 y = sg[tl];
             const double gx = (double)(y.x * scale), gy = (double)(y.y * scale);
-            const double inv = 1.0 / (f2 * det);   // Sigma^-1 = [[c11, -c01], [-c01, c00]] / (f^2 det C)
+            double det, inv;
+            const bool pd = kde_cov(c00, c01, c11, f2, det, inv);
             double m = -INFINITY;
             for (int q = 0; q < npos; ++q) {
                 const float2 v = sx[__builtin_amdgcn_readlane(rix, q) + tl];
                 const double dx = gx - (double)(v.x * scale), dy = gy - (double)(v.y * scale);
-                m = fmax(m, lane_value(rlp, q) - 0.5 * ((c11 * dx * dx - 2.0 * c01 * dx * dy + c00 * dy * dy) * inv));
+                m = fmax(m, lane_value(rlp, q) - 0.5 * kde_quad(c00, c01, c11, inv, dx, dy));
             }
             double sum = 0.0;
             for (int q = 0; q < npos; ++q) {
                 const float2 v = sx[__builtin_amdgcn_readlane(rix, q) + tl];
                 const double dx = gx - (double)(v.x * scale), dy = gy - (double)(v.y * scale);
-                sum += exp(lane_value(rlp, q) - 0.5 * ((c11 * dx * dx - 2.0 * c01 * dx * dy + c00 * dy * dy) * inv) - m);
+                sum += exp(lane_value(rlp, q) - 0.5 * kde_quad(c00, c01, c11, inv, dx, dy) - m);
             }
-            const double tf2 = 6.283185307179586 * f2;   // det(2 pi Sigma) = (2 pi f^2)^2 det C
-            double lp = log(sum) + m - 0.5 * log(tf2 * tf2 * det);
-            lp = lp < -20.0 ? -20.0 : lp;
-            lp = lane < ft && pd ? lp : 0.0;
+            const double lp = kde_clip(log(sum) + m - kde_log_norm(f2, det));
             sing |= lane < ft && !pd;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) lp += __shfl_xor(lp, o, 64);
-            acc += lp;
+            acc += wave_sum(lane < ft && pd ? lp : 0.0);
         }
         __syncthreads();   // (the next tile overwrites sx and sg)
     }
@@ -224,12 +185,7 @@ __global__ __launch_bounds__(256, R == 1 ? 6 : 2) void weighted_set_kernel(const
     red[2][tid] = t_t;
     if (w == 2) {
         const double pk = sp[lane];
-        double da = gw ? pk * (ga / Tf) : 0.0, df = gw ? pk * gl : 0.0;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            da += __shfl_xor(da, o, 64);
-            df += __shfl_xor(df, o, 64);
-        }
+        const double da = wave_sum(gw ? pk * (ga / Tf) : 0.0), df = wave_sum(gw ? pk * gl : 0.0);
         if (lane == 0) {
             sc[1] = da;
             sc[2] = df;
@@ -248,19 +204,7 @@ __global__ __launch_bounds__(256, R == 1 ? 6 : 2) void weighted_set_kernel(const
             sf[rank] = kf;
         }
         __builtin_amdgcn_wave_barrier();
-        float va = sa[lane], vf = sf[lane];
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const float ua = __shfl_up(va, o, 64), uf = __shfl_up(vf, o, 64);
-            if (lane >= o) {
-                va = fminf(va, ua);
-                vf = fminf(vf, uf);
-            }
-        }
-        if (lane < 63) {                         // (sample_spread_kernel's rule: a prefix that is all NaN gives +inf below 64 samples)
-            va = fminf(va, INFINITY);
-            vf = fminf(vf, INFINITY);
-        }
+        const float va = prefix_fmin64(sa[lane], lane), vf = prefix_fmin64(sf[lane], lane);
         if (lane < K) {
             if (ade_top) ade_top[(size_t)a * K + lane] = bad_row ? NAN : va;
             if (fde_top) fde_top[(size_t)a * K + lane] = bad_row ? NAN : vf;
@@ -282,10 +226,9 @@ __global__ __launch_bounds__(256, R == 1 ? 6 : 2) void weighted_set_kernel(const
     if (w != 0) return;
     double v[3];
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
+    for (int q = 0; q < 3; ++q) {   // (quad_then_wave_sum's order, spelled out: through the helper the <1, 23> form's scratch size moves)
         v[q] = ((red[q][lane] + red[q][lane + 64]) + red[q][lane + 128]) + red[q][lane + 192];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v[q] += __shfl_xor(v[q], o, 64);
+        v[q] = wave_sum(v[q]);
     }
     if (lane == 0) {
         const double nan = (double)NAN;
@@ -309,7 +252,6 @@ __global__ __launch_bounds__(256, R == 1 ? 6 : 2) void weighted_set_kernel(const
 static int weighted_check(const char* who, const float* pred, const float* weights, const float* gt, int n, int K, int Tf, const double* eade,
                           const double* efde, const double* es_ade, const double* es_fde, const double* apd, const double* fpd,
                           const double* neff) {
-    char b[256];
     const char* why = nullptr;
     if (!(pred && weights && gt))
         why = "null pointer (pred, weights and gt are required)";
@@ -319,18 +261,15 @@ static int weighted_check(const char* who, const float* pred, const float* weigh
         why = "n and Tf must be positive";
     else if (K < 1 || K > 64)
         why = "needs 1 <= K <= 64 (one lane per sample)";
-    if (!why) return 0;
-    snprintf(b, sizeof(b), "%s: %s", who, why);
-    stt_set_error(b);
-    return 1;
+    return why ? stt_refuse(who, why) : 0;
 }
 
 extern "C" int sttode_weighted_set(const float* pred, const float* weights, const float* gt, int n, int K, int Tf, float scale, double* eade,
                                    double* efde, double* es_ade, double* es_fde, double* apd, double* fpd, double* kde_nll, double* brier_ade,
                                    double* brier_fde, double* neff, float* ade_top, float* fde_top, void* stream) {
     if (weighted_check("sttode_weighted_set", pred, weights, gt, n, K, Tf, eade, efde, es_ade, es_fde, apd, fpd, neff)) return 1;
-    if (K <= WS_K1)
-        hipLaunchKernelGGL((weighted_set_kernel<1, WS_K1>), dim3(n), dim3(256), 0, (hipStream_t)stream, pred, weights, gt, K, Tf, scale, eade,
+    if (K <= SET_K1)
+        hipLaunchKernelGGL((weighted_set_kernel<1, SET_K1>), dim3(n), dim3(256), 0, (hipStream_t)stream, pred, weights, gt, K, Tf, scale, eade,
                            efde, es_ade, es_fde, apd, fpd, kde_nll, brier_ade, brier_fde, neff, ade_top, fde_top);
     else
         hipLaunchKernelGGL((weighted_set_kernel<8, 64>), dim3(n), dim3(256), 0, (hipStream_t)stream, pred, weights, gt, K, Tf, scale, eade, efde,

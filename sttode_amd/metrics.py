@@ -413,22 +413,22 @@ class Reduction:
 REDUCE_INIT = {'first': 0, 'maximin': 1}
 
 
-@torch.no_grad()
-def reduce_samples(pred, K, iters=10, from_frame=0, init='first'):
-    """Lloyd k-means of every agent's M sampled futures to K representatives, on the current stream (include/sttode_hip.h
-    sttode_reduce_samples states the iteration).  ``pred``: [n, M, Tf, 2], or [R, n, K_in, Tf, 2] -- R stacked outputs of inference,
-    M = R K_in, sample m = r K_in + k.  ``from_frame``: the first frame the distances look at (0: whole trajectories; -1: endpoints; negative
-    values count from the end); the representatives are full mean trajectories either way.  ``init``: 'first' (samples 0 .. K-1), 'maximin'
-    (farthest-point, deterministic) or a tensor [n, K, Tf, 2].  K <= 64, K <= M <= 4096.  Returns a ``Reduction``."""
+def _need_device(pred, what):
     if not (isinstance(pred, torch.Tensor) and pred.is_cuda):
-        raise capi.SttodeError('sample reduction runs on a HIP device only (no CPU fallback): pass device tensors')
+        raise capi.SttodeError(f'{what} runs on a HIP device only (no CPU fallback): pass device tensors')
+
+
+def _round_major(pred):
+    """``pred`` as [R, n, K_in, Tf, 2]: [n, M, Tf, 2] is R = 1."""
     if pred.dim() == 4:
         pred = pred.unsqueeze(0)
     if pred.dim() != 5 or pred.shape[4] != 2 or 0 in pred.shape:
         raise ValueError(f'pred must be [n, M, Tf, 2] or [R, n, K_in, Tf, 2] with no empty dimension, got {tuple(pred.shape)}')
-    dev = pred.device
-    pred = pred.to(torch.float32).contiguous()
-    R, n, K_in, Tf = pred.shape[:4]
+    return pred
+
+
+def _reduce_args(K, iters, from_frame, init, n, M, Tf, dev, what):
+    """(K, iters, first frame in [0, Tf), init mode, init tensor or None) of the two reductions after their checks."""
     K, iters, from_frame = int(K), int(iters), int(from_frame)
     if not -Tf <= from_frame < Tf:
         raise ValueError(f'from_frame must be in [-{Tf}, {Tf}), got {from_frame}')
@@ -440,12 +440,27 @@ def reduce_samples(pred, K, iters=10, from_frame=0, init='first'):
         mode, init_t = 2, torch.as_tensor(init, dtype=torch.float32).to(dev).contiguous()
         if tuple(init_t.shape) != (n, K, Tf, 2):
             raise ValueError(f'init must be [{n}, {K}, {Tf}, 2], got {tuple(init_t.shape)}')
-    if not 1 <= K <= 64 or not K <= R * K_in <= 4096:
-        raise ValueError(f'sample reduction needs 1 <= K <= 64 and K <= M <= 4096, got K = {K}, M = {R * K_in}')
+    if not 1 <= K <= 64 or not K <= M <= 4096:
+        raise ValueError(f'{what} needs 1 <= K <= 64 and K <= M <= 4096, got K = {K}, M = {M}')
+    return K, iters, from_frame % Tf, mode, init_t
+
+
+@torch.no_grad()
+def reduce_samples(pred, K, iters=10, from_frame=0, init='first'):
+    """Lloyd k-means of every agent's M sampled futures to K representatives, on the current stream (include/sttode_hip.h
+    sttode_reduce_samples states the iteration).  ``pred``: [n, M, Tf, 2], or [R, n, K_in, Tf, 2] -- R stacked outputs of inference,
+    M = R K_in, sample m = r K_in + k.  ``from_frame``: the first frame the distances look at (0: whole trajectories; -1: endpoints; negative
+    values count from the end); the representatives are full mean trajectories either way.  ``init``: 'first' (samples 0 .. K-1), 'maximin'
+    (farthest-point, deterministic) or a tensor [n, K, Tf, 2].  K <= 64, K <= M <= 4096.  Returns a ``Reduction``."""
+    _need_device(pred, 'sample reduction')
+    pred = _round_major(pred).to(torch.float32).contiguous()
+    dev = pred.device
+    R, n, K_in, Tf = pred.shape[:4]
+    K, iters, f0, mode, init_t = _reduce_args(K, iters, from_frame, init, n, R * K_in, Tf, dev, 'sample reduction')
     out = Reduction(n, R * K_in, K, Tf, dev)
     with torch.cuda.device(dev):
-        capi.call('sttode_reduce_samples', pred, n, R, K_in, Tf, K, iters, from_frame % Tf, mode, init_t, out.centroids, out.labels,
-                  out.counts, capi.stream_ptr())
+        capi.call('sttode_reduce_samples', pred, n, R, K_in, Tf, K, iters, f0, mode, init_t, out.centroids, out.labels, out.counts,
+                  capi.stream_ptr())
     return out
 
 
@@ -492,16 +507,11 @@ def reduce_scenes(pred, seg_ptr=None, K=None, iters=10, from_frame=0, init='firs
     run non-decreasing from 0 to n), or ``seg_len=N``: uniform segments of N agents (NBA games).  ``iters``, ``from_frame``, ``init`` as
     ``reduce_samples`` ('maximin' picks whole scene futures).  K <= 64, K <= M <= 4096; a segment may be all n agents.  Returns a
     ``SceneReduction``."""
-    if not (isinstance(pred, torch.Tensor) and pred.is_cuda):
-        raise capi.SttodeError('scene reduction runs on a HIP device only (no CPU fallback): pass device tensors')
+    _need_device(pred, 'scene reduction')
     if K is None:
         raise ValueError('scene reduction needs K, the number of representatives')
-    if pred.dim() == 4:
-        pred = pred.unsqueeze(0)
-    if pred.dim() != 5 or pred.shape[4] != 2 or 0 in pred.shape:
-        raise ValueError(f'pred must be [n, M, Tf, 2] or [R, n, K_in, Tf, 2] with no empty dimension, got {tuple(pred.shape)}')
+    pred = _round_major(pred).to(torch.float32).contiguous()
     dev = pred.device
-    pred = pred.to(torch.float32).contiguous()
     R, n, K_in, Tf = pred.shape[:4]
     if (seg_ptr is None) == (seg_len is None):
         raise ValueError('scene reduction needs seg_ptr [S+1] or seg_len=N (uniform segments), one of them')
@@ -514,25 +524,13 @@ def reduce_scenes(pred, seg_ptr=None, K=None, iters=10, from_frame=0, init='firs
         check_seg_ptr(seg_ptr, n)
     sp = seg_ptr_tensor(seg_ptr, dev)
     S = int(sp.numel()) - 1
-    K, iters, from_frame = int(K), int(iters), int(from_frame)
-    if not -Tf <= from_frame < Tf:
-        raise ValueError(f'from_frame must be in [-{Tf}, {Tf}), got {from_frame}')
-    if isinstance(init, str):
-        if init not in REDUCE_INIT:
-            raise ValueError(f"init must be 'first', 'maximin' or a tensor [n, K, Tf, 2], got {init!r}")
-        mode, init_t = REDUCE_INIT[init], None
-    else:
-        mode, init_t = 2, torch.as_tensor(init, dtype=torch.float32).to(dev).contiguous()
-        if tuple(init_t.shape) != (n, K, Tf, 2):
-            raise ValueError(f'init must be [{n}, {K}, {Tf}, 2], got {tuple(init_t.shape)}')
-    if not 1 <= K <= 64 or not K <= R * K_in <= 4096:
-        raise ValueError(f'scene reduction needs 1 <= K <= 64 and K <= M <= 4096, got K = {K}, M = {R * K_in}')
+    K, iters, f0, mode, init_t = _reduce_args(K, iters, from_frame, init, n, R * K_in, Tf, dev, 'scene reduction')
     if not 1 <= iters <= 1000:
         raise ValueError(f'iters must be in [1, 1000], got {iters}')
     out = SceneReduction(n, S, R * K_in, K, Tf, dev, sp)
     with torch.cuda.device(dev):
-        capi.call('sttode_reduce_scenes', pred, n, R, K_in, Tf, K, iters, from_frame % Tf, mode, init_t, sp, S, out.centroids, out.labels,
-                  out.counts, capi.stream_ptr())
+        capi.call('sttode_reduce_scenes', pred, n, R, K_in, Tf, K, iters, f0, mode, init_t, sp, S, out.centroids, out.labels, out.counts,
+                  capi.stream_ptr())
     return out
 
 
@@ -614,12 +612,8 @@ class SampleScores:
 
 def _large_inputs(pred, gt, what, need_gt=True, m_min=1):
     """(pred [R, n, K_in, Tf, 2] -- the caller's memory when it is contiguous float32 --, gt, R, n, K_in, Tf) after the entries' checks."""
-    if not (isinstance(pred, torch.Tensor) and pred.is_cuda):
-        raise capi.SttodeError(f'{what} runs on a HIP device only (no CPU fallback): pass device tensors')
-    if pred.dim() == 4:
-        pred = pred.unsqueeze(0)
-    if pred.dim() != 5 or pred.shape[4] != 2 or 0 in pred.shape:
-        raise ValueError(f'pred must be [n, M, Tf, 2] or [R, n, K_in, Tf, 2] with no empty dimension, got {tuple(pred.shape)}')
+    _need_device(pred, what)
+    pred = _round_major(pred)
     if pred.dtype != torch.float32:
         raise ValueError(f'pred must be float32, got {pred.dtype}')
     R, n, K_in, Tf = pred.shape[:4]
