@@ -6,7 +6,10 @@ widths -- hidden_dim 64, zdim 32, two decompose blocks, 2 Tp <= 32, 2 Tf <= 96 -
 tiles.  A model constructed with anything else takes this form instead: the same HIP kernels the training step runs (csrc/train*.hip:
 sttode_tlinear MFMA GEMMs over the row-major nn.Parameter storage, conv / GRU-sequence / LayerNorm / geodesic-attention kernels templated
 on the model width), layer by layer, driven by sttode_amd.training.Engine.  Results are held to the imported reference at the same 1e-4
-(tests/golden/dims.npz); PERFORMANCE CAVEAT: one launch per layer and activations through HBM -- roughly the training forward's rate, far
+(tests/golden/dims.npz); the training step has its parity pinned at every width class accepted below -- the five values against the reference,
+every gradient against the oracle's float64 autograd: num_decompose 3, zdim 16, hidden_dim 32 / 128, future_length 28 in
+tests/test_gpu_parity.py, num_decompose 1 / 5, past_length 20, future_length 60 / 36, zdim 64 and the mixed case in
+tests/test_generic_training_gpu.py (tests/golden/dims_steps.npz).  PERFORMANCE CAVEAT: one launch per layer and activations through HBM -- roughly the training forward's rate, far
 from the fused forms' -- stated in DESIGN.md.  No CPU / eager fallback here either: every network evaluation is a HIP kernel.
 """
 import torch

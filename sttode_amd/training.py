@@ -325,7 +325,10 @@ class Engine:
 
     @contextlib.contextmanager
     def group(self):
-        """Independent layers issued inside leave as ONE launch (sttode_tgemm_group: up to four per launch, scene sizes and batch sizes)."""
+        """Independent layers issued inside leave as ONE launch (sttode_tgemm_group: up to four per launch, scene sizes and batch sizes).
+        What is issued inside is QUEUED with raw pointers and launched when the group closes (or its queue is full): every tensor handed to
+        a call inside must stay referenced until then, or the allocator may give its memory to the next tensor allocated inside the group
+        (tests/test_generic_training_gpu.py::test_operands_of_grouped_launches_outlive_their_group)."""
         capi.call('sttode_tgemm_group', 1)
         try:
             yield
@@ -748,9 +751,10 @@ class Engine:
         P, g = self.P, self.grad
         da, db_ = dout_a, dout_b
         for li, (sa, sb) in ((2, (saved_a[1], saved_b[1])), (1, (saved_a[0], saved_b[0]))):
-            with self.group():
-                da = self.lin_bwd(da, P[f'{pre_a}layers.{li}.weight'], sa, g(f'{pre_a}layers.{li}.weight'), g(f'{pre_a}layers.{li}.bias'), mask=sa)
-                db_ = self.lin_bwd(db_, P[f'{pre_b}layers.{li}.weight'], sb, g(f'{pre_b}layers.{li}.weight'), g(f'{pre_b}layers.{li}.bias'), mask=sb)
+            with self.group():                                      # (the layer's inputs keep their names until the group has left: see group())
+                da_in = self.lin_bwd(da, P[f'{pre_a}layers.{li}.weight'], sa, g(f'{pre_a}layers.{li}.weight'), g(f'{pre_a}layers.{li}.bias'), mask=sa)
+                db_in = self.lin_bwd(db_, P[f'{pre_b}layers.{li}.weight'], sb, g(f'{pre_b}layers.{li}.weight'), g(f'{pre_b}layers.{li}.bias'), mask=sb)
+            da, db_ = da_in, db_in
         self.lin_bwd(da, P[pre_a + 'layers.0.weight'], inp, g(pre_a + 'layers.0.weight'), g(pre_a + 'layers.0.bias'), out=din)
         self.lin_bwd(db_, P[pre_b + 'layers.0.weight'], inp, g(pre_b + 'layers.0.weight'), g(pre_b + 'layers.0.bias'), out=din, accumulate=True)
 
@@ -855,14 +859,15 @@ class Engine:
                 t = self.new(m, 2 * Tp)
                 self.ew(EW_SUM_CUR, t, xsum, b['xh'], None, i0=2 * Tp, f0=K)
                 xsum = t
+        # one block: the sums' second operands are zeros.  They are named HERE: a piece issued inside a group is only queued, so a temporary
+        # handed to it would be freed before the launch leaves, and `rec`, allocated next, got its memory -- the prediction then read the
+        # reconstruction being written by the same launch (seen on the first step of a process, when the allocator has nothing else to give)
+        y1, x1 = (blocks[-1]['yh'], blocks[-1]['xh']) if nb > 1 else (self.zeros(m, 2 * Tf), self.zeros(m, 2 * Tp) if want_recover else None)
         with self.group():                                          # two independent pieces: one launch
-            if nb > 1:
-                self.ew(EW_SUM_CUR, pred, ysum, blocks[-1]['yh'], cur, i0=2 * Tf, f0=K)
-            else:
-                self.ew(EW_SUM_CUR, pred, ysum, self.zeros(m, 2 * Tf), cur, i0=2 * Tf, f0=K)
+            self.ew(EW_SUM_CUR, pred, ysum, y1, cur, i0=2 * Tf, f0=K)
             if want_recover:
                 rec = self.new(m, 2 * Tp)
-                self.ew(EW_SUM_CUR, rec, xsum, blocks[-1]['xh'] if nb > 1 else self.zeros(m, 2 * Tp), None, i0=2 * Tp, f0=K)
+                self.ew(EW_SUM_CUR, rec, xsum, x1, None, i0=2 * Tp, f0=K)
         return dict(blocks=blocks, b0=blocks[0], b1=blocks[-1], n=n, K=K, m=m, pred=pred, rec=rec)
 
     def decoder_live(self, d, best):

@@ -220,10 +220,24 @@ DIMS_CASES = {
     'mix': dict(hidden_dim=32, zdim=16, num_decompose=3, Tp_eth=6, Tf_eth=9, Tp_nba=4, Tf_nba=7),
 }
 DIMS_GRAD_CASES = ('nd3', 'zd16', 'hd32', 'hd128', 'tf28')   # forward() losses + backward() digests as well
+# Cases of the training step only (tests/golden/dims_steps.npz, made by tests/golden/make_dims_steps_golden.py): NOT in DIMS_CASES, which
+# drives dims.npz, the C-API symbol test and the parametrised inference tests.  Their seed index continues after DIMS_CASES' last entry.
+DIMS_EXTRA_CASES = {
+    'nd5': dict(num_decompose=5),                # 41 tape tensors in decoder_live: a second sttode_live_rows_gather launch (32 per launch)
+}
+# forward() losses + backward() digests of the widths DIMS_GRAD_CASES leaves out, each for a branch of sttode_amd/training.py only it runs
+DIMS_STEP_CASES = ('nd1', 'tp20', 'tf60', 'zd64', 'tf36_tp8', 'mix', 'nd5')
+
+
+def _dims_case(tag):
+    """-> (the case's overrides, its index: what feeds the seeds of dims_case_inputs)."""
+    if tag in DIMS_CASES:
+        return DIMS_CASES[tag], list(DIMS_CASES).index(tag)
+    return DIMS_EXTRA_CASES[tag], len(DIMS_CASES) + list(DIMS_EXTRA_CASES).index(tag)
 
 
 def dims_case_args(tag, dataset):
-    c = DIMS_CASES[tag]
+    c = _dims_case(tag)[0]
     ds = 'nba' if dataset == 'nba' else 'eth'
     a = make_args(dataset, c.get('Tp_' + ds, 5 if ds == 'nba' else 8), c.get('Tf_' + ds, 10 if ds == 'nba' else 12))
     a.hidden_dim, a.zdim, a.num_decompose = c.get('hidden_dim', 64), c.get('zdim', 32), c.get('num_decompose', 2)
@@ -239,7 +253,7 @@ def dims_case_weights(a, seed=1234):
 def dims_case_inputs(tag, dataset):
     """-> (args, inputs, z, (eps_q, eps_p1, eps_p20)): inputs = (obs [N,2,Tp], pred [N,2,Tf]) for 'eth', the loader dict for 'nba'."""
     from sttode_amd import scenes
-    ci = list(DIMS_CASES).index(tag)
+    ci = _dims_case(tag)[1]
     a = dims_case_args(tag, dataset)
     Tp, Tf, zd = a.past_length, a.future_length, a.zdim
     rng = np.random.default_rng(4000 + 10 * ci + (dataset == 'nba'))

@@ -3292,59 +3292,72 @@ def test_non_default_hyperparameters_vs_reference_golden(golden, tag):
                 m.reset_async()
 
 
+def _dims_oracle_steps(a, dataset, inputs, eps):
+    """The oracle's step on one dims case in fp32 and in float64 -> {double: (name -> gradient | None, the five values)}."""
+    from test_oracle_golden import _oracle_step
+    return {dbl: _oracle_step(a, dataset, inputs, eps, dbl) for dbl in (False, True)}
+
+
+def _dims_grads_vs_float64(got, g32, g64, what):
+    """Every parameter gradient of a step at non-default widths (``got``: name -> tensor | None) against the float64 autograd of the oracle
+    (``g64``), measured by the fp32 autograd of the same graph (``g32``); the per-parameter table goes through _dump_grad_table.
+    -> (the number of parameters compared: those the float64 oracle gives a gradient, the worst err_hip / max|g64|)."""
+    checked, bad, rows = 0, [], []
+    for name, gr in got.items():
+        g64p = g64[name]
+        if g64p is None:
+            assert gr is None or not bool(gr.any()), name
+            continue
+        assert gr is not None, name
+        g64n = g64p.numpy()
+        err_hip = np.abs(gr.cpu().numpy().astype(np.float64) - g64n).max()
+        err_f32 = np.abs(g32[name].numpy().astype(np.float64) - g64n).max()
+        rows.append((name, err_hip, err_f32, float(np.abs(g64n).max()), err_hip / (float(np.abs(g64n).max()) + 1e-30)))
+        # float64 yardstick as in the default-width tests, with 6x instead of 2x the fp32 autograd's own error: at these widths the random-recipe
+        # weights give activations of 1e3 and block-1 inputs x_true - x_hat_0 that cancel, so the fp32 autograd itself is off by 2e-4 of
+        # max|g| on the blocks' conv / GRU gradients (profiles/r05/grad_tables/dims_*.txt) and two summation orders differ by a few times that
+        # (floor 5e-4 of max|g| for the same rows: they sit at 2e-4 .. 4.3e-4 whichever summation order the trunk takes)
+        if not err_hip <= max(6 * err_f32, 5e-4 * np.abs(g64n).max()) + 1e-12:
+            bad.append((name, err_hip, err_f32, float(np.abs(g64n).max())))
+        checked += 1
+    _dump_grad_table(what, None, text=''.join('%-80s err_hip %.3e  err_fp32_autograd %.3e  max|g| %.3e  rel %.2e\n' % row for row in rows))
+    assert not bad, (what, bad[:6])
+    assert checked == sum(v is not None for v in g64.values())
+    return checked, max(row[4] for row in rows)
+
+
+def _dims_training_step(m, dataset, inputs, eps, ref_losses, what, ora, no_grad_too=True):
+    """One forward() + backward() of ``m`` on a dims case: the five values against ``ref_losses`` at rtol 1e-4, every parameter gradient
+    against the oracle's float64 autograd (``ora`` = _dims_oracle_steps(...)), then the no-grad forward() against the same five values.
+    -> (the five values, name -> gradient, the number of parameters compared, the worst err_hip / max|g64|)."""
+    eq, ep, e20 = (torch.from_numpy(e) for e in eps)
+    _dims_set(m, dataset, inputs)
+    m.zero_grad()
+    vals = m.forward(eps_q=eq, eps_p=ep, eps20=e20)
+    losses = [float(vals[0].detach())] + list(vals[1:])
+    np.testing.assert_allclose(losses, ref_losses, rtol=1e-4)
+    vals[0].backward()
+    got = {name: (p.grad.detach().clone() if p.grad is not None else None) for name, p in m.named_parameters()}
+    checked, worst = _dims_grads_vs_float64(got, ora[False][0], ora[True][0], what)
+    if no_grad_too:                                               # no-grad forward(): the same values
+        with torch.no_grad():
+            _dims_set(m, dataset, inputs)
+            v2 = m.forward(eps_q=eq, eps_p=ep, eps20=e20)
+        np.testing.assert_allclose([float(v2[0])] + list(v2[1:]), ref_losses, rtol=1e-4)
+    return losses, got, checked, worst
+
+
 @pytest.mark.parametrize('tag', ['nd3', 'zd16', 'hd32', 'hd128', 'tf28'])
 def test_non_default_hyperparameters_training_step_vs_reference(golden, tag):
     """forward() + backward() with non-default --num_decompose / --zdim / --hidden_dim / --future_length: the five loss values against the
-    imported reference's, every parameter gradient against the float64 autograd of the oracle (the yardstick of the default-width tests)."""
-    from helpers import dims_case_inputs
-    from test_oracle_golden import _dims_set_data, _oracle_for
+    imported reference's, every parameter gradient against the float64 autograd of the oracle (the yardstick of the default-width tests).
+    (The other accepted widths: tests/test_generic_training_gpu.py, on the same comparison.)"""
     g = golden('dims')
     for dataset in ('eth', 'nba'):
-        m, a, inputs, z, (eq, ep, e20) = _dims_model(tag, dataset)
+        m, a, inputs, z, eps = _dims_model(tag, dataset)
         k = f'{tag}_{dataset}_'
-        _dims_set(m, dataset, inputs)
-        m.zero_grad()
-        vals = m.forward(eps_q=torch.from_numpy(eq), eps_p=torch.from_numpy(ep), eps20=torch.from_numpy(e20))
-        np.testing.assert_allclose([float(vals[0].detach())] + list(vals[1:]), g[k + 'losses'], rtol=1e-4)
-        vals[0].backward()
-        grads = {}
-        for dbl in (False, True):
-            mm = _oracle_for(a, dbl)
-            prev = torch.get_default_dtype()
-            torch.set_default_dtype(torch.float64 if dbl else torch.float32)
-            try:
-                _dims_set_data(mm, dataset, inputs, dbl)
-                cast = (lambda t: torch.from_numpy(t).double()) if dbl else torch.from_numpy
-                mm.forward_loss_tensors(cast(eq), cast(ep), cast(e20))[0].backward()
-            finally:
-                torch.set_default_dtype(prev)
-            grads[dbl] = {n_: (p_.grad.clone() if p_.grad is not None else None) for n_, p_ in mm.named_parameters()}
-        checked, bad, rows = 0, [], []
-        for name, p in m.named_parameters():
-            g64 = grads[True][name]
-            if g64 is None:
-                assert p.grad is None or not bool(p.grad.any()), name
-                continue
-            g64n = g64.numpy()
-            err_hip = np.abs(p.grad.cpu().numpy().astype(np.float64) - g64n).max()
-            err_f32 = np.abs(grads[False][name].numpy().astype(np.float64) - g64n).max()
-            rows.append((name, err_hip, err_f32, float(np.abs(g64n).max()), err_hip / (float(np.abs(g64n).max()) + 1e-30)))
-            # float64 yardstick as in the default-width tests, with 6x instead of 2x the fp32 autograd's own error: at these widths the random-recipe
-            # weights give activations of 1e3 and block-1 inputs x_true - x_hat_0 that cancel, so the fp32 autograd itself is off by 2e-4 of
-            # max|g| on the blocks' conv / GRU gradients (profiles/r05/grad_tables/dims_*.txt) and two summation orders differ by a few times that
-            # (floor 5e-4 of max|g| for the same rows: they sit at 2e-4 .. 4.3e-4 whichever summation order the trunk takes)
-            if not err_hip <= max(6 * err_f32, 5e-4 * np.abs(g64n).max()) + 1e-12:
-                bad.append((name, err_hip, err_f32, float(np.abs(g64n).max())))
-            checked += 1
-        _dump_grad_table(f'dims_{k}', None, text=''.join('%-80s err_hip %.3e  err_fp32_autograd %.3e  max|g| %.3e  rel %.2e\n' % row
-                                                            for row in rows))
-        assert not bad, (k, [b_[0] for b_ in bad])
+        checked = _dims_training_step(m, dataset, inputs, eps, g[k + 'losses'], f'dims_{k}', _dims_oracle_steps(a, dataset, inputs, eps))[2]
         assert checked > 80
-        # no-grad forward(): the same values
-        with torch.no_grad():
-            _dims_set(m, dataset, inputs)
-            v2 = m.forward(eps_q=torch.from_numpy(eq), eps_p=torch.from_numpy(ep), eps20=torch.from_numpy(e20))
-        np.testing.assert_allclose([float(v2[0])] + list(v2[1:]), g[k + 'losses'], rtol=1e-4)
 
 
 def test_generic_form_staged_api_and_evaluation_loops():
