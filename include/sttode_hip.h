@@ -185,7 +185,9 @@ int sttode_chain_prog_len(int Tp, int Tf);
 int sttode_gru_cols32(const float* xin, int ldx, const float* pool, const int* prog, int prog_len, const float* consts, float* state,
                       int ncols, int Tp, void* stream);
 
-/* compute_ADE / compute_FDE per agent (utils/metrics.py:7-26): pred [n,K,Tf,2], gt [n,Tf,2] -> ade [n], fde [n]. */
+/* compute_ADE / compute_FDE per agent (utils/metrics.py:7-26): pred [n,K,Tf,2], gt [n,Tf,2] -> ade [n], fde [n]; any K >= 1.
+ * Non-finite samples: a sample whose mean (final) displacement is NaN is skipped by the minimum (fminf); an agent whose samples are all
+ * NaN gets +inf, at any K. */
 int sttode_best_of_k(const float* pred, const float* gt, int n, int K, int Tf, float scale, float* ade, float* fde, void* stream);
 /* The NBA evaluation's per-horizon metric (test.py:530-551): pred [n,K,Tf,2], gt [n,Tf,2] -> out [n,Tf,2]: for agent a and horizon h (frame
  * h - 1) out[a][h-1] = (min_k mean_{t < h} |scale (pred - gt)|, min_k |scale (pred_h - gt_h)|); the caller averages over agents and weighs by
@@ -193,11 +195,17 @@ int sttode_best_of_k(const float* pred, const float* gt, int n, int K, int Tf, f
 int sttode_horizon_metrics(const float* pred, const float* gt, int n, int K, int Tf, float scale, float* out, void* stream);
 /* Best-of-K selection per agent and per segment: compute_ADE / compute_FDE (utils/metrics.py:7-26), get_best_idx (:29-36) and
  * count_miss_samples (:39-48), the per-agent loop of test.py:193-205 (its ade per scene: :201-205).  pred [n,K,Tf,2], gt [n,Tf,2], K <= 64
- * (refused above that, nothing written).  Per agent: ade [n], fde [n] (the bits of sttode_best_of_k); best_ade_idx / best_fde_idx [n] = argmin
+ * (refused above that, nothing written).  Per agent: ade [n], fde [n] (the bits of sttode_best_of_k for every agent with at least one
+ * finite sample); best_ade_idx / best_fde_idx [n] = argmin
  * over k of the mean / final displacement, the lowest k on exact ties (np.argmin); miss [n] = fde > miss_threshold (1 / 0, strictly);
  * best [n,Tf,2] = pred[a, best_ade_idx[a]] (copied, unscaled).  Per segment s of the CSR seg_ptr [S+1] (scene_ptr; B segments of N for NBA):
  * seg_ade / seg_fde [S] = mean over agents seg_ptr[s] .. seg_ptr[s+1]-1, seg_miss [S] = their miss count, summed in a fixed order (no
- * atomics: the same bits on every run).  Every output but ade / fde may be NULL; seg_ptr may be NULL (S = 0) when no segment output is asked. */
+ * atomics: the same bits on every run); segment bounds are clamped to [0, n] with the end no lower than the start, and an empty segment
+ * gets NaN means and a zero count.  Every output but ade / fde may be NULL; seg_ptr may be NULL (S = 0) when no segment output is asked.
+ * Non-finite samples: a NaN sample is skipped, as in sttode_best_of_k, and never chosen.  An agent whose samples are all NaN gets index 0
+ * for both indices, best = its sample 0 (the gather stays inside the agent), and ade / fde = +inf at K < 64 (the idle lanes hold +inf; a
+ * miss) but NaN at K = 64 (every lane holds a NaN; NaN > miss_threshold is false: not a miss) -- there, and only there, its ade / fde are
+ * not sttode_best_of_k's +inf. */
 int sttode_best_of_k_select(const float* pred, const float* gt, int n, int K, int Tf, float scale, float miss_threshold, const int* seg_ptr,
                             int S, float* ade, float* fde, int* best_ade_idx, int* best_fde_idx, unsigned char* miss, float* best,
                             float* seg_ade, float* seg_fde, int* seg_miss, void* stream);

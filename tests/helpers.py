@@ -182,17 +182,22 @@ def oracle_grads(tag, dataset, Tp, Tf, g, drop=None, double=False):
     return grads, [float(v.detach()) for v in vals]
 
 
-def horizon_metrics_np(pred_nk, gt, scale=1.0):
-    """NumPy restatement of csrc/frontend.hip horizon_metrics_kernel, fp32 in the kernel's order: d = |scale (pred - gt)| (bok_dist: the two
-    squared differences added, then sqrt), a running sum over the frames, sum_h / h, minimum over the K samples.  pred_nk [n,K,Tf,2],
-    gt [n,Tf,2] -> [n,Tf,2]."""
+def bok_dist_np(pred_nk, gt, scale=1.0):
+    """NumPy restatement of csrc/frontend_body.hpp bok_dist in fp32: d = |scale (pred - gt)| = sqrtf(fmaf(dx, dx, dy * dy)).  pred_nk
+    [n,K,Tf,2], gt [n,Tf,2] -> [n,K,Tf] float32."""
     s = np.float32(scale)
     dx = (pred_nk[..., 0] - gt[:, None, :, 0]).astype(np.float32) * s
     dy = (pred_nk[..., 1] - gt[:, None, :, 1]).astype(np.float32) * s
     # sqrtf(fmaf(dx, dx, dy * dy)): the fused multiply-add through float64 (dx^2 is exact there; the sum rounds once more only when the two
     # terms' exponents differ by more than 5 bits AND the float64 result sits on a float32 tie: never seen, ~2^-29 per element)
     s2 = dx.astype(np.float64) * dx.astype(np.float64) + (dy * dy).astype(np.float32).astype(np.float64)
-    d = np.sqrt(s2.astype(np.float32)).astype(np.float32)                           # [n, K, Tf]
+    return np.sqrt(s2.astype(np.float32)).astype(np.float32)
+
+
+def horizon_metrics_np(pred_nk, gt, scale=1.0):
+    """NumPy restatement of csrc/frontend.hip horizon_metrics_kernel, fp32 in the kernel's order: d = |scale (pred - gt)| (bok_dist_np), a
+    running sum over the frames, sum_h / h, minimum over the K samples.  pred_nk [n,K,Tf,2], gt [n,Tf,2] -> [n,Tf,2]."""
+    d = bok_dist_np(pred_nk, gt, scale)                                             # [n, K, Tf]
     cum = np.zeros_like(d)
     run = np.zeros(d.shape[:2], np.float32)
     for t in range(d.shape[2]):

@@ -6,6 +6,8 @@ import os
 import numpy as np
 import pytest
 
+from helpers import bok_dist_np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -15,8 +17,7 @@ def select_np(pred, gt, scale=1.0, thr=1.0, seg_ptr=None):
     and the miss count.  Returns a dict of the kernel's outputs."""
     pred, gt = np.asarray(pred, np.float32), np.asarray(gt, np.float32)
     n, K, Tf = pred.shape[:3]
-    d = (pred - gt[:, None]) * np.float32(scale)
-    dist = np.sqrt(d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1])         # [n, K, Tf]
+    dist = bok_dist_np(pred, gt, scale)                                   # [n, K, Tf], with bok_dist's fused multiply-add
     s = np.zeros((n, K), np.float32)
     for t in range(Tf):
         s += dist[..., t]
