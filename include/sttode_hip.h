@@ -936,6 +936,32 @@ int sttode_large_kde_nll(const float* pred, const float* gt, int n, int R, int K
 long long int sttode_large_spread_ws(int n, int M);
 int sttode_large_spread(const float* pred, const float* gt, int n, int R, int K_in, int Tf, float scale, double div_scale, void* ws,
                         long ws_bytes, double* apd, double* fpd, double* pade, double* dlow, double* es_ade, double* es_fde, void* stream);
+/* Latent sets (csrc/latents.hip; added within ABI version 15): per agent a set of M = R K points of N(0, I) in zdim
+ * dimensions, placed rather than drawn independently -- what inference(z=), inference_async(z=) and inference_reduced(z=) take.
+ * z [R][n K][zdim] float32, row = agent K + k: set index m of an agent lives at round m / K, column m % K.  bits: NULL, or int32 of the same
+ * shape: the 32-bit integer x behind every drawn value, 0 where no value was drawn (the centre row, the mirrored rows).
+ * Integer stage, for agent a = first_agent + local index, drawn point j, dimension d (32-bit wrap-around arithmetic):
+ *   s(a, d) = Philox4x32-10(key = seed, counter = [a_lo, a_hi, d >> 2, 0])[d & 3]
+ *   kind 0 (Sobol): x = XOR over the set bits b of gray(j) = j ^ (j >> 1) of dirs[d 30 + b] << 2; dirs [zdim][30] on the device: the 30-bit
+ *     direction numbers of the sequence (sttode_amd/latents.py uploads torch.quasirandom.SobolEngine(zdim).sobolstate), then
+ *     scramble 0: x as is (point 0 is the corner u ~ 0 of every dimension, z ~ -6.34: for checks only);
+ *     scramble 1 (random digital shift): x ^ s(a, d);
+ *     scramble 2 (nested uniform scrambling by hash): brev(h(brev(x), s(a, d))), h the Laine-Karras hash in Burley's form (JCGT 2020):
+ *       x += s, x ^= x 0x6c50b47c, x ^= x 0xb82f1e52, x ^= x 0xc7afe638, x ^= x 0x8d22f6e6 -- every step triangular in the bits, so the
+ *       net properties of the sequence are kept exactly.
+ *   kind 1 (random): x = Philox4x32-10(key = seed, counter = [a_lo, a_hi, d >> 2, 1 + j])[d & 3]; scramble is ignored, dirs may be NULL.
+ * Value stage, in float64: u = (x + 0.5) 2^-32; truncate = t > 0: u <- Phi(-t) + u (Phi(t) - Phi(-t)), evaluated as 0.5 + (u - 0.5) w with
+ *   w = Phi(t) - Phi(-t) = erf(t / sqrt 2) -- the same number, since Phi(-t) + w / 2 = 0.5, and the form that keeps the digits of a value near
+ *   the mode; z = float32(Phi^-1(u)) (AS241 PPND16 on u - 0.5, which is exact), clamped to +-t when truncated.  |z| <= 6.34.
+ * Set composition, c = center, B = M - c: without antithetic set index c + j is drawn point j (j < B); with it H = ceil(B / 2) points are
+ *   drawn, index c + j is z_j and index c + H + j is -z_j (j < B - H); with center index 0 is the zero vector, the prior mode.
+ * Limits, refused by name before anything is launched or written: z non-NULL; n >= 1; K, R >= 1 and M = R K <= 65536; 1 <= zdim <= 1024;
+ *   first_agent >= 0; kind 0 or 1; scramble 0, 1 or 2; antithetic, center 0 or 1; truncate 0, or finite and >= 0.01; dirs non-NULL for
+ *   kind 0; center needs M >= 2.
+ * One launch on `stream`: no workspace, no atomics, two runs give the same bits, and an agent's rows depend on (seed, a) only -- the rows
+ * of agents 5..8 drawn with first_agent = 5 are rows 5..8 of a draw of 130 agents. */
+int sttode_latent_set(float* z, int* bits, const unsigned* dirs, int n, int K, int R, int zdim, long long first_agent,
+                      unsigned long long seed, int kind, int scramble, int antithetic, int center, float truncate, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Native forward pipeline: one call enqueues STTODENet.inference (model/STTODE.py:574-623) end to end.

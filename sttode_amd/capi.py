@@ -142,6 +142,8 @@ SIGNATURES = {
     'sttode_large_kde_nll': [_P, _P, _I, _I, _I, _I, _F, _P, _P],
     'sttode_large_spread_ws': [_I, _I],
     'sttode_large_spread': [_P, _P, _I, _I, _I, _I, _F, _D, _P, _L] + [_P] * 7,
+    # latent sets: scrambled Sobol / Philox, antithetic, centred, truncated (csrc/latents.hip; added within ABI version 15)
+    'sttode_latent_set': [_P, _P, _P, _I, _I, _I, _I, _L, ctypes.c_ulonglong, _I, _I, _I, _I, _F, _P],
     # attention core with a running maximum, two score modes, optional mask (csrc/attention.hip; added within ABI version 14)
     'sttode_attn_core': [_P, _P, _P, _P, _L, _P, _P, _P, _P, _I, _I, _I] + [_L] * 8 + [_F, _F, _I, _P],
     'sttode_attn_core_bwd': [_P, _P, _P, _P, _L, _P, _P, _P, _P, _I, _I, _I] + [_L] * 8 + [_F, _F, _I, _P],

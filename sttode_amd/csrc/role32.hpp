@@ -17,6 +17,7 @@
 // with attention length 1 so is everything up to the gate nonlinearity.  Attention groups > 1 (NBA): embed_qkv and mhgsa_attn run as
 // launches in front; g and the attention output are read from the workspace.
 #pragma once
+#include "philox.hpp"
 
 struct R32C {   // == packing.R32_CONSTS
     static constexpr int bc = 0, wlast = 64, bi = 128, bg = 192, ln1w = 256, ln1b = 320, l1b = 384, l2b = 1408, ln2w = 1472, ln2b = 1536,
@@ -108,15 +109,7 @@ __device__ __forceinline__ void table32(FD& fd, const float* bias, float* out, c
 // separate torch.randn kernel the draw waited ~0.7-1 ms per call for workgroup slots on a chip the chain launches keep full and held the
 // CU halves it got all that time (profiles/r04/cadence_*.txt); here it is ~10 k VALU instructions per role lane, issued beside the other
 // wave's MFMAs.  Workgroup wg writes the rows of its own 128 agents; the trajectory groups read them two launches later.
-__device__ __forceinline__ void philox4x32_10(unsigned (&c)[4], unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0], p1 = (unsigned long long)0xCD9E8D57u * c[2];
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ k0, n2 = (unsigned)(p0 >> 32) ^ c[3] ^ k1;
-        c[0] = n0; c[1] = (unsigned)p1; c[2] = n2; c[3] = (unsigned)p0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
+// (philox4x32_10: philox.hpp)
 __device__ __forceinline__ void latents32(float* z, unsigned k0, unsigned k1, int wg, int n, int K) {
     const int a0 = wg * 128, na = n - a0 < 128 ? n - a0 : 128;
     const long first4 = (long)a0 * K * 8;                       // float4 index of the first row of this workgroup's agents (32 floats per row)

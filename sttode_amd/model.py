@@ -160,6 +160,10 @@ class _LazyViews(dict):
 class STTODENet(nn.Module):
     ODE_TIME = 12.0  # ODEG_Encoder(encoder_layers, nlayer, 12): model/STTODE.py:195 -> one Euler step of size 12
     ODE_METHODS = {'euler': 0, 'rk4': 1, 'rk4_classic': 2}
+    # Where inference / inference_async / inference_reduced take their latents when no ``z`` is passed: None (default) = torch.randn, or the
+    # in-launch Philox draw of the lagged form; a ``latents.LatentSource`` (or any object with K, zdim, rounds, __call__(rows) and
+    # draw_rounds(n)) = its sets, handed in as ``z``.  A plain attribute: no constructor argument, no state_dict entry.
+    latent_source = None
 
     def __init__(self, args, device):
         super().__init__()
@@ -233,7 +237,7 @@ class STTODENet(nn.Module):
     # per-call state (tensors of the current batch, views of the workspace): plain attributes.  nn.Module.__setattr__ walks its
     # Parameter / Module / buffer checks on every assignment (~1.5 us each, ~17 per one-scene call of the evaluation loop)
     _PLAIN = frozenset(('_past', '_future', '_scene_ptr', '_mode', 'batch_size', 'agent_num', '_S', '_N', '_G', 'pre_motion_mask', 'fut_motion_mask',
-                        'scene_orig', '_pf', '_pf_thunk', '_ws', '_dbg', 'diverse_pred', '_plist'))
+                        'scene_orig', '_pf', '_pf_thunk', '_ws', '_dbg', 'diverse_pred', '_plist', 'latent_source'))
 
     def __setattr__(self, name, value):
         if name in STTODENet._PLAIN:
@@ -720,6 +724,27 @@ class STTODENet(nn.Module):
         lv = losses.tolist()
         return losses.sum(), lv[0], lv[1], lv[2], lv[3]
 
+    def _source_check(self, rounds=None):
+        """A ``latent_source`` built for another K, zdim or (inference_reduced) rounds is refused before anything is launched."""
+        src, a = self.latent_source, self.args
+        if (src.K, src.zdim) != (a.sample_k, a.zdim) or (rounds is not None and src.rounds != rounds):
+            raise ValueError(f'latent_source is built for K = {src.K}, zdim = {src.zdim}, rounds = {src.rounds}; this call needs K = {a.sample_k}, '
+                             f'zdim = {a.zdim}' + ('' if rounds is None else f', rounds = {rounds}'))
+
+    def _source_latents(self, n, rounds=None):
+        """Latents of a call of n agents from ``latent_source``: [n K, zdim] (rounds None: the source's next round), or the whole
+        [rounds, n K, zdim] of one draw."""
+        self._source_check(rounds)
+        return self.latent_source(n * self.args.sample_k) if rounds is None else self.latent_source.draw_rounds(n)
+
+    def _as_z(self, z, n):
+        """A caller's (or a source's) latents as the contiguous float32 device tensor [n K, zdim] the launches read."""
+        if not (isinstance(z, torch.Tensor) and z.is_cuda and z.dtype == torch.float32 and z.is_contiguous()):
+            z = _f32(z, self.device)
+        if tuple(z.shape) != (n * self.args.sample_k, self.args.zdim):
+            raise ValueError(f'z must be [{n * self.args.sample_k}, {self.args.zdim}], got {tuple(z.shape)}')
+        return z
+
     @torch.no_grad()
     def inference(self, data=None, z=None):
         """model/STTODE.py:574-623 -> [K, n, Tf, 2] in world coordinates (a permuted view, as in the reference).
@@ -734,6 +759,8 @@ class STTODENet(nn.Module):
         if self._mode is None:
             raise capi.SttodeError('call set_data / set_data_nba / set_scene_batch before inference()')
         K = a.sample_k
+        if z is None and self.latent_source is not None:
+            z = self._source_latents(self._past.shape[0])
         if self._generic:                                                # widths outside the fused forms: the layer-by-layer form (generic.py)
             if (self.ode_method, self.ode_steps) != ('euler', 1):
                 raise NotImplementedError('non-default integrators are built for the reference widths (hidden_dim 64, zdim 32, two blocks)')
@@ -831,6 +858,8 @@ class STTODENet(nn.Module):
         if z is not None and (getattr(z, 'ndim', 0) != 3 or z.shape[0] != rounds):
             raise ValueError(f'z must be [rounds = {rounds}, n * sample_k, zdim], got {tuple(getattr(z, "shape", ()))}')
         K = self.args.sample_k if K is None else int(K)
+        if z is None and self.latent_source is not None:                 # the M = rounds * sample_k samples of an agent: one sequence
+            z = self._source_latents(self._past.shape[0], rounds)
         buf = self._round_buffer(rounds, self._past.shape[0])
         for r in range(rounds):
             self.inference(None, z=None if z is None else z[r])
@@ -930,6 +959,11 @@ class STTODENet(nn.Module):
             raise capi.SttodeError('call set_data / set_data_nba / set_scene_batch before inference_async()')
         if sampler_plan is not None and (self._generic or z is not None):
             raise capi.SttodeError('inference_async: a sampler plan fills z itself and needs the lagged form of the reference widths')
+        from_source = self.latent_source is not None and z is None
+        if from_source:
+            if sampler_plan is not None:
+                raise capi.SttodeError('inference_async: a sampler plan fills z itself; clear latent_source for that call')
+            self._source_check()                                 # (the draw itself: below, once every other argument has passed)
         if self._generic:
             # widths outside the fused forms have no pipelined form: the call runs serially on the caller's stream; the handle keeps the
             # callers of the pipelined API (evaluate.eval_scenes / eval_nba) working unchanged
@@ -946,10 +980,7 @@ class STTODENet(nn.Module):
         # native model had been armed left the request armed for the next call)
         lagged = bool(capi.lib().sttode_async_is_lagged(nat.h, n))
         if z is not None:
-            if not (isinstance(z, torch.Tensor) and z.is_cuda and z.dtype == torch.float32 and z.is_contiguous()):
-                z = _f32(z, self.device)
-            if tuple(z.shape) != (n * K, a.zdim):
-                raise ValueError(f'z must be [{n * K}, {a.zdim}], got {tuple(z.shape)}')
+            z = self._as_z(z, n)
         if metrics_gt is not None and not (isinstance(metrics_gt, torch.Tensor) and metrics_gt.is_cuda and metrics_gt.dtype == torch.float32
                                            and metrics_gt.is_contiguous() and tuple(metrics_gt.shape) == (n, a.future_length, 2)):
             raise ValueError(f'metrics_gt must be a contiguous float32 device tensor [{n}, {a.future_length}, 2]')
@@ -957,6 +988,8 @@ class STTODENet(nn.Module):
             raise capi.SttodeError('pred_host=True needs the lagged pipelined form (a chain-sized batch, reference integrator)')
         if sampler_plan is not None and not lagged:
             raise capi.SttodeError('inference_async: a sampler plan needs the lagged pipelined form (a chain-sized batch, reference integrator)')
+        if from_source:
+            z = self._as_z(self._source_latents(n), n)
         slot = self._async_calls % max(2, min(8, int(self.async_depth)))
         key = (n, S, slot)
         if key not in self._async_bufs:
