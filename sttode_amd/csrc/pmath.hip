@@ -7,6 +7,7 @@
 // the vector result (or lane 0 the scalar).  HBM-bound: 1 read of each operand + 1 write.  The reference's epsilons
 // and clamps are kept verbatim (cited per op).
 #include "api_util.hpp"
+#include "pmath_curv.hpp"
 #include <cmath>
 
 enum PmathOp {
@@ -313,34 +314,34 @@ __global__ void oblique_dist_kernel(const float* __restrict__ p1, const float* _
 }
 
 // ---------------------------------------------------------------------------------------------------
-extern "C" int sttode_pmath_rowop(int op, const float* x, const float* y, float* out, float* out2, int rows, int d, float c,
-                                  void* stream) {
-    STT_REQUIRE(op >= 0 && op < OP_COUNT, "sttode_pmath_rowop: unknown op");
-    STT_REQUIRE(x && out && rows > 0 && d > 0, "sttode_pmath_rowop: null pointer or empty shape");
+// One host function per operation for its two exported forms (pmath_curv.hpp).  The device form: c_dev points to ONE float
+// that the kernels read, so a trainable curvature costs no host read and the call can be captured.  The same kernels, the same
+// arithmetic: for *c_dev == v the results are bitwise those of the float form at v.  The value cannot be checked here, so c > 0 is a rule
+// of the float form alone; the device form has the row ops 0..11 only (Oblique.proj has no curvature, 13/14 are internal).
+static int pmath_rowop(const char* who, int op, const float* x, const float* y, float* out, float* out2, int rows, int d, Curv cv,
+                       void* stream) {
+    PM_REQUIRE_CURV();
+    if (cv.dev) PM_REQUIRE(op >= 0 && op < OP_OBL_PROJ, "unknown op, or one without a device-curvature form");
+    else PM_REQUIRE(op >= 0 && op < OP_COUNT, "unknown op");
+    PM_REQUIRE(x && out && rows > 0 && d > 0, "null pointer or empty shape");
     const bool needs_y = op == OP_MOBIUS_ADD || op == OP_DIST || op == OP_LOGMAP || op == OP_EXPMAP;
-    STT_REQUIRE(!needs_y || y, "sttode_pmath_rowop: this op needs a second operand");
-    STT_REQUIRE((op != OP_MATVEC_FIN && op != OP_PMEAN_PREP) || out2, "sttode_pmath_rowop: this op needs the out2 buffer");
-    STT_REQUIRE(c > 0.f || op == OP_OBL_PROJ, "sttode_pmath_rowop: curvature c must be positive");
+    PM_REQUIRE(!needs_y || y, "this op needs a second operand");
+    PM_REQUIRE((op != OP_MATVEC_FIN && op != OP_PMEAN_PREP) || out2, "this op needs the out2 buffer");
+    PM_REQUIRE(cv.dev || cv.c > 0.f || op == OP_OBL_PROJ, "curvature c must be positive");
     hipLaunchKernelGGL(pmath_row_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, op, x, needs_y ? y : nullptr, out, out2,
-                       rows, d, c, (const float*)nullptr);
+                       rows, d, cv.c, cv.c_dev);
     STT_HIP(hipGetLastError());
     return 0;
 }
 
-// The forms with the curvature on the device: c_dev points to ONE float that the kernels read, so a trainable curvature
-// costs no host read and the call can be captured.  The same kernels, the same arithmetic: for *c_dev == v the results are bitwise those
-// of the float form at v.  The value cannot be checked here; the row ops 0..11 only (Oblique.proj has no curvature, 13/14 are internal).
+extern "C" int sttode_pmath_rowop(int op, const float* x, const float* y, float* out, float* out2, int rows, int d, float c,
+                                  void* stream) {
+    return pmath_rowop("sttode_pmath_rowop", op, x, y, out, out2, rows, d, curv_float(c), stream);
+}
+
 extern "C" int sttode_pmath_rowop_c(int op, const float* x, const float* y, float* out, float* out2, int rows, int d, const float* c_dev,
                                     void* stream) {
-    STT_REQUIRE(c_dev, "sttode_pmath_rowop_c: c_dev is NULL (the curvature is read from the device)");
-    STT_REQUIRE(op >= 0 && op < OP_OBL_PROJ, "sttode_pmath_rowop_c: unknown op, or one without a device-curvature form");
-    STT_REQUIRE(x && out && rows > 0 && d > 0, "sttode_pmath_rowop_c: null pointer or empty shape");
-    const bool needs_y = op == OP_MOBIUS_ADD || op == OP_DIST || op == OP_LOGMAP || op == OP_EXPMAP;
-    STT_REQUIRE(!needs_y || y, "sttode_pmath_rowop_c: this op needs a second operand");
-    hipLaunchKernelGGL(pmath_row_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, op, x, needs_y ? y : nullptr, out, out2,
-                       rows, d, 0.f, c_dev);
-    STT_HIP(hipGetLastError());
-    return 0;
+    return pmath_rowop("sttode_pmath_rowop_c", op, x, y, out, out2, rows, d, curv_dev(c_dev), stream);
 }
 
 extern "C" int sttode_pmath_scalar(int which, const float* x, float* out, long n, void* stream) {
@@ -357,51 +358,49 @@ extern "C" int sttode_pmath_riemannian_grad(const float* x, const float* g, floa
     return 0;
 }
 
-static int pmath_matvec_launch(const float* m, const float* x, float* mx_ws, float* xnorm_ws, float* out, int rows, int d, int O, float c,
-                               const float* c_dev, void* stream) {
+static int pmath_matvec(const char* who, const float* m, const float* x, float* mx_ws, float* xnorm_ws, float* out, int rows, int d, int O,
+                        Curv cv, void* stream) {
+    PM_REQUIRE_CURV();
+    PM_REQUIRE(m && x && mx_ws && xnorm_ws && out && rows > 0 && d > 0 && O > 0 && (cv.dev || cv.c > 0.f), "bad arguments");
     hipStream_t s = (hipStream_t)stream;
     const long tot = (long)rows * O;
     hipLaunchKernelGGL(rowdot_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, x, m, mx_ws, xnorm_ws, rows, d, O);
     hipLaunchKernelGGL(pmath_row_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, (int)OP_MATVEC_FIN, (const float*)mx_ws,
-                       (const float*)nullptr, out, xnorm_ws, rows, O, c, c_dev);
+                       (const float*)nullptr, out, xnorm_ws, rows, O, cv.c, cv.c_dev);
     STT_HIP(hipGetLastError());
     return 0;
 }
 
 extern "C" int sttode_pmath_matvec(const float* m, const float* x, float* mx_ws, float* xnorm_ws, float* out, int rows, int d, int O,
                                    float c, void* stream) {
-    STT_REQUIRE(m && x && mx_ws && xnorm_ws && out && rows > 0 && d > 0 && O > 0 && c > 0.f, "sttode_pmath_matvec: bad arguments");
-    return pmath_matvec_launch(m, x, mx_ws, xnorm_ws, out, rows, d, O, c, nullptr, stream);
+    return pmath_matvec("sttode_pmath_matvec", m, x, mx_ws, xnorm_ws, out, rows, d, O, curv_float(c), stream);
 }
 
 extern "C" int sttode_pmath_matvec_c(const float* m, const float* x, float* mx_ws, float* xnorm_ws, float* out, int rows, int d, int O,
                                      const float* c_dev, void* stream) {
-    STT_REQUIRE(c_dev, "sttode_pmath_matvec_c: c_dev is NULL (the curvature is read from the device)");
-    STT_REQUIRE(m && x && mx_ws && xnorm_ws && out && rows > 0 && d > 0 && O > 0, "sttode_pmath_matvec_c: bad arguments");
-    return pmath_matvec_launch(m, x, mx_ws, xnorm_ws, out, rows, d, O, 0.f, c_dev, stream);
+    return pmath_matvec("sttode_pmath_matvec_c", m, x, mx_ws, xnorm_ws, out, rows, d, O, curv_dev(c_dev), stream);
+}
+
+static int pmath_pair(const char* who, int which, const float* x, const float* y, const float* A, float* out, int P, int R, int d, Curv cv,
+                      void* stream) {
+    PM_REQUIRE_CURV();
+    PM_REQUIRE(x && y && out && P > 0 && R > 0 && d > 0 && (cv.dev || cv.c > 0.f) && which >= 0 && which <= 2, "bad arguments");
+    PM_REQUIRE(which != 2 || A, "hyperbolic_softmax needs A");
+    const long tot = (long)P * R;
+    hipLaunchKernelGGL(pmath_pair_kernel, dim3((unsigned)((tot + 127) / 128)), dim3(128), 0, (hipStream_t)stream, which, x, y, A, out, P, R,
+                       d, cv.c, cv.c_dev);
+    STT_HIP(hipGetLastError());
+    return 0;
 }
 
 extern "C" int sttode_pmath_pair(int which, const float* x, const float* y, const float* A, float* out, int P, int R, int d, float c,
                                  void* stream) {
-    STT_REQUIRE(x && y && out && P > 0 && R > 0 && d > 0 && c > 0.f && which >= 0 && which <= 2, "sttode_pmath_pair: bad arguments");
-    STT_REQUIRE(which != 2 || A, "sttode_pmath_pair: hyperbolic_softmax needs A");
-    const long tot = (long)P * R;
-    hipLaunchKernelGGL(pmath_pair_kernel, dim3((unsigned)((tot + 127) / 128)), dim3(128), 0, (hipStream_t)stream, which, x, y, A, out, P, R,
-                       d, c, (const float*)nullptr);
-    STT_HIP(hipGetLastError());
-    return 0;
+    return pmath_pair("sttode_pmath_pair", which, x, y, A, out, P, R, d, curv_float(c), stream);
 }
 
 extern "C" int sttode_pmath_pair_c(int which, const float* x, const float* y, const float* A, float* out, int P, int R, int d,
                                    const float* c_dev, void* stream) {
-    STT_REQUIRE(c_dev, "sttode_pmath_pair_c: c_dev is NULL (the curvature is read from the device)");
-    STT_REQUIRE(x && y && out && P > 0 && R > 0 && d > 0 && which >= 0 && which <= 2, "sttode_pmath_pair_c: bad arguments");
-    STT_REQUIRE(which != 2 || A, "sttode_pmath_pair_c: hyperbolic_softmax needs A");
-    const long tot = (long)P * R;
-    hipLaunchKernelGGL(pmath_pair_kernel, dim3((unsigned)((tot + 127) / 128)), dim3(128), 0, (hipStream_t)stream, which, x, y, A, out, P, R,
-                       d, 0.f, c_dev);
-    STT_HIP(hipGetLastError());
-    return 0;
+    return pmath_pair("sttode_pmath_pair_c", which, x, y, A, out, P, R, d, curv_dev(c_dev), stream);
 }
 
 extern "C" int sttode_pmath_mean(const float* x, float* yl_ws, float* lam_ws, float* out, int rows, int d, float c, void* stream) {

@@ -24,6 +24,7 @@
 // forms are described where they stand below.
 #include "api_util.hpp"
 #include "dual.hpp"
+#include "pmath_curv.hpp"
 #include "train_group.hpp"
 #include <cmath>
 
@@ -574,47 +575,39 @@ __global__ __launch_bounds__(256) void oblique_dist_bwd_kernel(int side, const f
 
 }  // namespace
 
-static int pmath_mean_bwd_launch(const float* x, const float* g, double* gS_ws, double* gL_ws, float* gx, int outer, int R, int inner, int d, float c,
-                                 const float* c_dev, double* gc_ws, float* gc, void* stream) {
+// poincare_mean backward: x [outer,R,inner,d], g [outer,inner,d] -> gx as x.  Workspaces gS_ws [outer inner d] and gL_ws [outer inner]
+// doubles.  Two launches; bitwise repeatable, no atomics.  Device form: gc_ws holds outer R inner + outer inner doubles (the rows'
+// shares, then the groups'), and gx may be NULL (c alone requires a gradient).
+static int pmath_mean_bwd(const char* who, const float* x, const float* g, double* gS_ws, double* gL_ws, float* gx, int outer, int R, int inner,
+                          int d, Curv cv, void* stream) {
+    PM_REQUIRE_CURV();
+    PM_REQUIRE(x && g && gS_ws && gL_ws && (cv.dev || gx), "null pointer");
+    PM_REQUIRE(!cv.dev || (cv.gc_ws && cv.gc), "gc_ws [rows + groups] doubles and gc [1] are required");
+    PM_REQUIRE(outer > 0 && R > 0 && inner > 0 && d > 0, "empty shape");
+    PM_REQUIRE((long)outer * R * inner <= 0x7fffffffL, "more than 2^31 - 1 rows");
+    PM_REQUIRE(cv.dev || (cv.c > 0.f && std::isfinite(cv.c)), "curvature c must be positive and finite");
     hipStream_t s = (hipStream_t)stream;
     const int groups = outer * inner, rows = groups * R;
-    if (gc_ws) {
-        hipLaunchKernelGGL((pmath_mean_group_bwd_kernel<true, true>), dim3((groups + 3) / 4), dim3(256), 0, s, x, g, gS_ws, gL_ws, groups, R, inner, d,
-                           0.f, c_dev, gc_ws + rows);
-        hipLaunchKernelGGL((pmath_mean_row_bwd_kernel<true, true>), dim3((rows + 3) / 4), dim3(256), 0, s, x, (const double*)gS_ws, (const double*)gL_ws,
-                           gx, rows, R, inner, d, 0.f, c_dev, gc_ws);
-        hipLaunchKernelGGL(pmath_gc_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)gc_ws, gc, (long)rows + groups);
-    } else {
-        hipLaunchKernelGGL((pmath_mean_group_bwd_kernel<false, false>), dim3((groups + 3) / 4), dim3(256), 0, s, x, g, gS_ws, gL_ws, groups, R, inner,
-                           d, c, (const float*)nullptr, (double*)nullptr);
-        hipLaunchKernelGGL((pmath_mean_row_bwd_kernel<false, false>), dim3((rows + 3) / 4), dim3(256), 0, s, x, (const double*)gS_ws,
-                           (const double*)gL_ws, gx, rows, R, inner, d, c, (const float*)nullptr, (double*)nullptr);
-    }
+    auto group = pmath_mean_group_bwd_kernel<true, true>;
+    auto row = pmath_mean_row_bwd_kernel<true, true>;
+    if (!cv.dev) group = pmath_mean_group_bwd_kernel<false, false>, row = pmath_mean_row_bwd_kernel<false, false>;
+    hipLaunchKernelGGL(group, dim3((groups + 3) / 4), dim3(256), 0, s, x, g, gS_ws, gL_ws, groups, R, inner, d, cv.c, cv.c_dev,
+                       cv.dev ? cv.gc_ws + rows : nullptr);
+    hipLaunchKernelGGL(row, dim3((rows + 3) / 4), dim3(256), 0, s, x, (const double*)gS_ws, (const double*)gL_ws, gx, rows, R, inner, d, cv.c,
+                       cv.c_dev, cv.gc_ws);
+    if (cv.dev) hipLaunchKernelGGL(pmath_gc_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)cv.gc_ws, cv.gc, (long)rows + groups);
     STT_HIP(hipGetLastError());
     return 0;
 }
 
-// poincare_mean backward: x [outer,R,inner,d], g [outer,inner,d] -> gx as x.  Workspaces gS_ws [outer inner d] and gL_ws [outer inner]
-// doubles.  Two launches; bitwise repeatable, no atomics.
 extern "C" int sttode_pmath_mean_bwd(const float* x, const float* g, double* gS_ws, double* gL_ws, float* gx, int outer, int R, int inner, int d,
                                      float c, void* stream) {
-    STT_REQUIRE(x && g && gS_ws && gL_ws && gx, "sttode_pmath_mean_bwd: null pointer");
-    STT_REQUIRE(outer > 0 && R > 0 && inner > 0 && d > 0, "sttode_pmath_mean_bwd: empty shape");
-    STT_REQUIRE((long)outer * R * inner <= 0x7fffffffL, "sttode_pmath_mean_bwd: more than 2^31 - 1 rows");
-    STT_REQUIRE(c > 0.f && std::isfinite(c), "sttode_pmath_mean_bwd: curvature c must be positive and finite");
-    return pmath_mean_bwd_launch(x, g, gS_ws, gL_ws, gx, outer, R, inner, d, c, nullptr, nullptr, nullptr, stream);
+    return pmath_mean_bwd("sttode_pmath_mean_bwd", x, g, gS_ws, gL_ws, gx, outer, R, inner, d, curv_float(c), stream);
 }
 
-// ... with the curvature on the device: gc_ws holds outer R inner + outer inner doubles (the rows' shares, then the groups'), gc [1] is
-// WRITTEN by pmath_gc_finish_kernel (a third launch).  gx may be NULL (c alone requires a gradient).
 extern "C" int sttode_pmath_mean_bwd_c(const float* x, const float* g, double* gS_ws, double* gL_ws, float* gx, int outer, int R, int inner,
                                        int d, const float* c_dev, double* gc_ws, float* gc, void* stream) {
-    STT_REQUIRE(c_dev, "sttode_pmath_mean_bwd_c: c_dev is NULL (the curvature is read from the device)");
-    STT_REQUIRE(x && g && gS_ws && gL_ws, "sttode_pmath_mean_bwd_c: null pointer");
-    STT_REQUIRE(gc_ws && gc, "sttode_pmath_mean_bwd_c: gc_ws [rows + groups] doubles and gc [1] are required");
-    STT_REQUIRE(outer > 0 && R > 0 && inner > 0 && d > 0, "sttode_pmath_mean_bwd_c: empty shape");
-    STT_REQUIRE((long)outer * R * inner <= 0x7fffffffL, "sttode_pmath_mean_bwd_c: more than 2^31 - 1 rows");
-    return pmath_mean_bwd_launch(x, g, gS_ws, gL_ws, gx, outer, R, inner, d, 0.f, c_dev, gc_ws, gc, stream);
+    return pmath_mean_bwd("sttode_pmath_mean_bwd_c", x, g, gS_ws, gL_ws, gx, outer, R, inner, d, curv_dev(c_dev, gc_ws, gc), stream);
 }
 
 extern "C" int sttode_oblique_proj_bwd(const float* p, const float* g, float* gp, int rows, int d, void* stream) {
@@ -640,165 +633,150 @@ extern "C" int sttode_oblique_dist_bwd(const float* p1, const float* p2, const f
 }
 
 // ---------------------------------------------------------------------------------------------------
+// One host function per backward pass for its two exported forms (pmath_curv.hpp).  The float form requires every gradient buffer and
+// checks c > 0; it launches the <false> instantiations and no finishing kernel.  The device form: the curvature is ONE
+// float on the device, c_dev, and gets a gradient.  Each row kernel (<true>) writes its rows' float64 shares of dL/dc to gc_ws (one double
+// per row of the op: rows, rows, P, B), pmath_gc_finish_kernel adds them in a fixed order and WRITES the float gc[0].  The tensor
+// gradients may be NULL when nothing needs them; where they are given, their values are bitwise those of the float form at c = *c_dev.
+// *c_dev cannot be checked here: a curvature that is not positive gives NaN, not a refusal.  (Where a function names both instantiations
+// of a kernel, it names them in the order the device code has always been emitted in.)
+static int pmath_rowop_bwd(const char* who, int op, const float* x, const float* y, const float* g, float* gx, float* gy, int rows, int d,
+                           Curv cv, void* stream) {
+    PM_REQUIRE_CURV();
+    PM_REQUIRE(op != 12, "Oblique.proj has no backward pass here");
+    PM_REQUIRE(op != 13 && op != 14, "the internal halves of mobius_matvec / poincare_mean have no backward pass here");
+    PM_REQUIRE(op >= 0 && op < OPB_COUNT, "unknown op");
+    PM_REQUIRE(x && g && (cv.dev || gx) && rows > 0 && d > 0, "null pointer or empty shape");
+    PM_REQUIRE(!cv.dev || (cv.gc_ws && cv.gc), "gc_ws [rows] doubles and gc [1] are required");
+    const bool needs_y = op == OPB_MOBIUS_ADD || op == OPB_DIST || op == OPB_LOGMAP || op == OPB_EXPMAP;
+    if (cv.dev) PM_REQUIRE(!needs_y || y, "this op needs a second operand y");
+    else PM_REQUIRE(!needs_y || (y && gy), "this op needs a second operand and its gradient buffer gy");
+    PM_REQUIRE(needs_y || !gy, "gy given for an op with one operand");
+    PM_REQUIRE(cv.dev || cv.c > 0.f, "curvature c must be positive");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(!cv.dev ? pmath_row_bwd_kernel<false> : pmath_row_bwd_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, s, op, x,
+                       needs_y ? y : nullptr, g, gx, needs_y ? gy : nullptr, rows, d, cv.c, cv.c_dev, cv.gc_ws);
+    if (cv.dev) hipLaunchKernelGGL(pmath_gc_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)cv.gc_ws, cv.gc, (long)rows);
+    STT_HIP(hipGetLastError());
+    return 0;
+}
+
 extern "C" int sttode_pmath_rowop_bwd(int op, const float* x, const float* y, const float* g, float* gx, float* gy, int rows, int d, float c,
                                       void* stream) {
-    STT_REQUIRE(op != 12, "sttode_pmath_rowop_bwd: Oblique.proj has no backward pass here");
-    STT_REQUIRE(op != 13 && op != 14, "sttode_pmath_rowop_bwd: the internal halves of mobius_matvec / poincare_mean have no backward pass here");
-    STT_REQUIRE(op >= 0 && op < OPB_COUNT, "sttode_pmath_rowop_bwd: unknown op");
-    STT_REQUIRE(x && g && gx && rows > 0 && d > 0, "sttode_pmath_rowop_bwd: null pointer or empty shape");
-    const bool needs_y = op == OPB_MOBIUS_ADD || op == OPB_DIST || op == OPB_LOGMAP || op == OPB_EXPMAP;
-    STT_REQUIRE(!needs_y || (y && gy), "sttode_pmath_rowop_bwd: this op needs a second operand and its gradient buffer gy");
-    STT_REQUIRE(needs_y || !gy, "sttode_pmath_rowop_bwd: gy given for an op with one operand");
-    STT_REQUIRE(c > 0.f, "sttode_pmath_rowop_bwd: curvature c must be positive");
-    hipLaunchKernelGGL(pmath_row_bwd_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, op, x, needs_y ? y : nullptr, g, gx,
-                       needs_y ? gy : nullptr, rows, d, c, (const float*)nullptr, (double*)nullptr);
-    STT_HIP(hipGetLastError());
-    return 0;
+    return pmath_rowop_bwd("sttode_pmath_rowop_bwd", op, x, y, g, gx, gy, rows, d, curv_float(c), stream);
 }
 
-// The _c forms: the curvature is ONE float on the device, c_dev, and gets a gradient.  Each row kernel writes its rows'
-// float64 shares of dL/dc to gc_ws (one double per row of the op: rows, rows, P, B), pmath_gc_finish_kernel adds them in a fixed order
-// and WRITES the float gc[0].  The tensor gradients may be NULL when nothing needs them; where they are given, their values are bitwise
-// those of the float form at c = *c_dev.  *c_dev cannot be checked here: a curvature that is not positive gives NaN, not a refusal.
 extern "C" int sttode_pmath_rowop_bwd_c(int op, const float* x, const float* y, const float* g, float* gx, float* gy, int rows, int d,
                                         const float* c_dev, double* gc_ws, float* gc, void* stream) {
-    STT_REQUIRE(c_dev, "sttode_pmath_rowop_bwd_c: c_dev is NULL (the curvature is read from the device)");
-    STT_REQUIRE(op != 12, "sttode_pmath_rowop_bwd_c: Oblique.proj has no backward pass here");
-    STT_REQUIRE(op != 13 && op != 14, "sttode_pmath_rowop_bwd_c: the internal halves of mobius_matvec / poincare_mean have no backward pass here");
-    STT_REQUIRE(op >= 0 && op < OPB_COUNT, "sttode_pmath_rowop_bwd_c: unknown op");
-    STT_REQUIRE(x && g && rows > 0 && d > 0, "sttode_pmath_rowop_bwd_c: null pointer or empty shape");
-    STT_REQUIRE(gc_ws && gc, "sttode_pmath_rowop_bwd_c: gc_ws [rows] doubles and gc [1] are required");
-    const bool needs_y = op == OPB_MOBIUS_ADD || op == OPB_DIST || op == OPB_LOGMAP || op == OPB_EXPMAP;
-    STT_REQUIRE(!needs_y || y, "sttode_pmath_rowop_bwd_c: this op needs a second operand y");
-    STT_REQUIRE(needs_y || !gy, "sttode_pmath_rowop_bwd_c: gy given for an op with one operand");
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(pmath_row_bwd_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, s, op, x, needs_y ? y : nullptr, g, gx,
-                       needs_y ? gy : nullptr, rows, d, 0.f, c_dev, gc_ws);
-    hipLaunchKernelGGL(pmath_gc_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)gc_ws, gc, (long)rows);
-    STT_HIP(hipGetLastError());
-    return 0;
+    return pmath_rowop_bwd("sttode_pmath_rowop_bwd_c", op, x, y, g, gx, gy, rows, d, curv_dev(c_dev, gc_ws, gc), stream);
 }
 
-// mobius_matvec backward.  gxn_ws [rows] receives dL/d|x| per row: an OUTPUT that no later launch reads (the row kernel puts that term
-// into gx itself); it must not be NULL.  mx = x m^T is recomputed into mx_ws by the training GEMM (the autograd function saves only m and x); after the
+// mobius_matvec backward.  mx = x m^T is recomputed into mx_ws by the training GEMM (the autograd function saves only m and x); after the
 // row kernel has read it, mx_ws holds the split sums of the weight gradient.  gx = gmx m + gxn x / |x| (sttode_tlinear, trans = 1, adding to
-// the rows the row kernel started); gm = gmx^T x (sttode_twgrad, which accumulates: gm is zeroed first).
+// the rows the row kernel started); gm = gmx^T x (sttode_twgrad, which accumulates: gm is zeroed first).  gxn_ws [rows] receives dL/d|x|
+// per row: an OUTPUT that no later launch reads (the row kernel puts that term into gx itself).
+// Float form: no buffer may be NULL, gxn_ws included.  Device form: gx and gm may each be NULL (then its GEMM is not run); gmx_ws may be
+// NULL when both are, gxn_ws always.
 // DEVIATION from the reference: a row with mx == 0 (a zero x row) gets a zero gradient; the reference's 0/0 behind torch.where gives NaN.
-extern "C" int sttode_pmath_matvec_bwd(const float* m, const float* x, const float* g, float* mx_ws, float* gmx_ws, float* gxn_ws, float* gx,
-                                       float* gm, int rows, int d, int O, float c, void* stream) {
-    STT_REQUIRE(m && x && g && mx_ws && gmx_ws && gxn_ws && gx && gm, "sttode_pmath_matvec_bwd: null pointer");
-    STT_REQUIRE(rows > 0 && d > 0 && O > 0, "sttode_pmath_matvec_bwd: rows, d, O must be positive");
-    STT_REQUIRE(c > 0.f, "sttode_pmath_matvec_bwd: curvature c must be positive");
-    STT_REQUIRE(!stt_tgemm_group_open(), "sttode_pmath_matvec_bwd: not inside a sttode_tgemm_group bracket (its products depend on each other)");
+static int pmath_matvec_bwd(const char* who, const float* m, const float* x, const float* g, float* mx_ws, float* gmx_ws, float* gxn_ws,
+                            float* gx, float* gm, int rows, int d, int O, Curv cv, void* stream) {
+    PM_REQUIRE_CURV();
+    PM_REQUIRE(m && x && g && mx_ws && (cv.dev || (gmx_ws && gxn_ws && gx && gm)), "null pointer");
+    PM_REQUIRE(gmx_ws || (!gx && !gm), "gx and gm need the workspace gmx_ws");
+    PM_REQUIRE(!cv.dev || (cv.gc_ws && cv.gc), "gc_ws [rows] doubles and gc [1] are required");
+    PM_REQUIRE(rows > 0 && d > 0 && O > 0, "rows, d, O must be positive");
+    PM_REQUIRE(cv.dev || cv.c > 0.f, "curvature c must be positive");
+    PM_REQUIRE(!stt_tgemm_group_open(), "not inside a sttode_tgemm_group bracket (its products depend on each other)");
     hipStream_t s = (hipStream_t)stream;
     if (int rc = sttode_tlinear(x, d, 1, m, d, 0, nullptr, nullptr, 0, mx_ws, O, rows, d, O, 0, 0, stream)) return rc;
-    hipLaunchKernelGGL(pmath_matvec_bwd_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, s, (const float*)mx_ws, x, g, gmx_ws, gxn_ws, gx, rows, d,
-                       O, c, (const float*)nullptr, (double*)nullptr);
-    STT_HIP(hipGetLastError());
-    if (int rc = sttode_tlinear(gmx_ws, O, 1, m, d, 1, nullptr, nullptr, 0, gx, d, rows, O, d, 0, 1, stream)) return rc;
-    STT_HIP(hipMemsetAsync(gm, 0, sizeof(float) * (size_t)O * d, s));
-    if (int rc = sttode_twgrad(gmx_ws, O, x, d, 1, gm, d, nullptr, rows, O, d, mx_ws, (long)rows * O, stream)) return rc;
-    return sttode_twgrad_flush();   // (inside a sttode_twgrad_defer bracket the split sums would otherwise be added later)
-}
-
-// mobius_matvec backward with the curvature on the device.  gx and gm may each be NULL (then its GEMM is not run); gmx_ws may be NULL when
-// both are, gxn_ws always.  mx_ws is always needed: x m^T is recomputed into it.
-extern "C" int sttode_pmath_matvec_bwd_c(const float* m, const float* x, const float* g, float* mx_ws, float* gmx_ws, float* gxn_ws, float* gx,
-                                         float* gm, int rows, int d, int O, const float* c_dev, double* gc_ws, float* gc, void* stream) {
-    STT_REQUIRE(c_dev, "sttode_pmath_matvec_bwd_c: c_dev is NULL (the curvature is read from the device)");
-    STT_REQUIRE(m && x && g && mx_ws, "sttode_pmath_matvec_bwd_c: null pointer");
-    STT_REQUIRE(gmx_ws || (!gx && !gm), "sttode_pmath_matvec_bwd_c: gx and gm need the workspace gmx_ws");
-    STT_REQUIRE(gc_ws && gc, "sttode_pmath_matvec_bwd_c: gc_ws [rows] doubles and gc [1] are required");
-    STT_REQUIRE(rows > 0 && d > 0 && O > 0, "sttode_pmath_matvec_bwd_c: rows, d, O must be positive");
-    STT_REQUIRE(!stt_tgemm_group_open(), "sttode_pmath_matvec_bwd_c: not inside a sttode_tgemm_group bracket (its products depend on each other)");
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = sttode_tlinear(x, d, 1, m, d, 0, nullptr, nullptr, 0, mx_ws, O, rows, d, O, 0, 0, stream)) return rc;
-    hipLaunchKernelGGL(pmath_matvec_bwd_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, s, (const float*)mx_ws, x, g, gmx_ws, gxn_ws, gx, rows, d,
-                       O, 0.f, c_dev, gc_ws);
-    hipLaunchKernelGGL(pmath_gc_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)gc_ws, gc, (long)rows);
+    hipLaunchKernelGGL(!cv.dev ? pmath_matvec_bwd_kernel<false> : pmath_matvec_bwd_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, s,
+                       (const float*)mx_ws, x, g, gmx_ws, gxn_ws, gx, rows, d, O, cv.c, cv.c_dev, cv.gc_ws);
+    if (cv.dev) hipLaunchKernelGGL(pmath_gc_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)cv.gc_ws, cv.gc, (long)rows);
     STT_HIP(hipGetLastError());
     if (gx)
         if (int rc = sttode_tlinear(gmx_ws, O, 1, m, d, 1, nullptr, nullptr, 0, gx, d, rows, O, d, 0, 1, stream)) return rc;
     if (!gm) return 0;
     STT_HIP(hipMemsetAsync(gm, 0, sizeof(float) * (size_t)O * d, s));
     if (int rc = sttode_twgrad(gmx_ws, O, x, d, 1, gm, d, nullptr, rows, O, d, mx_ws, (long)rows * O, stream)) return rc;
-    return sttode_twgrad_flush();
+    return sttode_twgrad_flush();   // (inside a sttode_twgrad_defer bracket the split sums would otherwise be added later)
+}
+
+extern "C" int sttode_pmath_matvec_bwd(const float* m, const float* x, const float* g, float* mx_ws, float* gmx_ws, float* gxn_ws, float* gx,
+                                       float* gm, int rows, int d, int O, float c, void* stream) {
+    return pmath_matvec_bwd("sttode_pmath_matvec_bwd", m, x, g, mx_ws, gmx_ws, gxn_ws, gx, gm, rows, d, O, curv_float(c), stream);
+}
+
+extern "C" int sttode_pmath_matvec_bwd_c(const float* m, const float* x, const float* g, float* mx_ws, float* gmx_ws, float* gxn_ws, float* gx,
+                                         float* gm, int rows, int d, int O, const float* c_dev, double* gc_ws, float* gc, void* stream) {
+    return pmath_matvec_bwd("sttode_pmath_matvec_bwd_c", m, x, g, mx_ws, gmx_ws, gxn_ws, gx, gm, rows, d, O, curv_dev(c_dev, gc_ws, gc), stream);
+}
+
+// dist_matrix backward.  Device form: gc_ws holds P doubles (the side-0 pass, one wave per x row, sums its partners' shares; the side-1
+// pass carries no share of dL/dc).  gx and gy may each be NULL; the side-1 pass runs only for gy.
+static int pmath_dist_matrix_bwd(const char* who, const float* x, const float* y, const float* g, float* gx, float* gy, int P, int R, int d,
+                                 Curv cv, void* stream) {
+    PM_REQUIRE_CURV();
+    PM_REQUIRE(x && y && g && (cv.dev || (gx && gy)), "null pointer");
+    PM_REQUIRE(!cv.dev || (cv.gc_ws && cv.gc), "gc_ws [P] doubles and gc [1] are required");
+    PM_REQUIRE(P > 0 && R > 0 && d > 0, "P, R, d must be positive");
+    PM_REQUIRE(cv.dev || cv.c > 0.f, "curvature c must be positive");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL((!cv.dev ? pmath_dist_matrix_bwd_kernel<false, false> : pmath_dist_matrix_bwd_kernel<true, true>), dim3((P + 3) / 4),
+                       dim3(256), 0, s, 0, x, y, g, gx, P, R, d, cv.c, cv.c_dev, cv.gc_ws);
+    if (gy)
+        hipLaunchKernelGGL((!cv.dev ? pmath_dist_matrix_bwd_kernel<false, false> : pmath_dist_matrix_bwd_kernel<false, true>), dim3((R + 3) / 4),
+                           dim3(256), 0, s, 1, x, y, g, gy, P, R, d, cv.c, cv.c_dev, (double*)nullptr);
+    if (cv.dev) hipLaunchKernelGGL(pmath_gc_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)cv.gc_ws, cv.gc, (long)P);
+    STT_HIP(hipGetLastError());
+    return 0;
 }
 
 extern "C" int sttode_pmath_dist_matrix_bwd(const float* x, const float* y, const float* g, float* gx, float* gy, int P, int R, int d, float c,
                                             void* stream) {
-    STT_REQUIRE(x && y && g && gx && gy, "sttode_pmath_dist_matrix_bwd: null pointer");
-    STT_REQUIRE(P > 0 && R > 0 && d > 0, "sttode_pmath_dist_matrix_bwd: P, R, d must be positive");
-    STT_REQUIRE(c > 0.f, "sttode_pmath_dist_matrix_bwd: curvature c must be positive");
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL((pmath_dist_matrix_bwd_kernel<false, false>), dim3((P + 3) / 4), dim3(256), 0, s, 0, x, y, g, gx, P, R, d, c,
-                       (const float*)nullptr, (double*)nullptr);
-    hipLaunchKernelGGL((pmath_dist_matrix_bwd_kernel<false, false>), dim3((R + 3) / 4), dim3(256), 0, s, 1, x, y, g, gy, P, R, d, c,
-                       (const float*)nullptr, (double*)nullptr);
-    STT_HIP(hipGetLastError());
-    return 0;
+    return pmath_dist_matrix_bwd("sttode_pmath_dist_matrix_bwd", x, y, g, gx, gy, P, R, d, curv_float(c), stream);
 }
 
-// dist_matrix backward with the curvature on the device: gc_ws holds P doubles (the side-0 pass, one wave per x row, sums its partners'
-// shares).  gx and gy may each be NULL; the side-1 pass runs only for gy.
 extern "C" int sttode_pmath_dist_matrix_bwd_c(const float* x, const float* y, const float* g, float* gx, float* gy, int P, int R, int d,
                                               const float* c_dev, double* gc_ws, float* gc, void* stream) {
-    STT_REQUIRE(c_dev, "sttode_pmath_dist_matrix_bwd_c: c_dev is NULL (the curvature is read from the device)");
-    STT_REQUIRE(x && y && g, "sttode_pmath_dist_matrix_bwd_c: null pointer");
-    STT_REQUIRE(gc_ws && gc, "sttode_pmath_dist_matrix_bwd_c: gc_ws [P] doubles and gc [1] are required");
-    STT_REQUIRE(P > 0 && R > 0 && d > 0, "sttode_pmath_dist_matrix_bwd_c: P, R, d must be positive");
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL((pmath_dist_matrix_bwd_kernel<true, true>), dim3((P + 3) / 4), dim3(256), 0, s, 0, x, y, g, gx, P, R, d, 0.f, c_dev, gc_ws);
-    if (gy)
-        hipLaunchKernelGGL((pmath_dist_matrix_bwd_kernel<false, true>), dim3((R + 3) / 4), dim3(256), 0, s, 1, x, y, g, gy, P, R, d, 0.f, c_dev,
-                           (double*)nullptr);
-    hipLaunchKernelGGL(pmath_gc_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)gc_ws, gc, (long)P);
-    STT_HIP(hipGetLastError());
-    return 0;
+    return pmath_dist_matrix_bwd("sttode_pmath_dist_matrix_bwd_c", x, y, g, gx, gy, P, R, d, curv_dev(c_dev, gc_ws, gc), stream);
 }
 
 // _hyperbolic_softmax backward: X [B,d], A [C,d], P [C,d], g [B,C] -> gX [B,d], gA [C,d], gP [C,d]; coef_ws [6,B,C] doubles.  Three launches
-// (coefficients once per pair, then one wave per X row and one wave per class row); bitwise repeatable.
-extern "C" int sttode_pmath_hsoftmax_bwd(const float* X, const float* A, const float* P, const float* g, double* coef_ws, float* gX, float* gA,
-                                         float* gP, int B, int C, int d, float c, void* stream) {
-    STT_REQUIRE(X && A && P && g && coef_ws && gX && gA && gP, "sttode_pmath_hsoftmax_bwd: null pointer");
-    STT_REQUIRE(B > 0 && C > 0 && d > 0, "sttode_pmath_hsoftmax_bwd: B, C, d must be positive");
-    STT_REQUIRE((long)B * C <= 0x7fffffffL, "sttode_pmath_hsoftmax_bwd: more than 2^31 - 1 pairs");
-    STT_REQUIRE(c > 0.f, "sttode_pmath_hsoftmax_bwd: curvature c must be positive");
+// (coefficients once per pair, then one wave per X row and one wave per class row); bitwise repeatable.  Device form: coef_ws holds
+// SEVEN planes [7,B,C] (the seventh: g d logit / dc), gc_ws B doubles (the X-row pass sums the seventh plane over the classes).  gX may
+// be NULL; gA and gP may be NULL together (then the class-row pass, which carries no share of dL/dc, is not run).
+static int pmath_hsoftmax_bwd(const char* who, const float* X, const float* A, const float* P, const float* g, double* coef_ws, float* gX,
+                              float* gA, float* gP, int B, int C, int d, Curv cv, void* stream) {
+    PM_REQUIRE_CURV();
+    PM_REQUIRE(X && A && P && g && coef_ws && (cv.dev || (gX && gA && gP)), "null pointer");
+    PM_REQUIRE(!gA == !gP, "gA and gP are given together or not at all");
+    PM_REQUIRE(!cv.dev || (cv.gc_ws && cv.gc), "gc_ws [B] doubles and gc [1] are required");
+    PM_REQUIRE(B > 0 && C > 0 && d > 0, "B, C, d must be positive");
+    PM_REQUIRE((long)B * C <= 0x7fffffffL, "more than 2^31 - 1 pairs");
+    PM_REQUIRE(cv.dev || cv.c > 0.f, "curvature c must be positive");
     hipStream_t s = (hipStream_t)stream;
     const long BC = (long)B * C;
-    hipLaunchKernelGGL(pmath_hsoftmax_coef_kernel<false>, dim3((unsigned)((BC + 3) / 4)), dim3(256), 0, s, X, A, P, g, coef_ws, B, C, d, c,
-                       (const float*)nullptr);
-    hipLaunchKernelGGL(pmath_hsoftmax_rowsum_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, s, 0, X, A, P, (const double*)coef_ws, gX, gA, gP, B, C,
-                       d, (double*)nullptr);
-    hipLaunchKernelGGL(pmath_hsoftmax_rowsum_kernel<false>, dim3((C + 3) / 4), dim3(256), 0, s, 1, X, A, P, (const double*)coef_ws, gX, gA, gP, B, C,
-                       d, (double*)nullptr);
+    auto coef = pmath_hsoftmax_coef_kernel<false>;
+    auto xrows = pmath_hsoftmax_rowsum_kernel<false>;
+    if (cv.dev) coef = pmath_hsoftmax_coef_kernel<true>, xrows = pmath_hsoftmax_rowsum_kernel<true>;
+    hipLaunchKernelGGL(coef, dim3((unsigned)((BC + 3) / 4)), dim3(256), 0, s, X, A, P, g, coef_ws, B, C, d, cv.c, cv.c_dev);
+    hipLaunchKernelGGL(xrows, dim3((B + 3) / 4), dim3(256), 0, s, 0, X, A, P, (const double*)coef_ws, gX, gA, gP, B, C, d, cv.gc_ws);
+    if (gA)
+        hipLaunchKernelGGL(pmath_hsoftmax_rowsum_kernel<false>, dim3((C + 3) / 4), dim3(256), 0, s, 1, X, A, P, (const double*)coef_ws, gX, gA, gP,
+                           B, C, d, (double*)nullptr);
+    if (cv.dev) hipLaunchKernelGGL(pmath_gc_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)cv.gc_ws, cv.gc, (long)B);
     STT_HIP(hipGetLastError());
     return 0;
 }
 
-// _hyperbolic_softmax backward with the curvature on the device: coef_ws holds SEVEN planes [7,B,C] (the seventh: g d logit / dc), gc_ws B
-// doubles (the X-row pass sums the seventh plane over the classes).  gX may be NULL; gA and gP may be NULL together (then the class-row
-// pass is not run).
+extern "C" int sttode_pmath_hsoftmax_bwd(const float* X, const float* A, const float* P, const float* g, double* coef_ws, float* gX, float* gA,
+                                         float* gP, int B, int C, int d, float c, void* stream) {
+    return pmath_hsoftmax_bwd("sttode_pmath_hsoftmax_bwd", X, A, P, g, coef_ws, gX, gA, gP, B, C, d, curv_float(c), stream);
+}
+
 extern "C" int sttode_pmath_hsoftmax_bwd_c(const float* X, const float* A, const float* P, const float* g, double* coef_ws, float* gX, float* gA,
                                            float* gP, int B, int C, int d, const float* c_dev, double* gc_ws, float* gc, void* stream) {
-    STT_REQUIRE(c_dev, "sttode_pmath_hsoftmax_bwd_c: c_dev is NULL (the curvature is read from the device)");
-    STT_REQUIRE(X && A && P && g && coef_ws, "sttode_pmath_hsoftmax_bwd_c: null pointer");
-    STT_REQUIRE(!gA == !gP, "sttode_pmath_hsoftmax_bwd_c: gA and gP are given together or not at all");
-    STT_REQUIRE(gc_ws && gc, "sttode_pmath_hsoftmax_bwd_c: gc_ws [B] doubles and gc [1] are required");
-    STT_REQUIRE(B > 0 && C > 0 && d > 0, "sttode_pmath_hsoftmax_bwd_c: B, C, d must be positive");
-    STT_REQUIRE((long)B * C <= 0x7fffffffL, "sttode_pmath_hsoftmax_bwd_c: more than 2^31 - 1 pairs");
-    hipStream_t s = (hipStream_t)stream;
-    const long BC = (long)B * C;
-    hipLaunchKernelGGL(pmath_hsoftmax_coef_kernel<true>, dim3((unsigned)((BC + 3) / 4)), dim3(256), 0, s, X, A, P, g, coef_ws, B, C, d, 0.f, c_dev);
-    hipLaunchKernelGGL(pmath_hsoftmax_rowsum_kernel<true>, dim3((B + 3) / 4), dim3(256), 0, s, 0, X, A, P, (const double*)coef_ws, gX, gA, gP, B, C,
-                       d, gc_ws);
-    if (gA)
-        hipLaunchKernelGGL(pmath_hsoftmax_rowsum_kernel<false>, dim3((C + 3) / 4), dim3(256), 0, s, 1, X, A, P, (const double*)coef_ws, gX, gA, gP, B,
-                           C, d, (double*)nullptr);
-    hipLaunchKernelGGL(pmath_gc_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)gc_ws, gc, (long)B);
-    STT_HIP(hipGetLastError());
-    return 0;
+    return pmath_hsoftmax_bwd("sttode_pmath_hsoftmax_bwd_c", X, A, P, g, coef_ws, gX, gA, gP, B, C, d, curv_dev(c_dev, gc_ws, gc), stream);
 }
 
 // Feature clipping x min(1, r / (|x| + 1e-5)) over rows (ToPoincare(clip_r=r)) and its backward pass.

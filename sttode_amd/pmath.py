@@ -63,6 +63,36 @@ def _gc_buffers(c, rows):
     return torch.empty(rows, dtype=torch.float64, device=c.device), torch.empty(1, dtype=torch.float32, device=c.device)
 
 
+def _save_curv(ctx, c, *tensors):
+    """Keeps a Function's tensors and its curvature for the backward pass: a tensor c with the tensors, a number as an attribute."""
+    dev = isinstance(c, torch.Tensor)
+    ctx.save_for_backward(*tensors, c if dev else None)
+    ctx.c = None if dev else c
+
+
+def _saved_curv(ctx):
+    """(*tensors, c) as _save_curv took them."""
+    saved = ctx.saved_tensors
+    return saved if ctx.c is None else saved[:-1] + (ctx.c,)
+
+
+def _wants(ctx, c):
+    """Which gradients the backward entry point is given buffers for: needs_input_grad with a tensor c; all of them with a number, whose
+    entry points require every buffer."""
+    return ctx.needs_input_grad if _on_device(c) else (True,) * len(ctx.needs_input_grad)
+
+
+def _bwd_call(name, c, want_c, gc_rows, *args):
+    """Calls the backward entry point `name` (a number c) or name + '_c' (a tensor c, followed by dL/dc's float64 workspace of gc_rows
+    rows and its result) with the curvature behind `args`.  Returns dL/dc in c's shape if want_c, else None."""
+    if not _on_device(c):
+        capi.call(name, *args, c, capi.stream_ptr())
+        return None
+    ws, gc = _gc_buffers(c, gc_rows)
+    capi.call(name + '_c', *args, c, ws, gc, capi.stream_ptr())
+    return gc.view(c.shape) if want_c else None
+
+
 def _row(op, x, y=None, c=1.0, scalar=False, keepdim=False):
     x = _prep(x)
     if y is not None:
@@ -92,33 +122,20 @@ class _RowOp(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, op, c, scalar, keepdim):
-        ctx.save_for_backward(x, y, c if _on_device(c) else None)
-        ctx.op, ctx.c, ctx.scalar = op, c if not _on_device(c) else None, scalar
+        _save_curv(ctx, c, x, y)
+        ctx.op, ctx.scalar = op, scalar
         return _row_fwd(op, x, y, c, scalar, keepdim)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        x, y, c = ctx.saved_tensors
-        if c is not None:
-            return _row_bwd_c(ctx.op, x, y, c, g, ctx.scalar, ctx.needs_input_grad[0] or ctx.needs_input_grad[1], ctx.needs_input_grad[3]) \
-                + (None, None)
-        xb, yb = x, y
-        if y is not None:
-            xb, yb = torch.broadcast_tensors(x, y)
-            xb, yb = xb.contiguous(), yb.contiguous()
-        d = xb.shape[-1]
-        rows = xb.numel() // d
-        g = _prep(g)
-        assert g.numel() == (rows if ctx.scalar else rows * d)
-        gx = torch.empty_like(xb)
-        gy = torch.empty_like(yb) if y is not None else None
-        capi.call('sttode_pmath_rowop_bwd', _OPS[ctx.op], xb, yb, g, gx, gy, rows, d, ctx.c, capi.stream_ptr())
-        return gx.sum_to_size(x.shape), (gy.sum_to_size(y.shape) if y is not None else None), None, None, None, None
+        x, y, c = _saved_curv(ctx)
+        want_x, want_y, _, want_c, _, _ = _wants(ctx, c)
+        return _row_bwd(ctx.op, x, y, c, g, ctx.scalar, want_x or want_y, want_c) + (None, None)
 
 
-def _row_bwd_c(op, x, y, c, g, scalar, want_tensors, want_c):
-    """The backward pass of a row op whose curvature is on the device: (gx, gy, None, gc)."""
+def _row_bwd(op, x, y, c, g, scalar, want_tensors, want_c):
+    """The backward pass of a row op on broadcast operands: (gx, gy, None, gc), each gradient in its operand's shape."""
     xb, yb = x, y
     if y is not None:
         xb, yb = torch.broadcast_tensors(x, y)
@@ -129,10 +146,8 @@ def _row_bwd_c(op, x, y, c, g, scalar, want_tensors, want_c):
     assert g.numel() == (rows if scalar else rows * d)
     gx = torch.empty_like(xb) if want_tensors else None
     gy = torch.empty_like(yb) if want_tensors and y is not None else None
-    ws, gc = _gc_buffers(c, rows)
-    capi.call('sttode_pmath_rowop_bwd_c', _OPS[op], xb, yb, g, gx, gy, rows, d, c, ws, gc, capi.stream_ptr())
-    return (gx.sum_to_size(x.shape) if gx is not None else None, gy.sum_to_size(y.shape) if gy is not None else None, None,
-            gc.view(c.shape) if want_c else None)
+    gc = _bwd_call('sttode_pmath_rowop_bwd', c, want_c, rows, _OPS[op], xb, yb, g, gx, gy, rows, d)
+    return gx.sum_to_size(x.shape) if gx is not None else None, gy.sum_to_size(y.shape) if gy is not None else None, None, gc
 
 
 def _scalar(which, x):
@@ -283,30 +298,23 @@ class _MatVec(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, m, x, c):
-        ctx.save_for_backward(m, x, c if _on_device(c) else None)
-        ctx.c = c if not _on_device(c) else None
+        _save_curv(ctx, c, m, x)
         return _matvec_fwd(m, x, c)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        m, x, c = ctx.saved_tensors
+        m, x, c = _saved_curv(ctx)
+        want_m, want_x, want_c = _wants(ctx, c)
         O, d = m.shape
         rows = x.numel() // d
         g = _prep(g)
         f = dict(dtype=torch.float32, device=x.device)
-        if c is not None:
-            want_m, want_x, want_c = ctx.needs_input_grad
-            mx = torch.empty(rows, O, **f)
-            gmx = torch.empty(rows, O, **f) if want_m or want_x else None
-            gx, gm = torch.empty_like(x) if want_x else None, torch.empty_like(m) if want_m else None
-            ws, gc = _gc_buffers(c, rows)
-            capi.call('sttode_pmath_matvec_bwd_c', m, x, g, mx, gmx, None, gx, gm, rows, d, O, c, ws, gc, capi.stream_ptr())
-            return gm, gx, gc.view(c.shape) if want_c else None
-        mx, gmx, gxn = torch.empty(rows, O, **f), torch.empty(rows, O, **f), torch.empty(rows, **f)   # gxn: an output the entry point requires; unused
-        gx, gm = torch.empty_like(x), torch.empty_like(m)
-        capi.call('sttode_pmath_matvec_bwd', m, x, g, mx, gmx, gxn, gx, gm, rows, d, O, ctx.c, capi.stream_ptr())
-        return gm, gx, None
+        mx = torch.empty(rows, O, **f)
+        gmx = torch.empty(rows, O, **f) if want_m or want_x else None
+        gxn = None if _on_device(c) else torch.empty(rows, **f)   # an output only the float entry point requires; unused
+        gx, gm = torch.empty_like(x) if want_x else None, torch.empty_like(m) if want_m else None
+        return gm, gx, _bwd_call('sttode_pmath_matvec_bwd', c, want_c, rows, m, x, g, mx, gmx, gxn, gx, gm, rows, d, O)
 
 
 class _DistMatrix(torch.autograd.Function):
@@ -314,23 +322,16 @@ class _DistMatrix(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, c):
-        ctx.save_for_backward(x, y, c if _on_device(c) else None)
-        ctx.c = c if not _on_device(c) else None
+        _save_curv(ctx, c, x, y)
         return _pair(0, x, y, None, c, (x.shape[0], y.shape[0]))
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        x, y, c = ctx.saved_tensors
-        if c is not None:
-            want_x, want_y, want_c = ctx.needs_input_grad
-            gx, gy = torch.empty_like(x) if want_x else None, torch.empty_like(y) if want_y else None
-            ws, gc = _gc_buffers(c, x.shape[0])
-            capi.call('sttode_pmath_dist_matrix_bwd_c', x, y, _prep(g), gx, gy, x.shape[0], y.shape[0], x.shape[1], c, ws, gc, capi.stream_ptr())
-            return gx, gy, gc.view(c.shape) if want_c else None
-        gx, gy = torch.empty_like(x), torch.empty_like(y)
-        capi.call('sttode_pmath_dist_matrix_bwd', x, y, _prep(g), gx, gy, x.shape[0], y.shape[0], x.shape[1], ctx.c, capi.stream_ptr())
-        return gx, gy, None
+        x, y, c = _saved_curv(ctx)
+        want_x, want_y, want_c = _wants(ctx, c)
+        gx, gy = torch.empty_like(x) if want_x else None, torch.empty_like(y) if want_y else None
+        return gx, gy, _bwd_call('sttode_pmath_dist_matrix_bwd', c, want_c, x.shape[0], x, y, _prep(g), gx, gy, x.shape[0], y.shape[0], x.shape[1])
 
 
 def _pair(which, x, y, A, c, shape):
@@ -357,23 +358,16 @@ class _MobiusAdditionBatch(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, c):
-        ctx.save_for_backward(x, y, c if _on_device(c) else None)
-        ctx.c = c if not _on_device(c) else None
+        _save_curv(ctx, c, x, y)
         return _pair(1, x, y, None, c, (x.shape[0], y.shape[0], x.shape[1]))
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        x, y, c = ctx.saved_tensors
-        shape = (x.shape[0], y.shape[0], x.shape[1])
-        if c is not None:
-            gx, gy, _, gc = _row_bwd_c('mobius_add', x.unsqueeze(1), y.unsqueeze(0), c, g, False,
-                                       ctx.needs_input_grad[0] or ctx.needs_input_grad[1], ctx.needs_input_grad[2])
-            return gx.view_as(x) if gx is not None else None, gy.view_as(y) if gy is not None else None, gc
-        xb, yb = x.unsqueeze(1).expand(shape).contiguous(), y.unsqueeze(0).expand(shape).contiguous()
-        gx, gy = torch.empty_like(xb), torch.empty_like(yb)
-        capi.call('sttode_pmath_rowop_bwd', _OPS['mobius_add'], xb, yb, _prep(g), gx, gy, shape[0] * shape[1], shape[2], ctx.c, capi.stream_ptr())
-        return gx.sum_to_size(x.unsqueeze(1).shape).view_as(x), gy.sum_to_size(y.unsqueeze(0).shape).view_as(y), None
+        x, y, c = _saved_curv(ctx)
+        want_x, want_y, want_c = _wants(ctx, c)
+        gx, gy, _, gc = _row_bwd('mobius_add', x.unsqueeze(1), y.unsqueeze(0), c, g, False, want_x or want_y, want_c)
+        return gx.view_as(x) if gx is not None else None, gy.view_as(y) if gy is not None else None, gc
 
 
 def _mobius_addition_batch(x, y, c):
@@ -390,27 +384,20 @@ class _HyperbolicSoftmax(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, X, A, P, c):
-        ctx.save_for_backward(X, A, P, c if _on_device(c) else None)
-        ctx.c = c if not _on_device(c) else None
+        _save_curv(ctx, c, X, A, P)
         return _pair(2, P, X, A, c, (X.shape[0], P.shape[0]))
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        X, A, P, c = ctx.saved_tensors
+        X, A, P, c = _saved_curv(ctx)
+        want_X, want_A, want_P, want_c = _wants(ctx, c)
         B, C, d = X.shape[0], P.shape[0], X.shape[1]
-        if c is not None:
-            want_X, want_A, want_P, want_c = ctx.needs_input_grad
-            ws = torch.empty(7, B, C, dtype=torch.float64, device=X.device)
-            gX = torch.empty_like(X) if want_X else None
-            gA, gP = (torch.empty_like(A), torch.empty_like(P)) if want_A or want_P else (None, None)
-            gws, gc = _gc_buffers(c, B)
-            capi.call('sttode_pmath_hsoftmax_bwd_c', X, A, P, _prep(g), ws, gX, gA, gP, B, C, d, c, gws, gc, capi.stream_ptr())
-            return gX, gA if want_A else None, gP if want_P else None, gc.view(c.shape) if want_c else None
-        ws = torch.empty(6, B, C, dtype=torch.float64, device=X.device)
-        gX, gA, gP = torch.empty_like(X), torch.empty_like(A), torch.empty_like(P)
-        capi.call('sttode_pmath_hsoftmax_bwd', X, A, P, _prep(g), ws, gX, gA, gP, B, C, d, ctx.c, capi.stream_ptr())
-        return gX, gA, gP, None
+        ws = torch.empty(7 if _on_device(c) else 6, B, C, dtype=torch.float64, device=X.device)   # the seventh plane: g d logit / dc
+        gX = torch.empty_like(X) if want_X else None
+        gA, gP = (torch.empty_like(A), torch.empty_like(P)) if want_A or want_P else (None, None)
+        gc = _bwd_call('sttode_pmath_hsoftmax_bwd', c, want_c, B, X, A, P, _prep(g), ws, gX, gA, gP, B, C, d)
+        return gX, gA if want_A else None, gP if want_P else None, gc
 
 
 def _hyperbolic_softmax(X, A, P, c):
@@ -487,29 +474,23 @@ class _PoincareMean(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, geom, c):
-        ctx.save_for_backward(x, c if _on_device(c) else None)
-        ctx.geom, ctx.c = geom, c if not _on_device(c) else None
+        _save_curv(ctx, c, x)
+        ctx.geom = geom
         return _mean_fwd(x, geom, c)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        x, c = ctx.saved_tensors
+        x, c = _saved_curv(ctx)
+        want_x, _, want_c = _wants(ctx, c)
         outer, R, inner, d, _ = ctx.geom
         groups = outer * inner
         g = _prep(g)
         assert g.numel() == groups * d
         gS = torch.empty(groups * d, dtype=torch.float64, device=x.device)
         gL = torch.empty(groups, dtype=torch.float64, device=x.device)
-        if c is not None:
-            want_x, _, want_c = ctx.needs_input_grad
-            gx = torch.empty_like(x) if want_x else None
-            ws, gc = _gc_buffers(c, groups * R + groups)
-            capi.call('sttode_pmath_mean_bwd_c', x, g, gS, gL, gx, outer, R, inner, d, c, ws, gc, capi.stream_ptr())
-            return gx, None, gc.view(c.shape) if want_c else None
-        gx = torch.empty_like(x)
-        capi.call('sttode_pmath_mean_bwd', x, g, gS, gL, gx, outer, R, inner, d, ctx.c, capi.stream_ptr())
-        return gx, None, None
+        gx = torch.empty_like(x) if want_x else None
+        return gx, None, _bwd_call('sttode_pmath_mean_bwd', c, want_c, groups * R + groups, x, g, gS, gL, gx, outer, R, inner, d)
 
 
 def poincare_mean(x, dim=0, c=1.0, *, differentiable=False):
