@@ -410,6 +410,16 @@ def call(name, *args, tag=None):
         raise SttodeError(f'{name} failed (status {rc}): {L.sttode_last_error().decode()}')
 
 
+def self_attn_groups(qkv, out, G, L, Nb, D, stream):
+    """Geodesic self-attention over the rows of a [G L Nb, 3 D] buffer of columns q | k | v (sttode_mhgsa_attn_groups, 8 heads of D / 8):
+    G groups of L rows by Nb slots, attention along L within a slot; scores are used untransposed (hyptransformerlib.py:261-265), i.e.
+    out_i = sum_j softmax_j(-d(k_i, q_j)) v_j.  ``out`` [G L Nb, D]."""
+    e, HD = qkv.element_size(), D // 8
+    gq, go = L * Nb * 3 * D, L * Nb * D
+    call('sttode_mhgsa_attn_groups', qkv.data_ptr() + D * e, qkv.data_ptr(), qkv.data_ptr() + 2 * D * e, out, G, gq, gq, gq, go, L, L, Nb,
+         Nb * 3 * D, 3 * D, Nb * 3 * D, 3 * D, Nb * 3 * D, 3 * D, Nb * D, D, 1.0, float(HD) ** -0.5, HD, stream)
+
+
 def sampler_joint_ws(n, K, S):
     """Bytes of workspace sttode_sampler_objective_joint(_bwd) need for n agents, K samples and S segments."""
     L = lib()

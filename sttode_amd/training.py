@@ -49,6 +49,17 @@ EW_MUL, EW_AXPY, EW_GATE_BWD, EW_EULER_FWD, EW_EULER_BWD, EW_RSAMPLE, EW_RELU_BW
 EW_TANH_BWD, EW_LATENT_BWD, EW_SUM_CUR, EW_EULER_BWD_CAT, EW_SCALE_ADD, EW_AXPY_ROWS = 10, 11, 12, 13, 14, 15
 ACT = {None: 0, 'relu': 1, 'tanh': 2, 'sigmoid': 3}
 _ATT = 'ODE_Encoder.odeblock.odefunc.layers.0.'
+_SA = _ATT + 'self_attn.temporal_attention_before.'
+# A trunk's parameters, role -> name below the trunk's prefix, in the order of capi.TRUNK_PTRS (the fused launch's table): the layers in
+# front of the ODE block, then the ODE block's encoder layer in the order of SttodeOdeStageBwd.w[] as well
+_FRONT = dict(fc1_w='input_fc.weight', fc1_b='input_fc.bias', pos_w='pos_encoder.fc.weight', pos_b='pos_encoder.fc.bias',
+              fc2_w='input_fc2.weight', fc2_b='input_fc2.bias', fc3_w='input_fc3.weight', fc3_b='input_fc3.bias')
+_LAYER = dict(inproj_w=_SA + 'in_proj_weight', inproj_b=_SA + 'in_proj_bias', out_w=_SA + 'out_proj.weight', out_b=_SA + 'out_proj.bias',
+              info_w=_ATT + 'self_attn.temporal_info.weight', info_b=_ATT + 'self_attn.temporal_info.bias',
+              gate_w=_ATT + 'self_attn.temporal_gate.weight', gate_b=_ATT + 'self_attn.temporal_gate.bias',
+              ln1_w=_ATT + 'norm1.weight', ln1_b=_ATT + 'norm1.bias', l1_w=_ATT + 'linear1.weight', l1_b=_ATT + 'linear1.bias',
+              l2_w=_ATT + 'linear2.weight', l2_b=_ATT + 'linear2.bias', ln2_w=_ATT + 'norm2.weight', ln2_b=_ATT + 'norm2.bias')
+assert tuple(_FRONT) + tuple(_LAYER) == capi.TRUNK_PTRS[:24] and len(_LAYER) == 16
 
 
 # the first block's conv + GRU once per agent.  False -- per trajectory column -- is a test reference only (the same test); part of the graph key
@@ -170,6 +181,26 @@ class Engine:
         """enc_in [n,T,4] -> feat[:, :64] = ftraj_input, feat[:, 64:128] = ODE encoder output.  Returns the tape."""
         return self.trunk_fwd_multi([(pre, enc_in, last, feat, drop_mask)])[0]
 
+    def _trunk_state(self, items, backward=False):
+        """The walkers' per-trunk state, one dict per trunk.  Forward items: (pre, enc_in, last, feat, drop), with a fresh tape under 't';
+        backward items: (tape, dfeat).  'w': the encoder layer's parameter names by role (_LAYER), 'L' / 'Nb': attention length and slots."""
+        net, D = self.net, self.D
+        L, Nb = (net.batch_size, net._N) if net._mode == 'nba' else (1, None)
+        S = []
+        for it in items:
+            if backward:
+                t, dfeat = it
+                assert dfeat.stride(1) == 1 and dfeat.shape[1] >= 2 * D
+                s = dict(t=t, pre=t['pre'], n=t['n'], T=t['T'], dfeat=dfeat, L=t['L'], Nb=t['Nb'], Ys=t.get('Ys'))
+            else:
+                pre, enc_in, last, feat, drop_mask = it
+                n, T = enc_in.shape[0], enc_in.shape[1]
+                s = dict(t={'n': n, 'T': T, 'pre': pre, 'feat': feat}, pre=pre, n=n, T=T, X0=enc_in.reshape(n * T, 4), last=last, feat=feat,
+                         drop=drop_mask, L=L, Nb=Nb if Nb is not None else n)
+            s['w'] = {k: s['pre'] + name for k, name in _LAYER.items()}
+            S.append(s)
+        return S
+
     def trunk_fwd_multi(self, items):
         """Forward of one or several trunks (past and future encoder: the same layers, separate weights, independent of each other).  Scene
         batches with T <= 12: each trunk is ONE launch (csrc/train_trunk.hip), two of them inside a group one launch together.  Otherwise
@@ -177,90 +208,94 @@ class Engine:
         prog = self.ode_program()
         if prog is not None:                                     # a non-default integrator: the stage program (_ode_trunk_fwd)
             return self._ode_trunk_fwd(items, *prog)
-        P, net = self.P, self.net
-        D, HD = self.D, self.HD
-        S = []
-        for pre, enc_in, last, feat, drop_mask in items:
-            n, T = enc_in.shape[0], enc_in.shape[1]
-            S.append(dict(t={'n': n, 'T': T, 'pre': pre, 'feat': feat}, pre=pre, a=pre + _ATT, n=n, T=T, X0=enc_in.reshape(n * T, 4), last=last, feat=feat,
-                          drop=drop_mask))
-        L, Nb = (net.batch_size, net._N) if net._mode == 'nba' else (1, None)
+        net, D = self.net, self.D
+        S = self._trunk_state(items)
+        L = S[0]['L']
+        pair = lambda: self.group() if len(S) > 1 else contextlib.nullcontext()
         if all(s['T'] <= 12 for s in S) and self.fused_trunk and D == 64:
             if L == 1:
-                with (self.group() if len(S) > 1 else contextlib.nullcontext()):
-                    return [self._trunk_fwd_fused(s['t'], s['X0'], s['last'], s['feat'], s['drop']) for s in S]
+                with pair():
+                    return [self._trunk_fwd_fused(s) for s in S]
             # attention over the forward-call batch (the NBA branch): each trunk as TWO launches -- up to the in-projection, then (the attention
             # kernel between) from the attention output on -- instead of twelve layer launches; both trunks of a phase in one launch
-            with (self.group() if len(S) > 1 else contextlib.nullcontext()):
-                tabs = [self._trunk_fwd_fused(s['t'], s['X0'], s['last'], s['feat'], s['drop'], phase=1) for s in S]
-            G = getattr(net, '_G', 1)
+            with pair():
+                tabs = [self._trunk_fwd_fused(s, phase=1) for s in S]
             for s, (t, src) in zip(S, tabs):
-                qkv, e = src['qkv'], 4
-                capi.call('sttode_mhgsa_attn_groups', qkv.data_ptr() + 64 * e, qkv.data_ptr(), qkv.data_ptr() + 128 * e, src['attn'], G, L * Nb * 192,
-                          L * Nb * 192, L * Nb * 192, L * Nb * 64, L, L, Nb, Nb * 192, 192, Nb * 192, 192, Nb * 192, 192, Nb * 64, 64, 1.0, 8.0 ** -0.5, 8, self.st)
-            with (self.group() if len(S) > 1 else contextlib.nullcontext()):
+                capi.self_attn_groups(src['qkv'], src['attn'], getattr(net, '_G', 1), L, s['Nb'], D, self.st)
+            with pair():
                 for s, (t, src) in zip(S, tabs):
                     self._trunk_launch(src, s['n'], s['T'], s['feat'], 2)
-            for t, src in tabs:
-                t.update(L=L, Nb=Nb, attn=src['attn'])
+            for s, (t, src) in zip(S, tabs):
+                t.update(L=L, Nb=s['Nb'], attn=src['attn'])
             return [t for t, _ in tabs]
         self._trunk_pre_layers(S)
+        ks, A = self._layer_fwd(S, [s['x'] for s in S], full_qkv=True)
         with self.group():
-            for s in S:
-                sa = s['a'] + 'self_attn.temporal_attention_before.'
-                s['qkv'] = self.lin(s['x'], P[sa + 'in_proj_weight'], P[sa + 'in_proj_bias'])
-        for s in S:
-            n, qkv = s['n'], s['qkv']
-            if L > 1:
-                s['attn'] = self.new(n, D)
-                e = qkv.element_size()
-                G = getattr(net, '_G', 1)                          # forward-call batches per call (set_data_nba with [G,B,N,...]): attention within each
-                gq, go = L * Nb * 3 * D, L * Nb * D
-                capi.call('sttode_mhgsa_attn_groups', qkv.data_ptr() + D * e, qkv.data_ptr(), qkv.data_ptr() + 2 * D * e, s['attn'], G, gq, gq, gq, go, L, L,
-                          Nb, Nb * 3 * D, 3 * D, Nb * 3 * D, 3 * D, Nb * 3 * D, 3 * D, Nb * D, D, 1.0, float(HD) ** -0.5, HD, self.st)
-            else:
-                s['attn'] = qkv[:, 2 * D:]                        # softmax over a single key == 1  =>  output == v
-        with self.group():
-            for s in S:
-                sa = s['a'] + 'self_attn.temporal_attention_before.'
-                s['ao'] = self.lin(s['attn'], P[sa + 'out_proj.weight'], P[sa + 'out_proj.bias'])
-        with self.group():                                       # temporal_info and temporal_gate read the same input: four layers, one launch
-            for s in S:
-                a = s['a']
-                s['tt'] = self.lin(s['ao'], P[a + 'self_attn.temporal_info.weight'], P[a + 'self_attn.temporal_info.bias'], act='tanh')
-                s['ss'] = self.lin(s['ao'], P[a + 'self_attn.temporal_gate.weight'], P[a + 'self_attn.temporal_gate.bias'], act='sigmoid')
-        with self.group():
-            for s in S:
-                s['gated'] = self.new(s['n'], D)
-                self.ew(EW_MUL, s['gated'], s['tt'], s['ss'])
-        for s in S:
-            a, n = s['a'], s['n']
-            s['xc'] = s['x'].contiguous()
-            s['h'], s['xh1'], s['rs1'] = self.new(n, D), self.new(n, D), self.new(n)
-            capi.call('sttode_add_ln_fwd', s['xc'], s['gated'], P[a + 'norm1.weight'], P[a + 'norm1.bias'], s['h'], s['xh1'], s['rs1'], n, D, self.st)
-        with self.group():
-            for s in S:
-                s['f1'] = self.lin(s['h'], P[s['a'] + 'linear1.weight'], P[s['a'] + 'linear1.bias'], act='relu')
-        with self.group():
-            for s in S:
-                s['f2'] = self.lin(s['f1'], P[s['a'] + 'linear2.weight'], P[s['a'] + 'linear2.bias'])
-        for s in S:
-            a, n = s['a'], s['n']
-            s['y'], s['xh2'], s['rs2'] = self.new(n, D), self.new(n, D), self.new(n)
-            capi.call('sttode_add_ln_fwd', s['h'], s['f2'], P[a + 'norm2.weight'], P[a + 'norm2.bias'], s['y'], s['xh2'], s['rs2'], n, D, self.st)
-        with self.group():
-            for s in S:
+            for s, a, k in zip(S, A, ks):
                 s['ode'] = self.new(s['n'], D)
-                self.ew(EW_EULER_FWD, s['ode'], s['xc'], s['y'], f0=net.ODE_TIME)
+                self.ew(EW_EULER_FWD, s['ode'], a['xc'], k, f0=net.ODE_TIME)
         out = []
-        for s in S:
+        for s, a in zip(S, A):
             s['feat'][:, D:2 * D] = s['ode']
             t = s['t']
-            t.update(X0=s['X0'], posin=s['posin'], tp=s['tp'], drop=s['drop'], h3in=s['h3in'], xc=s['xc'], qkv=s['qkv'], attn=s['attn'], ao=s['ao'],
-                     tt=s['tt'], ss=s['ss'], h=s['h'], xh1=s['xh1'], rs1=s['rs1'], f1=s['f1'], xh2=s['xh2'], rs2=s['rs2'], ode=s['ode'], L=L,
-                     Nb=Nb if Nb is not None else s['n'])
+            t.update(X0=s['X0'], posin=s['posin'], tp=s['tp'], drop=s['drop'], h3in=s['h3in'], ode=s['ode'], L=L, Nb=s['Nb'],
+                     **{k: a[k] for k in ('xc', 'qkv', 'attn', 'ao', 'tt', 'ss', 'h', 'xh1', 'rs1', 'f1', 'xh2', 'rs2')})
             out.append(t)
         return out
+
+    def _layer_fwd(self, S, Y, keep=None, full_qkv=False):
+        """k = f(Y) per trunk: the ODE block's TransformerEncoderLayer (in-projection, geodesic attention -- the value rows alone at attention
+        length 1 --, out_proj, tanh * sigmoid gate, add + LN1, FFN, add + LN2).  Layer i of every trunk in one group.  Y [n, D] per trunk,
+        row stride free: the in-projection reads it where it is, add + LN1 a contiguous copy ('xc'; Y itself when it is contiguous).
+        ``keep``: per trunk, buffers for the activations the weight gradients read (qkv, attn, ao, h, f1).  ``full_qkv``: at attention length
+        1 the whole in-projection, not just the value rows the layer reads (the default path's tape carries qkv).  Returns (k per trunk,
+        activations per trunk)."""
+        P, D, net = self.P, self.D, self.net
+        A = [dict(keep[i]) if keep is not None else {} for i in range(len(S))]
+        with self.group():
+            for s, y, a in zip(S, Y, A):
+                W, b = P[s['w']['inproj_w']], P[s['w']['inproj_b']]
+                if s['L'] > 1 or full_qkv:
+                    a['qkv'] = self.lin(y, W, b, out=a.get('qkv'))
+                else:
+                    a['attn'] = self.lin(y, W[2 * D:], b[2 * D:], out=a.get('attn'))
+        for s, a in zip(S, A):
+            if s['L'] > 1:
+                a['attn'] = a['attn'] if 'attn' in a else self.new(s['n'], D)
+                # (the forward-call batches of a call, set_data_nba with [G,B,N,...]: attention within each)
+                capi.self_attn_groups(a['qkv'], a['attn'], getattr(net, '_G', 1), s['L'], s['Nb'], D, self.st)
+            elif full_qkv:
+                a['attn'] = a['qkv'][:, 2 * D:]                  # softmax over a single key == 1  =>  output == v
+        with self.group():
+            for s, a in zip(S, A):
+                a['ao'] = self.lin(a['attn'], P[s['w']['out_w']], P[s['w']['out_b']], out=a.get('ao'))
+        with self.group():                                       # temporal_info and temporal_gate read the same input: four layers, one launch
+            for s, a in zip(S, A):
+                a['tt'] = self.lin(a['ao'], P[s['w']['info_w']], P[s['w']['info_b']], act='tanh')
+                a['ss'] = self.lin(a['ao'], P[s['w']['gate_w']], P[s['w']['gate_b']], act='sigmoid')
+        with self.group():
+            for s, a in zip(S, A):
+                a['gated'] = self.new(s['n'], D)
+                self.ew(EW_MUL, a['gated'], a['tt'], a['ss'])
+        for s, y, a in zip(S, Y, A):
+            n = s['n']
+            a['xc'] = y.contiguous()
+            a['h'] = a['h'] if 'h' in a else self.new(n, D)
+            a['xh1'], a['rs1'] = self.new(n, D), self.new(n)
+            capi.call('sttode_add_ln_fwd', a['xc'], a['gated'], P[s['w']['ln1_w']], P[s['w']['ln1_b']], a['h'], a['xh1'], a['rs1'], n, D, self.st)
+        with self.group():
+            for s, a in zip(S, A):
+                a['f1'] = self.lin(a['h'], P[s['w']['l1_w']], P[s['w']['l1_b']], act='relu', out=a.get('f1'))
+        with self.group():
+            for s, a in zip(S, A):
+                a['f2'] = self.lin(a['f1'], P[s['w']['l2_w']], P[s['w']['l2_b']])
+        ks = []
+        for s, a in zip(S, A):
+            n = s['n']
+            k, a['xh2'], a['rs2'] = self.new(n, D), self.new(n, D), self.new(n)
+            capi.call('sttode_add_ln_fwd', a['h'], a['f2'], P[s['w']['ln2_w']], P[s['w']['ln2_b']], k, a['xh2'], a['rs2'], n, D, self.st)
+            ks.append(k)
+        return tuple(ks), A
 
     def _trunk_pre_layers(self, S):
         """Layer by layer up to the ODE block's input (input_fc .. input_fc3, add_category): s['x'] = feat[:, :D] = ftraj_input."""
@@ -294,26 +329,18 @@ class Engine:
         tbl = (ctypes.c_void_p * len(capi.TRUNK_PTRS))(*[(src[k].data_ptr() if src.get(k) is not None else None) for k in capi.TRUNK_PTRS])
         capi.call('sttode_ttrunk_fwd', tbl, len(capi.TRUNK_PTRS), n, T, feat.stride(0), float(self.net.ODE_TIME), phase, self.st)
 
-    def _trunk_fwd_fused(self, t, X0, last, feat, drop_mask, phase=0, launch=True):
+    def _trunk_fwd_fused(self, s, phase=0, launch=True):
         """The same forward and the same tape in ONE launch (csrc/train_trunk.hip, attention length 1): the step is bound by the number of
         launches, and a trunk is 21 of them layer by layer.  ``phase=1``: only up to the in-projection (attention over the forward-call batch:
         the caller runs the attention and then phase 2 through _trunk_launch); returns (tape, pointer sources) then."""
         P, net = self.P, self.net
+        t, X0, feat, drop_mask = s['t'], s['X0'], s['feat'], s['drop']
         pre, n, T = t['pre'], t['n'], t['T']
-        a = pre + _ATT
-        sa = a + 'self_attn.temporal_attention_before.'
         out = dict(posin=self.new(n * T, 128), tp=self.new(n * T, 64), h3in=self.new(n, 68), xc=self.new(n, 64), qkv=self.new(n, 192),
                    ao=self.new(n, 64), tt=self.new(n, 64), ss=self.new(n, 64), h=self.new(n, 64), xh1=self.new(n, 64), rs1=self.new(n),
                    f1=self.new(n, 1024), xh2=self.new(n, 64), rs2=self.new(n), ode=self.new(n, 64))
-        src = dict(fc1_w=P[pre + 'input_fc.weight'], fc1_b=P[pre + 'input_fc.bias'], pos_w=P[pre + 'pos_encoder.fc.weight'],
-                   pos_b=P[pre + 'pos_encoder.fc.bias'], fc2_w=P[pre + 'input_fc2.weight'], fc2_b=P[pre + 'input_fc2.bias'],
-                   fc3_w=P[pre + 'input_fc3.weight'], fc3_b=P[pre + 'input_fc3.bias'], inproj_w=P[sa + 'in_proj_weight'],
-                   inproj_b=P[sa + 'in_proj_bias'], out_w=P[sa + 'out_proj.weight'], out_b=P[sa + 'out_proj.bias'],
-                   info_w=P[a + 'self_attn.temporal_info.weight'], info_b=P[a + 'self_attn.temporal_info.bias'],
-                   gate_w=P[a + 'self_attn.temporal_gate.weight'], gate_b=P[a + 'self_attn.temporal_gate.bias'],
-                   ln1_w=P[a + 'norm1.weight'], ln1_b=P[a + 'norm1.bias'], l1_w=P[a + 'linear1.weight'], l1_b=P[a + 'linear1.bias'],
-                   l2_w=P[a + 'linear2.weight'], l2_b=P[a + 'linear2.bias'], ln2_w=P[a + 'norm2.weight'], ln2_b=P[a + 'norm2.bias'],
-                   enc_in=X0, last=last, pe=getattr(net, pre[:-1]).pos_encoder.pe, drop=drop_mask, feat=feat, **out)
+        src = dict({k: P[pre + name] for k, name in _FRONT.items()}, **{k: P[name] for k, name in s['w'].items()},
+                   enc_in=X0, last=s['last'], pe=getattr(net, pre[:-1]).pos_encoder.pe, drop=drop_mask, feat=feat, **out)
         for k, v in src.items():
             assert v is None or v.is_contiguous() or k == 'feat', k
         if phase == 1:
@@ -347,72 +374,91 @@ class Engine:
         the number of launches, and the two trunks are 2 x 10 linear-layer backward launches otherwise."""
         if items[0][0].get('ode_prog') is not None:
             return self._ode_trunk_bwd(items)
-        P, g, net = self.P, self.grad, self.net
-        D, HD = self.D, self.HD
-        S = []
-        for t, dfeat in items:
-            pre = t['pre']
-            assert dfeat.stride(1) == 1 and dfeat.shape[1] >= 2 * D and dfeat.stride(0) < 65536
-            S.append(dict(t=t, pre=pre, a=pre + _ATT, op=pre + _ATT + 'self_attn.temporal_attention_before.', n=t['n'], T=t['T'], dfeat=dfeat))
+        D = self.D
+        S = self._trunk_state(items, backward=True)
         with self.group():
             for s in S:                                          # dx = dfeat[:, :64] + d, dy = T d, d = dfeat[:, 64:128] * (ode > 0): one piece,
                 n = s['n']                                       # reading the strided rows of dfeat (no .contiguous() copies)
+                assert s['dfeat'].stride(0) < 65536
                 s['dx'], s['dy'] = self.new(n, D), self.new(n, D)
                 self.ew(EW_EULER_BWD_CAT, s['dfeat'], s['t']['ode'], None, s['dx'], s['dy'], i0=s['dfeat'].stride(0) | ((D << 16) if D != 64 else 0),
-                        f0=net.ODE_TIME, count=n * D)
-        for s in S:
-            t, a, n = s['t'], s['a'], s['n']
-            s['dsum2'] = self.new(n, D)
-            capi.call('sttode_ln_bwd', s['dy'], t['xh2'], t['rs2'], P[a + 'norm2.weight'], s['dsum2'], g(a + 'norm2.weight'), g(a + 'norm2.bias'), n, D,
+                        f0=self.net.ODE_TIME, count=n * D)
+        self._layer_vjp(S, [s['t'] for s in S], [s['dy'] for s in S], into=[s['dx'] for s in S])
+        self._trunk_bwd_pre(S)                                   # s['dx'] is now the gradient wrt ftraj_input
+
+    def _layer_vjp(self, S, A, dk, into=None, keep=None):
+        """Gradient wrt the layer's input Y of every trunk, given the gradient dk of k = f(Y) and f's activations A (_layer_fwd's, or a tape
+        of the default path): LN2, linear2^T, the relu mask, linear1^T, LN1, the gate, temporal_info / temporal_gate^T, out_proj^T, the
+        attention and in_proj^T.  The LayerNorm parameter gradients accumulate here.  ``keep`` None: every linear layer's backward is ONE
+        launch with its weight gradient (lin_bwd), and the residual dh = dsum2 + W1^T df1 accumulates in place.  ``keep`` given (per
+        trunk, the chunk's column buffers): input gradients alone (lin_dx), every linear layer's output gradient written into ``keep`` for
+        the deferred weight-gradient pass (_ode_wgrad) -- dsum2 among them, so the residual is a piece of its own.  ``into``: per trunk, a
+        buffer the input gradient is ADDED to (the LN1 residual inside the gate's group, then the in-projection's part); None: new buffers.
+        Returns the input gradient per trunk."""
+        P, g, D = self.P, self.grad, self.D
+        assert into is None or keep is None                      # the default path passes ``into``, the stage program ``keep``: never both
+        K = keep if keep is not None else [{} for _ in S]
+
+        def back(s, dY, role, X, rows=None, **kw):
+            wn, bn = s['w'][role + '_w'], s['w'][role + '_b']
+            if keep is not None:
+                return self.lin_dx(dY, P[wn] if rows is None else P[wn][rows], **kw)
+            if rows is None:
+                return self.lin_bwd(dY, P[wn], X, g(wn), g(bn), **kw)
+            return self.lin_bwd(dY, P[wn][rows], X, g(wn)[rows], g(bn)[rows], **kw)
+
+        def ln_bwd(s, a, dY, x, rs, role, out):
+            capi.call('sttode_ln_bwd', dY, a[x], a[rs], P[s['w'][role + '_w']], out, g(s['w'][role + '_w']), g(s['w'][role + '_b']), s['n'], D,
                       self.scratch, self.scratch.numel(), self.st)
+            return out
+        for s, a, d, k in zip(S, A, dk, K):
+            if keep is None:
+                k['dsum2'] = self.new(s['n'], D)
+            ln_bwd(s, a, d, 'xh2', 'rs2', 'ln2', k['dsum2'])
         with self.group():
-            for s in S:
-                t, a = s['t'], s['a']
-                s['df1'] = self.lin_bwd(s['dsum2'], P[a + 'linear2.weight'], t['f1'], g(a + 'linear2.weight'), g(a + 'linear2.bias'), mask=t['f1'])
+            for s, a, k in zip(S, A, K):
+                k['df1'] = back(s, k['dsum2'], 'l2', a['f1'], mask=a['f1'], out=k.get('df1'))
+        with self.group():                                       # dh = dsum2 (residual branch of LN2(h + f)) + W1^T df1
+            if keep is None:
+                dh = [back(s, k['df1'], 'l1', a['h'], out=k['dsum2'], accumulate=True) for s, a, k in zip(S, A, K)]
+            else:
+                dh = [back(s, k['df1'], 'l1', a['h']) for s, a, k in zip(S, A, K)]
+        if keep is not None:                                     # (dsum2 stays as it is for _ode_wgrad)
+            with self.group():
+                for h, k in zip(dh, K):
+                    self.ew(EW_AXPY, h, k['dsum2'], f0=1.0)
+        d1 = [ln_bwd(s, a, h, 'xh1', 'rs1', 'ln1', self.new(s['n'], D)) for s, a, h in zip(S, A, dh)]
+        dY = d1 if into is None else into                     # (None: the residual branch of LN1(Y + gated) is the buffer itself)
         with self.group():
-            for s in S:                                          # dh = dsum2 (residual branch of LN2(h + f)) + W1^T df1
-                t, a = s['t'], s['a']
-                self.lin_bwd(s['df1'], P[a + 'linear1.weight'], t['h'], g(a + 'linear1.weight'), g(a + 'linear1.bias'), out=s['dsum2'], accumulate=True)
-        for s in S:
-            t, a, n = s['t'], s['a'], s['n']
-            s['dsum1'] = self.new(n, D)
-            capi.call('sttode_ln_bwd', s['dsum2'], t['xh1'], t['rs1'], P[a + 'norm1.weight'], s['dsum1'], g(a + 'norm1.weight'), g(a + 'norm1.bias'), n, D,
-                      self.scratch, self.scratch.numel(), self.st)
+            for s, a, k, d, dy in zip(S, A, K, d1, dY):
+                if into is not None:
+                    self.ew(EW_AXPY, dy, d, f0=1.0)              # residual branch of LN1(x + gated)
+                if keep is None:
+                    k['du'], k['dv'] = self.new(s['n'], D), self.new(s['n'], D)
+                self.ew(EW_GATE_BWD, d, a['tt'], a['ss'], k['du'], k['dv'])
         with self.group():
-            for s in S:
-                self.ew(EW_AXPY, s['dx'], s['dsum1'], f0=1.0)    # residual branch of LN1(x + gated)
-                s['du'], s['dv'] = self.new(s['n'], D), self.new(s['n'], D)
-                self.ew(EW_GATE_BWD, s['dsum1'], s['t']['tt'], s['t']['ss'], s['du'], s['dv'])
+            for s, a, k in zip(S, A, K):
+                k['dao'] = back(s, k['du'], 'info', a['ao'], out=k.get('dao'))
         with self.group():
-            for s in S:
-                t, a = s['t'], s['a']
-                s['dao'] = self.lin_bwd(s['du'], P[a + 'self_attn.temporal_info.weight'], t['ao'], g(a + 'self_attn.temporal_info.weight'),
-                                        g(a + 'self_attn.temporal_info.bias'))
+            for s, a, k in zip(S, A, K):
+                back(s, k['dv'], 'gate', a['ao'], out=k['dao'], accumulate=True)
         with self.group():
-            for s in S:
-                t, a = s['t'], s['a']
-                self.lin_bwd(s['dv'], P[a + 'self_attn.temporal_gate.weight'], t['ao'], g(a + 'self_attn.temporal_gate.weight'),
-                             g(a + 'self_attn.temporal_gate.bias'), out=s['dao'], accumulate=True)
+            for s, a, k in zip(S, A, K):
+                k['dattn'] = back(s, k['dao'], 'out', a['attn'], out=k.get('dattn'))
+        for s, a, k in zip(S, A, K):
+            if s['L'] > 1:
+                if keep is None:
+                    k['dqkv'] = self.new(s['n'], 3 * D)
+                capi.call('sttode_mhgsa_attn_bwd', a['qkv'], k['dattn'], k['dqkv'], s['L'], s['Nb'], self.HD, self.st)
         with self.group():
-            for s in S:
-                t, op = s['t'], s['op']
-                s['dattn'] = self.lin_bwd(s['dao'], P[op + 'out_proj.weight'], t['attn'], g(op + 'out_proj.weight'), g(op + 'out_proj.bias'))
-        for s in S:
-            t = s['t']
-            if t['L'] > 1:
-                s['dqkv'] = self.new(s['n'], 3 * D)
-                capi.call('sttode_mhgsa_attn_bwd', t['qkv'], s['dattn'], s['dqkv'], t['L'], t['Nb'], HD, self.st)
-        with self.group():
-            for s in S:
-                t, op = s['t'], s['op']
-                W, gW, gb = P[op + 'in_proj_weight'], g(op + 'in_proj_weight'), g(op + 'in_proj_bias')
-                if t['L'] > 1:
-                    self.lin_bwd(s['dqkv'], W, t['xc'], gW, gb, out=s['dx'], accumulate=True)
+            for s, a, k, dy in zip(S, A, K, dY):
+                if s['L'] > 1:
+                    back(s, k['dqkv'], 'inproj', a['xc'], out=dy, accumulate=True)
                 else:
                     # attention length 1 (scene batches): the softmax over one key is 1, the output is v -- dv = dattn, and the gradients of
                     # q and k are exactly zero (their rows of the in-projection's gradient stay the zeros of the flat buffer)
-                    self.lin_bwd(s['dattn'], W[2 * D:], t['xc'], gW[2 * D:], gb[2 * D:], out=s['dx'], accumulate=True)
-        self._trunk_bwd_pre(S)                                   # s['dx'] is now the gradient wrt ftraj_input
+                    back(s, k['dattn'], 'inproj', a['xc'], rows=slice(2 * D, None), out=dy, accumulate=True)
+        return tuple(dY)
 
     def _trunk_bwd_pre(self, S):
         """Backward of the layers in front of the ODE block (input_fc3 .. input_fc), s['dx'] = gradient wrt ftraj_input."""
@@ -478,121 +524,23 @@ class Engine:
         capi.call('sttode_ode_combine', jobs, len(S), D, self.st)
         return tuple(outs)
 
-    def _ode_f(self, S, Y, keep=None):
-        """k = f(Y) per trunk: the ODE block's TransformerEncoderLayer (in-projection, geodesic attention -- the value rows alone at attention
-        length 1 --, out_proj, tanh * sigmoid gate, add + LN1, FFN, add + LN2).  Layer i of every trunk in one group.  ``keep``: per trunk,
-        buffers for the activations the weight gradients read (qkv, attn, ao, h, f1); returns (k per trunk, activations per trunk)."""
-        P, D, HD, net = self.P, self.D, self.HD, self.net
-        A = [dict(keep[i]) if keep is not None else {} for i in range(len(S))]
-        with self.group():
-            for s, y, a in zip(S, Y, A):
-                W, b = P[s['op'] + 'in_proj_weight'], P[s['op'] + 'in_proj_bias']
-                if s['L'] > 1:
-                    a['qkv'] = self.lin(y, W, b, out=a.get('qkv'))
-                else:
-                    a['attn'] = self.lin(y, W[2 * D:], b[2 * D:], out=a.get('attn'))
-        for s, a in zip(S, A):
-            if s['L'] > 1:
-                qkv, L, Nb, e = a['qkv'], s['L'], s['Nb'], 4
-                a['attn'] = a['attn'] if 'attn' in a else self.new(s['n'], D)
-                gq, go = L * Nb * 3 * D, L * Nb * D
-                capi.call('sttode_mhgsa_attn_groups', qkv.data_ptr() + D * e, qkv.data_ptr(), qkv.data_ptr() + 2 * D * e, a['attn'], getattr(net, '_G', 1),
-                          gq, gq, gq, go, L, L, Nb, Nb * 3 * D, 3 * D, Nb * 3 * D, 3 * D, Nb * 3 * D, 3 * D, Nb * D, D, 1.0, float(HD) ** -0.5, HD, self.st)
-        with self.group():
-            for s, a in zip(S, A):
-                a['ao'] = self.lin(a['attn'], P[s['op'] + 'out_proj.weight'], P[s['op'] + 'out_proj.bias'], out=a.get('ao'))
-        with self.group():
-            for s, a in zip(S, A):
-                a['tt'] = self.lin(a['ao'], P[s['a'] + 'self_attn.temporal_info.weight'], P[s['a'] + 'self_attn.temporal_info.bias'], act='tanh')
-                a['ss'] = self.lin(a['ao'], P[s['a'] + 'self_attn.temporal_gate.weight'], P[s['a'] + 'self_attn.temporal_gate.bias'], act='sigmoid')
-        with self.group():
-            for s, a in zip(S, A):
-                a['gated'] = self.new(s['n'], D)
-                self.ew(EW_MUL, a['gated'], a['tt'], a['ss'])
-        for s, y, a in zip(S, Y, A):
-            n = s['n']
-            a['h'] = a['h'] if 'h' in a else self.new(n, D)
-            a['xh1'], a['rs1'] = self.new(n, D), self.new(n)
-            capi.call('sttode_add_ln_fwd', y, a['gated'], P[s['a'] + 'norm1.weight'], P[s['a'] + 'norm1.bias'], a['h'], a['xh1'], a['rs1'], n, D, self.st)
-        with self.group():
-            for s, a in zip(S, A):
-                a['f1'] = self.lin(a['h'], P[s['a'] + 'linear1.weight'], P[s['a'] + 'linear1.bias'], act='relu', out=a.get('f1'))
-        with self.group():
-            for s, a in zip(S, A):
-                a['f2'] = self.lin(a['f1'], P[s['a'] + 'linear2.weight'], P[s['a'] + 'linear2.bias'])
-        ks = []
-        for s, a in zip(S, A):
-            n = s['n']
-            k, a['xh2'], a['rs2'] = self.new(n, D), self.new(n, D), self.new(n)
-            capi.call('sttode_add_ln_fwd', a['h'], a['f2'], P[s['a'] + 'norm2.weight'], P[s['a'] + 'norm2.bias'], k, a['xh2'], a['rs2'], n, D, self.st)
-            ks.append(k)
-        return tuple(ks), A
-
-    def _ode_vjp(self, S, A, kb, keep):
-        """Gradient wrt the stage input Y of every trunk, given the gradient kb of k = f(Y) and f's activations A: LN2, linear2^T, the relu
-        mask, linear1^T, LN1, the gate, temporal_info / temporal_gate^T, out_proj^T, the attention and in_proj^T.  The LayerNorm parameter
-        gradients accumulate here; every linear layer's output gradient is written into ``keep`` for the deferred weight-gradient pass."""
-        P, g, D = self.P, self.grad, self.D
-        for s, a, d, k in zip(S, A, kb, keep):
-            capi.call('sttode_ln_bwd', d, a['xh2'], a['rs2'], P[s['a'] + 'norm2.weight'], k['dsum2'], g(s['a'] + 'norm2.weight'),
-                      g(s['a'] + 'norm2.bias'), s['n'], D, self.scratch, self.scratch.numel(), self.st)
-        with self.group():
-            for s, a, k in zip(S, A, keep):
-                self.lin_dx(k['dsum2'], P[s['a'] + 'linear2.weight'], mask=a['f1'], out=k['df1'])
-        with self.group():
-            for s, a, k in zip(S, A, keep):
-                a['dh'] = self.lin_dx(k['df1'], P[s['a'] + 'linear1.weight'])
-        with self.group():
-            for s, a, k in zip(S, A, keep):                    # dh = dsum2 (residual branch of LN2(h + f)) + W1^T df1
-                self.ew(EW_AXPY, a['dh'], k['dsum2'], f0=1.0)
-        dY = []
-        for s, a in zip(S, A):
-            d1 = self.new(s['n'], D)
-            capi.call('sttode_ln_bwd', a['dh'], a['xh1'], a['rs1'], P[s['a'] + 'norm1.weight'], d1, g(s['a'] + 'norm1.weight'), g(s['a'] + 'norm1.bias'),
-                      s['n'], D, self.scratch, self.scratch.numel(), self.st)
-            dY.append(d1)                                       # residual branch of LN1(Y + gated); the in-projection's part is added below
-        with self.group():
-            for a, k, d1 in zip(A, keep, dY):
-                self.ew(EW_GATE_BWD, d1, a['tt'], a['ss'], k['du'], k['dv'])
-        with self.group():
-            for s, k in zip(S, keep):
-                self.lin_dx(k['du'], P[s['a'] + 'self_attn.temporal_info.weight'], out=k['dao'])
-        with self.group():
-            for s, k in zip(S, keep):
-                self.lin_dx(k['dv'], P[s['a'] + 'self_attn.temporal_gate.weight'], out=k['dao'], accumulate=True)
-        with self.group():
-            for s, k in zip(S, keep):
-                self.lin_dx(k['dao'], P[s['op'] + 'out_proj.weight'], out=k['dattn'])
-        for s, a, k in zip(S, A, keep):
-            if s['L'] > 1:
-                capi.call('sttode_mhgsa_attn_bwd', a['qkv'], k['dattn'], k['dqkv'], s['L'], s['Nb'], self.HD, self.st)
-        with self.group():
-            for s, k, d1 in zip(S, keep, dY):
-                W = P[s['op'] + 'in_proj_weight']
-                if s['L'] > 1:
-                    self.lin_dx(k['dqkv'], W, out=d1, accumulate=True)
-                else:                                           # attention length 1: the output is v, q and k get no gradient
-                    self.lin_dx(k['dattn'], W[2 * D:], out=d1, accumulate=True)
-        return tuple(dY)
-
     def _ode_wgrad(self, S, K, c0, c1):
         """The deferred weight-gradient pass of stages c0 .. c1-1: ONE product per layer over all of their columns (stage j's rows of
         every buffer at (j - c0) n .. (j - c0 + 1) n; the in-projection reads the stage inputs where the tape keeps them)."""
         P, g, D = self.P, self.grad, self.D
         rows = [(c1 - c0) * s['n'] for s in S]
-        for dy, x, lay in (('dsum2', 'f1', 'linear2.'), ('df1', 'h', 'linear1.'), ('du', 'ao', 'self_attn.temporal_info.'),
-                           ('dv', 'ao', 'self_attn.temporal_gate.'), ('dao', 'attn', 'self_attn.temporal_attention_before.out_proj.')):
+        for dy, x, role in (('dsum2', 'f1', 'l2'), ('df1', 'h', 'l1'), ('du', 'ao', 'info'), ('dv', 'ao', 'gate'), ('dao', 'attn', 'out')):
             with self.group():
                 for s, k, m in zip(S, K, rows):
-                    self.wgrad(k[dy][:m], k[x][:m], g(s['a'] + lay + 'weight'), g(s['a'] + lay + 'bias'))
+                    self.wgrad(k[dy][:m], k[x][:m], g(s['w'][role + '_w']), g(s['w'][role + '_b']))
         for s, k, m in zip(S, K, rows):
             if 'ln' in k:                                       # (the fused dX chain) LayerNorm parameter gradients: column sums of its rows
-                for off, name in ((0, 'norm2.weight'), (D, 'norm2.bias'), (2 * D, 'norm1.weight'), (3 * D, 'norm1.bias')):
-                    capi.call('sttode_rows_reduce', g(s['a'] + name), D, k['ln'][:, off:], 4 * D, 1, D, m, 1, self.st)
+                for off, role in ((0, 'ln2_w'), (D, 'ln2_b'), (2 * D, 'ln1_w'), (3 * D, 'ln1_b')):
+                    capi.call('sttode_rows_reduce', g(s['w'][role]), D, k['ln'][:, off:], 4 * D, 1, D, m, 1, self.st)
         with self.group():
             for s, k, m in zip(S, K, rows):
                 Y = s['Ys'][c0 * s['n']:c1 * s['n']]
-                gW, gb = g(s['op'] + 'in_proj_weight'), g(s['op'] + 'in_proj_bias')
+                gW, gb = g(s['w']['inproj_w']), g(s['w']['inproj_b'])
                 if s['L'] > 1:
                     self.wgrad(k['dqkv'][:m], Y, gW, gb)
                 else:
@@ -604,19 +552,15 @@ class Engine:
         the stage loop inside the kernel).  Otherwise the layers in front as in the default path (the fused phase-1 launch when T <= 12),
         then the stage program with f layer by layer, both trunks' layer i in one group.  Tape: the layers in front, and the stage inputs
         Y_j alone ([stages * n, 64] per trunk); the backward pass recomputes f's activations from them."""
-        P, net, D = self.P, self.net, self.D
-        L, Nb = (net.batch_size, net._N) if net._mode == 'nba' else (1, None)
-        S = []
-        for pre, enc_in, last, feat, drop_mask in items:
-            n, T = enc_in.shape[0], enc_in.shape[1]
-            S.append(dict(t={'n': n, 'T': T, 'pre': pre, 'feat': feat}, pre=pre, a=pre + _ATT, op=pre + _ATT + 'self_attn.temporal_attention_before.',
-                          n=n, T=T, X0=enc_in.reshape(n * T, 4), last=last, feat=feat, drop=drop_mask, L=L, Nb=Nb if Nb is not None else n))
+        net, D = self.net, self.D
+        S = self._trunk_state(items)
+        L = S[0]['L']
         nst = steps * odestages.stages(method)
         for s in S:
             s['Ys'], s['yT'] = self.new(nst * s['n'], D), self.new(s['n'], D)
         fused = all(s['T'] <= 12 for s in S) and self.fused_trunk
         if fused and L == 1:
-            tabs = [self._trunk_fwd_fused(s['t'], s['X0'], s['last'], s['feat'], s['drop'], phase=1, launch=False) for s in S]
+            tabs = [self._trunk_fwd_fused(s, phase=1, launch=False) for s in S]
             ptrs = [(src[k].data_ptr() if src.get(k) is not None else None) for _, src in tabs for k in capi.TRUNK_PTRS]
             A, B = odestages.TABLEAU[method]
             prog = _OdeProgram(stages=len(B), steps=steps, h=float(net.ODE_TIME) / steps)
@@ -630,20 +574,18 @@ class Engine:
                       (ctypes.c_int * m)(*[s['T'] for s in S]), (ctypes.c_long * m)(*[s['feat'].stride(0) for s in S]),
                       (ctypes.c_void_p * m)(*[s['Ys'].data_ptr() for s in S]), (ctypes.c_void_p * m)(*[s['yT'].data_ptr() for s in S]),
                       ctypes.byref(prog), self.st)
-            for s, (t, _) in zip(S, tabs):
-                s['t'] = t
         else:
             if fused:                                            # phase 1 of the fused trunk launch, both trunks in one launch
                 with (self.group() if len(S) > 1 else contextlib.nullcontext()):
-                    tabs = [self._trunk_fwd_fused(s['t'], s['X0'], s['last'], s['feat'], s['drop'], phase=1) for s in S]
-                for s, (t, _) in zip(S, tabs):
-                    s['t'], s['y0'] = t, t['xc']
+                    tabs = [self._trunk_fwd_fused(s, phase=1) for s in S]
+                for s in S:
+                    s['y0'] = s['t']['xc']
             else:
                 self._trunk_pre_layers(S)
                 for s in S:
                     s['y0'] = s['x']
                     s['t'].update(X0=s['X0'], posin=s['posin'], tp=s['tp'], drop=s['drop'], h3in=s['h3in'])
-            odestages.integrate(lambda j, Y: self._ode_f(S, Y)[0], lambda terms, dst: self._ode_comb(S, terms, dst),
+            odestages.integrate(lambda j, Y: self._layer_fwd(S, Y)[0], lambda terms, dst: self._ode_comb(S, terms, dst),
                                 tuple(s['y0'] for s in S), net.ODE_TIME, method, steps)
         for s in S:
             s['t'].update(ode_prog=(method, steps), ode_fused=fused and L == 1, Ys=s['Ys'], yT=s['yT'], L=L, Nb=s['Nb'])
@@ -656,11 +598,8 @@ class Engine:
         jobs = (_OdeStageBwd * len(S))()
         closed = []
         for si, s in enumerate(S):
-            J, n, a, op = jobs[si], s['n'], s['a'], s['op']
-            for wi, name in enumerate((op + 'in_proj_weight', op + 'in_proj_bias', op + 'out_proj.weight', op + 'out_proj.bias',
-                                       a + 'self_attn.temporal_info.weight', a + 'self_attn.temporal_info.bias', a + 'self_attn.temporal_gate.weight',
-                                       a + 'self_attn.temporal_gate.bias', a + 'norm1.weight', a + 'norm1.bias', a + 'linear1.weight',
-                                       a + 'linear1.bias', a + 'linear2.weight', a + 'linear2.bias', a + 'norm2.weight', a + 'norm2.bias')):
+            J, n = jobs[si], s['n']
+            for wi, name in enumerate(s['w'].values()):         # (the order of _LAYER is the order of w[])
                 J.w[wi] = P[name].data_ptr()
             J.y, J.dy, J.n = s['Ys'][j * n:(j + 1) * n].data_ptr(), dY[si].data_ptr(), n
             for ti, (c, v) in enumerate(kb):
@@ -685,12 +624,8 @@ class Engine:
         D = self.D
         method, steps = items[0][0]['ode_prog']
         fused = items[0][0]['ode_fused']
-        S = []
-        for t, dfeat in items:
-            assert t['ode_prog'] == (method, steps) and t['ode_fused'] == fused and dfeat.stride(1) == 1 and dfeat.shape[1] >= 2 * D
-            pre = t['pre']
-            S.append(dict(t=t, pre=pre, a=pre + _ATT, op=pre + _ATT + 'self_attn.temporal_attention_before.', n=t['n'], T=t['T'], dfeat=dfeat,
-                          L=t['L'], Nb=t['Nb'], Ys=t['Ys']))
+        assert all(t['ode_prog'] == (method, steps) and t['ode_fused'] == fused for t, _ in items)
+        S = self._trunk_state(items, backward=True)
         acts = ('attn', 'ao', 'h', 'f1')
         width = dict(attn=D, ao=D, h=D, f1=1024, dsum2=D, df1=1024, du=D, dv=D, dao=D, dattn=D, qkv=3 * D, dqkv=3 * D, ln=4 * D)
         names = [acts + ('dsum2', 'df1', 'du', 'dv', 'dao', 'dattn') + (('ln',) if fused else ()) + (('qkv', 'dqkv') if s['L'] > 1 else ())
@@ -711,8 +646,8 @@ class Engine:
                 closed = self._ode_stage_bwd(S, j, kb, close, keep, dY)
             else:
                 Y = tuple(s['Ys'][j * s['n']:(j + 1) * s['n']] for s in S)
-                _, A = self._ode_f(S, Y, keep=[{k: kp[k] for k in kp if k in acts or k == 'qkv'} for kp in keep])
-                dY = self._ode_vjp(S, A, self._ode_comb(S, kb, None), keep)
+                _, A = self._layer_fwd(S, Y, keep=[{k: kp[k] for k in kp if k in acts or k == 'qkv'} for kp in keep])
+                dY = self._layer_vjp(S, A, self._ode_comb(S, kb, None), keep=keep)
                 closed = None if close is None else self._ode_comb(S, [(1.0, dY)] + close, None)
             if j == c0:
                 self._ode_wgrad(S, K, c0, c1)
@@ -725,45 +660,30 @@ class Engine:
         self._trunk_bwd_pre(S)
 
     # ---------------------------------------------------------------- decoder (Decoder.forward, model/STTODE.py:320-347)
-    def mlp_fwd(self, pre, inp):
+    def mlp_fwd(self, pres, inp):
+        """The three-layer MLPs ``pres`` over the same input (decoder_y alone, or decoder_y and decoder_x of a block: separate weights,
+        model/STTODE.py:71-77) layer by layer: at batch sizes the two products of a layer leave as one launch (sttode_tgemm_group); one
+        MLP's stay outside any group.  Returns (output, (a1, a2)) per MLP."""
         P = self.P
-        a1 = self.lin(inp, P[pre + 'layers.0.weight'], P[pre + 'layers.0.bias'], act='relu')
-        a2 = self.lin(a1, P[pre + 'layers.1.weight'], P[pre + 'layers.1.bias'], act='relu')
-        out = self.lin(a2, P[pre + 'layers.2.weight'], P[pre + 'layers.2.bias'])
-        return out, (a1, a2)
-
-    def mlp_fwd_pair(self, pre_a, pre_b, inp):
-        """decoder_y and decoder_x of a block (same input, separate weights, model/STTODE.py:71-77) layer by layer: at batch sizes the two
-        products of a layer leave as one launch (sttode_tgemm_group)."""
-        P = self.P
-        acts = []
-        xa = xb = inp
+        xs, acts = [inp] * len(pres), []
         for li, act in ((0, 'relu'), (1, 'relu'), (2, None)):
-            with self.group():
-                xa = self.lin(xa, P[f'{pre_a}layers.{li}.weight'], P[f'{pre_a}layers.{li}.bias'], act=act)
-                xb = self.lin(xb, P[f'{pre_b}layers.{li}.weight'], P[f'{pre_b}layers.{li}.bias'], act=act)
-            acts.append((xa, xb))
-        return (acts[2][0], (acts[0][0], acts[1][0])), (acts[2][1], (acts[0][1], acts[1][1]))
+            with (self.group() if len(pres) > 1 else contextlib.nullcontext()):
+                xs = [self.lin(x, P[f'{pre}layers.{li}.weight'], P[f'{pre}layers.{li}.bias'], act=act) for pre, x in zip(pres, xs)]
+            acts.append(xs)
+        return [(a3, (a1, a2)) for a1, a2, a3 in zip(*acts)]
 
-    def mlp_bwd_pair(self, pre_a, pre_b, inp, saved_a, saved_b, dout_a, dout_b, din):
-        """Backward of the pair: layers 2 and 1 of both MLPs side by side (four products per launch at batch sizes); their layer-0 input
-        gradients add into the same ``din``, so those two stay launches of their own, in order."""
+    def mlp_bwd(self, pres, inp, saved, douts, din):
+        """Backward of mlp_fwd: layers 2 and 1 of the MLPs side by side (four products per launch at batch sizes); their layer-0 input
+        gradients add into the same ``din``, so those stay launches of their own, in order."""
         P, g = self.P, self.grad
-        da, db_ = dout_a, dout_b
-        for li, (sa, sb) in ((2, (saved_a[1], saved_b[1])), (1, (saved_a[0], saved_b[0]))):
-            with self.group():                                      # (the layer's inputs keep their names until the group has left: see group())
-                da_in = self.lin_bwd(da, P[f'{pre_a}layers.{li}.weight'], sa, g(f'{pre_a}layers.{li}.weight'), g(f'{pre_a}layers.{li}.bias'), mask=sa)
-                db_in = self.lin_bwd(db_, P[f'{pre_b}layers.{li}.weight'], sb, g(f'{pre_b}layers.{li}.weight'), g(f'{pre_b}layers.{li}.bias'), mask=sb)
-            da, db_ = da_in, db_in
-        self.lin_bwd(da, P[pre_a + 'layers.0.weight'], inp, g(pre_a + 'layers.0.weight'), g(pre_a + 'layers.0.bias'), out=din)
-        self.lin_bwd(db_, P[pre_b + 'layers.0.weight'], inp, g(pre_b + 'layers.0.weight'), g(pre_b + 'layers.0.bias'), out=din, accumulate=True)
-
-    def mlp_bwd(self, pre, inp, saved, dout, din):
-        P, g = self.P, self.grad
-        a1, a2 = saved
-        da2 = self.lin_bwd(dout, P[pre + 'layers.2.weight'], a2, g(pre + 'layers.2.weight'), g(pre + 'layers.2.bias'), mask=a2)
-        da1 = self.lin_bwd(da2, P[pre + 'layers.1.weight'], a1, g(pre + 'layers.1.weight'), g(pre + 'layers.1.bias'), mask=a1)
-        self.lin_bwd(da1, P[pre + 'layers.0.weight'], inp, g(pre + 'layers.0.weight'), g(pre + 'layers.0.bias'), out=din)
+        ds = douts
+        for li in (2, 1):
+            with (self.group() if len(pres) > 1 else contextlib.nullcontext()):
+                nxt = [self.lin_bwd(d, P[f'{pre}layers.{li}.weight'], sv[li - 1], g(f'{pre}layers.{li}.weight'), g(f'{pre}layers.{li}.bias'), mask=sv[li - 1])
+                       for pre, sv, d in zip(pres, saved, ds)]
+            ds = nxt                                                # (the layer's inputs keep their names until the group has left: see group())
+        for i, (pre, d) in enumerate(zip(pres, ds)):
+            self.lin_bwd(d, P[pre + 'layers.0.weight'], inp, g(pre + 'layers.0.weight'), g(pre + 'layers.0.bias'), out=din, accumulate=i > 0)
 
     def block_fwd(self, i, past, K, xhat_prev, pf, z, want_x, inp=None):
         P = self.P
@@ -796,9 +716,9 @@ class Engine:
             capi.call('sttode_rows_copy', inp, IN, pf, _ld(pf), m, PFW, K, n, self.st)
             capi.call('sttode_rows_copy', inp[:, PFW:], IN, z, _ld(z), m, ZD, 1, m, self.st)
         if want_x:
-            (yh, sy), (xh, sx) = self.mlp_fwd_pair(pre + 'decoder_y.', pre + 'decoder_x.', inp)
+            (yh, sy), (xh, sx) = self.mlp_fwd([pre + 'decoder_y.', pre + 'decoder_x.'], inp)
         else:
-            (yh, sy), (xh, sx) = self.mlp_fwd(pre + 'decoder_y.', inp), (None, None)
+            (yh, sy), (xh, sx) = self.mlp_fwd([pre + 'decoder_y.'], inp)[0], (None, None)
         return dict(pre=pre, m=m, Tp=Tp, K=K, x=x, e=e, H=H, tapes=tapes, inp=inp, yh=yh, sy=sy, xh=xh, sx=sx, agent=agent)
 
     def block_bwd(self, b, dyh, dxh, need_dx):
@@ -808,9 +728,9 @@ class Engine:
         IN, ST = self.IN, self.ST
         din = self.new(m, IN)
         if dxh is not None:
-            self.mlp_bwd_pair(pre + 'decoder_y.', pre + 'decoder_x.', b['inp'], b['sy'], b['sx'], dyh, dxh, din)
+            self.mlp_bwd([pre + 'decoder_y.', pre + 'decoder_x.'], b['inp'], [b['sy'], b['sx']], [dyh, dxh], din)
         else:
-            self.mlp_bwd(pre + 'decoder_y.', b['inp'], b['sy'], dyh, din)
+            self.mlp_bwd([pre + 'decoder_y.'], b['inp'], [b['sy']], [dyh], din)
         dstate, lds, mg = din[:, ST:], IN, m
         if b.get('agent'):                                          # conv + GRU ran once per agent: its state gradient is the sum over the agent's columns
             assert not need_dx
@@ -977,21 +897,21 @@ class Engine:
         # gradient equals what S reference steps would accumulate (per-scene KL clamp and per-scene mean of the best-of-20 term)
         seg = net._mode == 'scenes' and net._S > 1
         sp, ags, S = (net._scene_ptr, ws['agent_scene'], net._S) if seg else (None, None, 0)
+        # what the three objective entries share: the inputs, the sizes and scales, then the values and the gradients they write
+        common = (d['pred'], d['rec'], fut, past, qzp, sp, ags, S, n, K1, 2 * Tf, 2 * Tp, zd, 1.0 / (B * Tf), 1.0 / (B * Tp), float(B * N),
+                  float(a.min_clip), losses, dpred, drec, dqzp)
+        tail = (self.scratch, self.scratch.numel(), self.st)
         if net._diverse_joint():
             # the scene-level best-of-K term: one prior sample per segment -- a scene of the CSR, the one scene, an NBA game --
             # so the gradient still lives in sample 0 plus one prior column per agent and `best` feeds decoder_live as it is
             if not live:
                 raise SttodeError("diverse_mode 'joint' is built on the live-column backward pass (its kernel writes the two live gradient "
                                   "rows per agent); _LIVE_COLUMNS = False has no dense joint form")
-            capi.call('sttode_loss_objective_joint', d['pred'], d['rec'], fut, past, qzp, sp, ags, S, n, K1, 2 * Tf, 2 * Tp, zd, 1.0 / (B * Tf),
-                      1.0 / (B * Tp), float(B * N), float(a.min_clip), losses, dpred, drec, dqzp, best, 0 if seg else net._joint_seg_len(n), None,
-                      self.scratch, self.scratch.numel(), self.st)
+            capi.call('sttode_loss_objective_joint', *common, best, 0 if seg else net._joint_seg_len(n), None, *tail)
         elif live:
-            capi.call('sttode_loss_objective_live', d['pred'], d['rec'], fut, past, qzp, sp, ags, S, n, K1, 2 * Tf, 2 * Tp, zd, 1.0 / (B * Tf),
-                      1.0 / (B * Tp), float(B * N), float(a.min_clip), losses, dpred, drec, dqzp, best, self.scratch, self.scratch.numel(), self.st)
+            capi.call('sttode_loss_objective_live', *common, best, *tail)
         else:
-            capi.call('sttode_loss_objective', d['pred'], d['rec'], fut, past, qzp, sp, ags, S, n, K1, 2 * Tf, 2 * Tp, zd, 1.0 / (B * Tf),
-                      1.0 / (B * Tp), float(B * N), float(a.min_clip), losses, dpred, drec, dqzp, self.scratch, self.scratch.numel(), self.st)
+            capi.call('sttode_loss_objective', *common, *tail)
         if getattr(self, 'publish', None) is not None:         # a step being captured: the values reach the host from HERE (see _GraphedStep)
             capi.call('sttode_publish_values', losses, 5, *self.publish, self.st)
         self.step_id = getattr(self, 'step_id', 0) + 1
